@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s of the gfx950 path-tracing device on BASELINE.json's configuration.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures `value` and nothing else: set-up (scene, BVH build, upload), W warm-up frames, K timed frames, the outputs of
+the last timed frame if --dump-outputs is given, one JSON line.  --full adds every other measurement listed below (both other film
+sinks, the CPU baseline, the instrumented pass, the rooflines, the secondary workloads; ~2.5 min) and writes the full record.
+
+--dump-outputs DIR writes what the last timed frame computed, as a caller of xpu_t::start ... join receives it: DIR/film.npy
+(float32 H x W x 4, the film reduced onto rank 0 at N > 1; a fixed, seeded sample of its pixels, film_sample.npy with their indices
+in film_sample_index.npy, if the film exceeds OUTPUT_BUDGET) and DIR/ray_counts.npy (float64: closest-hit rays, shadow rays, camera
+samples of that frame, summed over the ranks).  Same arguments, same inputs: two builds can be compared output for output.
 
 A step = one whole frame (xpu_t::start ... join, the reference's own "Rendering time" bracket, src/core.cpp:158-177) of the
 synthetic workload Soup(100k) 1280x720 256 spp, depth 9, pps 1 (BASELINE.json configs[1]).  ONE protocol at every N:
@@ -9,10 +18,10 @@ synthetic workload Soup(100k) 1280x720 256 spp, depth 9, pps 1 (BASELINE.json co
           renders into its own device film (HBM) and — N > 1 — the films are summed onto rank 0 with ONE reduce(sum) (RCCL over xGMI)
           INSIDE the bracket, before the next frame starts ("strong" scaling: total work is fixed).
           value = rays traced by ALL ranks (closest-hit + non-masked shadow rays) / max-over-ranks time of K frames.
-  value_two_frames_in_flight
+  value_two_frames_in_flight (--full)
           the same K frames with a second device object per rank (own stream, queues and tree) rendering alternate frames and the
           film reduce asynchronous beside them: a throughput, not a frame latency; reported at every N, never called `value`.
-  value_host_film (N = 1)
+  value_host_film (--full, N = 1)
           the frame handed to a host frame buffer through the xpu_t boundary's add_tile sink (14.7 MB over PCIe per frame).
 Scene upload and BVH build (xpu_t::preprocess) happen before the timed region: inputs are HBM-resident.
 
@@ -20,9 +29,10 @@ Scene upload and BVH build (xpu_t::preprocess) happen before the timed region: i
 process (before this process touches the GPU), relays rank 0's line and exits with the child's code; it fails when fewer than N
 devices are visible.  Under the driver's own torchrun launch WORLD_SIZE must equal --gpus.
 
-Output: the LAST stdout line is ONE compact JSON object (< 4 KB: metric, value, roofline, cpu_baseline, four secondary workloads reduced
-to value / ms / roofline fraction).  The FULL record — every operand of the roofline, counter diagnostics, CPU scaling table, complete
-secondary records — goes to --full-json (default gpurun_out/bench_full.json).  At N = 1 the full record carries:
+Output: the LAST stdout line is ONE compact JSON object (< 4 KB: metric, value, ms_per_step; with --full also roofline, cpu_baseline,
+the secondary workloads reduced to value / ms / roofline fraction).  The FULL record — every operand of the roofline, counter
+diagnostics, CPU scaling table, complete secondary records — goes to --full-json (with --full, by default bench_out/bench_full.json).
+With --full, at N = 1 the full record carries:
   roofline     of the dominant kernel, k_trace (closest-hit rays of a step + shadow rays of the previous step in one persistent
                launch; time = HIP events on the device's own stream around every launch of the timed steps).
                `frac` is WORK-based (bound "valu"): the node visits and triangle tests the frame needs (counted by the instrumented
@@ -64,13 +74,29 @@ L1_ADDR_PER_CLK_CU = 1.7  # measured ceiling of the vector L1 for an L1-RESIDENT
 # the same gather over larger tables (profiles/r04_l_pair_help.log, r04_m_l1_gather.log): the rate a uniform gather over a pool of the tree's size reaches
 GATHER_PER_CLK_CU_BY_TABLE = {"16 KB (L1-resident)": 1.67, "2.4 MB (inside one XCD's 4 MB L2)": 1.36, "7.7 MB (the 100 k soup's pool)": 0.81, "77 MB (the 1 M soup's pool)": 0.38}
 COUNT_LIB = os.path.join(ROOT, "phosphorus_mk2_amd", "libphx_hip_count.so")
+FULL_JSON = os.path.join(ROOT, "bench_out", "bench_full.json")  # --full's record unless --full-json names another place
+OUTPUT_BUDGET = 64 << 20  # bytes of --dump-outputs in all
+
+
+def _at_least(lo):
+    def check(s):
+        v = int(s)
+        if v < lo:
+            raise argparse.ArgumentTypeError(f"{v} < {lo}")
+        return v
+    return check
 
 
 def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=3)
-    p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--steps", type=_at_least(1), default=3, help="timed frames")
+    p.add_argument("--warmup", type=_at_least(0), default=1, help="untimed frames before them")
+    p.add_argument("--full", action="store_true",
+                   help="measure everything beside `value` too: host-film and two-frames-in-flight passes, CPU baseline, instrumented pass, "
+                        "rooflines, secondary workloads (the --no-* / --one-sink options below trim it); writes the full record")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed frame's outputs to DIR/*.npy (film, ray counts; see the module docstring)")
     p.add_argument("--triangles", type=int, default=100000)
     p.add_argument("--width", type=int, default=1280)
     p.add_argument("--height", type=int, default=720)
@@ -78,15 +104,16 @@ def parse(argv=None):
     p.add_argument("--depth", type=int, default=9)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--samples-in-flight", type=int, default=0)
-    p.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline, the instrumented pass and the secondary workloads")
-    p.add_argument("--no-secondary", action="store_true", help="skip the Soup(1 M) and config-4 records")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline, the instrumented pass and the secondary workloads")
+    p.add_argument("--no-secondary", action="store_true", help="--full: skip the Soup(1 M) and config-4 records")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="length of the headline CPU baseline run")
     p.add_argument("--cpu-spp", type=int, default=16, help="samples per pixel rendered per tile visit in the CPU baseline")
     p.add_argument("--bvh-builder", choices=["auto", "host", "device"], default="auto",
                    help="auto (host binned SAH up to 2 M triangles, device LBVH above), host, device")
     p.add_argument("--force-dist", action="store_true", help="use torch.distributed + the film reduce even at N=1")
-    p.add_argument("--one-sink", action="store_true", help="time `value` only: no host-film pass, no two-frames-in-flight pass (profiling captures: one frame per run)")
-    p.add_argument("--full-json", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"), help="where the full record goes (the stdout line is the compact one)")
+    p.add_argument("--one-sink", action="store_true", help="--full: no host-film pass, no two-frames-in-flight pass (a plain run has neither)")
+    p.add_argument("--full-json", default=None,
+                   help=f"where the full record goes (the stdout line is the compact one); with --full the default is {os.path.relpath(FULL_JSON, ROOT)}")
     return p.parse_args(argv)
 
 
@@ -637,6 +664,30 @@ def write_full(full, path):
         return None
 
 
+def dump_outputs(out_dir, film, ray_counts, budget=OUTPUT_BUDGET):
+    """--dump-outputs: the last timed frame's film (float32) and ray counts (float64) as out_dir/<name>.npy, at most `budget` bytes in
+    all.  A larger film is replaced by a fixed sample of its pixels (seed 0, sorted indices), so two runs write the same pixels.
+    -> {name: path}"""
+    film = np.ascontiguousarray(film, np.float32)
+    arrays = {"ray_counts": np.asarray(ray_counts, np.float64)}
+    room = budget - 4096 - sum(a.nbytes for a in arrays.values())  # 4 KB: the .npy headers
+    if film.nbytes <= room:
+        arrays["film"] = film
+    else:
+        px = film.reshape(-1, film.shape[-1])
+        n = room // (px.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+        arrays["film_sample"] = px[idx]
+        arrays["film_sample_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= budget - 4096
+    os.makedirs(out_dir, exist_ok=True)
+    paths = {}
+    for name, a in arrays.items():
+        paths[name] = os.path.join(out_dir, name + ".npy")
+        np.save(paths[name], a)
+    return paths
+
+
 VALUE_DEFINITION = ("rays of all ranks / max-over-ranks wall time of K frames, ONE frame in flight; inputs (scene, BVH) and the film stay in HBM, "
                     "N > 1: one reduce(sum) of the film to rank 0 inside the bracket; value_host_film = the same frames through the host "
                     "film sink (PCIe, the reference's own start...join bracket); value_two_frames_in_flight = pipelined throughput")
@@ -721,10 +772,15 @@ def main(argv=None):
     if rank == 0:
         film_np = film.cpu().numpy()  # the last frame of the timed region, reduced onto this rank
 
+    # the last timed frame's ray counts for --dump-outputs, summed over the ranks (collectives: every rank takes part)
+    ray_counts = [st["rays_closest"], st["rays_shadow"], st["camera_samples"]]
+    if use_dist and args.dump_outputs:
+        ray_counts = [pdist.sum_over_ranks(c, red_dev) for c in ray_counts]
+
     # ---- `value_two_frames_in_flight`: a second device object renders alternate frames, the reduce is asynchronous ----------------
     value_two = None
     hbm_two = None
-    if not args.one_sink:
+    if args.full and not args.one_sink:
         dev2 = xpu.HipDevice.make(opts); dev2.preprocess(scene)
         devs, tile_sets = [dev, dev2], [tiles, xpu.Tiles.make(W, H, 32, rank, world)]
         films = [film] + [torch.zeros_like(film) for _ in range(3 if use_dist else 1)]  # N > 1: four in turn, a reduce may still read one
@@ -778,7 +834,7 @@ def main(argv=None):
 
     # ---- `value_host_film` (N = 1): the same frames through the host film sink ----------------------------------------------------
     value_host = None
-    if not use_dist and not args.one_sink:
+    if args.full and not use_dist and not args.one_sink:
         host = xpu.Film(W, H, 4)
         rays_o = 0
         for i in range(1 + args.steps):  # one untimed frame sizes the pinned staging buffer
@@ -809,7 +865,8 @@ def main(argv=None):
             "metric": "Mrays/sec (primary+secondary)", "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic", **({"rehearsal": "all ranks on GPU 0, gloo reduce: not a scaling result"} if rehearsal else {}),
-            "value_definition": VALUE_DEFINITION, "value_host_film": value_host, "value_two_frames_in_flight": value_two,
+            "value_definition": VALUE_DEFINITION,
+            **({"value_host_film": value_host, "value_two_frames_in_flight": value_two} if args.full else {}),
             "config": {"workload": f"Soup({args.triangles}, seed 1234) {W}x{H} {args.spp} spp depth {args.depth} pps 1, "
                                    "1 emissive quad, Lambert 0.73 (BASELINE.json configs[1])",
                        "tiles": "32x32, tile (tx, ty) -> rank (tx + 3 ty) % n_gpus",
@@ -823,7 +880,9 @@ def main(argv=None):
                        "film_mean": float(film_np[..., :3].mean()), "film_finite": bool(np.isfinite(film_np).all())},
         }
         assert out["n_gpus"] == args.gpus
-        if world == 1 and not use_dist and not args.no_cpu_baseline:
+        if not args.full:
+            pass  # a plain run reports `value` alone: CPU baseline, instrumented pass, rooflines and secondary workloads are --full's
+        elif world == 1 and not use_dist and not args.no_cpu_baseline:
             work = count_work(args.triangles, W, H, args.spp, args.bvh_builder)
             base, ref_visits = cpu_baseline(scene, args)
             out["cpu_baseline"] = base
@@ -861,7 +920,9 @@ def main(argv=None):
                                                          "rays_per_launch", "kernel_rays_per_s", "stream_GBps", "stream_frac_of_hbm_peak")},
                                    "note": "rank 0's share of the frame; the work-based fraction and the counter diagnostics are reported at N = 1"}
         out["config"]["kernel_ms_per_step"] = {**kernel_ms(acc, args.steps), "frame": acc["frame_ms"] / args.steps}
-        path = write_full(out, args.full_json)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, film_np, ray_counts)
+        path = write_full(out, args.full_json or (FULL_JSON if args.full else None))
         print(compact_line(out, path), flush=True)
     if use_dist:
         dist.barrier()

@@ -142,15 +142,64 @@ def test_render_makes_one_device_on_a_multi_gpu_box(monkeypatch):
     assert len(xpu.HipDevice.discover(xpu.Options(device_ordinal=2))) == 1 and made == [2]
 
 
-def test_reference_patch_applies():
+PATCH = os.path.join(ROOT, "integration", "reference.patch")
+PATCH_PREIMAGE = os.path.join(ROOT, "tests", "golden", "reference_patch_preimage.json")
+
+
+def parse_patch(path):
+    """unified diff -> {file: [(old start, old count, pre-image bytes)]}; the pre-image is the hunk's context and removed lines, each
+    with its newline, as they must stand in the unpatched file.  A hunk body is read by its header's counts, as patch(1) does, and
+    every line outside a hunk must be a header line: a body longer or shorter than its header fails here."""
+    import re
+    files, hunks, cur, old_left, new_left = {}, None, None, 0, 0
+    for line in open(path, "rb").read().split(b"\n")[:-1]:
+        if old_left or new_left:
+            tag = line[:1]
+            assert tag in (b" ", b"-", b"+"), line
+            if tag != b"+":
+                cur[2] += line[1:] + b"\n"; old_left -= 1
+            if tag != b"-":
+                new_left -= 1
+            assert old_left >= 0 and new_left >= 0, line
+        elif line.startswith(b"--- a/"):
+            hunks = files.setdefault(line[6:].decode(), [])
+        elif line.startswith(b"@@"):
+            m = re.match(rb"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+            cur = [int(m[1]), int(m[2] or 1), b""]
+            old_left, new_left = cur[1], int(m[4] or 1)
+            hunks.append(cur)
+        else:
+            assert line.startswith((b"diff ", b"+++ b/")), line
+    assert not (old_left or new_left), "the last hunk is cut short"
+    return {f: [tuple(h) for h in hs] for f, hs in files.items()}
+
+
+def test_reference_patch_applies(tmp_path):
     """integration/reference.patch (the maintainer's change list: xpu_t::discover, four mesh_t accessors, the CMake source list,
-    parsed_options_t::host_only) still applies to the reference tree — a dry run, nothing is written"""
+    parsed_options_t::host_only) still applies to the reference tree, exactly where its hunks say.  The reference does not ship with
+    this repository: tests/golden/reference_patch_preimage.json holds, for every hunk, the SHA-256 of the lines the reference has at
+    that place (tests/golden/make_reference_patch_preimage.py), and the patch's own pre-image must hash to it.  Then the patch is
+    dry-run against a tree that holds those pre-images at those lines: it must apply without offset or fuzz."""
+    import hashlib
+    import json
     import shutil
     import subprocess
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "src")) or not shutil.which("patch"):
-        pytest.skip("no reference tree on this box")
-    r = subprocess.run(["patch", "-p1", "--dry-run", "--batch", "-d", ref, "-i", os.path.join(ROOT, "integration", "reference.patch")],
-                       capture_output=True, text=True)
+    want = json.load(open(PATCH_PREIMAGE))["files"]
+    got = parse_patch(PATCH)
+    assert sorted(got) == sorted(want) and len(got) == 5
+    for f, hunks in got.items():
+        assert [(s, n) for s, n, _ in hunks] == [(h["start"], h["count"]) for h in want[f]["hunks"]], f
+        for (start, n, pre), h in zip(hunks, want[f]["hunks"]):
+            assert hashlib.sha256(pre).hexdigest() == h["sha256"], f"{f}: hunk at line {start} does not match the reference"
+    if not shutil.which("patch"):
+        return
+    for f, hunks in got.items():  # the reference's line count, its hunk lines where they lie, placeholders elsewhere
+        lines = [b"placeholder %d\n" % (i + 1) for i in range(want[f]["lines"])]
+        for start, n, pre in hunks:
+            lines[start - 1:start - 1 + n] = [l + b"\n" for l in pre.split(b"\n")[:-1]]
+        p = tmp_path / f
+        p.parent.mkdir(parents=True, exist_ok=True)
+        p.write_bytes(b"".join(lines))
+    r = subprocess.run(["patch", "-p1", "--dry-run", "--batch", "-d", str(tmp_path), "-i", PATCH], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.count("checking file") == 5
+    assert r.stdout.count("checking file") == 5 and "offset" not in r.stdout and "fuzz" not in r.stdout, r.stdout

@@ -239,3 +239,44 @@ def test_bench_refuses_more_ranks_than_gpus():
         assert r.returncode == 2 and "GPU(s) visible" in r.stderr and not r.stdout.strip()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True, timeout=300, env=dict(env, WORLD_SIZE="4"))
     assert r.returncode == 2 and "WORLD_SIZE=4" in r.stderr
+
+
+def test_plain_run_is_the_default_and_steps_are_checked():
+    """`bench.py --gpus 1 --steps K --warmup W` times `value` alone; everything else is behind --full.  --steps sets the timed frames
+    (at least one), --warmup the untimed ones before them"""
+    import pytest
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs, a.full_json) == (7, 2, False, None, None)
+    a = bench.parse(["--full", "--dump-outputs", "out", "--steps", "1", "--warmup", "0"])
+    assert a.full and a.dump_outputs == "out" and (a.steps, a.warmup) == (1, 0)
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_writes_the_film_or_a_fixed_sample_of_it_within_the_budget(tmp_path):
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    film = rng.random((96, 160, 4), dtype=np.float32)
+    counts = [123456789012, 98765432101, 138240]
+    paths = bench.dump_outputs(str(tmp_path / "small"), film, counts)
+    assert sorted(paths) == ["film", "ray_counts"]
+    got = np.load(paths["film"])
+    assert got.dtype == np.float32 and np.array_equal(got, film)
+    got = np.load(paths["ray_counts"])
+    assert got.dtype == np.float64 and got.tolist() == counts  # exact in float64
+    # a film larger than the budget: the same seeded sample of pixels every time, float32 pixels and float64 indices, within the budget
+    budget = 100_000
+    runs = [bench.dump_outputs(str(tmp_path / d), film, counts, budget=budget) for d in ("a", "b")]
+    assert sorted(runs[0]) == ["film_sample", "film_sample_index", "ray_counts"]
+    for p in runs:
+        assert sum(os.path.getsize(f) for f in p.values()) <= budget
+    s, i = np.load(runs[0]["film_sample"]), np.load(runs[0]["film_sample_index"])
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == (len(i), 4) and len(i) > 3000
+    assert np.all(np.diff(i) > 0) and np.array_equal(s, film.reshape(-1, 4)[i.astype(np.int64)])
+    assert np.array_equal(s, np.load(runs[1]["film_sample"])) and np.array_equal(i, np.load(runs[1]["film_sample_index"]))
+    # BASELINE's config-4 film (3840 x 2160 x 4 float32, 133 MB) fits the 64 MB budget only as a sample
+    big = bench.dump_outputs(str(tmp_path / "c4"), np.zeros((2160, 3840, 4), np.float32), counts)
+    assert "film_sample" in big and sum(os.path.getsize(f) for f in big.values()) <= 64 << 20

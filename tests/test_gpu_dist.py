@@ -62,7 +62,7 @@ def test_two_ranks_on_one_gpu_sum_to_the_one_process_film(tmp_path):
 
 
 @pytest.mark.timeout(600)
-def test_bench_multi_rank_path_rehearsed_on_one_gpu():
+def test_bench_multi_rank_path_rehearsed_on_one_gpu(tmp_path):
     """`python bench.py --gpus 2` itself — the launch decision, the torch.distributed.run child, tile shard by rank, zero-initialised
     device films, ONE reduce to rank 0 inside the bracket, max-over-ranks time, rays summed over ranks, one compact JSON line relayed
     from rank 0 — rehearsed with two ranks on this box's one GPU (PHX_BENCH_REHEARSAL=1: both ranks on GPU 0, the reduce on gloo).
@@ -71,10 +71,10 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu():
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT")}
-    common = ["--triangles", "3000", "--width", "160", "--height", "96", "--spp", "9", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--triangles", "3000", "--width", "160", "--height", "96", "--spp", "9", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     recs = {}
     for n in (1, 2):
-        full = os.path.join(ROOT, "gpurun_out", f"bench_rehearsal_{n}.json")
+        full = str(tmp_path / f"bench_rehearsal_{n}.json")
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full-json", full] + common, capture_output=True, text=True, timeout=300,
                            env=dict(env, PHX_BENCH_REHEARSAL="1") if n > 1 else env)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -95,6 +95,37 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu():
     assert d1["roofline"]["kernel"] == "k_trace" and d1["roofline"]["avg_launch_ms"] > 0 and d1["roofline"]["stream_GBps"] > 0
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_value_alone_and_dumps_the_last_frame(tmp_path):
+    """A plain `bench.py` run (no --full) measures `value` and nothing else, and --dump-outputs writes the last timed frame: the film
+    and its ray counts.  Same arguments, same outputs — run to run, and between one process and two rehearsed ranks (film reduced
+    onto rank 0, counts summed over the ranks)."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT", "PHX_BENCH_REHEARSAL")}
+    common = ["--triangles", "3000", "--width", "160", "--height", "96", "--spp", "9", "--steps", "2", "--warmup", "1"]
+    runs = []
+    for n, tag in ((1, "a"), (1, "b"), (2, "c")):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dump-outputs", str(d)] + common, capture_output=True, text=True,
+                           timeout=300, env=dict(env, PHX_BENCH_REHEARSAL="1") if n > 1 else env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        runs.append((line, np.load(d / "film.npy"), np.load(d / "ray_counts.npy")))
+        assert sorted(os.listdir(d)) == ["film.npy", "ray_counts.npy"]
+    for line, film, counts in runs:
+        assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 2 and line["warmup"] == 1
+        assert abs(line["value"] - line["config"]["rays_per_step"] / line["ms_per_step"] / 1e3) < 1e-4 * line["value"]
+        assert "value_two_frames_in_flight" not in line and "value_host_film" not in line and line["roofline"] is None and line["cpu_baseline"] is None
+        assert line["full_record"] is None  # no full record without --full
+        assert film.dtype == np.float32 and film.shape == (96, 160, 4) and counts.dtype == np.float64 and counts.shape == (3,)
+        # (the line carries 6 significant digits)
+        assert abs(counts[0] + counts[1] - line["config"]["rays_per_step"]) <= 1e-5 * line["config"]["rays_per_step"] and counts[2] == 160 * 96 * 9
+        assert film[..., :3].max() > 0.05 and abs(float(film[..., :3].mean()) - line["config"]["film_mean"]) <= 1e-5 * line["config"]["film_mean"]
+    (_, f0, c0), (_, f1, c1), (_, f2, c2) = runs
+    assert bits_equal(f0, f1) and bits_equal(f0, f2) and np.array_equal(c0, c1) and np.array_equal(c0, c2)
+
+
 @pytest.mark.timeout(300)
 def test_bench_launched_with_a_mismatched_world_fails():
     import subprocess
@@ -103,7 +134,7 @@ def test_bench_launched_with_a_mismatched_world_fails():
 
 
 @pytest.mark.timeout(600)
-def test_bench_rccl_path_at_world_one():
+def test_bench_rccl_path_at_world_one(tmp_path):
     """`bench.py --force-dist`: the N > 1 code with the REAL backend (nccl = RCCL) at world size 1 — process group on the device,
     zero-initialised device film, the synchronous film reduce inside the bracket, the asynchronous one in the two-frames-in-flight
     pass, max / sum over ranks on the device — is what one GPU can exercise of the RCCL path.  Same rays and film as the plain run."""
@@ -111,8 +142,8 @@ def test_bench_rccl_path_at_world_one():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "PHX_BENCH_REHEARSAL")}
     env["MASTER_ADDR"] = "127.0.0.1"; env["MASTER_PORT"] = str(29900 + (os.getpid() % 90))
-    common = ["--triangles", "3000", "--width", "160", "--height", "96", "--spp", "9", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-              "--full-json", os.path.join(ROOT, "gpurun_out", "bench_force_dist.json")]
+    common = ["--triangles", "3000", "--width", "160", "--height", "96", "--spp", "9", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--full-json", str(tmp_path / "bench_force_dist.json")]
     recs = []
     for extra in ([], ["--force-dist"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra, capture_output=True, text=True, timeout=300, env=env)

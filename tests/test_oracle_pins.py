@@ -111,19 +111,26 @@ def test_option_defaults_and_stream_size_match_reference_object_code(orc):
 
 
 def test_live_ref_subset_if_present(orc):
-    so = os.path.join(ROOT, "oracle", "_ref", "libphx_ref_subset.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    ref = C.CDLL(so)
+    """the reference's object code on the inputs of tests/golden/ref_live_vectors.npz (generator: tests/golden/make_ref_live_vectors.py):
+    its stored outputs always, and — where oracle/_ref is built — the live library, whose Fresnel term must reproduce them bit for bit
+    (RCPPS is an approximation whose bits differ between CPU models: the reciprocal is checked against 1 / x only, as it always was)"""
+    V = np.load(os.path.join(ROOT, "tests", "golden", "ref_live_vectors.npz"))
     rng = np.random.default_rng(7)
     cosi = rng.uniform(-1, 1, 4096).astype(np.float32); eta = rng.uniform(0.3, 3.0, 4096).astype(np.float32)
-    a = np.zeros(4096, np.float32); b = np.zeros(4096, np.float32)
-    ref.ref_fresnel_dielectric(4096, fp(cosi), fp(eta), fp(a))
+    x = rng.uniform(0.01, 100, 8).astype(np.float32)
+    assert bits_equal(cosi, V["cosi"]) and bits_equal(eta, V["eta"]) and bits_equal(x, V["rcp_in"])
+    a, y = V["fresnel"], V["rcp"]
+    so = os.path.join(ROOT, "oracle", "_ref", "libphx_ref_subset.so")
+    if os.path.exists(so):
+        ref = C.CDLL(so)
+        a = np.zeros(4096, np.float32); y = np.zeros(8, np.float32)
+        ref.ref_fresnel_dielectric(4096, fp(cosi), fp(eta), fp(a))
+        ref.ref_rcp8(fp(x), fp(y))
+        assert bits_equal(a, V["fresnel"])
+    b = np.zeros(4096, np.float32)
     orc.load().orc_fresnel_dielectric(4096, fp(cosi), fp(eta), fp(b))
     assert bits_equal(a, b)
     # the reference's RCPPS wrapper vs the oracle's approx mode: same instruction on the same CPU
-    x = rng.uniform(0.01, 100, 8).astype(np.float32); y = np.zeros(8, np.float32)
-    ref.ref_rcp8(fp(x), fp(y))
     assert np.allclose(y, 1.0 / x, rtol=4e-4)
 
 
