@@ -94,7 +94,11 @@ typedef struct phx_lobe {
   uint32_t fac_mode;
   float    fac_ior;
   float    pre_weight[3]; /* product of the constant weights ABOVE the hit-dependent factor in the closure tree */
-  uint32_t pad;
+  /* Image texture on the colour weight (texture_node.osl's Cout into the closure's Cs): 0 = none, k = phx_scene.textures[k - 1].  At every
+   * surface hit the lobe's weight is weight * texel (one fp32 multiply per channel), looked up at the hit's interpolated mesh UV; the
+   * per-hit factor above then applies to that product, (pre_weight * term) * (weight * texel), and a lobe whose weight comes out all
+   * zero is not there at that hit.  Not allowed on the lobes of emitters or of the environment material. */
+  uint32_t texture;
 } phx_lobe;
 enum { PHX_FAC_NONE = 0, PHX_FAC_MIX_B = 1, PHX_FAC_MIX_A = 2 };
 
@@ -125,6 +129,10 @@ typedef struct phx_mesh {
   uint32_t        flags;     /* PHX_MESH_* */
   uint32_t        num_sets;
   const phx_face_set* sets;
+  /* texture coordinates (mesh_t::uvs), 2 floats (s, t) each; per vertex when PHX_MESH_UV_PER_VERTEX, per face corner (3 f + k) otherwise.
+   * Read only when some lobe is textured; a mesh without UVs has st = (0, 0) at every hit (mesh.cpp:240-241). */
+  const float*    uvs;
+  uint32_t        num_uvs;
 } phx_mesh;
 enum { PHX_MESH_UV_PER_VERTEX = 1, PHX_MESH_NORMALS_PER_VERTEX = 2 }; /* mesh_t::flags_t, src/mesh.hpp:20-23 */
 
@@ -140,6 +148,20 @@ typedef struct phx_camera {
   uint32_t film_height;
 } phx_camera;
 
+/* An RGB image texture (texture_node.osl).  Texels are linear fp32 RGB, no colour transform.  Row 0 is the first scanline and holds
+ * t in [0, 1/height) (OIIO's convention).  At (s, t): x = s*W - 0.5, y = t*H - 0.5 and PHX_TEX_LINEAR blends the four texels around
+ * (floor(x), floor(y)) bilinearly; PHX_TEX_CLOSEST reads texel (floor(s*W), floor(t*H)).  Wrap modes per axis; under PHX_WRAP_BLACK a
+ * texel outside the image reads as 0.  A non-finite coordinate, or |s*W| or |t*H| above 2^24, reads black.  No MIP maps, no bicubic. */
+typedef struct phx_texture {
+  uint32_t     width, height; /* 1 .. 65536 each, at most 2^26 texels */
+  const float* texels;        /* width * height RGB triples, row-major, rows top to bottom */
+  uint32_t     filter;        /* PHX_TEX_* */
+  uint32_t     swrap, twrap;  /* PHX_WRAP_* */
+  uint32_t     reserved[3];
+} phx_texture;
+enum { PHX_TEX_LINEAR = 0, PHX_TEX_CLOSEST = 1 };
+enum { PHX_WRAP_PERIODIC = 0, PHX_WRAP_CLAMP = 1, PHX_WRAP_BLACK = 2 };
+
 typedef struct phx_scene {
   uint32_t            num_meshes;
   const phx_mesh*     meshes;
@@ -147,6 +169,8 @@ typedef struct phx_scene {
   const phx_material* materials;
   int32_t             environment_material; /* -1 = none (scene_t::environment, src/scene.cpp:126) */
   phx_camera          camera;
+  uint32_t            num_textures;  /* phx_lobe.texture indexes this table (1-based) */
+  const phx_texture*  textures;
 } phx_scene;
 
 /* ---- frame: frame_state_t {sampler, tiles, film} (src/state.hpp:18-31) --------------- */
@@ -287,6 +311,12 @@ int phx_dev_bsdf_f(phx_device* dev, uint32_t material, uint32_t n_items, const f
 int phx_dev_bsdf_sample(phx_device* dev, uint32_t material, uint32_t n_items, const float* n,
                         const float* wi, const float* u2, float* wo_out, float* f_out,
                         float* pdf_out, uint32_t* flags_out);
+
+/* The image lookup the shade kernel applies to a textured lobe, run on the device for texture `texture` (0-based index into
+ * phx_scene.textures of the preprocessed scene) at n coordinates st (s, t per item): rgb per item.  A parity hook like phx_dev_bsdf_f.
+ * The texture table is uploaded only when some lobe of the preprocessed scene is textured: for a scene without a textured lobe every
+ * call returns PHX_ERR_ARG, as does an index past the table. */
+int phx_dev_texture_lookup(phx_device* dev, uint32_t texture, uint32_t n, const float* st, float* rgb);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

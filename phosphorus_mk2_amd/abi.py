@@ -14,6 +14,8 @@ MAX_LOBES = 8
 FAC_NONE, FAC_MIX_B, FAC_MIX_A = 0, 1, 2
 BVH_AUTO, BVH_DEVICE_LBVH, BVH_HOST_SAH = 0, 1, 2
 MESH_UV_PER_VERTEX, MESH_NORMALS_PER_VERTEX = 1, 2
+TEX_LINEAR, TEX_CLOSEST = 0, 1
+WRAP_PERIODIC, WRAP_CLAMP, WRAP_BLACK = 0, 1, 2
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -33,7 +35,7 @@ class Lobe(C.Structure):
     _fields_ = [
         ("type", C.c_uint32), ("weight", C.c_float * 3), ("alpha", C.c_float), ("eta", C.c_float),
         ("xalpha", C.c_float), ("yalpha", C.c_float), ("refract", C.c_uint32), ("r", C.c_float),
-        ("fac_mode", C.c_uint32), ("fac_ior", C.c_float), ("pre_weight", C.c_float * 3), ("pad", C.c_uint32),
+        ("fac_mode", C.c_uint32), ("fac_ior", C.c_float), ("pre_weight", C.c_float * 3), ("texture", C.c_uint32),
     ]
 
 
@@ -52,7 +54,14 @@ class Mesh(C.Structure):
     _fields_ = [
         ("vertices", f32p), ("num_vertices", C.c_uint32), ("normals", f32p), ("num_normals", C.c_uint32),
         ("faces", u32p), ("num_faces", C.c_uint32), ("smooth", u8p), ("flags", C.c_uint32),
-        ("num_sets", C.c_uint32), ("sets", C.POINTER(FaceSet)),
+        ("num_sets", C.c_uint32), ("sets", C.POINTER(FaceSet)), ("uvs", f32p), ("num_uvs", C.c_uint32),
+    ]
+
+
+class Texture(C.Structure):
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32), ("texels", f32p), ("filter", C.c_uint32),
+        ("swrap", C.c_uint32), ("twrap", C.c_uint32), ("reserved", C.c_uint32 * 3),
     ]
 
 
@@ -67,6 +76,7 @@ class Scene(C.Structure):
     _fields_ = [
         ("num_meshes", C.c_uint32), ("meshes", C.POINTER(Mesh)), ("num_materials", C.c_uint32),
         ("materials", C.POINTER(Material)), ("environment_material", C.c_int32), ("camera", Camera),
+        ("num_textures", C.c_uint32), ("textures", C.POINTER(Texture)),
     ]
 
 
@@ -109,6 +119,7 @@ EXPORTS = [
     "phx_discover", "phx_dev_make", "phx_dev_preprocess", "phx_dev_start", "phx_dev_join", "phx_dev_destroy",
     "phx_last_error", "phx_dev_get_stats", "phx_tiles_make", "phx_tiles_next", "phx_tiles_count", "phx_tiles_reset",
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
+    "phx_dev_texture_lookup",
 ]
 
 
@@ -133,5 +144,6 @@ def declare(lib):
     lib.phx_dev_bsdf_f.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p]; lib.phx_dev_bsdf_f.restype = C.c_int
     lib.phx_dev_bsdf_sample.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, u32p]
     lib.phx_dev_bsdf_sample.restype = C.c_int
+    lib.phx_dev_texture_lookup.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p]; lib.phx_dev_texture_lookup.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

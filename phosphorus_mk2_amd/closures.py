@@ -27,7 +27,14 @@ closure for `closure * 0`).  ONE hit-dependent input is supported, the one the r
 `fresnel_dielectric_node.out` driving `mix_closure_node.fac` (Blender's glass node = mix(refraction, glossy, fresnel),
 plugins/blender/blender/shader.hpp:306-335).  It cannot be baked into a number, so the recipe records it: the closures under
 that mix carry `fac_mode` / `fac_ior` / `pre_weight` and the device (bsdf.h: material_at_hit) and the oracle evaluate the factor
-at every hit.  Other hit-dependent inputs (textures, noise, normal maps) cannot be expressed and raise.
+at every hit.  The second one is an image texture on a closure's colour: `texture_node.Cout` driving the `Cs` of a BSDF node
+(what the exporter emits for every Image Texture node, plugins/blender/blender/shader.hpp:363-410).
+  texture_node.osl                  Cout = texture(filename, u, v, "swrap", swrap, "twrap", twrap)
+The closure's lobe records the constant weight accumulated ABOVE that point in `weight` and the image in `texture` (k + 1 for
+entry k of the `textures` list handed to the baker: {filename, swrap, twrap}); the device multiplies the texel in at every hit.
+`swrap` / `twrap` "periodic" (the default), "clamp" and "black" are expressible; "mirror" and "default" raise, and so do blur
+and explicit s / t inputs (the lookup is at the mesh's UV).  A texture feeding anything but a BSDF node's Cs (a mix's fac, a
+roughness, emission, another texture) raises.  Other hit-dependent inputs (noise, normal maps, environment maps) raise.
 """
 import math
 
@@ -78,7 +85,21 @@ class Add:
         self.a, self.b = a, b
 
 
+class Tex:
+    """the output of a texture_node: a colour known only at the hit (the image at the hit's UV)"""
+    def __init__(self, spec):
+        self.spec = spec  # {"filename", "swrap", "twrap"}: abi.WRAP_* values
+
+
+class MulTex:
+    """closure * texel: the image multiplies the closure's colour weight at every hit"""
+    def __init__(self, tex, closure):
+        self.tex, self.closure = tex, closure
+
+
 def mul(weight, closure):
+    if isinstance(weight, Tex):
+        return None if closure is None else MulTex(weight, closure)
     w = _color(weight)
     if closure is None or not w.any():
         return None  # OSL: closure * 0 is the null closure
@@ -135,10 +156,26 @@ def fresnel_dielectric_node(IoR=1.45, **_):
     return Fac(IoR)
 
 
+WRAPS = {"periodic": abi.WRAP_PERIODIC, "clamp": abi.WRAP_CLAMP, "black": abi.WRAP_BLACK}
+
+
+def texture_node(filename="", swrap="periodic", twrap="periodic", sblur=0.0, tblur=0.0, **extra):
+    if extra:
+        raise ValueError(f"texture_node: inputs {sorted(extra)} cannot be expressed (the lookup is at the mesh's UV)")
+    if f32(sblur) != 0 or f32(tblur) != 0:
+        raise ValueError("texture_node: sblur / tblur are not supported")
+    for name, w in (("swrap", swrap), ("twrap", twrap)):
+        if w not in WRAPS:
+            raise ValueError(f"texture_node: {name} {w!r} is not supported (periodic, clamp, black)")
+    if not filename:
+        raise ValueError("texture_node without a filename")
+    return Tex({"filename": str(filename), "swrap": WRAPS[swrap], "twrap": WRAPS[twrap]})
+
+
 def mix_closure_node(A=None, B=None, fac=0.5, **_):
     if isinstance(fac, Fac):  # Cout = A * (1 - fac) + B * fac with fac evaluated per hit
         return add(MulFac(abi.FAC_MIX_A, fac, A) if A is not None else None, MulFac(abi.FAC_MIX_B, fac, B) if B is not None else None)
-    if not np.isscalar(fac):
+    if not np.isscalar(fac) or isinstance(fac, Tex):
         raise ValueError("mix_closure_node.fac is driven by a node this baker cannot express (hit-dependent)")
     fac = f32(fac)
     return add(mul(f32(f32(1) - fac), A), mul(fac, B))
@@ -149,37 +186,56 @@ def add_node(A=None, B=None, **_):
 
 
 NODES = {f.__name__: f for f in (diffuse_bsdf_node, glossy_bsdf_node, refraction_bsdf_node, sheen_bsdf_node, transparent_bsdf_node,
-                                 diffuse_emitter_node, background_node, mix_closure_node, add_node, fresnel_dielectric_node)}
-UNBAKEABLE = {"fresnel_node", "texture_node", "normal_map_node", "random_noise_2d_node", "random_noise_3d_node",
+                                 diffuse_emitter_node, background_node, mix_closure_node, add_node, fresnel_dielectric_node, texture_node)}
+# the nodes whose Cs a texture may drive: their closure's weight is Cs
+TEXTURABLE = {diffuse_bsdf_node, glossy_bsdf_node, refraction_bsdf_node, sheen_bsdf_node, transparent_bsdf_node}
+UNBAKEABLE = {"fresnel_node", "normal_map_node", "random_noise_2d_node", "random_noise_3d_node",
               "musgrave_noise_3d_node", "environment_node", "mix_color_node", "blackbody_node"}
 
 
 # ---- material.cpp:218-305 -------------------------------------------------------------------------------
-def flatten(tree):
+def flatten(tree, textures=None):
     """eval_closure: closure tree -> MaterialDesc (lobes in visiting order, e = last emission/background weight).  The tree is
     walked as material.cpp:218-305 walks it: MUL multiplies the weight down, ADD visits A then B.  A Fresnel-driven factor
     splits a closure's weight into the constant part above it (pre_weight), the factor itself (fac_mode, fac_ior) and the
-    constant part below it (weight): at a hit the weight is (pre_weight * term) * weight, the same order of multiplications."""
+    constant part below it (weight): at a hit the weight is (pre_weight * term) * weight, the same order of multiplications.
+    A texture on a closure's colour: the lobe keeps the weight accumulated above it and `texture` = k + 1, k the texture's entry in
+    `textures` (a list of {filename, swrap, twrap}, extended here by the ones not in it yet)."""
     lobes, state = [], {"e": (0.0, 0.0, 0.0), "emitter": False}
+    if textures is None:
+        textures = []
 
-    def visit(c, w, fac=None):
+    def texture_id(spec):
+        if spec not in textures:
+            textures.append(spec)
+        return textures.index(spec) + 1
+
+    def visit(c, w, fac=None, tex=0):
         # w: the constant weight accumulated so far BELOW the hit-dependent factor (or all of it when there is none);
         # fac = (mode, ior, pre): the factor met on the way down and the constant weight accumulated ABOVE it
         if c is None:
             return
         if isinstance(c, Mul):
-            visit(c.closure, (w * c.weight).astype(f32), fac)
+            visit(c.closure, (w * c.weight).astype(f32), fac, tex)
+        elif isinstance(c, MulTex):
+            if tex:
+                raise ValueError("a texture behind another texture on one closure is not supported")
+            visit(c.closure, w, fac, texture_id(c.tex.spec))
         elif isinstance(c, MulFac):
             if fac is not None:
                 raise ValueError("a Fresnel-driven mix below another one: two hit-dependent factors on one closure are not supported")
+            if tex:
+                raise ValueError("a Fresnel-driven mix below a texture is not supported")
             visit(c.closure, np.ones(3, f32), (c.mode, c.fac.ior, w))
         elif isinstance(c, Add):
-            visit(c.a, w, fac)
-            visit(c.b, w, fac)
+            visit(c.a, w, fac, tex)
+            visit(c.b, w, fac, tex)
         else:
             if c.cid in (abi.LOBE_EMISSIVE, abi.LOBE_BACKGROUND):
                 if fac is not None:
                     raise ValueError("emission under a Fresnel-driven mix is not supported")
+                if tex:
+                    raise ValueError("textured emission is not supported")
                 state["e"] = tuple(float(x) for x in w)  # assignment: a later emission overwrites an earlier one
                 state["emitter"] = state["emitter"] or c.cid == abi.LOBE_EMISSIVE  # material.cpp:205-211
                 return
@@ -191,20 +247,21 @@ def flatten(tree):
                 extra = {"fac_mode": int(fac[0]), "fac_ior": float(fac[1]), "pre_weight": tuple(float(x) for x in fac[2])}
             lobes.append(LobeDesc(c.cid, tuple(float(x) for x in w), alpha=float(p.get("alpha", 0.0)), eta=float(p.get("eta", 0.0)),
                                   xalpha=float(p.get("xalpha", 0.0)), yalpha=float(p.get("yalpha", 0.0)), refract=int(p.get("refract", 0)),
-                                  r=float(p.get("r", 0.0)), **extra))
+                                  r=float(p.get("r", 0.0)), texture=tex, **extra))
     visit(tree, np.ones(3, f32))
     if len(lobes) > abi.MAX_LOBES:
         raise ValueError(f"{len(lobes)} lobes: bsdf_t holds at most {abi.MAX_LOBES} (src/bsdf.hpp:9)")
     return MaterialDesc(lobes=lobes, emission=state["e"], is_emitter=state["emitter"])
 
 
-def bake_material(desc):
-    """`desc`: one entry of the reference's YAML `materials:` map (already parsed, e.g. by yaml.safe_load)."""
+def bake_material(desc, textures=None):
+    """`desc`: one entry of the reference's YAML `materials:` map (already parsed, e.g. by yaml.safe_load).  `textures`: the scene's
+    list of texture specs {filename, swrap, twrap}, which the material's texture_nodes are added to (lobe.texture = index + 1)."""
     layers, order = {}, []
     for sh in desc["shaders"]:
         name, layer = sh["name"], sh["layer"]
         if name in UNBAKEABLE:
-            raise ValueError(f"shader {name!r} depends on the hit (texture / noise / view direction): not a constant closure recipe")
+            raise ValueError(f"shader {name!r} depends on the hit (noise / view direction / normal map): not a closure recipe this baker can express")
         if name not in NODES:
             raise ValueError(f"unknown shader {name!r}")
         params = {}
@@ -218,6 +275,8 @@ def bake_material(desc):
                 params[p["name"]] = str(p["value"])
             else:
                 raise ValueError("Unknown parameter type: " + t)  # material.hpp:79
+        if NODES[name] is texture_node:
+            texture_node(**params)  # its parameters are checked whether or not the node is connected (a texture without an image raises)
         layers[layer] = (NODES[name], params)
         order.append(layer)
     edges = {}
@@ -232,12 +291,15 @@ def bake_material(desc):
             for slot, src_layer, src_slot in edges.get(layer, []):
                 if src_slot not in ("Cout", "out") or (src_slot == "out" and layers[src_layer][0] is not fresnel_dielectric_node):
                     raise ValueError(f"connection from {src_layer}.{src_slot}: only closure outputs (Cout) and fresnel_dielectric_node.out can be expressed")
+                if layers[src_layer][0] is texture_node and (slot != "Cs" or fn not in TEXTURABLE):
+                    raise ValueError(f"texture {src_layer}.Cout into {layer}.{slot}: a texture can drive only the Cs of a BSDF node")
                 args[slot] = evaluate(src_layer)
             cache[layer] = fn(**args)
         return cache[layer]
-    return flatten(evaluate(order[-1]))
+    return flatten(evaluate(order[-1]), textures)
 
 
-def bake_materials(yaml_materials):
-    """name -> MaterialDesc for a whole `materials:` map; ids follow insertion order (scene_t::add, src/scene.cpp:84-90)."""
-    return {name: bake_material(d) for name, d in yaml_materials.items()}
+def bake_materials(yaml_materials, textures=None):
+    """name -> MaterialDesc for a whole `materials:` map; ids follow insertion order (scene_t::add, src/scene.cpp:84-90).  The
+    texture specs the materials use are collected in `textures` (see bake_material)."""
+    return {name: bake_material(d, textures) for name, d in yaml_materials.items()}

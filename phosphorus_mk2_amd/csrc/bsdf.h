@@ -39,7 +39,7 @@ struct DevMaterial {
   float ex, ey, ez;    // hits.e
   float sheen_L5;      // L(0.5, r) of the first sheen lobe of the material table (sheen.hpp:57 static)
   uint32_t per_hit;    // some lobe's weight depends on the hit (fac_mode != 0)
-  uint32_t pad;
+  uint32_t tex_lobes;  // bit k: lobe k's weight is multiplied by an image texel at the hit (DevScene::lobe_tex names the texture); 0 = none
   DevLobe lobes[8];
 };
 
@@ -143,6 +143,67 @@ PHX_HD bool lobe_weight_at_hit(const LobeT& l, const v3& n, const v3& view, v3& 
     if (w.x == 0.0f && w.y == 0.0f && w.z == 0.0f) return false;
   }
   return true;
+}
+
+// ---- image textures (phx_texture; the lookup of k_shade_g<.., TEX> and of phx_dev_texture_lookup) -----------------------------
+enum { TEX_LINEAR = 0, TEX_CLOSEST = 1, WRAP_PERIODIC = 0, WRAP_CLAMP = 1, WRAP_BLACK = 2 };  // PHX_TEX_*, PHX_WRAP_*
+struct DevTexture { uint32_t offset /* first texel in the scene's texel buffer */, width, height, modes /* filter | swrap << 8 | twrap << 16 */; };
+// What a lobe's texture lookup needs of its hit: the scene's tables, this material's row of lobe_tex (texture + 1 per lobe) and the hit's (s, t).
+struct TexHit { const DevTexture* textures; const float4* texels; const uint32_t* lobe_tex; float s, t; };
+
+// texel index of i on an axis of n texels; BLACK: `out` is set for an index outside the image (nothing is read then)
+PHX_HD int tex_wrap(int i, int n, uint32_t mode, bool& out) {
+  if (mode == WRAP_PERIODIC) { const int r = i % n; return r < 0 ? r + n : r; }
+  if (mode == WRAP_CLAMP) return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
+  if (i < 0 || i > n - 1) { out = true; return 0; }
+  return i;
+}
+PHX_HD v3 tex_texel(const float4* texels, const DevTexture& T, int i, int j) {
+  bool out = false;
+  const int x = tex_wrap(i, (int)T.width, (T.modes >> 8) & 0xffu, out), y = tex_wrap(j, (int)T.height, (T.modes >> 16) & 0xffu, out);
+  if (out) return v3(0.0f);
+  const float4 c = texels[T.offset + (uint32_t)y * T.width + (uint32_t)x];  // one 16-byte load per texel
+  return v3(c.x, c.y, c.z);
+}
+// OIIO's texel-centre convention (row 0 holds t in [0, 1/H)); no MIP level, no bicubic.  |s*W|, |t*H| <= 2^24 keeps every index an exact
+// int; anything else (NaN, inf, far away) reads black before an address is formed.
+PHX_HD v3 tex_lookup(const DevTexture* textures, const float4* texels, uint32_t tex, float s, float t) {
+  const DevTexture T = textures[tex];
+  const float sw = s * (float)T.width, th = t * (float)T.height;
+  if (!(fabsf(sw) <= 16777216.0f) || !(fabsf(th) <= 16777216.0f)) return v3(0.0f);
+  if ((T.modes & 0xffu) == TEX_CLOSEST) return tex_texel(texels, T, (int)floorf(sw), (int)floorf(th));
+  const float x = sw - 0.5f, y = th - 0.5f;
+  const float x0 = floorf(x), y0 = floorf(y);
+  const float fx = x - x0, fy = y - y0;
+  const int i = (int)x0, j = (int)y0;
+  const v3 t00 = tex_texel(texels, T, i, j), t10 = tex_texel(texels, T, i + 1, j);
+  const v3 t01 = tex_texel(texels, T, i, j + 1), t11 = tex_texel(texels, T, i + 1, j + 1);
+  const v3 c(t00.x + fx * (t10.x - t00.x), t00.y + fx * (t10.y - t00.y), t00.z + fx * (t10.z - t00.z));
+  const v3 d(t01.x + fx * (t11.x - t01.x), t01.y + fx * (t11.y - t01.y), t01.z + fx * (t11.z - t01.z));
+  return v3(c.x + fy * (d.x - c.x), c.y + fy * (d.y - c.y), c.z + fy * (d.z - c.z));
+}
+// lobe_weight_at_hit for lobe i of material m, with the image texture of a textured lobe (TEX): weight * texel first, then the per-hit
+// factor on that product, (pre * term) * (weight * texel); a textured lobe whose weight comes out all zero is not there at the hit.
+// TEX = false is lobe_weight_at_hit itself.
+template <bool PERHIT, bool TEX, typename MatT, typename LobeT>
+PHX_HD bool lobe_weight_of(const MatT& m, uint32_t i, const LobeT& l, const v3& n, const v3& view, v3& w, const TexHit& th) {
+  if constexpr (!TEX) {
+    return lobe_weight_at_hit<PERHIT>(l, n, view, w);
+  } else {
+    w = v3(l.wx, l.wy, l.wz);
+    const bool textured = ((m.tex_lobes >> i) & 1u) != 0u;
+    if (textured) {
+      const v3 c = tex_lookup(th.textures, th.texels, th.lobe_tex[i] - 1u, th.s, th.t);
+      w = v3(l.wx * c.x, l.wy * c.y, l.wz * c.z);
+    }
+    if (PERHIT && l.fac_mode != 0u) {
+      const float fac = fresnel_mix_factor(l.fac_ior, n, view);
+      const float term = l.fac_mode == 1u ? fac : 1.0f - fac;
+      w = v3((l.px * term) * w.x, (l.py * term) * w.y, (l.pz * term) * w.z);
+      if (w.x == 0.0f && w.y == 0.0f && w.z == 0.0f) return false;
+    }
+    return !(textured && w.x == 0.0f && w.y == 0.0f && w.z == 0.0f);
+  }
 }
 
 // ---- GGX ---------------------------------------------------------------------------------------
@@ -336,8 +397,8 @@ PHX_HD float lobe_eval(const LobeT& p, const v3& n, const Frame& fr, const v3& w
 // The tangent frame of the hit is the caller's (one per hit, shared with bsdf_sample).  wo = hits.wi (the view direction).
 // MatT: DevMaterial, or the same struct in the constant address space (PHX_CONST_MAT: a wave-uniform address is then read through the
 // scalar cache into SGPRs — k_shade_g's material-uniform waves).
-template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, typename MatT>
-PHX_HD v3 bsdf_f(const MatT& m, const v3& n, const Frame& fr, const v3& wi, const v3& wo) {
+template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, bool TEX = false, typename MatT>
+PHX_HD v3 bsdf_f(const MatT& m, const v3& n, const Frame& fr, const v3& wi, const v3& wo, const TexHit& th = TexHit{}) {
   v3 out(0.0f);
   if (m.num_lobes == 0) return out;
   const float atl = dot(n, wi);
@@ -347,7 +408,7 @@ PHX_HD v3 bsdf_f(const MatT& m, const v3& n, const Frame& fr, const v3& wi, cons
   for (uint32_t i = 0; i < nl; ++i) {
     const auto& p = m.lobes[MAXL == 1 ? 0u : i];
     v3 w;
-    if (!lobe_weight_at_hit<PERHIT>(p, n, wo, w)) continue;
+    if (!lobe_weight_of<PERHIT, TEX>(m, MAXL == 1 ? 0u : i, p, n, wo, w, th)) continue;
     if ((reflect && (p.flags & B_REFLECT)) || (!reflect && (p.flags & B_TRANSMIT))) {
       float ignored;
       v3 wi_ = wi, wo_ = wo;
@@ -365,15 +426,16 @@ PHX_HD v3 bsdf_f(const MatT& m, const v3& n, const v3& wi, const v3& wo) { retur
 // bsdf_t::sample, src/bsdf.cpp:133-248.  Returns f (already weighted); pdf == 0 terminates.  wi = hits.wi (the view direction).
 // PERHIT: the lobes of the hit are the baked lobes whose resolved weight is not all zero, in table order (lobe_weight_at_hit):
 // `keep` has a bit per baked lobe, `lobes` counts them, and the sampled index picks the index-th KEPT lobe.
-template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, typename MatT>
-PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, float u2, const v3& wi, v3& wo, float& pdf, uint32_t& sample_flags) {
+template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, bool TEX = false, typename MatT>
+PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, float u2, const v3& wi, v3& wo, float& pdf, uint32_t& sample_flags,
+                      const TexHit& th = TexHit{}) {
   pdf = 0.0f; sample_flags = 0; wo = v3(0.0f);
   uint32_t keep = 0xffu, lobes = MAXL == 1 ? (m.num_lobes ? 1u : 0u) : m.num_lobes;
-  if (PERHIT && m.per_hit) {
+  if ((PERHIT && m.per_hit) || (TEX && m.tex_lobes)) {
     keep = 0u; lobes = 0u;
     for (uint32_t i = 0; i < m.num_lobes; ++i) {
       v3 w;
-      if (lobe_weight_at_hit<true>(m.lobes[i], n, wi, w)) { keep |= 1u << i; ++lobes; }
+      if (TEX ? lobe_weight_of<PERHIT, TEX>(m, i, m.lobes[i], n, wi, w, th) : lobe_weight_at_hit<true>(m.lobes[i], n, wi, w)) { keep |= 1u << i; ++lobes; }
     }
   }
   if (lobes == 0) return v3(0.0f);
@@ -383,7 +445,7 @@ PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, flo
   if (MAXL == 1) index = 0;  // what the two lines above compute for lobes == 1 and u1 in [0, 1)
   const float u = fminf(u1 * fl - (float)index, 1.0f - FLT_EPSILON);
   uint32_t chosen = index;  // position of the index-th kept lobe in the baked table
-  if (PERHIT && m.per_hit) {
+  if ((PERHIT && m.per_hit) || (TEX && m.tex_lobes)) {
     uint32_t seen = 0;
     for (uint32_t i = 0; i < m.num_lobes; ++i)
       if (keep & (1u << i)) { if (seen == index) chosen = i; ++seen; }
@@ -476,7 +538,7 @@ PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, flo
   if (!pdf_set) pdf = 0.0f;
   if (pdf == 0.0f) return v3(0.0f);
   v3 pw;
-  (void)lobe_weight_at_hit<PERHIT>(p, n, wi, pw);
+  (void)lobe_weight_of<PERHIT, TEX>(m, MAXL == 1 ? 0u : chosen, p, n, wi, pw, th);
   v3 result = v3(res) * pw;
   int matched = 1;
 #pragma nounroll
@@ -490,7 +552,7 @@ PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, flo
         if (!DIFFUSE_ONLY) { PHX_PIN_V3(wi_); PHX_PIN_V3(wo_); }
         const float e = lobe_eval<DIFFUSE_ONLY>(q, n, fr, wi_, wo_, m.sheen_L5, lobe_pdf);
         v3 qw;
-        (void)lobe_weight_at_hit<PERHIT>(q, n, wi, qw);
+        (void)lobe_weight_of<PERHIT, TEX>(m, i, q, n, wi, qw, th);
         result = result + v3(e) * qw;
         pdf += lobe_pdf;
         ++matched;

@@ -94,8 +94,10 @@ struct phx_device {
   // scene
   DevBuf<PoolElem> d_pool; DevBuf<uint32_t> d_prim_material; DevBuf<float> d_elem_normals; DevBuf<float4> d_elem_shade; DevBuf<uint2> d_spill;
   DevBuf<DevMaterial> d_materials; DevBuf<DevMatLite> d_mat_lite; DevBuf<DevLight> d_lights; DevBuf<DevLightTri> d_light_tris;
+  // image textures: held only while the preprocessed scene has a textured lobe
+  DevBuf<float2> d_elem_uv; DevBuf<DevTexture> d_textures; DevBuf<float4> d_texels; DevBuf<uint32_t> d_lobe_tex; DevBuf<DevTexScene> d_tex_scene;
   DevScene scene{};
-  uint32_t num_materials = 0;
+  uint32_t num_materials = 0, num_textures = 0;
   uint64_t bvh_nodes = 0, bvh_bytes = 0, num_triangles = 0;
   double preprocess_ms = 0, bvh_build_ms = 0;
 
@@ -160,7 +162,8 @@ struct phx_device {
   uint64_t device_bytes() const {
     uint64_t b = d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
                  d_lights.bytes() + d_light_tris.bytes() + hit.bytes() + so.bytes() + sd.bytes() + sc.bytes() + pr.bytes() + pn.bytes() +
-                 counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes();
+                 counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
+                 d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes();
     for (int q = 0; q < 2; ++q) b += ro[q].bytes() + rd[q].bytes() + qs[q].bytes();
     return b;
   }
@@ -197,8 +200,9 @@ float roughness_to_alpha(float roughness) {
   return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
 }
 
-int bake_material(const phx_material& m, float sheen_L5, DevMaterial& out) {
+int bake_material(const phx_material& m, float sheen_L5, DevMaterial& out, uint32_t* lobe_tex /* 8: texture + 1 per baked lobe */) {
   std::memset(&out, 0, sizeof(out));
+  for (int k = 0; k < PHX_MAX_LOBES; ++k) lobe_tex[k] = 0;
   out.is_emitter = m.is_emitter; out.ex = m.emission[0]; out.ey = m.emission[1]; out.ez = m.emission[2];
   out.sheen_L5 = sheen_L5;
   if (m.num_lobes > PHX_MAX_LOBES) return 1;
@@ -210,6 +214,7 @@ int bake_material(const phx_material& m, float sheen_L5, DevMaterial& out) {
     l.fac_mode = s.fac_mode; l.fac_ior = s.fac_ior; l.px = s.pre_weight[0]; l.py = s.pre_weight[1]; l.pz = s.pre_weight[2];
     if (s.fac_mode > PHX_FAC_MIX_A) return 1;
     if (s.fac_mode != PHX_FAC_NONE) out.per_hit = 1;
+    if (s.texture) { out.tex_lobes |= 1u << k; lobe_tex[k] = s.texture; }  // (validated by the caller)
     switch (s.type) {
       case PHX_LOBE_DIFFUSE: l.flags = B_REFLECT | B_DIFFUSE; break;
       case PHX_LOBE_OREN_NAYAR: {  // oren_nayar_t::precompute, params.hpp:36-43
@@ -321,8 +326,36 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
   const auto t_pre0 = std::chrono::steady_clock::now();
 
+  // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
+  // non-emitting materials may carry one (textured emission is not supported)
+  if (s->num_textures && !s->textures) return fail(PHX_ERR_ARG, "scene with textures but a null texture table");
+  uint64_t total_texels = 0;
+  for (uint32_t t = 0; t < s->num_textures; ++t) {
+    const phx_texture& T = s->textures[t];
+    if (T.width == 0 || T.height == 0) return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " has zero size");
+    if (T.width > 65536u || T.height > 65536u || (uint64_t)T.width * T.height > (1ull << 26))
+      return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " too large (at most 65536 x 65536 and 2^26 texels)");
+    if (!T.texels) return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " without texels");
+    if (T.filter > PHX_TEX_CLOSEST || T.swrap > PHX_WRAP_BLACK || T.twrap > PHX_WRAP_BLACK) return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " with an unknown filter or wrap mode");
+    total_texels += (uint64_t)T.width * T.height;
+  }
+  if (total_texels > (1ull << 30)) return fail(PHX_ERR_ARG, "textures too large (at most 2^30 texels in all)");
+  bool any_tex = false;
+  for (uint32_t i = 0; i < s->num_materials; ++i) {
+    const phx_material& m = s->materials[i];
+    for (uint32_t k = 0; k < m.num_lobes && k < PHX_MAX_LOBES; ++k) {
+      const uint32_t t = m.lobes[k].texture;
+      if (!t) continue;
+      if (t > s->num_textures) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": lobe texture index out of range");
+      if (m.is_emitter || (int32_t)i == s->environment_material || m.lobes[k].type == PHX_LOBE_EMISSIVE || m.lobes[k].type == PHX_LOBE_BACKGROUND)
+        return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": textures on emitters / the environment are not supported");
+      any_tex = true;
+    }
+  }
+
   // triangles in scene_t::triangles() order: mesh order x face-set order (scene.cpp:58-62, mesh.cpp:118-128)
   std::vector<float> abc; std::vector<uint32_t> prim_material; std::vector<float> prim_normals;
+  std::vector<float2> prim_uv;  // any_tex: 3 corner UVs per primitive
   std::vector<DevLight> lights; std::vector<DevLightTri> light_tris;
   bool any_smooth = false;
   for (uint32_t mi = 0; mi < s->num_meshes; ++mi) {
@@ -331,7 +364,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   }
   for (uint32_t mi = 0; mi < s->num_meshes; ++mi) {
     const phx_mesh& m = s->meshes[mi];
-    if (!m.vertices || !m.faces || (m.num_sets && !m.sets)) return fail(PHX_ERR_ARG, "mesh with null arrays");
+    if (!m.vertices || !m.faces || (m.num_sets && !m.sets) || (any_tex && m.num_uvs && !m.uvs)) return fail(PHX_ERR_ARG, "mesh with null arrays");
     for (uint32_t si = 0; si < m.num_sets; ++si) {
       const phx_face_set& fs = m.sets[si];
       if (fs.material >= s->num_materials) return fail(PHX_ERR_ARG, "face set material out of range");
@@ -357,6 +390,18 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
           }
           prim_normals.insert(prim_normals.end(), nn, nn + 9);
         }
+        if (any_tex) {  // mesh_t::shading_parameters (mesh.cpp:239-257): UV indices per vertex or per face corner, like the normals; no UVs: (0, 0)
+          float2 uv[3] = {make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)};
+          if (m.num_uvs) {
+            const bool per_vertex = (m.flags & PHX_MESH_UV_PER_VERTEX) != 0;
+            const uint32_t ui[3] = {per_vertex ? ia : 3 * f, per_vertex ? ib : 3 * f + 1, per_vertex ? ic : 3 * f + 2};
+            for (int c = 0; c < 3; ++c) {
+              if (ui[c] >= m.num_uvs) return fail(PHX_ERR_ARG, "uv index out of range");
+              uv[c] = make_float2(m.uvs[2 * (size_t)ui[c]], m.uvs[2 * (size_t)ui[c] + 1]);
+            }
+          }
+          prim_uv.insert(prim_uv.end(), uv, uv + 3);
+        }
         if (emitter) {  // mesh_t::preprocess -> light_t::make_area (mesh.cpp:108-116), area_light_t (light.cpp:10-45)
           const v3 ab(b[0] - a[0], b[1] - a[1], b[2] - a[2]), ac(c[0] - a[0], c[1] - a[1], c[2] - a[2]);
           const v3 gn = normalize_inplace(cross(ab, ac));  // the flat face's normal as k_shade's shading_normal would compute it per sample
@@ -378,8 +423,9 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     for (uint32_t k = 0; k < s->materials[i].num_lobes && k < PHX_MAX_LOBES; ++k)
       if (s->materials[i].lobes[k].type == PHX_LOBE_SHEEN) { L5 = sheen_L(0.5f, s->materials[i].lobes[k].r); have = true; break; }
   std::vector<DevMaterial> mats(s->num_materials);
+  std::vector<uint32_t> lobe_tex(8 * (size_t)s->num_materials);
   for (uint32_t i = 0; i < s->num_materials; ++i)
-    if (bake_material(s->materials[i], L5, mats[i])) return fail(PHX_ERR_ARG, "material with an unknown closure id");
+    if (bake_material(s->materials[i], L5, mats[i], lobe_tex.data() + 8 * (size_t)i)) return fail(PHX_ERR_ARG, "material with an unknown closure id");
 
   {  // per light: the pick pdf and the emission of its material, as k_shade evaluated them per sample until round 2
     const float nlf = (float)lights.size();
@@ -470,13 +516,36 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   } else {
     d->d_elem_normals.release();
   }
+  if (any_tex) {
+    // corner UVs by POOL ELEMENT, like the normals; every texture's texels as float4 (one 16-byte load per texel) behind a small table
+    DevBuf<float2> d_prim_uv;
+    if ((rc = d_prim_uv.upload(prim_uv))) return rc;
+    if ((rc = d->d_elem_uv.alloc(3 * bvh_elems))) return rc;
+    launch_permute_uvs(d->stream, d_prim_uv.p, d_elem_of_prim.p, d->d_elem_uv.p, ntri);
+    HIPCHK(hipGetLastError());
+    std::vector<DevTexture> tabs(s->num_textures);
+    std::vector<float4> texels((size_t)total_texels);
+    uint32_t off = 0;
+    for (uint32_t t = 0; t < s->num_textures; ++t) {
+      const phx_texture& T = s->textures[t];
+      const uint32_t nt = T.width * T.height;
+      tabs[t] = DevTexture{off, T.width, T.height, T.filter | (T.swrap << 8) | (T.twrap << 16)};
+      for (uint32_t k = 0; k < nt; ++k) texels[off + k] = make_float4(T.texels[3 * (size_t)k], T.texels[3 * (size_t)k + 1], T.texels[3 * (size_t)k + 2], 0.0f);
+      off += nt;
+    }
+    if ((rc = d->d_textures.upload(tabs)) || (rc = d->d_texels.upload(texels)) || (rc = d->d_lobe_tex.upload(lobe_tex))) return rc;
+    const std::vector<DevTexScene> ts{DevTexScene{d->d_elem_uv.p, d->d_textures.p, d->d_texels.p, d->d_lobe_tex.p}};
+    if ((rc = d->d_tex_scene.upload(ts))) return rc;
+    HIPCHK(hipStreamSynchronize(d->stream));  // d_prim_uv goes out of scope
+  } else {
+    d->d_elem_uv.release(); d->d_textures.release(); d->d_texels.release(); d->d_lobe_tex.release(); d->d_tex_scene.release();
+  }
   HIPCHK(hipStreamSynchronize(d->stream));  // d_elem_of_prim (and the normals in primitive order) go out of scope below
 
   DevScene& sc = d->scene;
   sc.pool = reinterpret_cast<const uint32_t*>(d->d_pool.p);
   sc.tris = reinterpret_cast<const TriRec*>(d->d_pool.p);
   sc.grid = bvh_grid;
-  sc.prim_material = d->d_prim_material.p;
   sc.elem_normals = any_smooth ? d->d_elem_normals.p : nullptr;
   sc.elem_shade = d->d_elem_shade.p;
   sc.materials = d->d_materials.p;
@@ -488,6 +557,8 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   sc.ratio = (float)s->camera.film_width / (float)s->camera.film_height;
   sc.width = s->camera.film_width; sc.height = s->camera.film_height;
   sc.aperture_radius = s->camera.aperture_radius; sc.focal_distance = s->camera.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
+  sc.any_tex = any_tex ? 1u : 0u;
+  sc.tex = any_tex ? d->d_tex_scene.p : nullptr;
   sc.max_depth = d->opt.path_depth;
   sc.stack_levels = bvh_depth;
   sc.num_elems = (uint32_t)bvh_elems;
@@ -495,7 +566,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, d->hip_device));
     sc.num_cus = (uint32_t)prop.multiProcessorCount;
   }
-  sc.diffuse_only = 1;
+  sc.diffuse_only = any_tex ? 0 : 1;  // textured lobes are shaded by k_shade_g<.., TEX> only
   for (auto& m : mats) { if (m.per_hit) sc.diffuse_only = 0; for (uint32_t k = 0; k < m.num_lobes; ++k) if (m.lobes[k].type != L_DIFFUSE) sc.diffuse_only = 0; }
   sc.mat_lite = nullptr;
   sc.any_per_hit = 0;
@@ -516,6 +587,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     }
   }
   d->num_materials = s->num_materials;
+  d->num_textures = any_tex ? s->num_textures : 0;
   d->bvh_nodes = bvh_node_count;
   d->bvh_bytes = bvh_elems * sizeof(PoolElem);
   d->bvh_build_ms = std::chrono::duration<double, std::milli>(t_bvh1 - t_bvh0).count();
@@ -589,7 +661,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 0: return sizeof(phx_options); case 1: return sizeof(phx_lobe); case 2: return sizeof(phx_material);
     case 3: return sizeof(phx_face_set); case 4: return sizeof(phx_mesh); case 5: return sizeof(phx_camera);
     case 6: return sizeof(phx_scene); case 7: return sizeof(phx_tile); case 8: return sizeof(phx_frame);
-    case 9: return sizeof(phx_stats);
+    case 9: return sizeof(phx_stats); case 10: return sizeof(phx_texture);
     default: return 0;
   }
 }
@@ -708,6 +780,23 @@ static int dev_bsdf_sample_impl(phx_device* d, uint32_t material, uint32_t n, co
   HIPCHK(hipMemcpy(flags, fl.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return PHX_OK;
 }
+
+static int dev_texture_lookup_impl(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) {
+  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "texture_lookup before preprocess");
+  if (texture >= d->num_textures) return fail(PHX_ERR_ARG, "texture out of range (textures are kept only for scenes with a textured lobe)");
+  if (n == 0) return PHX_OK;
+  if (!st || !rgb) return fail(PHX_ERR_ARG, "texture_lookup: null argument");
+  DeviceScope on(d->hip_device);
+  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+  DevBuf<float> a, o; int rc;
+  if ((rc = kat_upload(st, 2 * (size_t)n, a)) || (rc = o.alloc(3 * (size_t)n))) return rc;
+  launch_texture_lookup(d->stream, d->d_textures.p, d->d_texels.p, texture, n, a.p, o.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(rgb, o.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return PHX_OK;
+}
+int phx_dev_texture_lookup(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) { return guarded([&]() { return dev_texture_lookup_impl(d, texture, n, st, rgb); }); }
 
 int phx_dev_copy_bvh(phx_device* d, void* out, uint64_t capacity, uint64_t* bytes, float* grid6) {
   if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "copy_bvh before preprocess");

@@ -27,11 +27,19 @@ struct DevLightTri { float ax, ay, az, bx, by, bz, cx, cy, cz, nx, ny, nz; uint3
 // A material of a scene in which every material is at most ONE Lambert lobe (the soups, the Cornell box): 32 B instead of 544
 struct DevMatLite { float wx, wy, wz; uint32_t lobes_flags /* num_lobes | flags << 8 */; float ex, ey, ez; uint32_t pad; };
 
+// The image textures of a scene as k_shade_g<., ., ., TEX> reads them (one record in device memory, read through the scalar cache)
+struct DevTexScene {
+  const float2* elem_uv;          // 3 x (s, t) per POOL ELEMENT, indexed like `tris` (the triangle's corner UVs, mesh_t::shading_parameters)
+  const DevTexture* textures;     // per texture: offset into `texels`, width, height, filter / wrap modes
+  const float4* texels;           // every texture's texels, RGB + 0, row-major, one 16-byte load per texel
+  const uint32_t* lobe_tex;       // 8 per material: texture + 1 of lobe k (DevMaterial::tex_lobes says which are textured)
+};
+
 struct DevScene {
   const uint32_t* pool;           // the BVH8 pool: 16 words per element, element 0 = root nodelet (bvh8.h)
   const TriRec* tris;             // the same pool seen as triangle records (hit records carry pool indices)
   SceneGrid grid;                 // grid of the nodelets' origins
-  const uint32_t* prim_material;  // per primitive (scene_t::triangles() order): material | smooth << 31
+  const DevTexScene* tex;         // image textures of the scene (device memory), or nullptr when no lobe is textured
   const float4* elem_shade;       // per POOL ELEMENT (indexed like `tris`): what shading needs of a hit triangle in 16 bytes — its geometric normal
                                   // normalize((v1-v0) x (v2-v0)) (mesh.cpp:201-215, computed once at preprocess by the shade kernels' own expression) and
                                   // material | smooth << 31 — instead of the 64-byte triangle record (round 6)
@@ -55,7 +63,11 @@ struct DevScene {
   uint2* stack_spill;             // k_trace<., SPILL>: stack entries below the levels kept in LDS, [level - lds_levels][thread of the grid]
   uint32_t spill_stride;          // threads of the largest k_trace grid (0 = every level is in LDS)
   float aperture_radius, focal_distance;  // camera_t (entities/camera.hpp:24-29): thin lens when aperture_radius != 0 (camera.hpp:140-147)
+  uint32_t any_tex;               // some lobe is textured: k_shade_g<., ., ., TEX> shades every step (sc.tex is set).  (This word and `tex` take
+                                  // the struct's tail padding and the slot of a pointer no kernel read: DevScene keeps its size and layout, so
+                                  // the kernels that take it by value compile to the same code as before textures existed)
 };
+static_assert(sizeof(DevScene) == 240, "DevScene is every kernel's first argument: its size fixes the offsets of the ones behind it");
 
 // counters (x CNT_STRIDE words): [0],[1] ray-queue lengths (ping-pong); [2],[3] shadow-queue lengths (by step parity); [4],[5] chunk cursors
 // every counter on its own 128-byte line: the queue-length counters take one atomic per k_shade workgroup and one address (line)
@@ -124,6 +136,7 @@ void launch_film(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples
 // triangles' `prim` from primitive to pool element (they look their normals up in the same table)
 void launch_build_shade_recs(hipStream_t stream, const TriRec* tris, const uint32_t* elem_of_prim, float4* elem_shade, uint32_t num_prims);
 void launch_permute_normals(hipStream_t stream, const float* prim_normals, const uint32_t* elem_of_prim, float* elem_normals, uint32_t num_prims);
+void launch_permute_uvs(hipStream_t stream, const float2* prim_uv, const uint32_t* elem_of_prim, float2* elem_uv, uint32_t num_prims);
 void launch_remap_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32_t num_light_tris, const uint32_t* elem_of_prim);
 void launch_scatter_film(hipStream_t stream, const PassBuffers& pb, float* device_film, uint32_t film_width);
 
@@ -132,5 +145,6 @@ void launch_trace_rays(hipStream_t stream, const DevScene& sc, uint32_t n, const
 void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3);
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags);
+void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb);
 
 }  // namespace phx

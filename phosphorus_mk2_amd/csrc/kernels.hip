@@ -826,6 +826,18 @@ __device__ __forceinline__ v3 shading_normal(const VertexNormals& N, bool smooth
   return geometric;
 }
 
+// k_shade_g<.., TEX>: the three corner UVs of the hit's pool element, requested with its shade record like the vertex normals, and the hit's
+// (s, t) by mesh_t::shading_parameters (src/mesh.cpp:177-181,239-257): w = (1 - u) - v, st = (w * uv0 + u * uv1) + v * uv2
+struct CornerUVs { float2 a, b, c; };
+__device__ __forceinline__ CornerUVs request_corner_uvs(const float2* elem_uv, uint32_t elem) {
+  const float2* p = elem_uv + 3 * (size_t)elem;
+  return CornerUVs{p[0], p[1], p[2]};
+}
+__device__ __forceinline__ float2 hit_st(const CornerUVs& C, float u, float v) {
+  const float w = (1 - u) - v;
+  return make_float2((w * C.a.x + u * C.b.x) + v * C.c.x, (w * C.a.y + u * C.b.y) + v * C.c.y);
+}
+
 __device__ __forceinline__ float luminance(const v3& c) {  // color::y, src/utils/color.hpp:13-16
   return (float)0.212671 * c.x + (float)0.715160 * c.y + (float)0.072169 * c.z;
 }
@@ -1175,7 +1187,8 @@ __device__ __forceinline__ void ring_append(bool want, const float4& r0, const f
     }
   }
 }
-template <bool PERHIT /* some material's closure weights depend on the hit (glass) */, bool FIRST, bool LENS = false /* FIRST: thin-lens camera */>
+template <bool PERHIT /* some material's closure weights depend on the hit (glass) */, bool FIRST, bool LENS = false /* FIRST: thin-lens camera */,
+          bool TEX = false /* some lobe's weight is multiplied by an image texel (DevScene::any_tex) */>
 __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves_per_eu(PHX_SHADE_WAVES_G, 8))) k_shade_g(DevScene sc, PassBuffers pb, int q, int sq, uint32_t sample0) {
   constexpr int BLOCK = PHX_SHADE_BLOCK_G, ITEMS = PHX_SHADE_ITEMS_G, WINDOW = BLOCK * ITEMS, NB = PHX_SHADE_BUCKETS;
   static_assert(WINDOW <= 65536 && BLOCK >= NB + 2 && NB == 64, "perm holds 16-bit positions; one wave scans the NB material buckets");
@@ -1195,6 +1208,11 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
   __shared__ uint32_t tri_sorted[TRI_LDS ? WINDOW : 1];  // the hit's pool index (0xffffffff = miss) at its sorted position
   const uint32_t count = pb.counters[q * CNT_STRIDE];
   if (blockIdx.x == 0 && threadIdx.x == 0) zero_cursors(pb.counters);  // the next k_trace pulls its chunks from here
+  DevTexScene tx{};  // TEX: the scene's texture tables, four pointers in SGPRs (constant address space: s_load)
+  if constexpr (TEX) {
+    const __attribute__((address_space(4))) DevTexScene* ctx = (const __attribute__((address_space(4))) DevTexScene*)sc.tex;
+    tx.elem_uv = ctx->elem_uv; tx.textures = ctx->textures; tx.texels = ctx->texels; tx.lobe_tex = ctx->lobe_tex;
+  }
   PHX_PHASE_DECL
 #if PHX_SHADE_TIMING
   unsigned long long ph_rounds = 0, ph_windows = 0;
@@ -1331,6 +1349,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
       bool alive = false, want_shadow = false, hit_surface = false;
       uint32_t path = 0, depth = 0, key = 0;
       v3 p, n, wo, beta;
+      float2 st = make_float2(0.0f, 0.0f);  // TEX: the hit's texture coordinates
       uint32_t mat = 0;  // the hit's material: an INDEX — bsdf_f / bsdf_sample read the recipe through the scalar cache, one distinct material of the wave at a time
       if (live) {
         float4 a, b, bd;
@@ -1339,12 +1358,16 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
         // TRI_LDS: the hit's pool index comes from the sort phase (LDS), so its shade record and vertex normals are requested HERE, beside the
         // hit record and the ray, not after the hit record has landed (one memory round trip less on the critical path of a round)
         uint32_t tri_early = 0xffffffffu; float4 S_early = make_float4(0.f, 0.f, 0.f, 0.f); VertexNormals VN_early{v3(0.0f), v3(0.0f), v3(0.0f)};
+        CornerUVs UV_early{};  // TEX: the corner UVs travel with the shade record and the normals (the texel gathers then wait on u, v only)
         if constexpr (TRI_LDS && STAGE1) {
           tri_early = next_tri; S_early = next_S;
-          if (tri_early != 0xffffffffu) VN_early = request_vertex_normals(sc, tri_early);
+          if (tri_early != 0xffffffffu) { VN_early = request_vertex_normals(sc, tri_early); if constexpr (TEX) UV_early = request_corner_uvs(tx.elem_uv, tri_early); }
         } else if constexpr (TRI_LDS) {
           tri_early = tri_sorted[sorted_slot(k)];
-          if (tri_early != 0xffffffffu) { S_early = sc.elem_shade[tri_early]; VN_early = request_vertex_normals(sc, tri_early); }
+          if (tri_early != 0xffffffffu) {
+            S_early = sc.elem_shade[tri_early]; VN_early = request_vertex_normals(sc, tri_early);
+            if constexpr (TEX) UV_early = request_corner_uvs(tx.elem_uv, tri_early);
+          }
         }
         if (FIRST) {
           v3 co, cd;
@@ -1373,8 +1396,13 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           hit_surface = true;
           VertexNormals VN;
           float4 S;  // (geometric normal, material | smooth << 31): DevScene::elem_shade
-          if constexpr (TRI_LDS) { VN = VN_early; S = S_early; }
-          else { VN = request_vertex_normals(sc, tri); if constexpr (STAGE1) S = next_S; else S = sc.elem_shade[tri]; }
+          CornerUVs UV{};
+          if constexpr (TRI_LDS) { VN = VN_early; S = S_early; if constexpr (TEX) UV = UV_early; }
+          else {
+            VN = request_vertex_normals(sc, tri); if constexpr (STAGE1) S = next_S; else S = sc.elem_shade[tri];
+            if constexpr (TEX) UV = request_corner_uvs(tx.elem_uv, tri);
+          }
+          if constexpr (TEX) st = hit_st(UV, h.y, h.z);
           const uint32_t pm = f2u(S.w);
           p = o + d * h.x;            // hits.p = p + wi*d
           wo = -d;                    // hits.wi = -wi
@@ -1434,7 +1462,10 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           if (sdot(n, sh_d) >= 0.0f) {
             // li(), spt.hpp:212-255 — evaluated before the occlusion test; k_trace adds it if the ray is unoccluded
             v3 f(0.0f);
-            if constexpr (PHX_SCALAR_F && (!PERHIT || PHX_SCALAR_F_PERHIT)) {
+            if constexpr (TEX) {  // the material's lobes with the texels at (s, t); the lookups read the hit's own row of lobe_tex
+              const TexHit th{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y};
+              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT, true>(cm, n, fr, sh_d, wo, th)));
+            } else if constexpr (PHX_SCALAR_F && (!PERHIT || PHX_SCALAR_F_PERHIT)) {
               PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT>(cm, n, fr, sh_d, wo)));
             } else {
               f = bsdf_f<false, 8, PERHIT>(sc.materials[mat], n, fr, sh_d, wo);
@@ -1474,9 +1505,16 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             const float u1 = draw_f32(key, b1 + DIM_BSDF_U), u2 = draw_f32(key, b1 + DIM_BSDF_V);
 #if PHX_SCALAR_S
             v3 f(0.0f);
-            PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl)));
+            if constexpr (TEX) {
+              const TexHit th{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y};
+              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT, true>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl, th)));
+            } else {
+              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl)));
+            }
 #else
-            const v3 f = bsdf_sample<false, 8, PERHIT>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl);
+            v3 f;
+            if constexpr (TEX) f = bsdf_sample<false, 8, PERHIT, true>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl, TexHit{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y});
+            else f = bsdf_sample<false, 8, PERHIT>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl);
 #endif
             if ((f.x == 0.0f && f.y == 0.0f && f.z == 0.0f) || pdf == 0.0f) {
               alive = false;
@@ -1629,6 +1667,13 @@ __global__ void __launch_bounds__(64) k_bsdf_sample(const DevMaterial* mat, uint
   if (p == 0.0f) { wo = v3(0.0f); f = v3(0.0f); fl = 0; }
   wo3[3 * i] = wo.x; wo3[3 * i + 1] = wo.y; wo3[3 * i + 2] = wo.z;
   f3[3 * i] = f.x; f3[3 * i + 1] = f.y; f3[3 * i + 2] = f.z; pdf[i] = p; flags[i] = fl;
+}
+
+__global__ void __launch_bounds__(64) k_texture_lookup(const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const v3 c = tex_lookup(textures, texels, tex, st[2 * i], st[2 * i + 1]);
+  rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
 }
 
 // ---- launches ---------------------------------------------------------------------------------------
@@ -1784,6 +1829,18 @@ void launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
     return;
   }
   const dim3 g(shade_grid(sc, capacity, PHX_SHADE_BLOCK_G * PHX_SHADE_ITEMS_G, PHX_SHADE_BLOCK_G)), b(PHX_SHADE_BLOCK_G);
+  if (sc.any_tex) {  // textured scenes: the same kernel with the texel lookups compiled in
+    if (sc.any_per_hit) {
+      if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else hipLaunchKernelGGL((k_shade_g<true, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+    } else {
+      if (lens) hipLaunchKernelGGL((k_shade_g<false, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<false, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else hipLaunchKernelGGL((k_shade_g<false, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+    }
+    return;
+  }
   if (sc.any_per_hit) {
     if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
     else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
@@ -1831,6 +1888,14 @@ __global__ void k_permute_normals(const float* __restrict__ prim_normals, const 
 #pragma unroll
   for (int k = 0; k < 9; ++k) elem_normals[9 * (size_t)e + k] = prim_normals[9 * (size_t)p + k];
 }
+__global__ void k_permute_uvs(const float2* __restrict__ prim_uv, const uint32_t* __restrict__ elem_of_prim, float2* __restrict__ elem_uv, uint32_t n) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t e = elem_of_prim[p];
+  if (e == 0xffffffffu) return;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) elem_uv[3 * (size_t)e + k] = prim_uv[3 * (size_t)p + k];
+}
 __global__ void k_remap_light_tris(DevLightTri* __restrict__ lt, uint32_t n, const uint32_t* __restrict__ elem_of_prim) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < n && lt[i].smooth) lt[i].prim = elem_of_prim[lt[i].prim];
@@ -1841,6 +1906,9 @@ void launch_build_shade_recs(hipStream_t stream, const TriRec* tris, const uint3
 }
 void launch_permute_normals(hipStream_t stream, const float* prim_normals, const uint32_t* elem_of_prim, float* elem_normals, uint32_t num_prims) {
   if (num_prims) hipLaunchKernelGGL(k_permute_normals, dim3((num_prims + 255) / 256), dim3(256), 0, stream, prim_normals, elem_of_prim, elem_normals, num_prims);
+}
+void launch_permute_uvs(hipStream_t stream, const float2* prim_uv, const uint32_t* elem_of_prim, float2* elem_uv, uint32_t num_prims) {
+  if (num_prims) hipLaunchKernelGGL(k_permute_uvs, dim3((num_prims + 255) / 256), dim3(256), 0, stream, prim_uv, elem_of_prim, elem_uv, num_prims);
 }
 void launch_remap_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32_t num_light_tris, const uint32_t* elem_of_prim) {
   if (num_light_tris) hipLaunchKernelGGL(k_remap_light_tris, dim3((num_light_tris + 255) / 256), dim3(256), 0, stream, light_tris, num_light_tris, elem_of_prim);
@@ -1863,6 +1931,9 @@ void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags) {
   hipLaunchKernelGGL(k_bsdf_sample, dim3((n + 63) / 64), dim3(64), 0, stream, mat, n, n3, wi3, u2, wo3, f3, pdf, flags);
+}
+void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
+  hipLaunchKernelGGL(k_texture_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, n, st, rgb);
 }
 
 }  // namespace phx

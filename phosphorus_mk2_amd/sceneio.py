@@ -8,8 +8,13 @@ position/at/up and then drops them, src/codecs/scene/entities.hpp:18-33) with th
 `fov = 2*atan2(sensor_width/2, focal_length)` (src/codecs/scene/alembic.hpp:69); an optional `dof: {fstop, focus-distance}` block
 turns the thin lens on with the Blender importer's convention (plugins/blender/import.hpp:573-579).
 
-OBJ subset: v, vn, f (polygons are fan-triangulated; v//vn and v/vt/vn index forms), usemtl NAME (one face set per
-material, material ids = order of the YAML `materials` map, src/scene.cpp:84-90), `s off|0` / `s 1` (flat / smooth).
+OBJ subset: v, vt, vn, f (polygons are fan-triangulated; v, v/vt, v//vn and v/vt/vn index forms), usemtl NAME (one face set per
+material, material ids = order of the YAML `materials` map, src/scene.cpp:84-90), `s off|0` / `s 1` (flat / smooth).  UVs are
+per vertex when every corner's vt index is its v index, per face corner otherwise (mesh_t::flags_t UVPerVertex, src/mesh.hpp:20-23);
+a corner without vt has UV (0, 0).
+
+Image textures (texture_node, baked by closures.py): `filename` is resolved relative to the YAML file and read with numpy alone —
+binary PPM (P6, 8 bit, value / 255), PFM (rows flipped to top first) or `.npy` ((H, W, 3) or (H, W) float) — as linear RGB.
 """
 import math
 import os
@@ -18,11 +23,11 @@ import numpy as np
 import yaml
 
 from . import abi, closures
-from .scenes import CameraDesc, MeshDesc, SceneDesc
+from .scenes import CameraDesc, MeshDesc, SceneDesc, TextureDesc
 
 
 def load_obj(path, material_ids, default_material=0):
-    verts, norms, faces, fnorm, smooth, fmat = [], [], [], [], [], []
+    verts, norms, texco, faces, fnorm, fuv, smooth, fmat = [], [], [], [], [], [], [], []
     cur_mat, cur_smooth = default_material, False
     for line in open(path):
         t = line.split()
@@ -32,6 +37,8 @@ def load_obj(path, material_ids, default_material=0):
             verts.append([float(x) for x in t[1:4]])
         elif t[0] == "vn":
             norms.append([float(x) for x in t[1:4]])
+        elif t[0] == "vt":
+            texco.append([float(x) for x in t[1:3]] + [0.0] * (3 - len(t)))
         elif t[0] == "usemtl":
             if t[1] not in material_ids:
                 raise ValueError(f"{path}: usemtl {t[1]!r} is not in the scene's materials")
@@ -43,15 +50,20 @@ def load_obj(path, material_ids, default_material=0):
             for tok in t[1:]:
                 p = tok.split("/")
                 vi = int(p[0]); vi = vi - 1 if vi > 0 else len(verts) + vi
-                ni = None
+                ti = ni = None
+                if len(p) >= 2 and p[1]:
+                    ti = int(p[1]); ti = ti - 1 if ti > 0 else len(texco) + ti
+                    if not 0 <= ti < len(texco):
+                        raise ValueError(f"{path}: vt index {p[1]} out of range")
                 if len(p) == 3 and p[2]:
                     ni = int(p[2]); ni = ni - 1 if ni > 0 else len(norms) + ni
-                idx.append((vi, ni))
+                idx.append((vi, ni, ti))
             for k in range(1, len(idx) - 1):
                 tri = (idx[0], idx[k], idx[k + 1])
-                faces.append([v for v, _ in tri])
-                fnorm.append([n for _, n in tri])
-                smooth.append(1 if (cur_smooth and all(n is not None for _, n in tri)) else 0)
+                faces.append([v for v, _, _ in tri])
+                fnorm.append([n for _, n, _ in tri])
+                fuv.append([u for _, _, u in tri])
+                smooth.append(1 if (cur_smooth and all(n is not None for _, n, _ in tri)) else 0)
                 fmat.append(cur_mat)
     if not faces:
         raise ValueError(f"{path}: no faces")
@@ -66,7 +78,81 @@ def load_obj(path, material_ids, default_material=0):
             if n is not None:
                 nrm[3 * f + c] = na[n]
     sets = [(int(m), np.nonzero(fmat == m)[0].astype(np.uint32)) for m in sorted(set(fmat.tolist()))]
-    return MeshDesc(vertices=verts, faces=faces, normals=nrm, smooth=np.array(smooth, np.uint8), sets=sets, flags=abi.MESH_UV_PER_VERTEX)
+    # UVs: per vertex when the file indexes them like the positions (every corner's vt index is its v index), per face corner otherwise
+    flags, uvs = abi.MESH_UV_PER_VERTEX, None
+    if texco:
+        ta = np.array(texco, np.float32)
+        corner_uv = [u for tri in fuv for u in tri]
+        corner_v = faces.reshape(-1).tolist()
+        if len(ta) == len(verts) and all(u == v for u, v in zip(corner_uv, corner_v)):
+            uvs = ta
+        else:
+            flags = 0
+            uvs = np.zeros((len(corner_uv), 2), np.float32)
+            for c, u in enumerate(corner_uv):
+                if u is not None:
+                    uvs[c] = ta[u]
+    return MeshDesc(vertices=verts, faces=faces, normals=nrm, smooth=np.array(smooth, np.uint8), sets=sets, flags=flags, uvs=uvs)
+
+
+def _ppm_tokens(data, n):
+    """the first n whitespace-separated header tokens of a PNM file (comments skipped) and the offset right behind the last one"""
+    toks, i = [], 0
+    while len(toks) < n:
+        while i < len(data) and data[i:i + 1].isspace():
+            i += 1
+        if data[i:i + 1] == b"#":
+            while i < len(data) and data[i:i + 1] not in (b"\n", b"\r"):
+                i += 1
+            continue
+        j = i
+        while j < len(data) and not data[j:j + 1].isspace():
+            j += 1
+        if j == i:
+            raise ValueError("truncated PPM header")
+        toks.append(data[i:j]); i = j
+    return toks, i + 1  # one whitespace character separates the header from the raster
+
+
+def load_ppm(path):
+    """binary PPM (P6) with 8-bit samples -> (H, W, 3) float32 value / 255, row 0 = the top row"""
+    data = open(path, "rb").read()
+    (magic, w, h, maxval), off = _ppm_tokens(data, 4)
+    w, h, maxval = int(w), int(h), int(maxval)
+    if magic != b"P6" or maxval != 255:
+        raise ValueError(f"{path}: only binary 8-bit PPM (P6, maxval 255) is supported")
+    raster = np.frombuffer(data, np.uint8, count=w * h * 3, offset=off)
+    return (raster.astype(np.float32) / np.float32(255.0)).reshape(h, w, 3)
+
+
+def load_pfm(path):
+    """PFM (PF: RGB, Pf: grey) -> (H, W, 3) float32, row 0 = the top row (the file stores the bottom row first)"""
+    data = open(path, "rb").read()
+    (magic, w, h, scale), off = _ppm_tokens(data, 4)
+    w, h, scale = int(w), int(h), float(scale)
+    if magic not in (b"PF", b"Pf"):
+        raise ValueError(f"{path}: not a PFM file")
+    c = 3 if magic == b"PF" else 1
+    img = np.frombuffer(data, "<f4" if scale < 0 else ">f4", count=w * h * c, offset=off).astype(np.float32).reshape(h, w, c)
+    img = img[::-1]
+    return np.ascontiguousarray(np.repeat(img, 3, axis=2) if c == 1 else img)
+
+
+def load_image(path):
+    """a texture's texels by the file's extension: .ppm, .pfm or .npy"""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".ppm":
+        return load_ppm(path)
+    if ext == ".pfm":
+        return load_pfm(path)
+    if ext == ".npy":
+        a = np.load(path).astype(np.float32)
+        if a.ndim == 2:
+            a = np.repeat(a[:, :, None], 3, axis=2)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"{path}: expected an (H, W, 3) or (H, W) array, not {a.shape}")
+        return np.ascontiguousarray(a)
+    raise ValueError(f"{path}: unsupported image format {ext!r} (.ppm, .pfm, .npy)")
 
 
 def look_at(position, at, up):
@@ -83,7 +169,9 @@ def look_at(position, at, up):
 def load_scene(path, width=1280, height=720):
     cfg = yaml.safe_load(open(path))
     base = os.path.dirname(os.path.abspath(path))
-    baked = closures.bake_materials(cfg["materials"])
+    tex_specs = []
+    baked = closures.bake_materials(cfg["materials"], tex_specs)
+    textures = [TextureDesc(load_image(os.path.join(base, t["filename"])), abi.TEX_LINEAR, t["swrap"], t["twrap"]) for t in tex_specs]
     names = list(baked)
     ids = {n: i for i, n in enumerate(names)}
     meshes = [load_obj(os.path.join(base, d["path"]), ids, ids.get(d.get("material", names[0]), 0)) for d in cfg.get("data", [])]
@@ -102,7 +190,7 @@ def load_scene(path, width=1280, height=720):
     world = cfg.get("world") or {}
     if "environment" in world:
         env = ids[world["environment"]]  # import_world_data, scene.cpp:30-36
-    return SceneDesc(meshes, [baked[n] for n in names], camera, environment_material=env, name=os.path.basename(path))
+    return SceneDesc(meshes, [baked[n] for n in names], camera, environment_material=env, name=os.path.basename(path), textures=textures)
 
 
 def save_pfm(path, rgb):

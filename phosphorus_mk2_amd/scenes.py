@@ -26,6 +26,7 @@ class LobeDesc:
     fac_mode: int = 0          # abi.FAC_*: per-hit Fresnel mix factor on this closure's weight (glass)
     fac_ior: float = 0.0
     pre_weight: Tuple[float, float, float] = (1.0, 1.0, 1.0)
+    texture: int = 0           # 0: none; k: the weight is multiplied per hit by SceneDesc.textures[k - 1] at the hit's UV
 
 
 @dataclass
@@ -43,8 +44,12 @@ class MeshDesc:
     normals: np.ndarray = None  # (m,3) f32
     smooth: np.ndarray = None   # (k,) u8
     flags: int = abi.MESH_UV_PER_VERTEX | abi.MESH_NORMALS_PER_VERTEX
+    uvs: np.ndarray = None      # (u,2) f32 (s, t): per vertex with MESH_UV_PER_VERTEX, else per face corner (3 f + k)
 
     def __post_init__(self):
+        if self.uvs is None:
+            self.uvs = np.zeros((0, 2), np.float32)
+        self.uvs = np.ascontiguousarray(self.uvs, dtype=np.float32).reshape(-1, 2)
         self.vertices = np.ascontiguousarray(self.vertices, dtype=np.float32).reshape(-1, 3)
         self.faces = np.ascontiguousarray(self.faces, dtype=np.uint32).reshape(-1, 3)
         if self.normals is None:
@@ -54,6 +59,20 @@ class MeshDesc:
             self.smooth = np.zeros(len(self.faces), np.uint8)
         self.smooth = np.ascontiguousarray(self.smooth, dtype=np.uint8)
         self.sets = [(int(m), np.ascontiguousarray(f, dtype=np.uint32)) for m, f in self.sets]
+
+
+@dataclass
+class TextureDesc:
+    """An RGB image texture (phx_texture): texels (H, W, 3) linear f32, row 0 = the first scanline (t in [0, 1/H))."""
+    texels: np.ndarray
+    filter: int = abi.TEX_LINEAR
+    swrap: int = abi.WRAP_PERIODIC
+    twrap: int = abi.WRAP_PERIODIC
+
+    def __post_init__(self):
+        self.texels = np.ascontiguousarray(self.texels, dtype=np.float32)
+        if self.texels.ndim != 3 or self.texels.shape[2] != 3:
+            raise ValueError(f"texels must be (H, W, 3), not {self.texels.shape}")
 
 
 @dataclass
@@ -78,6 +97,7 @@ class SceneDesc:
     camera: CameraDesc
     environment_material: int = -1
     name: str = "scene"
+    textures: List[TextureDesc] = field(default_factory=list)
 
     @property
     def num_triangles(self):
@@ -98,6 +118,7 @@ class SceneDesc:
                 d.alpha, d.eta, d.xalpha, d.yalpha, d.refract, d.r = l.alpha, l.eta, l.xalpha, l.yalpha, l.refract, l.r
                 d.fac_mode, d.fac_ior = l.fac_mode, l.fac_ior
                 d.pre_weight[:] = [np.float32(x) for x in l.pre_weight]
+                d.texture = l.texture
         meshes = (abi.Mesh * len(self.meshes))()
         for i, m in enumerate(self.meshes):
             sets = (abi.FaceSet * len(m.sets))()
@@ -116,6 +137,8 @@ class SceneDesc:
             meshes[i].flags = m.flags
             meshes[i].num_sets = len(m.sets)
             meshes[i].sets = sets
+            meshes[i].uvs = m.uvs.ctypes.data_as(abi.f32p)
+            meshes[i].num_uvs = len(m.uvs)
         s = abi.Scene()
         s.num_meshes = len(self.meshes)
         s.meshes = meshes
@@ -128,6 +151,15 @@ class SceneDesc:
         s.camera.aperture_radius = self.camera.aperture_radius
         s.camera.film_width = self.camera.width
         s.camera.film_height = self.camera.height
+        if self.textures:
+            texs = (abi.Texture * len(self.textures))()
+            for i, t in enumerate(self.textures):
+                texs[i].height, texs[i].width = t.texels.shape[0], t.texels.shape[1]
+                texs[i].texels = t.texels.ctypes.data_as(abi.f32p)
+                texs[i].filter, texs[i].swrap, texs[i].twrap = t.filter, t.swrap, t.twrap
+            s.num_textures = len(self.textures)
+            s.textures = texs
+            keep.append(texs)
         keep += [mats, meshes, self]
         return s, keep
 
@@ -395,6 +427,53 @@ def showroom_materials(per_hit_glass=True):
     z = closure_zoo()
     g = [glass(1.45, 0.0, (0.95, 0.98, 0.95), (1.0, 1.0, 1.0)), glass(1.33, 0.2, (0.9, 0.9, 1.0), (0.9, 0.9, 0.9))] if per_hit_glass else [z[10], z[5]]
     return z + [diffuse(0.7, 0.2, 0.2), diffuse(0.2, 0.7, 0.2), diffuse(0.2, 0.2, 0.7), diffuse(0.5, 0.5, 0.1)] + g
+
+
+def procedural_texture(size, seed=0):
+    """A (size, size, 3) f32 image in [0.05, 0.95]: a smooth colour gradient under a checker of 16 x 16 squares and some noise."""
+    rng = np.random.default_rng(seed)
+    y, x = np.meshgrid(np.linspace(0.0, 1.0, size, dtype=np.float32), np.linspace(0.0, 1.0, size, dtype=np.float32), indexing="ij")
+    check = ((np.floor(x * 16) + np.floor(y * 16)) % 2).astype(np.float32)
+    img = np.stack([0.2 + 0.6 * x, 0.2 + 0.6 * y, 0.5 + 0.3 * (check - 0.5)], -1) * (0.8 + 0.2 * check)[..., None]
+    img += rng.uniform(-0.05, 0.05, img.shape).astype(np.float32)
+    return np.clip(img, 0.05, 0.95).astype(np.float32)
+
+
+def _sphere_uvs(m):
+    """per-vertex lat/long UVs of a showroom sphere (its vertices are rings x segments around its centre)"""
+    c = m.vertices.mean(0)
+    d = m.vertices - c
+    d /= np.maximum(np.linalg.norm(d, axis=1, keepdims=True), 1e-12)
+    s = (np.arctan2(d[:, 2], d[:, 0]) / (2.0 * np.pi)) % 1.0
+    t = np.arccos(np.clip(d[:, 1], -1.0, 1.0)) / np.pi
+    return np.stack([s, t], 1).astype(np.float32)
+
+
+def textured_showroom(n=500_000, width=1920, height=1080, tex_size=2048, baked=False, seed=0):
+    """bmw_showroom() with the diffuse recipes (the room and the sphere materials of one Lambert lobe) driven by image textures: one
+    procedural tex_size^2 LINEAR texture per recipe, per-vertex lat/long UVs on the spheres, per-corner UVs on the room's quads.
+    baked=True: the same scene with 1 x 1 textures holding each image's mean, i.e. the per-hit path with constant texels (the cost
+    of the texel gathers is the difference of the two)."""
+    s = bmw_showroom(n, width, height)
+    quad_uv = np.array([[0, 0], [1, 0], [1, 1], [0, 0], [1, 1], [0, 1]], np.float32)  # _quad's two faces (a b c), (a c d)
+    for m in s.meshes:
+        if len(m.faces) == 2:
+            m.uvs = quad_uv * 3.0  # the room's walls repeat the image 3 x 3 times (PERIODIC)
+            m.flags = m.flags & ~abi.MESH_UV_PER_VERTEX
+        else:
+            m.uvs = _sphere_uvs(m)
+    textures = []
+    for i, mat in enumerate(s.materials):
+        if mat.is_emitter or len(mat.lobes) != 1 or mat.lobes[0].type != abi.LOBE_DIFFUSE:
+            continue
+        img = procedural_texture(tex_size, seed + i)
+        if baked:
+            img = img.reshape(-1, 3).mean(0, dtype=np.float64).astype(np.float32).reshape(1, 1, 3)
+        textures.append(TextureDesc(img, abi.TEX_LINEAR))
+        mat.lobes[0].texture = len(textures)
+    s.textures = textures
+    s.name = f"textured_showroom{n}" + ("_baked" if baked else "")
+    return s
 
 
 def bmw_showroom(n=500_000, width=1920, height=1080, per_hit_glass=True):

@@ -299,6 +299,15 @@ class HipDevice:
                                                         fl.ctypes.data_as(abi.u32p)), "phx_dev_bsdf_sample")
         return wo, f, pdf, fl
 
+    def texture_lookup(self, texture, st):
+        """The shade kernel's image lookup on the device: texture `texture` (0-based index into SceneDesc.textures of the preprocessed
+        scene, which must have a textured lobe) at st (n, 2) -> rgb (n, 3) f32."""
+        st = np.ascontiguousarray(st, np.float32).reshape(-1, 2)
+        out = np.zeros((len(st), 3), np.float32)
+        _check(self._lib, self._lib.phx_dev_texture_lookup(self._h, texture, len(st), st.ctypes.data_as(abi.f32p), out.ctypes.data_as(abi.f32p)),
+               "phx_dev_texture_lookup")
+        return out
+
     def bvh_pool(self):
         """the acceleration structure as the kernels read it: (uint32 array [elements, 16], grid lo[3], grid cell[3]) — phx_dev_copy_bvh"""
         n = C.c_uint64(0); grid = np.zeros(6, np.float32)
