@@ -106,9 +106,23 @@ typedef struct phx_material {
   uint32_t num_lobes;   /* 0 for pure emitters (diffuse_emitter_node.osl) */
   uint32_t is_emitter;  /* material_t::is_emitter, src/material.cpp:487 */
   float    emission[3]; /* weight of the emission()/background() closure: hits.e */
-  uint32_t pad[3];
+  /* Environment map (environment_node.osl's Cout = environment(filename, I) into background_node.Cs): 0 = none, k = phx_scene.textures[k - 1].
+   * Allowed ONLY on phx_scene.environment_material (PHX_ERR_ARG elsewhere: textured surface emission is not supported).  Where a path
+   * misses every surface (camera rays included) with direction d = (x, y, z), it adds beta * e with e = emission * texel(s, t), one fp32
+   * multiply per channel; the environment is never sampled by next-event estimation.  (s, t) restates OpenImageIO's documented lat-long
+   * convention (latlong_up "y" by default, or "z"), computed in binary64 from the fp32 components widened to double, operation by
+   * operation in the order written (no contraction), each result rounded to fp32 once; INV_2PI and INV_PI are the doubles nearest
+   * 1/(2 pi) and 1/pi:
+   *   PHX_ENV_LATLONG_Y_UP: s = 0.5 + atan2(-x, z) * INV_2PI   t = 0.5 - atan2(y, sqrt(z*z + x*x)) * INV_PI
+   *   PHX_ENV_LATLONG_Z_UP: s = 0.5 + atan2( y, x) * INV_2PI   t = 0.5 - atan2(z, sqrt(x*x + y*y)) * INV_PI
+   * It is a restatement, not pinned to OpenImageIO's object code.  The texel is the phx_texture lookup with the texture's own filter and
+   * wrap modes (OpenImageIO's lat-long wrap is swrap periodic, twrap clamp); no MIP maps, no blur.  A zero or non-finite d reads black. */
+  uint32_t emission_texture;
+  uint32_t emission_mapping; /* PHX_ENV_LATLONG_*; any other value is PHX_ERR_ARG */
+  uint32_t pad;
   phx_lobe lobes[PHX_MAX_LOBES];
 } phx_material;
+enum { PHX_ENV_LATLONG_Y_UP = 0, PHX_ENV_LATLONG_Z_UP = 1 };
 
 /* mesh_t::face_set_t, src/mesh.hpp:26-41 */
 typedef struct phx_face_set {
@@ -314,9 +328,14 @@ int phx_dev_bsdf_sample(phx_device* dev, uint32_t material, uint32_t n_items, co
 
 /* The image lookup the shade kernel applies to a textured lobe, run on the device for texture `texture` (0-based index into
  * phx_scene.textures of the preprocessed scene) at n coordinates st (s, t per item): rgb per item.  A parity hook like phx_dev_bsdf_f.
- * The texture table is uploaded only when some lobe of the preprocessed scene is textured: for a scene without a textured lobe every
- * call returns PHX_ERR_ARG, as does an index past the table. */
+ * The texture table is uploaded only when some lobe of the preprocessed scene is textured or its environment has an image: for any
+ * other scene every call returns PHX_ERR_ARG, as does an index past the table. */
 int phx_dev_texture_lookup(phx_device* dev, uint32_t texture, uint32_t n, const float* st, float* rgb);
+
+/* The environment's e on a miss as the shade kernel computes it (phx_material.emission_texture: mapping, lookup and multiply), run on
+ * the device for n directions dirs (x, y, z per item) against the preprocessed scene's environment: rgb per item.  A parity hook.
+ * PHX_ERR_STATE before preprocess; PHX_ERR_ARG when the scene's environment has no image. */
+int phx_dev_environment_lookup(phx_device* dev, uint32_t n, const float* dirs, float* rgb);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -16,6 +16,7 @@ BVH_AUTO, BVH_DEVICE_LBVH, BVH_HOST_SAH = 0, 1, 2
 MESH_UV_PER_VERTEX, MESH_NORMALS_PER_VERTEX = 1, 2
 TEX_LINEAR, TEX_CLOSEST = 0, 1
 WRAP_PERIODIC, WRAP_CLAMP, WRAP_BLACK = 0, 1, 2
+ENV_LATLONG_Y_UP, ENV_LATLONG_Z_UP = 0, 1
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -42,7 +43,7 @@ class Lobe(C.Structure):
 class Material(C.Structure):
     _fields_ = [
         ("num_lobes", C.c_uint32), ("is_emitter", C.c_uint32), ("emission", C.c_float * 3),
-        ("pad", C.c_uint32 * 3), ("lobes", Lobe * MAX_LOBES),
+        ("emission_texture", C.c_uint32), ("emission_mapping", C.c_uint32), ("pad", C.c_uint32), ("lobes", Lobe * MAX_LOBES),
     ]
 
 
@@ -119,7 +120,7 @@ EXPORTS = [
     "phx_discover", "phx_dev_make", "phx_dev_preprocess", "phx_dev_start", "phx_dev_join", "phx_dev_destroy",
     "phx_last_error", "phx_dev_get_stats", "phx_tiles_make", "phx_tiles_next", "phx_tiles_count", "phx_tiles_reset",
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
-    "phx_dev_texture_lookup",
+    "phx_dev_texture_lookup", "phx_dev_environment_lookup",
 ]
 
 
@@ -145,5 +146,6 @@ def declare(lib):
     lib.phx_dev_bsdf_sample.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, u32p]
     lib.phx_dev_bsdf_sample.restype = C.c_int
     lib.phx_dev_texture_lookup.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p]; lib.phx_dev_texture_lookup.restype = C.c_int
+    lib.phx_dev_environment_lookup.argtypes = [vp, C.c_uint32, f32p, f32p]; lib.phx_dev_environment_lookup.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

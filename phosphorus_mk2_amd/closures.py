@@ -34,7 +34,13 @@ The closure's lobe records the constant weight accumulated ABOVE that point in `
 entry k of the `textures` list handed to the baker: {filename, swrap, twrap}); the device multiplies the texel in at every hit.
 `swrap` / `twrap` "periodic" (the default), "clamp" and "black" are expressible; "mirror" and "default" raise, and so do blur
 and explicit s / t inputs (the lookup is at the mesh's UV).  A texture feeding anything but a BSDF node's Cs (a mix's fac, a
-roughness, emission, another texture) raises.  Other hit-dependent inputs (noise, normal maps, environment maps) raise.
+roughness, emission, another texture) raises.  The third is an environment map: `environment_node.Cout` driving `background_node.Cs`
+(the exporter's Environment Texture node on the world, plugins/blender/blender/shader.hpp:376-377, 440).
+  environment_node.osl              Cout = environment(filename, I, "sblur", sblur, "tblur", tblur)
+It bakes into the material's `emission` (the constant weight accumulated above it, `power` included) and `emission_texture` (k + 1
+for the spec {filename, swrap periodic, twrap clamp}: OpenImageIO's lat-long wrap); the device multiplies the texel at the ray's
+direction in on a miss.  Blur, an environment_node anywhere but a background's Cs and a texture_node into a background (a miss has
+no UV) raise.  Other hit-dependent inputs (noise, normal maps) raise.
 """
 import math
 
@@ -97,7 +103,21 @@ class MulTex:
         self.tex, self.closure = tex, closure
 
 
+class Env:
+    """the output of an environment_node: a colour known only on a miss (the image in the ray's direction)"""
+    def __init__(self, spec):
+        self.spec = spec  # {"filename", "swrap", "twrap"}: periodic / clamp
+
+
+class MulEnv:
+    """background closure * environment texel: the image multiplies the environment's emission on every miss"""
+    def __init__(self, env, closure):
+        self.env, self.closure = env, closure
+
+
 def mul(weight, closure):
+    if isinstance(weight, Env):
+        raise ValueError("an environment_node can drive only the Cs of a background_node")
     if isinstance(weight, Tex):
         return None if closure is None else MulTex(weight, closure)
     w = _color(weight)
@@ -149,6 +169,11 @@ def diffuse_emitter_node(power=1.0, Cs=1.0, **_):
 
 
 def background_node(Cs=0.0, power=1.0, **_):
+    if isinstance(Cs, Env):  # Cs * power * background() with Cs the texel: power joins the constant weight, the image multiplies on a miss
+        c = mul(f32(power), Comp(abi.LOBE_BACKGROUND))
+        return None if c is None else MulEnv(Cs, c)
+    if isinstance(Cs, Tex):
+        raise ValueError("texture_node into a background_node: a miss has no UV (use an environment_node)")
     return mul(_color(Cs) * f32(power), Comp(abi.LOBE_BACKGROUND))
 
 
@@ -172,10 +197,20 @@ def texture_node(filename="", swrap="periodic", twrap="periodic", sblur=0.0, tbl
     return Tex({"filename": str(filename), "swrap": WRAPS[swrap], "twrap": WRAPS[twrap]})
 
 
+def environment_node(filename="", sblur=0.0, tblur=0.0, **extra):
+    if extra:
+        raise ValueError(f"environment_node: inputs {sorted(extra)} cannot be expressed (the lookup is in the ray's direction)")
+    if f32(sblur) != 0 or f32(tblur) != 0:
+        raise ValueError("environment_node: sblur / tblur are not supported")
+    if not filename:
+        raise ValueError("environment_node without a filename")
+    return Env({"filename": str(filename), "swrap": abi.WRAP_PERIODIC, "twrap": abi.WRAP_CLAMP})
+
+
 def mix_closure_node(A=None, B=None, fac=0.5, **_):
     if isinstance(fac, Fac):  # Cout = A * (1 - fac) + B * fac with fac evaluated per hit
         return add(MulFac(abi.FAC_MIX_A, fac, A) if A is not None else None, MulFac(abi.FAC_MIX_B, fac, B) if B is not None else None)
-    if not np.isscalar(fac) or isinstance(fac, Tex):
+    if not np.isscalar(fac) or isinstance(fac, (Tex, Env)):
         raise ValueError("mix_closure_node.fac is driven by a node this baker cannot express (hit-dependent)")
     fac = f32(fac)
     return add(mul(f32(f32(1) - fac), A), mul(fac, B))
@@ -186,11 +221,12 @@ def add_node(A=None, B=None, **_):
 
 
 NODES = {f.__name__: f for f in (diffuse_bsdf_node, glossy_bsdf_node, refraction_bsdf_node, sheen_bsdf_node, transparent_bsdf_node,
-                                 diffuse_emitter_node, background_node, mix_closure_node, add_node, fresnel_dielectric_node, texture_node)}
+                                 diffuse_emitter_node, background_node, mix_closure_node, add_node, fresnel_dielectric_node, texture_node,
+                                 environment_node)}
 # the nodes whose Cs a texture may drive: their closure's weight is Cs
 TEXTURABLE = {diffuse_bsdf_node, glossy_bsdf_node, refraction_bsdf_node, sheen_bsdf_node, transparent_bsdf_node}
 UNBAKEABLE = {"fresnel_node", "normal_map_node", "random_noise_2d_node", "random_noise_3d_node",
-              "musgrave_noise_3d_node", "environment_node", "mix_color_node", "blackbody_node"}
+              "musgrave_noise_3d_node", "mix_color_node", "blackbody_node"}
 
 
 # ---- material.cpp:218-305 -------------------------------------------------------------------------------
@@ -201,7 +237,7 @@ def flatten(tree, textures=None):
     constant part below it (weight): at a hit the weight is (pre_weight * term) * weight, the same order of multiplications.
     A texture on a closure's colour: the lobe keeps the weight accumulated above it and `texture` = k + 1, k the texture's entry in
     `textures` (a list of {filename, swrap, twrap}, extended here by the ones not in it yet)."""
-    lobes, state = [], {"e": (0.0, 0.0, 0.0), "emitter": False}
+    lobes, state = [], {"e": (0.0, 0.0, 0.0), "emitter": False, "env": 0}
     if textures is None:
         textures = []
 
@@ -210,13 +246,15 @@ def flatten(tree, textures=None):
             textures.append(spec)
         return textures.index(spec) + 1
 
-    def visit(c, w, fac=None, tex=0):
+    def visit(c, w, fac=None, tex=0, env=0):
         # w: the constant weight accumulated so far BELOW the hit-dependent factor (or all of it when there is none);
         # fac = (mode, ior, pre): the factor met on the way down and the constant weight accumulated ABOVE it
         if c is None:
             return
         if isinstance(c, Mul):
-            visit(c.closure, (w * c.weight).astype(f32), fac, tex)
+            visit(c.closure, (w * c.weight).astype(f32), fac, tex, env)
+        elif isinstance(c, MulEnv):
+            visit(c.closure, w, fac, tex, texture_id(c.env.spec))
         elif isinstance(c, MulTex):
             if tex:
                 raise ValueError("a texture behind another texture on one closure is not supported")
@@ -228,8 +266,8 @@ def flatten(tree, textures=None):
                 raise ValueError("a Fresnel-driven mix below a texture is not supported")
             visit(c.closure, np.ones(3, f32), (c.mode, c.fac.ior, w))
         elif isinstance(c, Add):
-            visit(c.a, w, fac, tex)
-            visit(c.b, w, fac, tex)
+            visit(c.a, w, fac, tex, env)
+            visit(c.b, w, fac, tex, env)
         else:
             if c.cid in (abi.LOBE_EMISSIVE, abi.LOBE_BACKGROUND):
                 if fac is not None:
@@ -237,6 +275,7 @@ def flatten(tree, textures=None):
                 if tex:
                     raise ValueError("textured emission is not supported")
                 state["e"] = tuple(float(x) for x in w)  # assignment: a later emission overwrites an earlier one
+                state["env"] = env
                 state["emitter"] = state["emitter"] or c.cid == abi.LOBE_EMISSIVE  # material.cpp:205-211
                 return
             p = c.params
@@ -251,7 +290,7 @@ def flatten(tree, textures=None):
     visit(tree, np.ones(3, f32))
     if len(lobes) > abi.MAX_LOBES:
         raise ValueError(f"{len(lobes)} lobes: bsdf_t holds at most {abi.MAX_LOBES} (src/bsdf.hpp:9)")
-    return MaterialDesc(lobes=lobes, emission=state["e"], is_emitter=state["emitter"])
+    return MaterialDesc(lobes=lobes, emission=state["e"], is_emitter=state["emitter"], emission_texture=state["env"])
 
 
 def bake_material(desc, textures=None):
@@ -275,8 +314,8 @@ def bake_material(desc, textures=None):
                 params[p["name"]] = str(p["value"])
             else:
                 raise ValueError("Unknown parameter type: " + t)  # material.hpp:79
-        if NODES[name] is texture_node:
-            texture_node(**params)  # its parameters are checked whether or not the node is connected (a texture without an image raises)
+        if NODES[name] in (texture_node, environment_node):
+            NODES[name](**params)  # its parameters are checked whether or not the node is connected (a texture without an image raises)
         layers[layer] = (NODES[name], params)
         order.append(layer)
     edges = {}
@@ -293,6 +332,8 @@ def bake_material(desc, textures=None):
                     raise ValueError(f"connection from {src_layer}.{src_slot}: only closure outputs (Cout) and fresnel_dielectric_node.out can be expressed")
                 if layers[src_layer][0] is texture_node and (slot != "Cs" or fn not in TEXTURABLE):
                     raise ValueError(f"texture {src_layer}.Cout into {layer}.{slot}: a texture can drive only the Cs of a BSDF node")
+                if layers[src_layer][0] is environment_node and (slot != "Cs" or fn is not background_node):
+                    raise ValueError(f"environment {src_layer}.Cout into {layer}.{slot}: an environment map can drive only the Cs of a background_node")
                 args[slot] = evaluate(src_layer)
             cache[layer] = fn(**args)
         return cache[layer]

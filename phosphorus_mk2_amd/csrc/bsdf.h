@@ -182,6 +182,34 @@ PHX_HD v3 tex_lookup(const DevTexture* textures, const float4* texels, uint32_t 
   const v3 d(t01.x + fx * (t11.x - t01.x), t01.y + fx * (t11.y - t01.y), t01.z + fx * (t11.z - t01.z));
   return v3(c.x + fy * (d.x - c.x), c.y + fy * (d.y - c.y), c.z + fy * (d.z - c.z));
 }
+// ---- environment maps (phx_material.emission_texture; the miss branch of k_shade_g<.., ENV> and phx_dev_environment_lookup) ---------
+enum { ENV_LATLONG_Y_UP = 0, ENV_LATLONG_Z_UP = 1 };  // PHX_ENV_*
+// (s, t) of direction d by OpenImageIO's lat-long convention, in binary64 from the widened fp32 components, each result rounded to fp32
+// once (phx_xpu.h states the formulas); the library builds with -ffp-contract=off, so every operation is rounded as written.  false for a
+// zero or non-finite d.
+PHX_HD bool env_latlong_st(const v3& d, uint32_t mapping, float& s, float& t) {
+  if (!(fabsf(d.x) <= FLT_MAX) || !(fabsf(d.y) <= FLT_MAX) || !(fabsf(d.z) <= FLT_MAX) || (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f)) return false;
+  const double INV_2PI = 0x1.45f306dc9c883p-3, INV_PI = 0x1.45f306dc9c883p-2;  // the doubles nearest 1/(2 pi), 1/pi
+  const double x = (double)d.x, y = (double)d.y, z = (double)d.z;
+  double ss, tt;
+  if (mapping == ENV_LATLONG_Z_UP) {
+    ss = 0.5 + atan2(y, x) * INV_2PI;
+    tt = 0.5 - atan2(z, sqrt(x * x + y * y)) * INV_PI;
+  } else {
+    ss = 0.5 + atan2(-x, z) * INV_2PI;
+    tt = 0.5 - atan2(y, sqrt(z * z + x * x)) * INV_PI;
+  }
+  s = (float)ss; t = (float)tt;
+  return true;
+}
+// the environment's e on a miss in direction d: emission * texel(s, t) (one fp32 multiply per channel); black for a direction without (s, t)
+PHX_HD v3 env_emission(const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t mapping, const v3& d, const v3& emission) {
+  float s, t;
+  if (!env_latlong_st(d, mapping, s, t)) return v3(0.0f);
+  const v3 c = tex_lookup(textures, texels, tex, s, t);
+  return v3(emission.x * c.x, emission.y * c.y, emission.z * c.z);
+}
+
 // lobe_weight_at_hit for lobe i of material m, with the image texture of a textured lobe (TEX): weight * texel first, then the per-hit
 // factor on that product, (pre * term) * (weight * texel); a textured lobe whose weight comes out all zero is not there at the hit.
 // TEX = false is lobe_weight_at_hit itself.

@@ -98,6 +98,7 @@ struct phx_device {
   DevBuf<float2> d_elem_uv; DevBuf<DevTexture> d_textures; DevBuf<float4> d_texels; DevBuf<uint32_t> d_lobe_tex; DevBuf<DevTexScene> d_tex_scene;
   DevScene scene{};
   uint32_t num_materials = 0, num_textures = 0;
+  uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission
   uint64_t bvh_nodes = 0, bvh_bytes = 0, num_triangles = 0;
   double preprocess_ms = 0, bvh_build_ms = 0;
 
@@ -351,7 +352,15 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
         return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": textures on emitters / the environment are not supported");
       any_tex = true;
     }
+    // an environment map: only on the environment material (textured surface emission would need UVs at NEE's light samples)
+    if (m.emission_mapping > PHX_ENV_LATLONG_Z_UP) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": unknown emission_mapping");
+    if (m.emission_texture) {
+      if ((int32_t)i != s->environment_material)
+        return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": emission_texture is allowed only on the environment material");
+      if (m.emission_texture > s->num_textures) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": emission_texture index out of range");
+    }
   }
+  const uint32_t env_tex = s->environment_material >= 0 ? s->materials[s->environment_material].emission_texture : 0u;  // texture + 1, 0 = none
 
   // triangles in scene_t::triangles() order: mesh order x face-set order (scene.cpp:58-62, mesh.cpp:118-128)
   std::vector<float> abc; std::vector<uint32_t> prim_material; std::vector<float> prim_normals;
@@ -516,13 +525,18 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   } else {
     d->d_elem_normals.release();
   }
-  if (any_tex) {
-    // corner UVs by POOL ELEMENT, like the normals; every texture's texels as float4 (one 16-byte load per texel) behind a small table
+  if (any_tex || env_tex) {
+    // corner UVs by POOL ELEMENT, like the normals (textured lobes only); every texture's texels as float4 (one 16-byte load per texel)
+    // behind a small table
     DevBuf<float2> d_prim_uv;
-    if ((rc = d_prim_uv.upload(prim_uv))) return rc;
-    if ((rc = d->d_elem_uv.alloc(3 * bvh_elems))) return rc;
-    launch_permute_uvs(d->stream, d_prim_uv.p, d_elem_of_prim.p, d->d_elem_uv.p, ntri);
-    HIPCHK(hipGetLastError());
+    if (any_tex) {
+      if ((rc = d_prim_uv.upload(prim_uv))) return rc;
+      if ((rc = d->d_elem_uv.alloc(3 * bvh_elems))) return rc;
+      launch_permute_uvs(d->stream, d_prim_uv.p, d_elem_of_prim.p, d->d_elem_uv.p, ntri);
+      HIPCHK(hipGetLastError());
+    } else {
+      d->d_elem_uv.release(); d->d_lobe_tex.release();
+    }
     std::vector<DevTexture> tabs(s->num_textures);
     std::vector<float4> texels((size_t)total_texels);
     uint32_t off = 0;
@@ -533,8 +547,10 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
       for (uint32_t k = 0; k < nt; ++k) texels[off + k] = make_float4(T.texels[3 * (size_t)k], T.texels[3 * (size_t)k + 1], T.texels[3 * (size_t)k + 2], 0.0f);
       off += nt;
     }
-    if ((rc = d->d_textures.upload(tabs)) || (rc = d->d_texels.upload(texels)) || (rc = d->d_lobe_tex.upload(lobe_tex))) return rc;
-    const std::vector<DevTexScene> ts{DevTexScene{d->d_elem_uv.p, d->d_textures.p, d->d_texels.p, d->d_lobe_tex.p}};
+    if ((rc = d->d_textures.upload(tabs)) || (rc = d->d_texels.upload(texels)) || (any_tex && (rc = d->d_lobe_tex.upload(lobe_tex)))) return rc;
+    const uint32_t env_mapping = env_tex ? s->materials[s->environment_material].emission_mapping : 0u;
+    const std::vector<DevTexScene> ts{DevTexScene{any_tex ? d->d_elem_uv.p : nullptr, d->d_textures.p, d->d_texels.p, any_tex ? d->d_lobe_tex.p : nullptr,
+                                                  env_tex ? env_tex - 1u : 0u, env_mapping}};
     if ((rc = d->d_tex_scene.upload(ts))) return rc;
     HIPCHK(hipStreamSynchronize(d->stream));  // d_prim_uv goes out of scope
   } else {
@@ -557,8 +573,8 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   sc.ratio = (float)s->camera.film_width / (float)s->camera.film_height;
   sc.width = s->camera.film_width; sc.height = s->camera.film_height;
   sc.aperture_radius = s->camera.aperture_radius; sc.focal_distance = s->camera.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
-  sc.any_tex = any_tex ? 1u : 0u;
-  sc.tex = any_tex ? d->d_tex_scene.p : nullptr;
+  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (env_tex ? SC_TEX_ENV : 0u);
+  sc.tex = sc.any_tex ? d->d_tex_scene.p : nullptr;
   sc.max_depth = d->opt.path_depth;
   sc.stack_levels = bvh_depth;
   sc.num_elems = (uint32_t)bvh_elems;
@@ -566,7 +582,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, d->hip_device));
     sc.num_cus = (uint32_t)prop.multiProcessorCount;
   }
-  sc.diffuse_only = any_tex ? 0 : 1;  // textured lobes are shaded by k_shade_g<.., TEX> only
+  sc.diffuse_only = sc.any_tex ? 0 : 1;  // textured lobes and environment maps are shaded by k_shade_g<.., TEX, ENV> only
   for (auto& m : mats) { if (m.per_hit) sc.diffuse_only = 0; for (uint32_t k = 0; k < m.num_lobes; ++k) if (m.lobes[k].type != L_DIFFUSE) sc.diffuse_only = 0; }
   sc.mat_lite = nullptr;
   sc.any_per_hit = 0;
@@ -587,7 +603,10 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     }
   }
   d->num_materials = s->num_materials;
-  d->num_textures = any_tex ? s->num_textures : 0;
+  d->num_textures = sc.any_tex ? s->num_textures : 0;
+  d->env_tex = env_tex;
+  d->env_mapping = env_tex ? s->materials[s->environment_material].emission_mapping : 0u;
+  for (int c = 0; c < 3; ++c) d->env_e[c] = env_tex ? s->materials[s->environment_material].emission[c] : 0.0f;
   d->bvh_nodes = bvh_node_count;
   d->bvh_bytes = bvh_elems * sizeof(PoolElem);
   d->bvh_build_ms = std::chrono::duration<double, std::milli>(t_bvh1 - t_bvh0).count();
@@ -797,6 +816,23 @@ static int dev_texture_lookup_impl(phx_device* d, uint32_t texture, uint32_t n, 
   return PHX_OK;
 }
 int phx_dev_texture_lookup(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) { return guarded([&]() { return dev_texture_lookup_impl(d, texture, n, st, rgb); }); }
+
+static int dev_environment_lookup_impl(phx_device* d, uint32_t n, const float* dirs, float* rgb) {
+  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "environment_lookup before preprocess");
+  if (!d->env_tex) return fail(PHX_ERR_ARG, "environment_lookup: the scene's environment has no image");
+  if (n == 0) return PHX_OK;
+  if (!dirs || !rgb) return fail(PHX_ERR_ARG, "environment_lookup: null argument");
+  DeviceScope on(d->hip_device);
+  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+  DevBuf<float> a, o; int rc;
+  if ((rc = kat_upload(dirs, 3 * (size_t)n, a)) || (rc = o.alloc(3 * (size_t)n))) return rc;
+  launch_environment_lookup(d->stream, d->d_textures.p, d->d_texels.p, d->env_tex - 1u, d->env_mapping, d->env_e[0], d->env_e[1], d->env_e[2], n, a.p, o.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(rgb, o.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return PHX_OK;
+}
+int phx_dev_environment_lookup(phx_device* d, uint32_t n, const float* dirs, float* rgb) { return guarded([&]() { return dev_environment_lookup_impl(d, n, dirs, rgb); }); }
 
 int phx_dev_copy_bvh(phx_device* d, void* out, uint64_t capacity, uint64_t* bytes, float* grid6) {
   if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "copy_bvh before preprocess");

@@ -33,13 +33,17 @@ struct DevTexScene {
   const DevTexture* textures;     // per texture: offset into `texels`, width, height, filter / wrap modes
   const float4* texels;           // every texture's texels, RGB + 0, row-major, one 16-byte load per texel
   const uint32_t* lobe_tex;       // 8 per material: texture + 1 of lobe k (DevMaterial::tex_lobes says which are textured)
+  uint32_t env_tex;               // k_shade_g<.., ENV>: the environment's image (0-based index into `textures`)
+  uint32_t env_mapping;           // and its lat-long mapping (ENV_LATLONG_*)
 };
+// DevScene::any_tex bits: which image lookups the shade kernels compile in
+enum { SC_TEX_LOBES = 1u /* some lobe is textured: TEX */, SC_TEX_ENV = 2u /* the environment has an image: ENV */ };
 
 struct DevScene {
   const uint32_t* pool;           // the BVH8 pool: 16 words per element, element 0 = root nodelet (bvh8.h)
   const TriRec* tris;             // the same pool seen as triangle records (hit records carry pool indices)
   SceneGrid grid;                 // grid of the nodelets' origins
-  const DevTexScene* tex;         // image textures of the scene (device memory), or nullptr when no lobe is textured
+  const DevTexScene* tex;         // image textures of the scene (device memory), or nullptr when no lobe is textured and the environment has no image
   const float4* elem_shade;       // per POOL ELEMENT (indexed like `tris`): what shading needs of a hit triangle in 16 bytes — its geometric normal
                                   // normalize((v1-v0) x (v2-v0)) (mesh.cpp:201-215, computed once at preprocess by the shade kernels' own expression) and
                                   // material | smooth << 31 — instead of the 64-byte triangle record (round 6)
@@ -63,7 +67,8 @@ struct DevScene {
   uint2* stack_spill;             // k_trace<., SPILL>: stack entries below the levels kept in LDS, [level - lds_levels][thread of the grid]
   uint32_t spill_stride;          // threads of the largest k_trace grid (0 = every level is in LDS)
   float aperture_radius, focal_distance;  // camera_t (entities/camera.hpp:24-29): thin lens when aperture_radius != 0 (camera.hpp:140-147)
-  uint32_t any_tex;               // some lobe is textured: k_shade_g<., ., ., TEX> shades every step (sc.tex is set).  (This word and `tex` take
+  uint32_t any_tex;               // SC_TEX_* bits: some lobe is textured (k_shade_g<., ., ., TEX>) / the environment has an image (k_shade_g<.., ENV>);
+                                  // either one: k_shade_g shades every step and sc.tex is set.  (This word and `tex` take
                                   // the struct's tail padding and the slot of a pointer no kernel read: DevScene keeps its size and layout, so
                                   // the kernels that take it by value compile to the same code as before textures existed)
 };
@@ -146,5 +151,7 @@ void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags);
 void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb);
+void launch_environment_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t mapping, float ex, float ey, float ez,
+                               uint32_t n, const float* dirs, float* rgb);
 
 }  // namespace phx

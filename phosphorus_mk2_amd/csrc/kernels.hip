@@ -1188,7 +1188,8 @@ __device__ __forceinline__ void ring_append(bool want, const float4& r0, const f
   }
 }
 template <bool PERHIT /* some material's closure weights depend on the hit (glass) */, bool FIRST, bool LENS = false /* FIRST: thin-lens camera */,
-          bool TEX = false /* some lobe's weight is multiplied by an image texel (DevScene::any_tex) */>
+          bool TEX = false /* some lobe's weight is multiplied by an image texel (DevScene::any_tex & SC_TEX_LOBES) */,
+          bool ENV = false /* the environment has an image: a miss reads it in the ray's direction (DevScene::any_tex & SC_TEX_ENV) */>
 __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves_per_eu(PHX_SHADE_WAVES_G, 8))) k_shade_g(DevScene sc, PassBuffers pb, int q, int sq, uint32_t sample0) {
   constexpr int BLOCK = PHX_SHADE_BLOCK_G, ITEMS = PHX_SHADE_ITEMS_G, WINDOW = BLOCK * ITEMS, NB = PHX_SHADE_BUCKETS;
   static_assert(WINDOW <= 65536 && BLOCK >= NB + 2 && NB == 64, "perm holds 16-bit positions; one wave scans the NB material buckets");
@@ -1208,10 +1209,12 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
   __shared__ uint32_t tri_sorted[TRI_LDS ? WINDOW : 1];  // the hit's pool index (0xffffffff = miss) at its sorted position
   const uint32_t count = pb.counters[q * CNT_STRIDE];
   if (blockIdx.x == 0 && threadIdx.x == 0) zero_cursors(pb.counters);  // the next k_trace pulls its chunks from here
-  DevTexScene tx{};  // TEX: the scene's texture tables, four pointers in SGPRs (constant address space: s_load)
-  if constexpr (TEX) {
+  DevTexScene tx{};  // TEX / ENV: the scene's texture tables, pointers in SGPRs (constant address space: s_load)
+  if constexpr (TEX || ENV) {
     const __attribute__((address_space(4))) DevTexScene* ctx = (const __attribute__((address_space(4))) DevTexScene*)sc.tex;
-    tx.elem_uv = ctx->elem_uv; tx.textures = ctx->textures; tx.texels = ctx->texels; tx.lobe_tex = ctx->lobe_tex;
+    if constexpr (TEX) { tx.elem_uv = ctx->elem_uv; tx.textures = ctx->textures; tx.texels = ctx->texels; tx.lobe_tex = ctx->lobe_tex; }
+    else { tx.textures = ctx->textures; tx.texels = ctx->texels; }
+    if constexpr (ENV) { tx.env_tex = ctx->env_tex; tx.env_mapping = ctx->env_mapping; }
   }
   PHX_PHASE_DECL
 #if PHX_SHADE_TIMING
@@ -1413,7 +1416,12 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
         } else {
           // miss: environment lighting (deferred_shading_kernel.hpp:65-70, spt.hpp:199-202); the slot is MASKED|SHADOW in the
           // reference's shadow stream (spt.hpp:138-141): rays_masked = rays_closest - rays_shadow
-          if (sc.env_material >= 0) { const DevMaterial& m = sc.materials[sc.env_material]; add_e = v3(m.ex, m.ey, m.ez); }
+          if (sc.env_material >= 0) {
+            const DevMaterial& m = sc.materials[sc.env_material]; add_e = v3(m.ex, m.ey, m.ez);
+            // ENV: e = emission * texel at the ray's direction (environment_node.osl: environment(filename, I)); the binary64 mapping runs
+            // on this branch only
+            if constexpr (ENV) add_e = env_emission(tx.textures, tx.texels, tx.env_tex, tx.env_mapping, d, add_e);
+          }
           add_rad = true;
           if (FIRST && pb.pn) pb.pn[path] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
@@ -1669,6 +1677,14 @@ __global__ void __launch_bounds__(64) k_bsdf_sample(const DevMaterial* mat, uint
   f3[3 * i] = f.x; f3[3 * i + 1] = f.y; f3[3 * i + 2] = f.z; pdf[i] = p; flags[i] = fl;
 }
 
+__global__ void __launch_bounds__(64) k_environment_lookup(const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t mapping, float ex, float ey,
+                                                           float ez, uint32_t n, const float* dirs, float* rgb) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const v3 c = env_emission(textures, texels, tex, mapping, v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]), v3(ex, ey, ez));
+  rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+}
+
 __global__ void __launch_bounds__(64) k_texture_lookup(const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1829,6 +1845,30 @@ void launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
     return;
   }
   const dim3 g(shade_grid(sc, capacity, PHX_SHADE_BLOCK_G * PHX_SHADE_ITEMS_G, PHX_SHADE_BLOCK_G)), b(PHX_SHADE_BLOCK_G);
+  if (sc.any_tex & SC_TEX_ENV) {  // an environment image: the same kernels with the lookup on the miss branch (and the texel lookups of TEX)
+    if (sc.any_tex & SC_TEX_LOBES) {
+      if (sc.any_per_hit) {
+        if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else hipLaunchKernelGGL((k_shade_g<true, false, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      } else {
+        if (lens) hipLaunchKernelGGL((k_shade_g<false, true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<false, true, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else hipLaunchKernelGGL((k_shade_g<false, false, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      }
+    } else {
+      if (sc.any_per_hit) {
+        if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else hipLaunchKernelGGL((k_shade_g<true, false, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      } else {
+        if (lens) hipLaunchKernelGGL((k_shade_g<false, true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<false, true, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        else hipLaunchKernelGGL((k_shade_g<false, false, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      }
+    }
+    return;
+  }
   if (sc.any_tex) {  // textured scenes: the same kernel with the texel lookups compiled in
     if (sc.any_per_hit) {
       if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
@@ -1931,6 +1971,10 @@ void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags) {
   hipLaunchKernelGGL(k_bsdf_sample, dim3((n + 63) / 64), dim3(64), 0, stream, mat, n, n3, wi3, u2, wo3, f3, pdf, flags);
+}
+void launch_environment_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t mapping, float ex, float ey, float ez,
+                               uint32_t n, const float* dirs, float* rgb) {
+  hipLaunchKernelGGL(k_environment_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, mapping, ex, ey, ez, n, dirs, rgb);
 }
 void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
   hipLaunchKernelGGL(k_texture_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, n, st, rgb);

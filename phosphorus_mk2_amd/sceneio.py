@@ -14,7 +14,11 @@ per vertex when every corner's vt index is its v index, per face corner otherwis
 a corner without vt has UV (0, 0).
 
 Image textures (texture_node, baked by closures.py): `filename` is resolved relative to the YAML file and read with numpy alone —
-binary PPM (P6, 8 bit, value / 255), PFM (rows flipped to top first) or `.npy` ((H, W, 3) or (H, W) float) — as linear RGB.
+binary PPM (P6, 8 bit, value / 255), PFM (rows flipped to top first), Radiance `.hdr` (RGBE, flat or new-style run-length scanlines,
+`-Y H +X W` only) or `.npy` ((H, W, 3) or (H, W) float) — as linear RGB.
+
+Environment maps (environment_node into the world material's background_node.Cs): `world: {environment: <material>, environment-up: y|z}`
+selects OpenImageIO's lat-long layout with +y (the default) or +z up (phx_material.emission_mapping).
 """
 import math
 import os
@@ -138,9 +142,74 @@ def load_pfm(path):
     return np.ascontiguousarray(np.repeat(img, 3, axis=2) if c == 1 else img)
 
 
+def load_hdr(path):
+    """Radiance picture (#?RADIANCE / #?RGBE, FORMAT=32-bit_rle_rgbe, resolution line `-Y H +X W`) -> (H, W, 3) float32, row 0 = the
+    file's first scanline.  Scanlines are flat RGBE or new-style run-length encoded (per component; runs of count - 128 copies, else count
+    literal bytes); old-style runs, other formats and orientations raise.  Decoding is Radiance's colr_color: (m + 0.5) * 2^(e - 136)
+    per channel, and e = 0 is black."""
+    data = open(path, "rb").read()
+    lines, i = [], 0
+    while True:  # header lines up to the first empty one
+        j = data.find(b"\n", i)
+        if j < 0:
+            raise ValueError(f"{path}: truncated Radiance header")
+        line = data[i:j].rstrip(b"\r"); i = j + 1
+        if not line:
+            break
+        lines.append(line)
+    if not lines or lines[0] not in (b"#?RADIANCE", b"#?RGBE"):
+        raise ValueError(f"{path}: not a Radiance picture (#?RADIANCE / #?RGBE)")
+    for line in lines[1:]:
+        if line.startswith(b"FORMAT=") and line[7:].strip() != b"32-bit_rle_rgbe":
+            raise ValueError(f"{path}: format {line[7:].decode(errors='replace')!r} is not supported (32-bit_rle_rgbe)")
+    j = data.find(b"\n", i)
+    res = data[i:j if j >= 0 else len(data)].split()
+    if len(res) != 4 or res[0] != b"-Y" or res[2] != b"+X" or not res[1].isdigit() or not res[3].isdigit():
+        raise ValueError(f"{path}: resolution {data[i:j].decode(errors='replace')!r}: only '-Y H +X W' is supported")
+    H, W = int(res[1]), int(res[3])
+    if H == 0 or W == 0 or j < 0:
+        raise ValueError(f"{path}: empty or truncated picture")
+    buf = np.frombuffer(data, np.uint8, offset=j + 1)
+    out = np.zeros((H, W, 4), np.uint8)
+    p = 0
+    for y in range(H):
+        if 8 <= W <= 0x7fff and p + 4 <= len(buf) and buf[p] == 2 and buf[p + 1] == 2 and buf[p + 2] < 128:
+            if (int(buf[p + 2]) << 8 | int(buf[p + 3])) != W:
+                raise ValueError(f"{path}: scanline {y}: run-length length does not match the width")
+            p += 4
+            for c in range(4):
+                x = 0
+                while x < W:
+                    if p >= len(buf):
+                        raise ValueError(f"{path}: truncated scanline {y}")
+                    n = int(buf[p]); p += 1
+                    if n > 128:
+                        n -= 128
+                        if x + n > W or p >= len(buf):
+                            raise ValueError(f"{path}: scanline {y}: bad run")
+                        out[y, x:x + n, c] = buf[p]; p += 1
+                    else:
+                        if n == 0 or x + n > W or p + n > len(buf):
+                            raise ValueError(f"{path}: scanline {y}: bad literal run")
+                        out[y, x:x + n, c] = buf[p:p + n]; p += n
+                    x += n
+        else:
+            if p + 4 * W > len(buf):
+                raise ValueError(f"{path}: truncated scanline {y}")
+            row = buf[p:p + 4 * W].reshape(W, 4)
+            if ((row[:, 0] == 1) & (row[:, 1] == 1) & (row[:, 2] == 1)).any():
+                raise ValueError(f"{path}: scanline {y}: old-style run-length encoding is not supported")
+            out[y] = row; p += 4 * W
+    e = out[..., 3].astype(np.int64)
+    f = np.where(e == 0, 0.0, np.ldexp(1.0, e - 136))
+    return ((out[..., :3].astype(np.float64) + 0.5) * f[..., None]).astype(np.float32)
+
+
 def load_image(path):
-    """a texture's texels by the file's extension: .ppm, .pfm or .npy"""
+    """a texture's texels by the file's extension: .ppm, .pfm, .hdr or .npy"""
     ext = os.path.splitext(path)[1].lower()
+    if ext == ".hdr":
+        return load_hdr(path)
     if ext == ".ppm":
         return load_ppm(path)
     if ext == ".pfm":
@@ -152,7 +221,7 @@ def load_image(path):
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"{path}: expected an (H, W, 3) or (H, W) array, not {a.shape}")
         return np.ascontiguousarray(a)
-    raise ValueError(f"{path}: unsupported image format {ext!r} (.ppm, .pfm, .npy)")
+    raise ValueError(f"{path}: unsupported image format {ext!r} (.ppm, .pfm, .hdr, .npy)")
 
 
 def look_at(position, at, up):
@@ -190,7 +259,16 @@ def load_scene(path, width=1280, height=720):
     world = cfg.get("world") or {}
     if "environment" in world:
         env = ids[world["environment"]]  # import_world_data, scene.cpp:30-36
-    return SceneDesc(meshes, [baked[n] for n in names], camera, environment_material=env, name=os.path.basename(path), textures=textures)
+    up = str(world.get("environment-up", "y"))
+    if up not in ("y", "z"):
+        raise ValueError(f"{path}: world environment-up {up!r}: y or z")
+    mats = [baked[n] for n in names]
+    for i, m in enumerate(mats):
+        if m.emission_texture and i != env:
+            raise ValueError(f"{path}: material {names[i]!r} has an environment map but is not the world's environment")
+    if env >= 0:
+        mats[env].emission_mapping = abi.ENV_LATLONG_Z_UP if up == "z" else abi.ENV_LATLONG_Y_UP
+    return SceneDesc(meshes, mats, camera, environment_material=env, name=os.path.basename(path), textures=textures)
 
 
 def save_pfm(path, rgb):

@@ -34,6 +34,8 @@ class MaterialDesc:
     lobes: List[LobeDesc] = field(default_factory=list)
     emission: Tuple[float, float, float] = (0.0, 0.0, 0.0)
     is_emitter: bool = False
+    emission_texture: int = 0   # environment map: k = textures[k - 1] (the environment material only), 0 = none
+    emission_mapping: int = abi.ENV_LATLONG_Y_UP  # abi.ENV_LATLONG_*
 
 
 @dataclass
@@ -111,6 +113,7 @@ class SceneDesc:
             mats[i].num_lobes = len(m.lobes)
             mats[i].is_emitter = 1 if m.is_emitter else 0
             mats[i].emission[:] = [np.float32(x) for x in m.emission]
+            mats[i].emission_texture, mats[i].emission_mapping = m.emission_texture, m.emission_mapping
             for j, l in enumerate(m.lobes):
                 d = mats[i].lobes[j]
                 d.type = l.type
@@ -473,6 +476,45 @@ def textured_showroom(n=500_000, width=1920, height=1080, tex_size=2048, baked=F
         mat.lobes[0].texture = len(textures)
     s.textures = textures
     s.name = f"textured_showroom{n}" + ("_baked" if baked else "")
+    return s
+
+
+def procedural_sky(width=2048, height=1024, sun_elevation=0.5, sun_azimuth=0.6, sun_radius=0.035, sun=(1500.0, 1350.0, 1100.0)):
+    """A lat-long HDR sky (height, width, 3) f32 for abi.ENV_LATLONG_Y_UP: texel (i, j) holds the direction of s = (i + 0.5) / W,
+    t = (j + 0.5) / H, elevation pi (0.5 - t) and azimuth 2 pi (s - 0.5) measured from +z towards -x.  A blue gradient from the
+    horizon to the zenith, a darker ground below the horizon and a small, bright sun disc (`sun_radius` radians, radiance `sun`)."""
+    s = (np.arange(width, dtype=np.float64) + 0.5) / width
+    t = (np.arange(height, dtype=np.float64) + 0.5) / height
+    el = np.pi * (0.5 - t)[:, None] * np.ones((1, width))
+    az = 2.0 * np.pi * (s - 0.5)[None, :] * np.ones((height, 1))
+    d = np.stack([-np.cos(el) * np.sin(az), np.sin(el), np.cos(el) * np.cos(az)], -1)
+    up = np.clip(np.sin(el), 0.0, 1.0)[..., None]
+    horizon, zenith, ground = np.array([0.9, 0.95, 1.0]), np.array([0.15, 0.35, 0.9]), np.array([0.25, 0.22, 0.2])
+    img = np.where(el[..., None] >= 0.0, horizon + (zenith - horizon) * np.sqrt(up), ground * (1.0 + 0.5 * np.sin(el)[..., None]))
+    sd = np.array([-np.cos(sun_elevation) * np.sin(sun_azimuth), np.sin(sun_elevation), np.cos(sun_elevation) * np.cos(sun_azimuth)])
+    img = np.where((d @ sd >= np.cos(sun_radius))[..., None], np.asarray(sun, np.float64), img)
+    return img.astype(np.float32)
+
+
+def environment_showroom(n=500_000, width=1920, height=1080, sky=(2048, 1024), mode="image"):
+    """The OPEN showroom (showroom() with showroom_materials() on its spheres, its ceiling light kept) lit through its open side by
+    procedural_sky(*sky) as a Y-up lat-long environment map.  mode "image": the sky image; "mean": a 1 x 1 image of the sky's mean (the
+    same kernels, whose lookups then read one texel); "constant": no image, the environment's emission is the sky's mean (the kernels
+    without the environment lookup)."""
+    s = showroom(n, width=width, height=height, materials=showroom_materials())
+    img = procedural_sky(*sky)
+    mean = img.reshape(-1, 3).mean(0, dtype=np.float64).astype(np.float32)
+    if mode == "constant":
+        s.materials.append(MaterialDesc(lobes=[], emission=tuple(float(x) for x in mean)))
+    else:
+        if mode == "mean":
+            img = mean.reshape(1, 1, 3)
+        elif mode != "image":
+            raise ValueError(f"mode {mode!r}: image, mean or constant")
+        s.textures = [TextureDesc(img, abi.TEX_LINEAR, abi.WRAP_PERIODIC, abi.WRAP_CLAMP)]
+        s.materials.append(MaterialDesc(lobes=[], emission=(1.0, 1.0, 1.0), emission_texture=1, emission_mapping=abi.ENV_LATLONG_Y_UP))
+    s.environment_material = len(s.materials) - 1
+    s.name = f"environment_showroom{n}_{mode}"
     return s
 
 

@@ -308,6 +308,15 @@ class HipDevice:
                "phx_dev_texture_lookup")
         return out
 
+    def environment_lookup(self, dirs):
+        """The shade kernel's environment on a miss, on the device: e = emission * texel(s, t) of the preprocessed scene's environment
+        image at directions dirs (n, 3) -> rgb (n, 3) f32 (phx_dev_environment_lookup; DeviceError when the environment has no image)."""
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros((len(dirs), 3), np.float32)
+        _check(self._lib, self._lib.phx_dev_environment_lookup(self._h, len(dirs), dirs.ctypes.data_as(abi.f32p), out.ctypes.data_as(abi.f32p)),
+               "phx_dev_environment_lookup")
+        return out
+
     def bvh_pool(self):
         """the acceleration structure as the kernels read it: (uint32 array [elements, 16], grid lo[3], grid cell[3]) — phx_dev_copy_bvh"""
         n = C.c_uint64(0); grid = np.zeros(6, np.float32)
