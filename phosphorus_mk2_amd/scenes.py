@@ -423,6 +423,46 @@ def showroom(n, seed=5, width=1280, height=720, materials=None, closed=False):
     return SceneDesc(meshes, mats, CameraDesc(width, height, 1.9), name=f"showroom{n}{'_closed' if closed else ''}")
 
 
+def deep_comb(n=400, ratio=1.08, width=64, height=48, material=None, lamp=True):
+    """A scene whose BVH is DEEP, so that k_trace's stack reaches the levels it keeps in HBM: a geometric comb of n triangles at
+    x_i = ratio^i (i = 0 .. n - 1), each in the plane x = x_i, facing the origin (geometric normal -x) and 0.5 x_i across, so that every
+    one subtends the same angle from the origin.  The binned SAH builder peels such a comb into a chain (depth 16 for 400 x 1.08 and for
+    200 x 1.2), and a ray that travels +x along it pushes one pending sibling group per level.  Past x ~ 1e13 the fp32 products of the
+    triangle test (~x^3) overflow, so rays that far out miss; keep ratio^n near the defaults'.  `material` is the comb's (default: sharp
+    glass, IoR 1.45, whose refracted rays carry on down the comb); `lamp` adds a 2 x 2 emissive quad at x = -0.3 facing +x, behind the
+    camera.  The camera stands at the origin and looks down +x (fov 0.6)."""
+    x = (np.float64(ratio) ** np.arange(int(n), dtype=np.float64))[:, None]
+    # equilateral, side 0.5 x_i, centred on the x axis; (b - a) x (c - a) points -x, towards the camera
+    h, c = 0.25 * x, x / (4.0 * math.sqrt(3.0))  # half the side; the centre's distance from a side
+    verts = np.stack([np.concatenate([x, h, -c], 1), np.concatenate([x, -h, -c], 1), np.concatenate([x, 0.0 * x, 2.0 * c], 1)], 1).astype(np.float32)
+    faces = np.arange(3 * int(n), dtype=np.uint32).reshape(-1, 3)
+    mats = [material if material is not None else glass(1.45)]
+    meshes = [MeshDesc(vertices=verts.reshape(-1, 3), faces=faces, sets=[(0, np.arange(int(n), dtype=np.uint32))])]
+    if lamp:
+        mats.append(emitter(*LE))
+        meshes.append(_quad((-0.3, -1.0, -1.0), (-0.3, 1.0, -1.0), (-0.3, 1.0, 1.0), (-0.3, -1.0, 1.0), 1))  # n = +x
+    sc = SceneDesc(meshes, mats, CameraDesc(width, height, 0.6), name=f"deep_comb{int(n)}")
+    # the camera turned a quarter turn to the right about y: (0, 0, -1) -> (1, 0, 0) (CameraDesc.to_world, Imath row-vector convention)
+    M = np.eye(4, dtype=np.float32)
+    M[:3, :3] = np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], np.float32)
+    sc.camera.to_world = M
+    return sc
+
+
+def deep_comb_rays(count, n=400, ratio=1.08, seed=0):
+    """`count` rays of deep_comb(n, ratio) that travel +x along it: each starts just past a random triangle k of the comb with x_k <= 1e12,
+    off the axis by up to a third of that triangle's inradius, so that it hits triangle k + 1.  (Further out the fp32 products of the
+    triangle test, ~x^3, overflow: the device and the oracle then agree on a miss.)  -> (o, d, tmax = FLT_MAX) float32 arrays; a walk down
+    the comb takes one stack level per level of the tree."""
+    rng = np.random.default_rng(seed)
+    kmax = min(int(n) - 1, int(math.floor(12.0 / math.log10(ratio))))
+    x = np.float64(ratio) ** rng.integers(0, kmax, count)
+    off = rng.uniform(-1.0, 1.0, (count, 2)) * (x / (12.0 * math.sqrt(3.0)))[:, None]
+    o = np.concatenate([(x * (1.0 + 1e-3))[:, None], off], 1).astype(np.float32)
+    d = np.tile(np.array([[1.0, 0.0, 0.0]], np.float32), (count, 1))
+    return o, d, np.full(count, np.finfo(np.float32).max, np.float32)
+
+
 def showroom_materials(per_hit_glass=True):
     """the 16 closure recipes of the BMW stand-in (closure_zoo() + four diffuse tints) plus Blender's glass node twice — sharp
     (IoR 1.45) and frosted (IoR 1.33, roughness 0.2) — whose closure weights depend on the hit (k_shade_g<PERHIT>): 18 materials.

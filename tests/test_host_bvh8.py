@@ -171,3 +171,40 @@ def test_any_hit_answers_do_not_depend_on_the_visiting_order(host_bvh8):
     host_bvh8.hb8_free(h4)
     assert info4[0] > 1.5 * info8[0] and info4[1] == info8[1] == len(abc) and info4[2] > info8[2]  # more, narrower nodes; every triangle once
     assert np.array_equal(full["prim"], narrow["prim"]) and bits_equal(full["t"], narrow["t"]) and narrow["node_visits"] > full["node_visits"]
+
+
+SPILL_LDS_LEVELS = 7  # kernels.hip: PHX_SPILL_LDS_LEVELS, the stack levels k_trace's SPILL plan keeps in LDS (the rest live in HBM)
+
+
+@pytest.mark.parametrize("n,ratio,lamp", [(400, 1.08, True), (200, 1.2, True), (400, 1.08, False)])
+def test_deep_comb_walks_reach_the_spilled_stack_levels(host_bvh8, orc, n, ratio, lamp):
+    """scenes.deep_comb: the host builder peels the comb into a chain (depth >= 14), and a ray that travels +x along it takes one stack
+    level per level — past the 7 that k_trace's SPILL plan keeps in LDS, never past depth - 1.  Closest and any hits along the chain
+    are the oracle's (brute force and stream traversal, device tie rule) bit for bit: the walk the GPU tests render is the right one."""
+    from phosphorus_mk2_amd import scenes
+    sc = scenes.deep_comb(n, ratio, lamp=lamp)
+    abc = tri_abc(sc)
+    h = host_bvh8.hb8_build(fp(abc), len(abc), 4)
+    info = (C.c_uint64 * 3)(); host_bvh8.hb8_info(h, info)
+    depth = info[2]
+    o, d, tm = scenes.deep_comb_rays(20000, n, ratio, seed=5)
+    g = trace(host_bvh8, h, o, d, tm)
+    print(f"\n[comb {n} x {ratio}, lamp {lamp}] host tree depth {depth}, {info[0]} nodes; +x rays: max stack {g['max_stack']}")
+    assert info[1] == len(abc) and depth >= 14
+    assert SPILL_LDS_LEVELS + 4 <= g["max_stack"] <= depth - 1
+    hit = g["prim"] != 0xffffffff
+    assert hit.mean() > 0.99 and (g["prim"][hit] < n).all()
+    tm2 = (o[:, 0] * np.float32(ratio - 1.0) * np.random.default_rng(6).uniform(0.0, 2.0, len(o)).astype(np.float32)).astype(np.float32)
+    a = trace(host_bvh8, h, o, d, tm2, any_hit=True)
+    host_bvh8.hb8_free(h)
+    orc.set_tie_rule(1)
+    try:
+        O = orc.Oracle(sc, spp=1)
+        for brute in (True, False):
+            r = O.trace(o, d, tm, brute=brute)
+            assert np.array_equal(g["prim"], r["prim"]) and bits_equal(g["t"], r["t"]) and bits_equal(g["u"], r["u"]) and bits_equal(g["v"], r["v"])
+            b = O.trace(o, d, tm2, shadow=True, brute=brute)
+            assert np.array_equal(a["prim"] != 0xffffffff, b["hit"])
+    finally:
+        orc.set_tie_rule(0)
+    assert 0.2 < b["hit"].mean() < 0.8
