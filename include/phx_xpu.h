@@ -90,7 +90,19 @@ typedef struct phx_lobe {
    *   fac = fresnel_dielectric(dot(I, N), backfacing ? 1 / max(1e-5, fac_ior) : max(1e-5, fac_ior))      (src/shaders/fresnel.h)
    * and the closure's weight is (pre_weight * term) * weight with term = fac (PHX_FAC_MIX_B) or 1 - fac (PHX_FAC_MIX_A), in the
    * order material_t::eval_closure multiplies down the tree (src/material.cpp:218-305); a closure whose weight comes out all
-   * zero is not there at that hit (OSL: closure * 0 is the null closure).  PHX_FAC_NONE: weight is the whole constant weight. */
+   * zero is not there at that hit (OSL: closure * 0 is the null closure).  PHX_FAC_NONE: weight is the whole constant weight.
+   *
+   * Image mask (texture_node.Cout -> luminance_node.in, luminance_node.out -> mix_closure_node.fac: src/shaders/luminance_node.osl is the
+   * node set's only colour -> float node): the low byte of fac_mode is the mode, PHX_FAC_TEX_B or PHX_FAC_TEX_A, and bits 8..31 name the
+   * mask image, 1-based into phx_scene.textures (PHX_FAC_PACK(mode, k), PHX_FAC_MODE, PHX_FAC_TEXTURE).  At every surface hit with
+   * interpolated mesh UV (s, t)
+   *   c   = the phx_texture lookup of image k at (s, t), with the image's own filter and wrap modes
+   *   fac = (c.r * 0.2126f + c.g * 0.7152f) + c.b * 0.0722f        (fp32, in this order, no contraction; NOT clamped)
+   * and term = fac (PHX_FAC_TEX_B) or 1 - fac (PHX_FAC_TEX_A); the weight is (pre_weight * term) * (weight * colour texel), the colour
+   * texel being 1 without `texture`, and a lobe whose weight comes out all zero is not there at that hit (it counts neither in the lobe
+   * choice of bsdf_t::sample nor in bsdf_t::f).  A restatement, not pinned to OSL's object code.  fac_ior is ignored for the two image
+   * modes; bits 8..31 must be zero for the other modes; one lobe has one factor (Fresnel or image), different lobes of one material may
+   * differ.  Like `texture`, not allowed on the lobes of emitters or of the environment material; a mesh without UVs has (s, t) = (0, 0). */
   uint32_t fac_mode;
   float    fac_ior;
   float    pre_weight[3]; /* product of the constant weights ABOVE the hit-dependent factor in the closure tree */
@@ -100,7 +112,10 @@ typedef struct phx_lobe {
    * zero is not there at that hit.  Not allowed on the lobes of emitters or of the environment material. */
   uint32_t texture;
 } phx_lobe;
-enum { PHX_FAC_NONE = 0, PHX_FAC_MIX_B = 1, PHX_FAC_MIX_A = 2 };
+enum { PHX_FAC_NONE = 0, PHX_FAC_MIX_B = 1, PHX_FAC_MIX_A = 2, PHX_FAC_TEX_B = 3, PHX_FAC_TEX_A = 4 };
+#define PHX_FAC_MODE(x)       ((uint32_t)(x) & 0xffu)               /* the mode of a phx_lobe.fac_mode word */
+#define PHX_FAC_TEXTURE(x)    ((uint32_t)(x) >> 8)                  /* its mask image: 0 = none, k = phx_scene.textures[k - 1] */
+#define PHX_FAC_PACK(mode, k) (((uint32_t)(mode) & 0xffu) | ((uint32_t)(k) << 8))
 
 typedef struct phx_material {
   uint32_t num_lobes;   /* 0 for pure emitters (diffuse_emitter_node.osl) */
@@ -183,7 +198,7 @@ typedef struct phx_scene {
   const phx_material* materials;
   int32_t             environment_material; /* -1 = none (scene_t::environment, src/scene.cpp:126) */
   phx_camera          camera;
-  uint32_t            num_textures;  /* phx_lobe.texture indexes this table (1-based) */
+  uint32_t            num_textures;  /* phx_lobe.texture, the mask of phx_lobe.fac_mode and phx_material.emission_texture index this table (1-based) */
   const phx_texture*  textures;
 } phx_scene;
 
@@ -319,7 +334,8 @@ int phx_dev_trace(phx_device* dev, uint32_t n, const float* o, const float* d, c
                   int shadow, float* t, float* u, float* v, uint32_t* prim, uint8_t* hit);
 
 /* bsdf_t::f (src/bsdf.cpp:113-131) and bsdf_t::sample (:133-248) evaluated on the device for
- * material `material` with shading normal n[i]: KAT hooks.  Vectors are xyz per item. */
+ * material `material` with shading normal n[i]: KAT hooks.  Vectors are xyz per item.  They take no texture coordinates: a colour
+ * texture is left out (the baked weight is used) and a material with image-masked lobes is PHX_ERR_ARG. */
 int phx_dev_bsdf_f(phx_device* dev, uint32_t material, uint32_t n_items, const float* n,
                    const float* wi, const float* wo, float* f_out);
 int phx_dev_bsdf_sample(phx_device* dev, uint32_t material, uint32_t n_items, const float* n,
@@ -328,9 +344,17 @@ int phx_dev_bsdf_sample(phx_device* dev, uint32_t material, uint32_t n_items, co
 
 /* The image lookup the shade kernel applies to a textured lobe, run on the device for texture `texture` (0-based index into
  * phx_scene.textures of the preprocessed scene) at n coordinates st (s, t per item): rgb per item.  A parity hook like phx_dev_bsdf_f.
- * The texture table is uploaded only when some lobe of the preprocessed scene is textured or its environment has an image: for any
+ * The texture table is uploaded only when some lobe of the preprocessed scene is textured or masked, or its environment has an image: for any
  * other scene every call returns PHX_ERR_ARG, as does an index past the table. */
 int phx_dev_texture_lookup(phx_device* dev, uint32_t texture, uint32_t n, const float* st, float* rgb);
+
+/* The closure weights of a hit as the shade kernel resolves them: for every baked lobe of material `material` of the preprocessed scene (its
+ * surface closures in table order; emission / background entries are not lobes) the weight at shading normal n[i], view direction wi[i]
+ * (hits.wi) and texture coordinates st[i] — Fresnel factor, colour texture and image mask alike.  w receives PHX_MAX_LOBES x 3 floats per
+ * item (zero past the material's lobes); bit k of kept[i] is set when lobe k is there at that hit.  st is not read (and may be NULL) for a
+ * scene in which no lobe has a texture or a mask.  A parity hook.  PHX_ERR_STATE before preprocess, PHX_ERR_ARG for a material out of range. */
+int phx_dev_lobe_weights(phx_device* dev, uint32_t material, uint32_t n_items, const float* n, const float* wi, const float* st,
+                         float* w, uint32_t* kept);
 
 /* The environment's e on a miss as the shade kernel computes it (phx_material.emission_texture: mapping, lookup and multiply), run on
  * the device for n directions dirs (x, y, z per item) against the preprocessed scene's environment: rgb per item.  A parity hook.

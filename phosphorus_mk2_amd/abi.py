@@ -11,7 +11,24 @@ LOBE_EMISSIVE, LOBE_DIFFUSE, LOBE_OREN_NAYAR, LOBE_REFLECTION = 0, 1, 2, 4
 LOBE_REFRACTION, LOBE_MICROFACET, LOBE_SHEEN, LOBE_BACKGROUND, LOBE_TRANSPARENT = 8, 16, 32, 64, 128
 BSDF_DIFFUSE, BSDF_GLOSSY, BSDF_SPECULAR, BSDF_REFLECT, BSDF_TRANSMIT = 1, 2, 4, 8, 16
 MAX_LOBES = 8
-FAC_NONE, FAC_MIX_B, FAC_MIX_A = 0, 1, 2
+FAC_NONE, FAC_MIX_B, FAC_MIX_A, FAC_TEX_B, FAC_TEX_A = 0, 1, 2, 3, 4
+
+
+def fac_pack(mode, texture=0):
+    """PHX_FAC_PACK: a phx_lobe.fac_mode word from a mode and, for the FAC_TEX_* modes, the mask image (1-based into the scene's textures)"""
+    return (int(mode) & 0xff) | (int(texture) << 8)
+
+
+def fac_mode(word):
+    """PHX_FAC_MODE"""
+    return int(word) & 0xff
+
+
+def fac_texture(word):
+    """PHX_FAC_TEXTURE"""
+    return int(word) >> 8
+
+
 BVH_AUTO, BVH_DEVICE_LBVH, BVH_HOST_SAH = 0, 1, 2
 MESH_UV_PER_VERTEX, MESH_NORMALS_PER_VERTEX = 1, 2
 TEX_LINEAR, TEX_CLOSEST = 0, 1
@@ -120,7 +137,7 @@ EXPORTS = [
     "phx_discover", "phx_dev_make", "phx_dev_preprocess", "phx_dev_start", "phx_dev_join", "phx_dev_destroy",
     "phx_last_error", "phx_dev_get_stats", "phx_tiles_make", "phx_tiles_next", "phx_tiles_count", "phx_tiles_reset",
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
-    "phx_dev_texture_lookup", "phx_dev_environment_lookup",
+    "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
 ]
 
 
@@ -147,5 +164,6 @@ def declare(lib):
     lib.phx_dev_bsdf_sample.restype = C.c_int
     lib.phx_dev_texture_lookup.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p]; lib.phx_dev_texture_lookup.restype = C.c_int
     lib.phx_dev_environment_lookup.argtypes = [vp, C.c_uint32, f32p, f32p]; lib.phx_dev_environment_lookup.restype = C.c_int
+    lib.phx_dev_lobe_weights.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, u32p]; lib.phx_dev_lobe_weights.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

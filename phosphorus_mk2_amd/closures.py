@@ -40,7 +40,15 @@ roughness, emission, another texture) raises.  The third is an environment map: 
 It bakes into the material's `emission` (the constant weight accumulated above it, `power` included) and `emission_texture` (k + 1
 for the spec {filename, swrap periodic, twrap clamp}: OpenImageIO's lat-long wrap); the device multiplies the texel at the ray's
 direction in on a miss.  Blur, an environment_node anywhere but a background's Cs and a texture_node into a background (a miss has
-no UV) raise.  Other hit-dependent inputs (noise, normal maps) raise.
+no UV) raise.  The fourth is an image mask on a mix: `texture_node.Cout -> luminance_node.in`, `luminance_node.out -> mix_closure_node.fac`
+(luminance_node is the node set's only colour -> float node, so the only way an image reaches a float input).
+  luminance_node.osl                out = in[0] * 0.2126 + in[1] * 0.7152 + in[2] * 0.0722
+The closures under that mix carry `fac_mode` FAC_TEX_A (A's side, 1 - fac) / FAC_TEX_B (B's side, fac), `fac_texture` (k + 1 in the
+`textures` list, with the texture node's wrap modes) and `pre_weight`, like the Fresnel mix; the device looks the mask up at every hit.
+A constant colour into luminance_node folds to a constant fac.  One closure takes ONE hit-dependent factor: a mask under a mask, a
+mask over or under a Fresnel mix, emission or background under a masked mix raise, and so does luminance_node.out into anything but a
+mix's fac or an environment_node into luminance_node.  A colour texture on a closure's Cs under a masked mix is fine (both indices on one
+lobe).  Other hit-dependent inputs (noise, normal maps) raise.
 """
 import math
 
@@ -80,8 +88,14 @@ class Fac:
         self.ior = f32(ior)
 
 
+class Lum:
+    """the output of a luminance_node driven by a texture_node: a float known only at the hit (the luminance of the image at the hit's UV)"""
+    def __init__(self, tex):
+        self.tex = tex
+
+
 class MulFac:
-    """closure * fac (mode FAC_MIX_B) or closure * (1 - fac) (mode FAC_MIX_A) with fac a Fac"""
+    """closure * fac (mode FAC_MIX_B / FAC_TEX_B) or closure * (1 - fac) (mode FAC_MIX_A / FAC_TEX_A) with fac a Fac / a Lum"""
     def __init__(self, mode, fac, closure):
         self.mode, self.fac, self.closure = mode, fac, closure
 
@@ -181,6 +195,19 @@ def fresnel_dielectric_node(IoR=1.45, **_):
     return Fac(IoR)
 
 
+def luminance_node(**inputs):
+    """out = in[0] * 0.2126 + in[1] * 0.7152 + in[2] * 0.0722 in fp32, in this order (`in` is no Python identifier: it arrives by name)"""
+    c = inputs.pop("in", 0.0)
+    if isinstance(c, Env):
+        raise ValueError("an environment_node can drive only the Cs of a background_node")
+    if isinstance(c, Tex):
+        return Lum(c)
+    if inputs or not (np.isscalar(c) or isinstance(c, (dict, list, tuple, np.ndarray))):
+        raise ValueError("luminance_node: its input `in` takes a constant colour or a texture_node")
+    c = _color(c)
+    return f32(f32(f32(c[0] * f32(0.2126)) + f32(c[1] * f32(0.7152))) + f32(c[2] * f32(0.0722)))
+
+
 WRAPS = {"periodic": abi.WRAP_PERIODIC, "clamp": abi.WRAP_CLAMP, "black": abi.WRAP_BLACK}
 
 
@@ -210,6 +237,8 @@ def environment_node(filename="", sblur=0.0, tblur=0.0, **extra):
 def mix_closure_node(A=None, B=None, fac=0.5, **_):
     if isinstance(fac, Fac):  # Cout = A * (1 - fac) + B * fac with fac evaluated per hit
         return add(MulFac(abi.FAC_MIX_A, fac, A) if A is not None else None, MulFac(abi.FAC_MIX_B, fac, B) if B is not None else None)
+    if isinstance(fac, Lum):  # the same mix with fac the luminance of an image at the hit
+        return add(MulFac(abi.FAC_TEX_A, fac, A) if A is not None else None, MulFac(abi.FAC_TEX_B, fac, B) if B is not None else None)
     if not np.isscalar(fac) or isinstance(fac, (Tex, Env)):
         raise ValueError("mix_closure_node.fac is driven by a node this baker cannot express (hit-dependent)")
     fac = f32(fac)
@@ -222,7 +251,7 @@ def add_node(A=None, B=None, **_):
 
 NODES = {f.__name__: f for f in (diffuse_bsdf_node, glossy_bsdf_node, refraction_bsdf_node, sheen_bsdf_node, transparent_bsdf_node,
                                  diffuse_emitter_node, background_node, mix_closure_node, add_node, fresnel_dielectric_node, texture_node,
-                                 environment_node)}
+                                 environment_node, luminance_node)}
 # the nodes whose Cs a texture may drive: their closure's weight is Cs
 TEXTURABLE = {diffuse_bsdf_node, glossy_bsdf_node, refraction_bsdf_node, sheen_bsdf_node, transparent_bsdf_node}
 UNBAKEABLE = {"fresnel_node", "normal_map_node", "random_noise_2d_node", "random_noise_3d_node",
@@ -236,7 +265,8 @@ def flatten(tree, textures=None):
     splits a closure's weight into the constant part above it (pre_weight), the factor itself (fac_mode, fac_ior) and the
     constant part below it (weight): at a hit the weight is (pre_weight * term) * weight, the same order of multiplications.
     A texture on a closure's colour: the lobe keeps the weight accumulated above it and `texture` = k + 1, k the texture's entry in
-    `textures` (a list of {filename, swrap, twrap}, extended here by the ones not in it yet)."""
+    `textures` (a list of {filename, swrap, twrap}, extended here by the ones not in it yet).  An image mask is a factor like the Fresnel
+    one with the image in place of the ior: fac_mode FAC_TEX_*, `fac_texture` = k + 1 in the same list."""
     lobes, state = [], {"e": (0.0, 0.0, 0.0), "emitter": False, "env": 0}
     if textures is None:
         textures = []
@@ -248,7 +278,7 @@ def flatten(tree, textures=None):
 
     def visit(c, w, fac=None, tex=0, env=0):
         # w: the constant weight accumulated so far BELOW the hit-dependent factor (or all of it when there is none);
-        # fac = (mode, ior, pre): the factor met on the way down and the constant weight accumulated ABOVE it
+        # fac = (mode, ior, pre, mask): the factor met on the way down (its ior, or its mask image k + 1) and the constant weight accumulated ABOVE it
         if c is None:
             return
         if isinstance(c, Mul):
@@ -260,18 +290,25 @@ def flatten(tree, textures=None):
                 raise ValueError("a texture behind another texture on one closure is not supported")
             visit(c.closure, w, fac, texture_id(c.tex.spec))
         elif isinstance(c, MulFac):
+            masked = isinstance(c.fac, Lum)
             if fac is not None:
+                if masked or fac[3]:
+                    raise ValueError("an image-masked mix and another hit-dependent mix (a mask or a Fresnel factor) on one closure: "
+                                     "two hit-dependent factors on one closure are not supported")
                 raise ValueError("a Fresnel-driven mix below another one: two hit-dependent factors on one closure are not supported")
             if tex:
                 raise ValueError("a Fresnel-driven mix below a texture is not supported")
-            visit(c.closure, np.ones(3, f32), (c.mode, c.fac.ior, w))
+            if masked:
+                visit(c.closure, np.ones(3, f32), (c.mode, f32(0), w, texture_id(c.fac.tex.spec)))
+            else:
+                visit(c.closure, np.ones(3, f32), (c.mode, c.fac.ior, w, 0))
         elif isinstance(c, Add):
             visit(c.a, w, fac, tex, env)
             visit(c.b, w, fac, tex, env)
         else:
             if c.cid in (abi.LOBE_EMISSIVE, abi.LOBE_BACKGROUND):
                 if fac is not None:
-                    raise ValueError("emission under a Fresnel-driven mix is not supported")
+                    raise ValueError("emission under an image-masked mix is not supported" if fac[3] else "emission under a Fresnel-driven mix is not supported")
                 if tex:
                     raise ValueError("textured emission is not supported")
                 state["e"] = tuple(float(x) for x in w)  # assignment: a later emission overwrites an earlier one
@@ -283,7 +320,7 @@ def flatten(tree, textures=None):
                 raise ValueError(f"unsupported distribution {p['distribution']!r} (src/bsdf.cpp:53-71)")
             extra = {}
             if fac is not None:
-                extra = {"fac_mode": int(fac[0]), "fac_ior": float(fac[1]), "pre_weight": tuple(float(x) for x in fac[2])}
+                extra = {"fac_mode": int(fac[0]), "fac_ior": float(fac[1]), "pre_weight": tuple(float(x) for x in fac[2]), "fac_texture": int(fac[3])}
             lobes.append(LobeDesc(c.cid, tuple(float(x) for x in w), alpha=float(p.get("alpha", 0.0)), eta=float(p.get("eta", 0.0)),
                                   xalpha=float(p.get("xalpha", 0.0)), yalpha=float(p.get("yalpha", 0.0)), refract=int(p.get("refract", 0)),
                                   r=float(p.get("r", 0.0)), texture=tex, **extra))
@@ -328,10 +365,13 @@ def bake_material(desc, textures=None):
             fn, params = layers[layer]
             args = dict(params)
             for slot, src_layer, src_slot in edges.get(layer, []):
-                if src_slot not in ("Cout", "out") or (src_slot == "out" and layers[src_layer][0] is not fresnel_dielectric_node):
-                    raise ValueError(f"connection from {src_layer}.{src_slot}: only closure outputs (Cout) and fresnel_dielectric_node.out can be expressed")
-                if layers[src_layer][0] is texture_node and (slot != "Cs" or fn not in TEXTURABLE):
-                    raise ValueError(f"texture {src_layer}.Cout into {layer}.{slot}: a texture can drive only the Cs of a BSDF node")
+                if src_slot not in ("Cout", "out") or (src_slot == "out" and layers[src_layer][0] not in (fresnel_dielectric_node, luminance_node)):
+                    raise ValueError(f"connection from {src_layer}.{src_slot}: only closure outputs (Cout), fresnel_dielectric_node.out and luminance_node.out can be expressed")
+                if layers[src_layer][0] is luminance_node and (src_slot != "out" or slot != "fac" or fn is not mix_closure_node):
+                    raise ValueError(f"luminance {src_layer}.{src_slot} into {layer}.{slot}: luminance_node.out can drive only the fac of a mix_closure_node")
+                to_mask = fn is luminance_node and slot == "in"  # texture_node.Cout -> luminance_node.in: the one way an image reaches a mix's fac
+                if layers[src_layer][0] is texture_node and not to_mask and (slot != "Cs" or fn not in TEXTURABLE):
+                    raise ValueError(f"texture {src_layer}.Cout into {layer}.{slot}: a texture can drive only the Cs of a BSDF node or a luminance_node")
                 if layers[src_layer][0] is environment_node and (slot != "Cs" or fn is not background_node):
                     raise ValueError(f"environment {src_layer}.Cout into {layer}.{slot}: an environment map can drive only the Cs of a background_node")
                 args[slot] = evaluate(src_layer)

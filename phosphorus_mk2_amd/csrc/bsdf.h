@@ -29,8 +29,8 @@ struct DevLobe {       // a lobe after add_lobe()/precompute() (src/bsdf.hpp:54-
   float xalpha, yalpha;
   uint32_t refract;
   float r;             // sheen roughness
-  uint32_t fac_mode;   // PHX_FAC_*: per-hit Fresnel mix factor on the weight (material_at_hit)
-  float fac_ior;
+  uint32_t fac_mode;   // PHX_FAC_* (the mode byte alone): per-hit mix factor on the weight — Fresnel (1, 2) or the luminance of an image (3, 4)
+  float fac_ior;       // Fresnel modes: the ior.  Image modes: the BITS of this word are the mask's texture + 1 (lobe_mask_texture)
   float px, py, pz;    // constant weights above the factor in the closure tree
 };
 struct DevMaterial {
@@ -210,10 +210,21 @@ PHX_HD v3 env_emission(const DevTexture* textures, const float4* texels, uint32_
   return v3(emission.x * c.x, emission.y * c.y, emission.z * c.z);
 }
 
+// ---- image masks on closure mixes (PHX_FAC_TEX_B / PHX_FAC_TEX_A; k_shade_g<.., MASK>) ------------------------------------------
+enum { FAC_NONE = 0, FAC_MIX_B = 1, FAC_MIX_A = 2, FAC_TEX_B = 3, FAC_TEX_A = 4 };  // the mode byte of phx_lobe.fac_mode
+PHX_HD uint32_t bits_of(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+PHX_HD float float_of_bits(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
+// texture + 1 of a masked lobe's image: the mode has no ior, so the index travels in that word (DevLobe keeps its 64 bytes)
+template <typename LobeT>
+PHX_HD uint32_t lobe_mask_texture(const LobeT& l) { return bits_of(l.fac_ior); }
+// luminance_node.osl: the mix factor an image gives, fp32 in this order
+PHX_HD float mask_luminance(const v3& c) { return (c.x * 0.2126f + c.y * 0.7152f) + c.z * 0.0722f; }
+
 // lobe_weight_at_hit for lobe i of material m, with the image texture of a textured lobe (TEX): weight * texel first, then the per-hit
 // factor on that product, (pre * term) * (weight * texel); a textured lobe whose weight comes out all zero is not there at the hit.
-// TEX = false is lobe_weight_at_hit itself.
-template <bool PERHIT, bool TEX, typename MatT, typename LobeT>
+// TEX = false is lobe_weight_at_hit itself.  MASK (with PERHIT and TEX): the factor of a lobe in an image mode is the luminance of its mask's
+// texel at the hit's (s, t), looked up here like the colour texel (nothing is kept per hit); it is not clamped.
+template <bool PERHIT, bool TEX, bool MASK = false, typename MatT, typename LobeT>
 PHX_HD bool lobe_weight_of(const MatT& m, uint32_t i, const LobeT& l, const v3& n, const v3& view, v3& w, const TexHit& th) {
   if constexpr (!TEX) {
     return lobe_weight_at_hit<PERHIT>(l, n, view, w);
@@ -223,6 +234,19 @@ PHX_HD bool lobe_weight_of(const MatT& m, uint32_t i, const LobeT& l, const v3& 
     if (textured) {
       const v3 c = tex_lookup(th.textures, th.texels, th.lobe_tex[i] - 1u, th.s, th.t);
       w = v3(l.wx * c.x, l.wy * c.y, l.wz * c.z);
+    }
+    if constexpr (MASK) {
+      static_assert(PERHIT, "a mask is a per-hit factor");
+      const uint32_t mode = l.fac_mode;
+      if (mode != 0u) {
+        float fac;
+        if (mode >= (uint32_t)FAC_TEX_B) fac = mask_luminance(tex_lookup(th.textures, th.texels, lobe_mask_texture(l) - 1u, th.s, th.t));
+        else fac = fresnel_mix_factor(l.fac_ior, n, view);
+        const float term = (mode & 1u) ? fac : 1.0f - fac;  // MIX_B, TEX_B: fac; MIX_A, TEX_A: 1 - fac
+        w = v3((l.px * term) * w.x, (l.py * term) * w.y, (l.pz * term) * w.z);
+        if (w.x == 0.0f && w.y == 0.0f && w.z == 0.0f) return false;
+      }
+      return !(textured && w.x == 0.0f && w.y == 0.0f && w.z == 0.0f);
     }
     if (PERHIT && l.fac_mode != 0u) {
       const float fac = fresnel_mix_factor(l.fac_ior, n, view);
@@ -425,7 +449,7 @@ PHX_HD float lobe_eval(const LobeT& p, const v3& n, const Frame& fr, const v3& w
 // The tangent frame of the hit is the caller's (one per hit, shared with bsdf_sample).  wo = hits.wi (the view direction).
 // MatT: DevMaterial, or the same struct in the constant address space (PHX_CONST_MAT: a wave-uniform address is then read through the
 // scalar cache into SGPRs — k_shade_g's material-uniform waves).
-template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, bool TEX = false, typename MatT>
+template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, bool TEX = false, bool MASK = false, typename MatT>
 PHX_HD v3 bsdf_f(const MatT& m, const v3& n, const Frame& fr, const v3& wi, const v3& wo, const TexHit& th = TexHit{}) {
   v3 out(0.0f);
   if (m.num_lobes == 0) return out;
@@ -436,7 +460,7 @@ PHX_HD v3 bsdf_f(const MatT& m, const v3& n, const Frame& fr, const v3& wi, cons
   for (uint32_t i = 0; i < nl; ++i) {
     const auto& p = m.lobes[MAXL == 1 ? 0u : i];
     v3 w;
-    if (!lobe_weight_of<PERHIT, TEX>(m, MAXL == 1 ? 0u : i, p, n, wo, w, th)) continue;
+    if (!lobe_weight_of<PERHIT, TEX, MASK>(m, MAXL == 1 ? 0u : i, p, n, wo, w, th)) continue;
     if ((reflect && (p.flags & B_REFLECT)) || (!reflect && (p.flags & B_TRANSMIT))) {
       float ignored;
       v3 wi_ = wi, wo_ = wo;
@@ -454,7 +478,7 @@ PHX_HD v3 bsdf_f(const MatT& m, const v3& n, const v3& wi, const v3& wo) { retur
 // bsdf_t::sample, src/bsdf.cpp:133-248.  Returns f (already weighted); pdf == 0 terminates.  wi = hits.wi (the view direction).
 // PERHIT: the lobes of the hit are the baked lobes whose resolved weight is not all zero, in table order (lobe_weight_at_hit):
 // `keep` has a bit per baked lobe, `lobes` counts them, and the sampled index picks the index-th KEPT lobe.
-template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, bool TEX = false, typename MatT>
+template <bool DIFFUSE_ONLY = false, int MAXL = 8, bool PERHIT = false, bool TEX = false, bool MASK = false, typename MatT>
 PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, float u2, const v3& wi, v3& wo, float& pdf, uint32_t& sample_flags,
                       const TexHit& th = TexHit{}) {
   pdf = 0.0f; sample_flags = 0; wo = v3(0.0f);
@@ -463,7 +487,7 @@ PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, flo
     keep = 0u; lobes = 0u;
     for (uint32_t i = 0; i < m.num_lobes; ++i) {
       v3 w;
-      if (TEX ? lobe_weight_of<PERHIT, TEX>(m, i, m.lobes[i], n, wi, w, th) : lobe_weight_at_hit<true>(m.lobes[i], n, wi, w)) { keep |= 1u << i; ++lobes; }
+      if (TEX ? lobe_weight_of<PERHIT, TEX, MASK>(m, i, m.lobes[i], n, wi, w, th) : lobe_weight_at_hit<true>(m.lobes[i], n, wi, w)) { keep |= 1u << i; ++lobes; }
     }
   }
   if (lobes == 0) return v3(0.0f);
@@ -566,7 +590,7 @@ PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, flo
   if (!pdf_set) pdf = 0.0f;
   if (pdf == 0.0f) return v3(0.0f);
   v3 pw;
-  (void)lobe_weight_of<PERHIT, TEX>(m, MAXL == 1 ? 0u : chosen, p, n, wi, pw, th);
+  (void)lobe_weight_of<PERHIT, TEX, MASK>(m, MAXL == 1 ? 0u : chosen, p, n, wi, pw, th);
   v3 result = v3(res) * pw;
   int matched = 1;
 #pragma nounroll
@@ -580,7 +604,7 @@ PHX_HD v3 bsdf_sample(const MatT& m, const v3& n, const Frame& fr, float u1, flo
         if (!DIFFUSE_ONLY) { PHX_PIN_V3(wi_); PHX_PIN_V3(wo_); }
         const float e = lobe_eval<DIFFUSE_ONLY>(q, n, fr, wi_, wo_, m.sheen_L5, lobe_pdf);
         v3 qw;
-        (void)lobe_weight_of<PERHIT, TEX>(m, i, q, n, wi, qw, th);
+        (void)lobe_weight_of<PERHIT, TEX, MASK>(m, i, q, n, wi, qw, th);
         result = result + v3(e) * qw;
         pdf += lobe_pdf;
         ++matched;

@@ -98,6 +98,7 @@ struct phx_device {
   DevBuf<float2> d_elem_uv; DevBuf<DevTexture> d_textures; DevBuf<float4> d_texels; DevBuf<uint32_t> d_lobe_tex; DevBuf<DevTexScene> d_tex_scene;
   DevScene scene{};
   uint32_t num_materials = 0, num_textures = 0;
+  std::vector<uint8_t> mat_masked;  // per material: some lobe's factor is an image mask (the untextured KAT hooks refuse those)
   uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission
   uint64_t bvh_nodes = 0, bvh_bytes = 0, num_triangles = 0;
   double preprocess_ms = 0, bvh_build_ms = 0;
@@ -212,9 +213,12 @@ int bake_material(const phx_material& m, float sheen_L5, DevMaterial& out, uint3
     const phx_lobe& s = m.lobes[i];
     DevLobe& l = out.lobes[k];
     l.type = s.type; l.wx = s.weight[0]; l.wy = s.weight[1]; l.wz = s.weight[2];
-    l.fac_mode = s.fac_mode; l.fac_ior = s.fac_ior; l.px = s.pre_weight[0]; l.py = s.pre_weight[1]; l.pz = s.pre_weight[2];
-    if (s.fac_mode > PHX_FAC_MIX_A) return 1;
-    if (s.fac_mode != PHX_FAC_NONE) out.per_hit = 1;
+    // the device lobe holds the mode byte alone; an image mode has no ior and keeps its mask's texture + 1 in that word's bits (validated by the caller)
+    const uint32_t mode = PHX_FAC_MODE(s.fac_mode);
+    l.fac_mode = mode; l.fac_ior = mode >= PHX_FAC_TEX_B ? float_of_bits(PHX_FAC_TEXTURE(s.fac_mode)) : s.fac_ior;
+    l.px = s.pre_weight[0]; l.py = s.pre_weight[1]; l.pz = s.pre_weight[2];
+    if (mode > PHX_FAC_TEX_A) return 1;
+    if (mode != PHX_FAC_NONE) out.per_hit = 1;
     if (s.texture) { out.tex_lobes |= 1u << k; lobe_tex[k] = s.texture; }  // (validated by the caller)
     switch (s.type) {
       case PHX_LOBE_DIFFUSE: l.flags = B_REFLECT | B_DIFFUSE; break;
@@ -341,10 +345,20 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     total_texels += (uint64_t)T.width * T.height;
   }
   if (total_texels > (1ull << 30)) return fail(PHX_ERR_ARG, "textures too large (at most 2^30 texels in all)");
-  bool any_tex = false;
+  bool any_tex = false, any_mask = false;  // any_tex: some lobe reads an image at the hit's UV (colour texture or mask)
   for (uint32_t i = 0; i < s->num_materials; ++i) {
     const phx_material& m = s->materials[i];
     for (uint32_t k = 0; k < m.num_lobes && k < PHX_MAX_LOBES; ++k) {
+      // an image mask on the closure's mix factor (fac_mode: mode byte + the mask's texture): the same rules as a colour texture
+      const uint32_t mode = PHX_FAC_MODE(m.lobes[k].fac_mode), mask = PHX_FAC_TEXTURE(m.lobes[k].fac_mode);
+      if (mode > PHX_FAC_TEX_A) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": unknown fac_mode");
+      if (mode < PHX_FAC_TEX_B && mask) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": fac_mode names a mask texture but its mode is not PHX_FAC_TEX_*");
+      if (mode >= PHX_FAC_TEX_B) {
+        if (mask == 0 || mask > s->num_textures) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": mask texture index out of range");
+        if (m.is_emitter || (int32_t)i == s->environment_material || m.lobes[k].type == PHX_LOBE_EMISSIVE || m.lobes[k].type == PHX_LOBE_BACKGROUND)
+          return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": masks on emitters / the environment are not supported");
+        any_tex = any_mask = true;
+      }
       const uint32_t t = m.lobes[k].texture;
       if (!t) continue;
       if (t > s->num_textures) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": lobe texture index out of range");
@@ -573,7 +587,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   sc.ratio = (float)s->camera.film_width / (float)s->camera.film_height;
   sc.width = s->camera.film_width; sc.height = s->camera.film_height;
   sc.aperture_radius = s->camera.aperture_radius; sc.focal_distance = s->camera.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
-  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (env_tex ? SC_TEX_ENV : 0u);
+  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u);
   sc.tex = sc.any_tex ? d->d_tex_scene.p : nullptr;
   sc.max_depth = d->opt.path_depth;
   sc.stack_levels = bvh_depth;
@@ -603,6 +617,9 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     }
   }
   d->num_materials = s->num_materials;
+  d->mat_masked.assign(s->num_materials, 0);
+  for (uint32_t i = 0; i < s->num_materials; ++i)
+    for (uint32_t k = 0; k < mats[i].num_lobes; ++k) if (mats[i].lobes[k].fac_mode >= PHX_FAC_TEX_B) d->mat_masked[i] = 1;
   d->num_textures = sc.any_tex ? s->num_textures : 0;
   d->env_tex = env_tex;
   d->env_mapping = env_tex ? s->materials[s->environment_material].emission_mapping : 0u;
@@ -764,6 +781,7 @@ int phx_dev_bsdf_f(phx_device* d, uint32_t material, uint32_t n, const float* n3
 static int dev_bsdf_f_impl(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3) {
   if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "bsdf_f before preprocess");
   if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
+  if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_f: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
   if (n == 0) return PHX_OK;
   DeviceScope on(d->hip_device);
   if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
@@ -784,6 +802,7 @@ static int dev_bsdf_sample_impl(phx_device* d, uint32_t material, uint32_t n, co
                         float* wo3, float* f3, float* pdf, uint32_t* flags) {
   if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "bsdf_sample before preprocess");
   if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
+  if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_sample: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
   if (n == 0) return PHX_OK;
   DeviceScope on(d->hip_device);
   if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
@@ -816,6 +835,29 @@ static int dev_texture_lookup_impl(phx_device* d, uint32_t texture, uint32_t n, 
   return PHX_OK;
 }
 int phx_dev_texture_lookup(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) { return guarded([&]() { return dev_texture_lookup_impl(d, texture, n, st, rgb); }); }
+
+static int dev_lobe_weights_impl(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
+  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "lobe_weights before preprocess");
+  if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
+  if (n == 0) return PHX_OK;
+  const bool tex = (d->scene.any_tex & SC_TEX_LOBES) != 0;  // the scene's lobes read images: st is needed
+  if (!n3 || !wi3 || !w || !kept || (tex && !st)) return fail(PHX_ERR_ARG, "lobe_weights: null argument");
+  DeviceScope on(d->hip_device);
+  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+  DevBuf<float> a, b, c, o; DevBuf<uint32_t> k; int rc;
+  if ((rc = kat_upload(n3, 3 * (size_t)n, a)) || (rc = kat_upload(wi3, 3 * (size_t)n, b)) || (tex && (rc = kat_upload(st, 2 * (size_t)n, c))) ||
+      (rc = o.alloc(3 * PHX_MAX_LOBES * (size_t)n)) || (rc = k.alloc((size_t)n))) return rc;
+  launch_lobe_weights(d->stream, d->d_materials.p + material, tex ? d->d_textures.p : nullptr, d->d_texels.p, tex ? d->d_lobe_tex.p + 8 * (size_t)material : nullptr,
+                      n, a.p, b.p, c.p, o.p, k.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(w, o.p, 3 * PHX_MAX_LOBES * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(kept, k.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return PHX_OK;
+}
+int phx_dev_lobe_weights(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
+  return guarded([&]() { return dev_lobe_weights_impl(d, material, n, n3, wi3, st, w, kept); });
+}
 
 static int dev_environment_lookup_impl(phx_device* d, uint32_t n, const float* dirs, float* rgb) {
   if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "environment_lookup before preprocess");

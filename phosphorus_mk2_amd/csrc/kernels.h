@@ -37,7 +37,8 @@ struct DevTexScene {
   uint32_t env_mapping;           // and its lat-long mapping (ENV_LATLONG_*)
 };
 // DevScene::any_tex bits: which image lookups the shade kernels compile in
-enum { SC_TEX_LOBES = 1u /* some lobe is textured: TEX */, SC_TEX_ENV = 2u /* the environment has an image: ENV */ };
+enum { SC_TEX_LOBES = 1u /* some lobe is textured or masked: TEX */, SC_TEX_ENV = 2u /* the environment has an image: ENV */,
+       SC_TEX_MASK = 4u /* some lobe's mix factor is an image (PHX_FAC_TEX_*): MASK, always with SC_TEX_LOBES and any_per_hit */ };
 
 struct DevScene {
   const uint32_t* pool;           // the BVH8 pool: 16 words per element, element 0 = root nodelet (bvh8.h)
@@ -150,6 +151,10 @@ void launch_trace_rays(hipStream_t stream, const DevScene& sc, uint32_t n, const
 void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3);
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags);
+// every baked lobe's weight at a hit (3 x 8 floats per item, zero where the lobe is not there) and the mask of kept lobes; textures == nullptr: a
+// scene without a texture table (st is not read)
+void launch_lobe_weights(hipStream_t stream, const DevMaterial* mat, const DevTexture* textures, const float4* texels, const uint32_t* lobe_tex, uint32_t n,
+                         const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept);
 void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb);
 void launch_environment_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t mapping, float ex, float ey, float ez,
                                uint32_t n, const float* dirs, float* rgb);

@@ -1189,7 +1189,8 @@ __device__ __forceinline__ void ring_append(bool want, const float4& r0, const f
 }
 template <bool PERHIT /* some material's closure weights depend on the hit (glass) */, bool FIRST, bool LENS = false /* FIRST: thin-lens camera */,
           bool TEX = false /* some lobe's weight is multiplied by an image texel (DevScene::any_tex & SC_TEX_LOBES) */,
-          bool ENV = false /* the environment has an image: a miss reads it in the ray's direction (DevScene::any_tex & SC_TEX_ENV) */>
+          bool ENV = false /* the environment has an image: a miss reads it in the ray's direction (DevScene::any_tex & SC_TEX_ENV) */,
+          bool MASK = false /* some lobe's mix factor is the luminance of an image texel (DevScene::any_tex & SC_TEX_MASK; with PERHIT and TEX) */>
 __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves_per_eu(PHX_SHADE_WAVES_G, 8))) k_shade_g(DevScene sc, PassBuffers pb, int q, int sq, uint32_t sample0) {
   constexpr int BLOCK = PHX_SHADE_BLOCK_G, ITEMS = PHX_SHADE_ITEMS_G, WINDOW = BLOCK * ITEMS, NB = PHX_SHADE_BUCKETS;
   static_assert(WINDOW <= 65536 && BLOCK >= NB + 2 && NB == 64, "perm holds 16-bit positions; one wave scans the NB material buckets");
@@ -1472,7 +1473,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             v3 f(0.0f);
             if constexpr (TEX) {  // the material's lobes with the texels at (s, t); the lookups read the hit's own row of lobe_tex
               const TexHit th{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y};
-              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT, true>(cm, n, fr, sh_d, wo, th)));
+              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT, true, MASK>(cm, n, fr, sh_d, wo, th)));
             } else if constexpr (PHX_SCALAR_F && (!PERHIT || PHX_SCALAR_F_PERHIT)) {
               PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT>(cm, n, fr, sh_d, wo)));
             } else {
@@ -1515,13 +1516,13 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             v3 f(0.0f);
             if constexpr (TEX) {
               const TexHit th{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y};
-              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT, true>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl, th)));
+              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT, true, MASK>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl, th)));
             } else {
               PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl)));
             }
 #else
             v3 f;
-            if constexpr (TEX) f = bsdf_sample<false, 8, PERHIT, true>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl, TexHit{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y});
+            if constexpr (TEX) f = bsdf_sample<false, 8, PERHIT, true, MASK>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl, TexHit{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y});
             else f = bsdf_sample<false, 8, PERHIT>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl);
 #endif
             if ((f.x == 0.0f && f.y == 0.0f && f.z == 0.0f) || pdf == 0.0f) {
@@ -1692,6 +1693,26 @@ __global__ void __launch_bounds__(64) k_texture_lookup(const DevTexture* texture
   rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
 }
 
+// phx_dev_lobe_weights: lobe_weight_of as k_shade_g<.., TEX, ., MASK> (TEXTURED) or k_shade_g<PERHIT> (scenes without a texture table) resolves it
+template <bool TEXTURED>
+__global__ void __launch_bounds__(64) k_lobe_weights(const DevMaterial* mat, const DevTexture* textures, const float4* texels, const uint32_t* lobe_tex, uint32_t n,
+                                                     const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DevMaterial& m = *mat;
+  const v3 nn(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]), view(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]);
+  TexHit th{};
+  if constexpr (TEXTURED) th = TexHit{textures, texels, lobe_tex, st[2 * i], st[2 * i + 1]};
+  uint32_t keep = 0u;
+  for (uint32_t k = 0; k < 8u; ++k) {
+    v3 lw(0.0f);
+    if (k < m.num_lobes && lobe_weight_of<true, TEXTURED, TEXTURED>(m, k, m.lobes[k], nn, view, lw, th)) keep |= 1u << k;
+    float* o = w + 3 * (8 * (size_t)i + k);
+    o[0] = lw.x; o[1] = lw.y; o[2] = lw.z;
+  }
+  kept[i] = keep;
+}
+
 // ---- launches ---------------------------------------------------------------------------------------
 static inline uint32_t blocks_for(uint32_t n) { return (n + PHX_BLOCK - 1) / PHX_BLOCK; }
 void launch_begin_pass(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples) {
@@ -1845,6 +1866,18 @@ void launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
     return;
   }
   const dim3 g(shade_grid(sc, capacity, PHX_SHADE_BLOCK_G * PHX_SHADE_ITEMS_G, PHX_SHADE_BLOCK_G)), b(PHX_SHADE_BLOCK_G);
+  if (sc.any_tex & SC_TEX_MASK) {  // image masks on closure mixes: per-hit weights with a texel lookup (PERHIT, TEX and MASK together)
+    if (sc.any_tex & SC_TEX_ENV) {
+      if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else hipLaunchKernelGGL((k_shade_g<true, false, false, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+    } else {
+      if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      else hipLaunchKernelGGL((k_shade_g<true, false, false, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+    }
+    return;
+  }
   if (sc.any_tex & SC_TEX_ENV) {  // an environment image: the same kernels with the lookup on the miss branch (and the texel lookups of TEX)
     if (sc.any_tex & SC_TEX_LOBES) {
       if (sc.any_per_hit) {
@@ -1975,6 +2008,11 @@ void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, 
 void launch_environment_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t mapping, float ex, float ey, float ez,
                                uint32_t n, const float* dirs, float* rgb) {
   hipLaunchKernelGGL(k_environment_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, mapping, ex, ey, ez, n, dirs, rgb);
+}
+void launch_lobe_weights(hipStream_t stream, const DevMaterial* mat, const DevTexture* textures, const float4* texels, const uint32_t* lobe_tex, uint32_t n,
+                         const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
+  if (textures) hipLaunchKernelGGL(k_lobe_weights<true>, dim3((n + 63) / 64), dim3(64), 0, stream, mat, textures, texels, lobe_tex, n, n3, wi3, st, w, kept);
+  else hipLaunchKernelGGL(k_lobe_weights<false>, dim3((n + 63) / 64), dim3(64), 0, stream, mat, textures, texels, lobe_tex, n, n3, wi3, st, w, kept);
 }
 void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
   hipLaunchKernelGGL(k_texture_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, n, st, rgb);

@@ -129,6 +129,30 @@ def load_ppm(path):
     return (raster.astype(np.float32) / np.float32(255.0)).reshape(h, w, 3)
 
 
+def load_pgm(path):
+    """greyscale PGM, binary (P5) or plain (P2), maxval up to 65535 (P5: 16-bit samples are big-endian) -> (H, W, 3) float32 value /
+    maxval replicated to RGB, row 0 = the top row: what a mask is usually painted as"""
+    data = open(path, "rb").read()
+    (magic, w, h, maxval), off = _ppm_tokens(data, 4)
+    if magic not in (b"P2", b"P5"):
+        raise ValueError(f"{path}: only greyscale PGM (P2, P5) is supported")
+    w, h, maxval = int(w), int(h), int(maxval)
+    if w <= 0 or h <= 0 or not 0 < maxval < 65536:
+        raise ValueError(f"{path}: bad PGM header")
+    if magic == b"P5":
+        dt = np.uint8 if maxval < 256 else np.dtype(">u2")
+        if len(data) - off < w * h * np.dtype(dt).itemsize:
+            raise ValueError(f"{path}: truncated PGM raster")
+        raster = np.frombuffer(data, dt, count=w * h, offset=off)
+    else:
+        vals = [t for line in data[off - 1:].split(b"\n") for t in line.split(b"#")[0].split()]
+        if len(vals) < w * h:
+            raise ValueError(f"{path}: truncated PGM raster")
+        raster = np.array([int(t) for t in vals[:w * h]], np.int64)
+    grey = (raster.astype(np.float32) / np.float32(maxval)).reshape(h, w)
+    return np.ascontiguousarray(np.repeat(grey[:, :, None], 3, axis=2))
+
+
 def load_pfm(path):
     """PFM (PF: RGB, Pf: grey) -> (H, W, 3) float32, row 0 = the top row (the file stores the bottom row first)"""
     data = open(path, "rb").read()
@@ -206,12 +230,14 @@ def load_hdr(path):
 
 
 def load_image(path):
-    """a texture's texels by the file's extension: .ppm, .pfm, .hdr or .npy"""
+    """a texture's texels by the file's extension: .ppm, .pgm (grey, replicated to RGB), .pfm (PF, or Pf grey), .hdr or .npy"""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".hdr":
         return load_hdr(path)
     if ext == ".ppm":
         return load_ppm(path)
+    if ext == ".pgm":
+        return load_pgm(path)
     if ext == ".pfm":
         return load_pfm(path)
     if ext == ".npy":
@@ -221,7 +247,7 @@ def load_image(path):
         if a.ndim != 3 or a.shape[2] != 3:
             raise ValueError(f"{path}: expected an (H, W, 3) or (H, W) array, not {a.shape}")
         return np.ascontiguousarray(a)
-    raise ValueError(f"{path}: unsupported image format {ext!r} (.ppm, .pfm, .hdr, .npy)")
+    raise ValueError(f"{path}: unsupported image format {ext!r} (.ppm, .pgm, .pfm, .hdr, .npy)")
 
 
 def look_at(position, at, up):

@@ -5,7 +5,7 @@ inputs of SURVEY §8(d): the Cornell box (C1) and Soup(N, seed) triangle soups (
 A `SceneDesc` owns numpy arrays; `pack()` builds the ctypes `phx_scene` that points into them.
 """
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List, Tuple
 
 import numpy as np
@@ -23,10 +23,11 @@ class LobeDesc:
     yalpha: float = 0.0
     refract: int = 0
     r: float = 0.0
-    fac_mode: int = 0          # abi.FAC_*: per-hit Fresnel mix factor on this closure's weight (glass)
+    fac_mode: int = 0          # abi.FAC_*: per-hit mix factor on this closure's weight: Fresnel (glass) or the luminance of an image (FAC_TEX_*)
     fac_ior: float = 0.0
     pre_weight: Tuple[float, float, float] = (1.0, 1.0, 1.0)
     texture: int = 0           # 0: none; k: the weight is multiplied per hit by SceneDesc.textures[k - 1] at the hit's UV
+    fac_texture: int = 0       # FAC_TEX_B / FAC_TEX_A: the mask image, k = SceneDesc.textures[k - 1] (its luminance at the hit's UV is the mix factor)
 
 
 @dataclass
@@ -119,7 +120,7 @@ class SceneDesc:
                 d.type = l.type
                 d.weight[:] = [np.float32(x) for x in l.weight]
                 d.alpha, d.eta, d.xalpha, d.yalpha, d.refract, d.r = l.alpha, l.eta, l.xalpha, l.yalpha, l.refract, l.r
-                d.fac_mode, d.fac_ior = l.fac_mode, l.fac_ior
+                d.fac_mode, d.fac_ior = abi.fac_pack(l.fac_mode, l.fac_texture), l.fac_ior
                 d.pre_weight[:] = [np.float32(x) for x in l.pre_weight]
                 d.texture = l.texture
         meshes = (abi.Mesh * len(self.meshes))()
@@ -516,6 +517,75 @@ def textured_showroom(n=500_000, width=1920, height=1080, tex_size=2048, baked=F
         mat.lobes[0].texture = len(textures)
     s.textures = textures
     s.name = f"textured_showroom{n}" + ("_baked" if baked else "")
+    return s
+
+
+def mask_luminance(rgb):
+    """the mix factor an image texel gives (luminance_node.osl), fp32 in the device's order: (r * 0.2126 + g * 0.7152) + b * 0.0722"""
+    c = np.asarray(rgb, np.float32)
+    return np.float32(np.float32(np.float32(c[0] * np.float32(0.2126)) + np.float32(c[1] * np.float32(0.7152))) + np.float32(c[2] * np.float32(0.0722)))
+
+
+def resolve_masks(mat, texel_of):
+    """`mat` with its image-masked lobes (FAC_TEX_*) resolved for hits at which mask k reads the constant texel texel_of(k): FAC_NONE lobes
+    of weight (pre_weight * term) * weight, computed in fp32 in the device's order, all-zero ones dropped — the material such a hit sees."""
+    f32 = np.float32
+    lobes = []
+    for l in mat.lobes:
+        if l.fac_mode not in (abi.FAC_TEX_B, abi.FAC_TEX_A):
+            lobes.append(replace(l))
+            continue
+        if l.texture:
+            raise ValueError("resolve_masks: a masked lobe with a colour texture has no constant weight")
+        fac = mask_luminance(texel_of(l.fac_texture))
+        term = fac if l.fac_mode == abi.FAC_TEX_B else f32(f32(1.0) - fac)
+        w = tuple(float(f32(f32(f32(p) * term) * f32(x))) for p, x in zip(l.pre_weight, l.weight))
+        if any(x != 0.0 for x in w):
+            lobes.append(replace(l, weight=w, fac_mode=abi.FAC_NONE, fac_ior=0.0, pre_weight=(1.0, 1.0, 1.0), fac_texture=0))
+    return replace(mat, lobes=lobes)
+
+
+def procedural_mask(size, seed=0):
+    """A (size, size, 3) f32 grey image in [0, 1] with regions of exactly 0 and exactly 1 (where a masked mix drops one side): the red
+    channel of procedural_texture() stretched past both ends and clipped."""
+    g = procedural_texture(size, seed)[..., 0]
+    grey = np.clip((g - np.float32(0.35)) * np.float32(3.0), 0.0, 1.0).astype(np.float32)
+    return np.ascontiguousarray(np.repeat(grey[:, :, None], 3, axis=2))
+
+
+def masked_showroom(n=500_000, width=1920, height=1080, tex_size=2048, mode="image", seed=0):
+    """bmw_showroom() with its diffuse recipes (the room and the sphere materials of one Lambert lobe) turned into
+    mix(diffuse, glossy, mask): the Lambert lobe on the mix's A side, a GGX lobe (roughness 0.3) on its B side, the factor the luminance of
+    one procedural tex_size^2 LINEAR grey image per recipe (UVs as in textured_showroom()).
+    mode "image": those masks.  "one_texel": 1 x 1 images holding each mask's mean — the same kernels (k_shade_g<.., MASK>) whose lookups
+    hit one texel.  "baked": the mix each one_texel mask gives resolved into constant FAC_NONE weights (resolve_masks), no image, no UVs:
+    today's kernels, and bit for bit the film of "one_texel"."""
+    if mode not in ("image", "one_texel", "baked"):
+        raise ValueError(f"masked_showroom: unknown mode {mode!r}")
+    s = bmw_showroom(n, width, height)
+    quad_uv = np.array([[0, 0], [1, 0], [1, 1], [0, 0], [1, 1], [0, 1]], np.float32)
+    if mode != "baked":
+        for m in s.meshes:
+            if len(m.faces) == 2:
+                m.uvs = quad_uv * 3.0
+                m.flags = m.flags & ~abi.MESH_UV_PER_VERTEX
+            else:
+                m.uvs = _sphere_uvs(m)
+    textures = []
+    for i, mat in enumerate(s.materials):
+        if mat.is_emitter or len(mat.lobes) != 1 or mat.lobes[0].type != abi.LOBE_DIFFUSE:
+            continue
+        img = procedural_mask(tex_size, seed + i)
+        if mode != "image":
+            img = img.reshape(-1, 3).mean(0, dtype=np.float64).astype(np.float32).reshape(1, 1, 3)
+        textures.append(TextureDesc(img, abi.TEX_LINEAR))
+        k = len(textures)
+        mat.lobes = [replace(mat.lobes[0], fac_mode=abi.FAC_TEX_A, fac_texture=k),
+                     LobeDesc(abi.LOBE_MICROFACET, (0.9, 0.9, 0.9), xalpha=0.09, yalpha=0.09, fac_mode=abi.FAC_TEX_B, fac_texture=k)]
+        if mode == "baked":
+            mat.lobes = resolve_masks(mat, lambda j: textures[j - 1].texels[0, 0]).lobes
+    s.textures = [] if mode == "baked" else textures
+    s.name = f"masked_showroom{n}_{mode}"
     return s
 
 

@@ -299,6 +299,21 @@ class HipDevice:
                                                         fl.ctypes.data_as(abi.u32p)), "phx_dev_bsdf_sample")
         return wo, f, pdf, fl
 
+    def lobe_weights(self, material, n, wi, st=None):
+        """The closure weights of material `material` as the shade kernel resolves them at n hits (shading normal n, view direction wi =
+        hits.wi, texture coordinates st): (w (n, MAX_LOBES, 3) f32, kept (n,) u32 with bit k set where baked lobe k is there at the hit).
+        st may be omitted for a scene without textured or masked lobes."""
+        n = np.ascontiguousarray(n, np.float32).reshape(-1, 3); wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        k = len(wi)
+        st = np.zeros((k, 2), np.float32) if st is None else np.ascontiguousarray(st, np.float32).reshape(-1, 2)
+        if len(n) != k or len(st) != k:
+            raise ValueError("lobe_weights: n, wi and st must have one row per item")
+        w = np.zeros((k, abi.MAX_LOBES, 3), np.float32); kept = np.zeros(k, np.uint32)
+        fp = lambda a: a.ctypes.data_as(abi.f32p)
+        _check(self._lib, self._lib.phx_dev_lobe_weights(self._h, material, k, fp(n), fp(wi), fp(st), fp(w), kept.ctypes.data_as(abi.u32p)),
+               "phx_dev_lobe_weights")
+        return w, kept
+
     def texture_lookup(self, texture, st):
         """The shade kernel's image lookup on the device: texture `texture` (0-based index into SceneDesc.textures of the preprocessed
         scene, which must have a textured lobe) at st (n, 2) -> rgb (n, 3) f32."""
