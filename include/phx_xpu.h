@@ -235,6 +235,26 @@ typedef struct phx_frame {
 } phx_frame;
 
 /* ---- statistics ------------------------------------------------------------------------ */
+/* The shade kernels (kernels.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
+ * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
+enum {
+  PHX_SHADE_PASS_LATER   = 0, /* a later bounce */
+  PHX_SHADE_PASS_CAMERA  = 1, /* the camera rays' pass, through a pinhole */
+  PHX_SHADE_PASS_LENS    = 2, /* the camera rays' pass, through a lens (aperture_radius != 0) */
+  PHX_SHADE_PASSES       = 3
+};
+enum {
+  PHX_SHADE_FAMILY_LAMBERT1 = 0,  /* k_shade<2>: at most one Lambert lobe per material */
+  PHX_SHADE_FAMILY_LAMBERT  = 1,  /* k_shade<1>: Lambert lobes only */
+  PHX_SHADE_FAMILY_GENERAL  = 2,  /* k_shade_g: 2 + (PERHIT | TEX << 1 | ENV << 2), i.e. families 2 to 9 */
+  PHX_SHADE_G_PERHIT        = 1,  /* ... some closure weight depends on the hit (glass) */
+  PHX_SHADE_G_TEX           = 2,  /* ... some lobe reads an image */
+  PHX_SHADE_G_ENV           = 4,  /* ... the environment has an image */
+  PHX_SHADE_FAMILY_MASK     = 10, /* k_shade_g with image masks on closure mixes (PERHIT, TEX and MASK) */
+  PHX_SHADE_FAMILY_MASK_ENV = 11, /* ... and an environment image */
+  PHX_SHADE_FAMILIES        = 12,
+  PHX_SHADE_KERNELS         = 36  /* PHX_SHADE_FAMILIES * PHX_SHADE_PASSES */
+};
 typedef struct phx_stats {
   uint64_t camera_samples;   /* primary rays generated */
   uint64_t rays_closest;     /* non-masked slots presented to closest-hit trace */
@@ -290,6 +310,7 @@ typedef struct phx_stats {
   uint64_t tri_pairs_pending;  /* instrumented: pending (ray, triangle) pairs of a wave at its triangle-block executions, summed (each execution tests one per pending lane) */
   uint64_t tri_pairs_hist[8];  /* instrumented: those executions by the wave's pending pairs: <= 8, 16, 24, 32, 48, 64, 96, more */
   uint64_t trace_stack_packed; /* 1: k_trace keeps 5-byte stack entries in LDS (deep trees: more of the tree is staged), 0: 8-byte entries */
+  uint64_t shade_kernels;      /* bit (family * 3 + pass) set for every shade kernel launched by the last frame (PHX_SHADE_FAMILY_*, PHX_SHADE_PASS_*) */
 } phx_stats;
 
 typedef struct phx_device phx_device; /* opaque */

@@ -34,6 +34,40 @@ MESH_UV_PER_VERTEX, MESH_NORMALS_PER_VERTEX = 1, 2
 TEX_LINEAR, TEX_CLOSEST = 0, 1
 WRAP_PERIODIC, WRAP_CLAMP, WRAP_BLACK = 0, 1, 2
 ENV_LATLONG_Y_UP, ENV_LATLONG_Z_UP = 0, 1
+# Stats.shade_kernels: bit (family * SHADE_PASSES + pass) for every shade kernel the last frame launched (PHX_SHADE_*)
+SHADE_PASS_LATER, SHADE_PASS_CAMERA, SHADE_PASS_LENS, SHADE_PASSES = 0, 1, 2, 3
+SHADE_FAMILY_LAMBERT1, SHADE_FAMILY_LAMBERT, SHADE_FAMILY_GENERAL = 0, 1, 2  # k_shade<2>, k_shade<1>, k_shade_g: 2 + (PERHIT | TEX | ENV)
+SHADE_G_PERHIT, SHADE_G_TEX, SHADE_G_ENV = 1, 2, 4
+SHADE_FAMILY_MASK, SHADE_FAMILY_MASK_ENV, SHADE_FAMILIES, SHADE_KERNELS = 10, 11, 12, 36
+
+
+def shade_kernel_bit(family, pass_):
+    """the bit of Stats.shade_kernels (its index, not its mask) of `family` in pass `pass_`"""
+    if not (0 <= family < SHADE_FAMILIES and 0 <= pass_ < SHADE_PASSES):
+        raise ValueError(f"no shade kernel (family {family}, pass {pass_})")
+    return family * SHADE_PASSES + pass_
+
+
+def shade_kernel_name(bit):
+    """the instantiation behind bit `bit` of Stats.shade_kernels, as launch_shade (kernels.hip) spells it"""
+    if not 0 <= bit < SHADE_KERNELS:
+        raise ValueError(f"no shade kernel has bit {bit}")
+    family, p = divmod(bit, SHADE_PASSES)
+    first, lens = ("false", "false") if p == SHADE_PASS_LATER else ("true", "true" if p == SHADE_PASS_LENS else "false")
+    if family < SHADE_FAMILY_GENERAL:
+        return f"k_shade<{2 if family == SHADE_FAMILY_LAMBERT1 else 1}, {first}, {lens}>"
+    g = family - SHADE_FAMILY_GENERAL
+    perhit, tex, env, mask = bool(g & SHADE_G_PERHIT), bool(g & SHADE_G_TEX), bool(g & SHADE_G_ENV), False
+    if family >= SHADE_FAMILY_MASK:
+        perhit, tex, env, mask = True, True, family == SHADE_FAMILY_MASK_ENV, True
+    b = lambda x: "true" if x else "false"
+    tags = [t for t, on in (("PERHIT", perhit), ("TEX", tex), ("ENV", env), ("MASK", mask)) if on]
+    return f"k_shade_g<{b(perhit)}, {first}, {lens}, {b(tex)}, {b(env)}, {b(mask)}>" + (f" ({' + '.join(tags)})" if tags else "")
+
+
+def shade_kernel_names(mask):
+    """the kernels of a Stats.shade_kernels word, for assertion messages"""
+    return [shade_kernel_name(b) for b in range(SHADE_KERNELS) if int(mask) >> b & 1] + ([f"unknown bits {int(mask) >> SHADE_KERNELS:#x}"] if int(mask) >> SHADE_KERNELS else [])
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -129,6 +163,7 @@ class Stats(C.Structure):
         ("shade_kernel_ms", C.c_double), ("shade_launches", C.c_uint64), ("shade_general", C.c_uint64), ("primary_ms", C.c_double), ("primary_launches", C.c_uint64),
         ("primary_packets", C.c_uint64), ("primary_fallbacks", C.c_uint64), ("primary_node_tests", C.c_uint64), ("primary_tri_tests", C.c_uint64), ("primary_tri_lanes_hit", C.c_uint64),
         ("device_bytes", C.c_uint64), ("tri_pairs_pending", C.c_uint64), ("tri_pairs_hist", C.c_uint64 * 8), ("trace_stack_packed", C.c_uint64),
+        ("shade_kernels", C.c_uint64),
     ]
 
 

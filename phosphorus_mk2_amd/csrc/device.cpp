@@ -1209,7 +1209,7 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
       // step 0: the capacity.  Step 1: the length k_trace(1) — the longest launch of a pass, enqueued just above — publishes as it starts.
       // Later steps: the length published one step earlier (the device then still has two launches queued while the host waits).
       const uint32_t shade_cap = (grid_by_queue && bounce >= 1) ? std::max(queue_bound(pass, bounce == 1 ? 1u : bounce - 1, cap), 1u) : cap;
-      if ((rc = timed_launch(3, [&]() { launch_shade(stream, scene, B, q, sq_write, shade_cap, s0, bounce == 0); }))) return rc;
+      if ((rc = timed_launch(3, [&]() { stats.shade_kernels |= launch_shade(stream, scene, B, q, sq_write, shade_cap, s0, bounce == 0); }))) return rc;
       q ^= 1;
     }
     if ((rc = timed_launch(0, [&]() { launch_trace(stream, scene, B, q, (int)((opt.path_depth - 1) & 1), 0, 1, cap); }))) return rc;

@@ -136,7 +136,8 @@ void launch_trace(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
 // writes the hit records of queue q and does k_trace's start-of-step bookkeeping
 void launch_trace_primary(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, uint32_t npaths, uint32_t sample0, int q, int sq);
 // shades queue q, appends survivors to queue q^1 and NEE rays to shadow queue sq
-void launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t capacity, uint32_t sample0, int camera_rays);
+// -> the launched kernel's bit of phx_stats::shade_kernels
+uint64_t launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t capacity, uint32_t sample0, int camera_rays);
 void launch_film(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples, float inv_spp_pps);
 // preprocess: vertex normals from scene_t::triangles() order to pool-element order (elem_of_prim: the builders' map), and the smooth light
 // triangles' `prim` from primitive to pool element (they look their normals up in the same table)

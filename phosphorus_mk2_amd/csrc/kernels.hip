@@ -13,6 +13,7 @@
 //               queues with __ballot/__popcll compaction (one global atomic per 512-thread workgroup)
 //   k_film      the per-sample film add of tile_renderer_t::render_tile (src/xpu/cpu.cpp:175-198), in sample order
 #include "kernels.h"
+#include "../../include/phx_xpu.h"  // PHX_SHADE_*: the bits of phx_stats::shade_kernels
 
 #include <algorithm>
 #include <cstddef>
@@ -1850,78 +1851,97 @@ static uint32_t shade_grid(const DevScene& sc, uint32_t capacity, uint32_t per_w
   const uint32_t need = (capacity + per_wg - 1) / per_wg;
   return std::max(1u, std::min(need, resident * (uint32_t)mul));
 }
-void launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t capacity, uint32_t sample0, int camera_rays) {
+// One shade launch and the bit of phx_stats::shade_kernels that names it: both come from the same template arguments, so the bit reports
+// the kernel that ran and not a second reading of the scene's flags.
+template <bool FIRST, bool LENS> constexpr uint32_t shade_pass() {
+  static_assert(FIRST || !LENS, "the lens bends camera rays only");
+  return LENS ? PHX_SHADE_PASS_LENS : FIRST ? PHX_SHADE_PASS_CAMERA : PHX_SHADE_PASS_LATER;
+}
+template <int MATS, bool FIRST, bool LENS>
+static uint64_t shade_d(dim3 g, dim3 b, hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t sample0) {
+  constexpr uint32_t bit = (MATS == 2 ? PHX_SHADE_FAMILY_LAMBERT1 : PHX_SHADE_FAMILY_LAMBERT) * PHX_SHADE_PASSES + shade_pass<FIRST, LENS>();
+  static_assert(bit < PHX_SHADE_KERNELS, "phx_stats::shade_kernels: a kernel without a bit");
+  hipLaunchKernelGGL((k_shade<MATS, FIRST, LENS>), g, b, 0, stream, sc, pb, q, sq, sample0);
+  return 1ull << bit;
+}
+template <bool PERHIT, bool FIRST, bool LENS, bool TEX, bool ENV, bool MASK>
+static uint64_t shade_g(dim3 g, dim3 b, hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t sample0) {
+  static_assert(!MASK || (PERHIT && TEX), "image masks are per-hit weights with a texel lookup");
+  constexpr uint32_t family = MASK ? (ENV ? PHX_SHADE_FAMILY_MASK_ENV : PHX_SHADE_FAMILY_MASK)
+                                   : PHX_SHADE_FAMILY_GENERAL + ((PERHIT ? PHX_SHADE_G_PERHIT : 0) | (TEX ? PHX_SHADE_G_TEX : 0) | (ENV ? PHX_SHADE_G_ENV : 0));
+  constexpr uint32_t bit = family * PHX_SHADE_PASSES + shade_pass<FIRST, LENS>();
+  static_assert(bit < PHX_SHADE_KERNELS, "phx_stats::shade_kernels: a kernel without a bit");
+  hipLaunchKernelGGL((k_shade_g<PERHIT, FIRST, LENS, TEX, ENV, MASK>), g, b, 0, stream, sc, pb, q, sq, sample0);
+  return 1ull << bit;
+}
+uint64_t launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t capacity, uint32_t sample0, int camera_rays) {
   const bool lens = camera_rays && sc.aperture_radius != 0.0f;  // camera_t::is_pinhole, entities/camera.hpp:37
   if (sc.diffuse_only) {
     const dim3 g((capacity + PHX_SHADE_BLOCK_D - 1) / PHX_SHADE_BLOCK_D), b(PHX_SHADE_BLOCK_D);
     if (sc.diffuse_only == 2) {
-      if (lens) hipLaunchKernelGGL((k_shade<2, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) hipLaunchKernelGGL((k_shade<2, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else hipLaunchKernelGGL((k_shade<2, false>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      if (lens) return shade_d<2, true, true>(g, b, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) return shade_d<2, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+      else return shade_d<2, false, false>(g, b, stream, sc, pb, q, sq, sample0);
     } else {
-      if (lens) hipLaunchKernelGGL((k_shade<1, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) hipLaunchKernelGGL((k_shade<1, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else hipLaunchKernelGGL((k_shade<1, false>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      if (lens) return shade_d<1, true, true>(g, b, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) return shade_d<1, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+      else return shade_d<1, false, false>(g, b, stream, sc, pb, q, sq, sample0);
     }
-    return;
   }
   const dim3 g(shade_grid(sc, capacity, PHX_SHADE_BLOCK_G * PHX_SHADE_ITEMS_G, PHX_SHADE_BLOCK_G)), b(PHX_SHADE_BLOCK_G);
   if (sc.any_tex & SC_TEX_MASK) {  // image masks on closure mixes: per-hit weights with a texel lookup (PERHIT, TEX and MASK together)
     if (sc.any_tex & SC_TEX_ENV) {
-      if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else hipLaunchKernelGGL((k_shade_g<true, false, false, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      if (lens) return shade_g<true, true, true, true, true, true>(g, b, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) return shade_g<true, true, false, true, true, true>(g, b, stream, sc, pb, q, sq, sample0);
+      else return shade_g<true, false, false, true, true, true>(g, b, stream, sc, pb, q, sq, sample0);
     } else {
-      if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else hipLaunchKernelGGL((k_shade_g<true, false, false, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      if (lens) return shade_g<true, true, true, true, false, true>(g, b, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) return shade_g<true, true, false, true, false, true>(g, b, stream, sc, pb, q, sq, sample0);
+      else return shade_g<true, false, false, true, false, true>(g, b, stream, sc, pb, q, sq, sample0);
     }
-    return;
   }
   if (sc.any_tex & SC_TEX_ENV) {  // an environment image: the same kernels with the lookup on the miss branch (and the texel lookups of TEX)
     if (sc.any_tex & SC_TEX_LOBES) {
       if (sc.any_per_hit) {
-        if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else hipLaunchKernelGGL((k_shade_g<true, false, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        if (lens) return shade_g<true, true, true, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) return shade_g<true, true, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else return shade_g<true, false, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
       } else {
-        if (lens) hipLaunchKernelGGL((k_shade_g<false, true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<false, true, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else hipLaunchKernelGGL((k_shade_g<false, false, false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        if (lens) return shade_g<false, true, true, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) return shade_g<false, true, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else return shade_g<false, false, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
       }
     } else {
       if (sc.any_per_hit) {
-        if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else hipLaunchKernelGGL((k_shade_g<true, false, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        if (lens) return shade_g<true, true, true, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) return shade_g<true, true, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else return shade_g<true, false, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
       } else {
-        if (lens) hipLaunchKernelGGL((k_shade_g<false, true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) hipLaunchKernelGGL((k_shade_g<false, true, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-        else hipLaunchKernelGGL((k_shade_g<false, false, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+        if (lens) return shade_g<false, true, true, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else if (camera_rays) return shade_g<false, true, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
+        else return shade_g<false, false, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
       }
     }
-    return;
   }
   if (sc.any_tex) {  // textured scenes: the same kernel with the texel lookups compiled in
     if (sc.any_per_hit) {
-      if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else hipLaunchKernelGGL((k_shade_g<true, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      if (lens) return shade_g<true, true, true, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) return shade_g<true, true, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+      else return shade_g<true, false, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
     } else {
-      if (lens) hipLaunchKernelGGL((k_shade_g<false, true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) hipLaunchKernelGGL((k_shade_g<false, true, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-      else hipLaunchKernelGGL((k_shade_g<false, false, false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
+      if (lens) return shade_g<false, true, true, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+      else if (camera_rays) return shade_g<false, true, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+      else return shade_g<false, false, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
     }
-    return;
   }
   if (sc.any_per_hit) {
-    if (lens) hipLaunchKernelGGL((k_shade_g<true, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-    else if (camera_rays) hipLaunchKernelGGL((k_shade_g<true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-    else hipLaunchKernelGGL((k_shade_g<true, false>), g, b, 0, stream, sc, pb, q, sq, sample0);
+    if (lens) return shade_g<true, true, true, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+    else if (camera_rays) return shade_g<true, true, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+    else return shade_g<true, false, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
   } else {
-    if (lens) hipLaunchKernelGGL((k_shade_g<false, true, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-    else if (camera_rays) hipLaunchKernelGGL((k_shade_g<false, true>), g, b, 0, stream, sc, pb, q, sq, sample0);
-    else hipLaunchKernelGGL((k_shade_g<false, false>), g, b, 0, stream, sc, pb, q, sq, sample0);
+    if (lens) return shade_g<false, true, true, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+    else if (camera_rays) return shade_g<false, true, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
+    else return shade_g<false, false, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
   }
 }
 void launch_trace_primary(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, uint32_t npaths, uint32_t sample0, int q, int sq) {

@@ -203,3 +203,26 @@ def test_reference_patch_applies(tmp_path):
     r = subprocess.run(["patch", "-p1", "--dry-run", "--batch", "-d", str(tmp_path), "-i", PATCH], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("checking file") == 5 and "offset" not in r.stdout and "fuzz" not in r.stdout, r.stdout
+
+
+def test_shade_kernel_constants_match_the_header():
+    """abi's SHADE_* constants are the header's PHX_SHADE_* enumerators, read from its text; the kernel count is families x passes, fits the
+    64 bits of phx_stats::shade_kernels, and every bit has a name of its own"""
+    from phosphorus_mk2_amd import abi
+    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
+    declared = {name: int(value) for name, value in re.findall(r"\bPHX_SHADE_([A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    mirrored = {k[len("SHADE_"):]: v for k, v in vars(abi).items() if k.startswith("SHADE_") and isinstance(v, int)}
+    assert declared == mirrored and len(declared) == 14, sorted(set(declared.items()) ^ set(mirrored.items()))
+    assert abi.SHADE_KERNELS == abi.SHADE_FAMILIES * abi.SHADE_PASSES == 36 <= 64
+    assert abi.SHADE_FAMILY_GENERAL + (abi.SHADE_G_PERHIT | abi.SHADE_G_TEX | abi.SHADE_G_ENV) + 1 == abi.SHADE_FAMILY_MASK
+    assert re.search(r"uint64_t\s+shade_kernels;[^\n]*\n\} phx_stats;", hdr)  # appended: no earlier field moves
+    assert abi.Stats._fields_[-1][0] == "shade_kernels"
+    names = [abi.shade_kernel_name(b) for b in range(abi.SHADE_KERNELS)]
+    assert len(set(names)) == abi.SHADE_KERNELS
+    assert names[abi.shade_kernel_bit(abi.SHADE_FAMILY_LAMBERT1, abi.SHADE_PASS_LATER)] == "k_shade<2, false, false>"
+    assert names[abi.shade_kernel_bit(abi.SHADE_FAMILY_MASK_ENV, abi.SHADE_PASS_LENS)].startswith("k_shade_g<true, true, true, true, true, true>")
+    assert names[abi.shade_kernel_bit(abi.SHADE_FAMILY_GENERAL + abi.SHADE_G_TEX, abi.SHADE_PASS_CAMERA)].startswith("k_shade_g<false, true, false, true, false, false>")
+    for bad in (-1, abi.SHADE_KERNELS):
+        with pytest.raises(ValueError):
+            abi.shade_kernel_name(bad)
+    assert abi.shade_kernel_names(0b101) == [names[0], names[2]]

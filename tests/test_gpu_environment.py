@@ -287,6 +287,10 @@ def test_textured_box_with_environment_image(xpu):
     assert bits_equal(fa[..., :3], fb[..., :3])
     assert not bits_equal(fa[..., :3], fn[..., :3])
     assert sa["device_bytes"] >= sb["device_bytes"]
+    from phosphorus_mk2_amd import abi  # PERHIT + TEX + ENV on the pinhole camera; tests/test_gpu_shade_kernels.py compares this family with the oracle
+    family = abi.SHADE_FAMILY_GENERAL + (abi.SHADE_G_PERHIT | abi.SHADE_G_TEX | abi.SHADE_G_ENV)
+    want = (1 << abi.shade_kernel_bit(family, abi.SHADE_PASS_CAMERA)) | (1 << abi.shade_kernel_bit(family, abi.SHADE_PASS_LATER))
+    assert sa["shade_kernels"] == want, abi.shade_kernel_names(sa["shade_kernels"])
 
 
 # ---- 7. refusals ------------------------------------------------------------------------------------------------------------------------------

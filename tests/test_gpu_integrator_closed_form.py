@@ -85,37 +85,47 @@ HALF_4X4 = scenes.TextureDesc(np.full((4, 4, 3), 0.5, np.float32), abi.TEX_LINEA
 HALF_1X1 = scenes.TextureDesc(np.full((1, 1, 3), 0.5, np.float32), abi.TEX_LINEAR, abi.WRAP_PERIODIC, abi.WRAP_PERIODIC)
 TEXTURED = scenes.MaterialDesc([replace(GGX.lobes[0], texture=1)])
 TEXTURED_GLASS = scenes.MaterialDesc([replace(GLASS.lobes[0], texture=1), GLASS.lobes[1]])
-# name: (scene, the oracle's scene (None: the same; textures and environment images baked in), render options, shade_general,
+LAMBERT1, GENERAL = abi.SHADE_FAMILY_LAMBERT1, abi.SHADE_FAMILY_GENERAL
+
+
+def K(family, lens=False):
+    """the two kernels a frame of this family launches: the camera rays' (through a pinhole or a lens) and the later bounces'"""
+    first = abi.SHADE_PASS_LENS if lens else abi.SHADE_PASS_CAMERA
+    return (1 << abi.shade_kernel_bit(family, first)) | (1 << abi.shade_kernel_bit(family, abi.SHADE_PASS_LATER))
+
+
+# name: (scene, the oracle's scene (None: the same; textures and environment images baked in), render options,
+#        the shade kernels of the frame (phx_stats::shade_kernels: the instantiation the comment above the entry names and its later-bounce twin),
 #        the standard error's key in SE_VARIANT (None: the plain cavity's, whose film this one must repeat bit for bit),
 #        the key under which cases with the same oracle film share it)
 CAVITIES = {
     # k_shade<2>: sc.diffuse_only == 2 (every material has at most one Lambert lobe, no textures)
-    "plain": (lambda: I.cavity(), None, {}, 0, None, "plain"),
-    "plain_host_builder": (lambda: I.cavity(), None, {"bvh_builder": "host"}, 0, None, "plain"),
-    "plain_device_builder": (lambda: I.cavity(), None, {"bvh_builder": "device"}, 0, None, "plain"),
-    "plain_3_in_flight": (lambda: I.cavity(), None, {"samples_in_flight": 3}, 0, None, "plain"),
+    "plain": (lambda: I.cavity(), None, {}, K(LAMBERT1), None, "plain"),
+    "plain_host_builder": (lambda: I.cavity(), None, {"bvh_builder": "host"}, K(LAMBERT1), None, "plain"),
+    "plain_device_builder": (lambda: I.cavity(), None, {"bvh_builder": "device"}, K(LAMBERT1), None, "plain"),
+    "plain_3_in_flight": (lambda: I.cavity(), None, {"samples_in_flight": 3}, K(LAMBERT1), None, "plain"),
     # k_shade<2, true, true>: the same with sc.aperture_radius != 0 on the camera rays' pass
-    "plain_lens": (lambda: _lens(I.cavity()), None, {}, 0, "lens", "lens"),
+    "plain_lens": (lambda: _lens(I.cavity()), None, {}, K(LAMBERT1, True), "lens", "lens"),
     # k_shade_g<false>: sc.diffuse_only == 0 (a GGX lobe exists), sc.any_per_hit == 0, sc.any_tex == 0
-    "hidden_ggx": (lambda: I.cavity(hidden=GGX), None, {}, 1, None, "hidden_ggx"),
-    "hidden_ggx_3_in_flight": (lambda: I.cavity(hidden=GGX), None, {"samples_in_flight": 3, "bvh_builder": "host"}, 1, None, "hidden_ggx"),
+    "hidden_ggx": (lambda: I.cavity(hidden=GGX), None, {}, K(GENERAL), None, "hidden_ggx"),
+    "hidden_ggx_3_in_flight": (lambda: I.cavity(hidden=GGX), None, {"samples_in_flight": 3, "bvh_builder": "host"}, K(GENERAL), None, "hidden_ggx"),
     # k_shade_g<false, true, true>: the thin lens on the general kernel
-    "hidden_ggx_lens": (lambda: _lens(I.cavity(hidden=GGX)), None, {}, 1, "lens", "hidden_ggx_lens"),
+    "hidden_ggx_lens": (lambda: _lens(I.cavity(hidden=GGX)), None, {}, K(GENERAL, True), "lens", "hidden_ggx_lens"),
     # k_shade_g<true> (PERHIT): sc.any_per_hit == 1 (the glass node's Fresnel mix)
-    "hidden_glass": (lambda: I.cavity(hidden=GLASS), None, {}, 1, None, "hidden_glass"),
+    "hidden_glass": (lambda: I.cavity(hidden=GLASS), None, {}, K(GENERAL + abi.SHADE_G_PERHIT), None, "hidden_glass"),
     # k_shade_g<false, ., ., true> (TEX): sc.any_tex & SC_TEX_LOBES -- the texture is on the hidden triangle; the device takes no textured lobe
     # on an emitter (phx_xpu.h), so the wall's rho cannot be split into weight x texel: test_lambert_floor_under_the_environment does that
-    "texture_kernel": (lambda: I.cavity(hidden=TEXTURED, textures=[HALF_4X4]), lambda: I.cavity(hidden=GGX), {}, 1, None, "hidden_ggx"),
+    "texture_kernel": (lambda: I.cavity(hidden=TEXTURED, textures=[HALF_4X4]), lambda: I.cavity(hidden=GGX), {}, K(GENERAL + abi.SHADE_G_TEX), None, "hidden_ggx"),
     # k_shade_g<true, ., ., true> (PERHIT + TEX)
-    "texture_kernel_per_hit": (lambda: I.cavity(hidden=TEXTURED_GLASS, textures=[HALF_4X4]), lambda: I.cavity(hidden=GLASS), {}, 1, None, "hidden_glass"),
+    "texture_kernel_per_hit": (lambda: I.cavity(hidden=TEXTURED_GLASS, textures=[HALF_4X4]), lambda: I.cavity(hidden=GLASS), {}, K(GENERAL + (abi.SHADE_G_TEX | abi.SHADE_G_PERHIT)), None, "hidden_glass"),
     # k_shade_g<false, ., ., false, true> (ENV): sc.any_tex & SC_TEX_ENV, an environment image that no path of the closed cavity sees
-    "environment_image": (lambda: _env_image(I.cavity(), (8.0, 8.0, 8.0), 0.5), lambda: _constant_env(I.cavity(), (4.0, 4.0, 4.0)), {}, 1, None, "constant_environment"),
+    "environment_image": (lambda: _env_image(I.cavity(), (8.0, 8.0, 8.0), 0.5), lambda: _constant_env(I.cavity(), (4.0, 4.0, 4.0)), {}, K(GENERAL + abi.SHADE_G_ENV), None, "constant_environment"),
     # k_shade_g<false, ., ., true, true> (TEX + ENV)
     "texture_kernel_and_environment_image": (lambda: _env_image(I.cavity(hidden=TEXTURED, textures=[HALF_4X4]), (8.0, 8.0, 8.0), 0.5),
-                                             lambda: _constant_env(I.cavity(), (4.0, 4.0, 4.0)), {}, 1, None, "constant_environment"),
+                                             lambda: _constant_env(I.cavity(), (4.0, 4.0, 4.0)), {}, K(GENERAL + (abi.SHADE_G_TEX | abi.SHADE_G_ENV)), None, "constant_environment"),
     # a ragged film: 24 x 13 is one partial 32 x 32 tile (the oracle, like the reference, takes tile widths that are multiples of 8 only)
-    "film_24x13": (lambda: I.cavity(width=24, height=13), None, {}, 0, "film_24x13", "film_24x13"),
-    "film_24x13_hidden_ggx": (lambda: I.cavity(width=24, height=13, hidden=GGX), None, {"samples_in_flight": 3}, 1, "film_24x13", "film_24x13_hidden_ggx"),
+    "film_24x13": (lambda: I.cavity(width=24, height=13), None, {}, K(LAMBERT1), "film_24x13", "film_24x13"),
+    "film_24x13_hidden_ggx": (lambda: I.cavity(width=24, height=13, hidden=GGX), None, {"samples_in_flight": 3}, K(GENERAL), "film_24x13", "film_24x13_hidden_ggx"),
 }
 # relative standard errors (r, g, b) of the film mean of the variants whose camera or film differs from the plain cavity's (colour, depth 5,
 # 256 spp, seed 5), measured on the CPU oracle like SE_MEAN
@@ -130,11 +140,12 @@ def test_cavity_on_every_shade_path(xpu, oracle, name):
     """The coloured cavity at depth 5 through each shade kernel.  The comment above each entry of CAVITIES names the instantiation and the
     DevScene state that selects it in launch_shade (kernels.hip): sc.diffuse_only == 2 -> k_shade<2>; 0 -> k_shade_g, <PERHIT> with
     sc.any_per_hit, <TEX> / <ENV> with sc.any_tex & SC_TEX_LOBES / SC_TEX_ENV, the LENS twins with sc.aperture_radius != 0 on the camera
-    rays' pass.  Stats' shade_general tells k_shade from k_shade_g."""
-    make, make_ref, opts, general, se_key, ref_key = CAVITIES[name]
+    rays' pass.  Stats' shade_kernels names the instantiations the frame launched: exactly the entry's two."""
+    make, make_ref, opts, kernels, se_key, ref_key = CAVITIES[name]
     sc = make()
     film, st = device(xpu, sc, DEPTH, **opts)
-    assert st["shade_general"] == general
+    assert st["shade_kernels"] == kernels, (abi.shade_kernel_names(st["shade_kernels"]), abi.shade_kernel_names(kernels))
+    assert st["shade_general"] == (0 if kernels in (K(LAMBERT1), K(LAMBERT1, True)) else 1)
     ref, ost = oracle(ref_key, make_ref or make, DEPTH)
     same(film, st, ref, ost)
     T.check_cavity(f64(film), st, RHO, 1, DEPTH, se=None if se_key is None else SE_VARIANT[se_key])

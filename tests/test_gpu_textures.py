@@ -121,11 +121,12 @@ def _bake_material(m, texel):
     return scenes.MaterialDesc(lobes, m.emission, m.is_emitter)
 
 
-def grid_box(per_vertex=True, nx=8, ny=6, width=64, height=48, lens=False):
+def grid_box(per_vertex=True, nx=8, ny=6, width=64, height=48, lens=False, glass=True):
     """(textured scene, baked scene): the Cornell box whose back wall is a grid of nx x ny quads, each quad's UV triangles strictly inside
     one texel of TEX43 (CLOSEST).  Materials on the grid, by quad: textured Lambert; Lambert + glossy with the Lambert textured (it drops
     on the black texel); Blender's glass node with its refraction colour textured (per-hit Fresnel x texture).  The baked scene has
-    the same face sets in the same order, each with the material of its texel baked in."""
+    the same face sets in the same order, each with the material of its texel baked in.  glass=False leaves the glass material out: no
+    closure weight of the scene then depends on the hit (k_shade_g<false, ., ., true>, TEX without PERHIT)."""
     from phosphorus_mk2_amd import abi, scenes
     D, MF = abi.LOBE_DIFFUSE, abi.LOBE_MICROFACET
     box = scenes.cornell(width, height)
@@ -133,10 +134,11 @@ def grid_box(per_vertex=True, nx=8, ny=6, width=64, height=48, lens=False):
     assert back.vertices[:, 2].max() == -3.5
     tex_mats = [scenes.MaterialDesc([scenes.LobeDesc(D, (0.8, 0.75, 0.7), texture=1)]),
                 scenes.MaterialDesc([scenes.LobeDesc(D, (0.7, 0.7, 0.7), texture=1), scenes.LobeDesc(MF, (0.3, 0.3, 0.3), xalpha=0.09, yalpha=0.09)])]
-    glass = scenes.glass(1.45, 0.0, (0.95, 0.98, 0.95), (1.0, 1.0, 1.0))
-    assert glass.lobes[0].type == abi.LOBE_REFRACTION and glass.lobes[0].fac_mode != 0
-    glass.lobes[0].texture = 1
-    tex_mats.append(glass)
+    if glass:
+        glass = scenes.glass(1.45, 0.0, (0.95, 0.98, 0.95), (1.0, 1.0, 1.0))
+        assert glass.lobes[0].type == abi.LOBE_REFRACTION and glass.lobes[0].fac_mode != 0
+        glass.lobes[0].texture = 1
+        tex_mats.append(glass)
     base = len(box.materials)
     mats_t = box.materials + tex_mats
     mats_b = list(box.materials)
