@@ -18,21 +18,14 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdlib>
+#include <type_traits>
 
 namespace phx {
 
 #define PHX_BLOCK 256
-#ifndef PHX_PERM_LUT
-#define PHX_PERM_LUT 1  /* 1: the octant permutations of the hit masks come from a 2 KB table in LDS instead of 2 x 15 VALU instructions */
-#endif
+#define PHX_PERM_LUT_BYTES 2048u  /* k_trace: the octant permutations of the hit masks come from a table in LDS (8 octants x 256 masks) instead of 2 x 15 VALU instructions */
 #ifndef PHX_COUNT
 #define PHX_COUNT 0  /* 1: instrumented build that counts node visits and triangle tests (bench.py's device-layout byte model) */
-#endif
-#ifndef PHX_SHADE_TIMING
-#define PHX_SHADE_TIMING 0  /* probe builds only: s_memtime around k_shade_g's sort phase and shading rounds, summed into DevStats fields the count build uses (block_append2 below tests it too) */
-#endif
-#ifndef PHX_SHADE_PREFETCH
-#define PHX_SHADE_PREFETCH 2  /* k_shade_g: 1 = hit record and ray of the next round are requested before this round's append; 2 = and the path state (a queue record since round 6) right after it — the hit triangle's 16-byte shade record goes with stage 1, its index being in LDS (PHX_SHADE_TRI_LDS) — (35.9 / 35.3 / 34.8 ms for 0 / 1 / 2: profiles/r05_c_shade_prefetch_ab.log) */
 #endif
 
 __device__ __forceinline__ uint32_t f2u(float f) { return __float_as_uint(f); }
@@ -57,7 +50,7 @@ __device__ __forceinline__ float u2f(uint32_t u) { return __uint_as_float(u); }
 // each other (two barriers and one atomic latency per workgroup instead of four and two).
 template <int SHADE_BLOCK>
 __device__ __forceinline__ void block_append2(bool want_a, uint32_t* counter_a, bool want_b, uint32_t* counter_b, uint32_t* lds /* [2 * (waves + 1)] */,
-                                              uint32_t& at_a, uint32_t& at_b, unsigned long long* probe = nullptr /* PHX_SHADE_TIMING: ticks of the atomics' round trips, their number */) {
+                                              uint32_t& at_a, uint32_t& at_b) {
   static_assert(SHADE_BLOCK >= 128 && SHADE_BLOCK % 64 == 0, "block_append2: wave 0 sums queue A, wave 1 queue B");
   const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6, nwaves = SHADE_BLOCK >> 6;
   const unsigned long long mask_a = __ballot(want_a), mask_b = __ballot(want_b);
@@ -69,14 +62,7 @@ __device__ __forceinline__ void block_append2(bool want_a, uint32_t* counter_a, 
     uint32_t total = 0;
 #pragma nounroll
     for (uint32_t w = 0; w < nwaves; ++w) { const uint32_t c = cnt[w]; cnt[w] = total; total += c; }
-#if PHX_SHADE_TIMING
-    const long long ta_ = clock64();
-#endif
     cnt[nwaves] = total ? atomicAdd(wave == 0 ? counter_a : counter_b, total) : 0u;
-#if PHX_SHADE_TIMING
-    static_assert(offsetof(DevStats, tri_pending_lane_iters) == offsetof(DevStats, idle_lane_iters) + sizeof(unsigned long long), "probe[0] / probe[1] are DevStats::idle_lane_iters / tri_pending_lane_iters");
-    if (probe) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); atomicAdd(&probe[0], (unsigned long long)(clock64() - ta_)); atomicAdd(&probe[1], 1ull); }
-#endif
   }
   __syncthreads();
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -166,10 +152,6 @@ struct LdsStack {
 // One stream serves BOTH queues: lanes are refilled from the workgroup's shadow-ray range first, then from
 // its closest-hit range; the any-hit / closest-hit distinction is a per-lane flag, so a launch has a single
 // drain phase (the tail where rays run out and lanes idle) instead of one per queue.
-#ifndef PHX_STEPS_PER_REFILL
-#define PHX_STEPS_PER_REFILL 1
-#endif
-// Sensitivity probes (profiles/README.md), never in the product build: extra FMAs / extra 16-byte loads per node visit.
 // The chunks of the persistent launch are handed out in two levels.  A WORKGROUP takes 16 chunks' worth of
 // consecutive rays from the global cursor at a time; its waves take their chunks from that range through a 64-bit word in LDS
 // (next | end << 32: one ds_add returns a consistent pair).  The wave that finds the range used up fetches the next one
@@ -179,9 +161,6 @@ struct LdsStack {
 // workload and were removed in round 3 — the history is in EXPERIMENTS.md, Part B section 3.)
 #ifndef PHX_WG_CHUNKS
 #define PHX_WG_CHUNKS 16u  /* chunks in a workgroup's range (fewer when the queue is too short to give every workgroup four ranges) */
-#endif
-#ifndef PHX_XCD_SEGMENTS
-#define PHX_XCD_SEGMENTS 1  /* a workgroup takes its ranges from its XCD's eighth of the queue first */
 #endif
 #ifndef PHX_SPILL_FROM_LEVELS
 #define PHX_SPILL_FROM_LEVELS 10u  /* trees with this many stack levels or more keep only PHX_SPILL_LDS_LEVELS of them in LDS */
@@ -195,17 +174,8 @@ struct LdsStack {
 // workgroup stage 256 more nodelets (281 -> 537).  Measured (profiles/r06_f_packed_stack_ab.log): k_trace -2.3 % on BASELINE config 4 (10 M
 // triangles), -4.0 % on the closed showroom (depth 13); trees whose stacks fit LDS gain nothing from more staged nodelets (100 k: +0.7 %, the
 // second LDS access per push / pop; 1 M: +-0) and keep 8-byte entries.  Pools of < 2^24 elements only (1 GB; larger ones: 8-byte entries).
-// 0 = never, 1 = the SPILL plan, 2 = every plan (A/B).
+// 0 = never (the nopack twin library), 1 = the SPILL plan.
 #define PHX_STACK_PACKED 1
-#endif
-#ifndef PHX_PROBE_VALU
-#define PHX_PROBE_VALU 0
-#endif
-#ifndef PHX_PROBE_VMEM
-#define PHX_PROBE_VMEM 0
-#endif
-#ifndef PHX_PROBE_VMEM_DWORD
-#define PHX_PROBE_VMEM_DWORD 0
 #endif
 #define PHX_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))  /* wave-uniform by construction: keep it in an SGPR */
 #ifndef PHX_TRACE_WATCHDOG
@@ -275,7 +245,6 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
               else if (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) st = 2;
               else {
                 const uint32_t cwg = phase == 0u ? dq.r0 : dq.r1;
-#if PHX_XCD_SEGMENTS
                 // the next range of this XCD's segment of the queue; when that is used up, of the next segment that has one (cursor[8 + phase])
                 uint32_t nb = qn, seg_end = qn, sgm = cursor[8 + phase];
                 for (uint32_t tries = 0; tries < CNT_SEGS; ++tries, sgm = (sgm + 1u) & (CNT_SEGS - 1u)) {
@@ -288,12 +257,6 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
                 if (nb >= seg_end) { __hip_atomic_store(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); st = 2; }
                 else {
                   const uint32_t end = min(nb + cwg, seg_end);
-#else
-                const uint32_t nb = atomicAdd(&dq.cursor[phase * CNT_SEGS * CNT_STRIDE], cwg) + gridDim.x * cwg;
-                if (nb >= qn) { __hip_atomic_store(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); st = 2; }
-                else {
-                  const uint32_t end = min(nb + cwg, qn);
-#endif
                   got_lo = nb; got_hi = min(nb + c, end); st = 0;  // the fetching wave keeps the range's first chunk
                   __hip_atomic_store(pack, (unsigned long long)(nb + c) | ((unsigned long long)end << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
@@ -390,33 +353,7 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
 #pragma unroll
         for (int k = 0; k < 4; ++k) { const uint4 v = s4[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
       }
-#if PHX_PROBE_VMEM
-      // sensitivity probe (never in the product build): PHX_PROBE_VMEM more 16-byte loads per node visit, from the neighbouring element
-      if (!in_lds) {
-        const uint4* s4 = reinterpret_cast<const uint4*>(sc.pool) + (size_t)(ni ^ 1u) * 4u;
-#pragma unroll
-        for (int k = 0; k < PHX_PROBE_VMEM; ++k) {
-#if PHX_PROBE_VMEM_DWORD
-          w[2] ^= s4[k].x & (refill_min >> 31);   // same addresses, a quarter of the bytes
-#else
-          const uint4 v = s4[k]; w[2] ^= (v.x ^ v.y ^ v.z ^ v.w) & (refill_min >> 31);
-#endif
-        }
-      }
-#endif
-#if PHX_PERM_LUT
-      uint32_t hm = node_hitmask(w, sc.grid, r, tbest, [&](uint32_t m) { return (uint32_t)perm_lut[(r.oct_inv << 8) | m]; });
-#else
-      uint32_t hm = node_hitmask(w, sc.grid, r, tbest);
-#endif
-#if PHX_PROBE_VALU
-      {  // sensitivity probe (never in the product build): PHX_PROBE_VALU more v_fma_f32 per node visit
-        float x = tbest;
-#pragma unroll
-        for (int k = 0; k < PHX_PROBE_VALU; ++k) x = __builtin_fmaf(x, 0.99999f, 1.0e-3f);
-        hm ^= f2u(x) & (refill_min >> 31);
-      }
-#endif
+      const uint32_t hm = node_hitmask(w, sc.grid, r, tbest, [&](uint32_t m) { return (uint32_t)perm_lut[(r.oct_inv << 8) | m]; });
       ng_base = w[3];                // the children of the node just visited: nodelets and triangle records, in slot order
       ng_hits = hm & 0xff0000ffu;    // pending inner children | valid mask
       const uint32_t tnew = (hm >> 8) & TG_PENDING;  // hit leaf slots of this node -> bits 8..15
@@ -527,7 +464,7 @@ __global__ void __launch_bounds__(BLOCK, 8) k_trace(DevScene sc, PassBuffers pb,
   uint32_t* stack_words = reinterpret_cast<uint32_t*>(stack);
   uint32_t* valid_rows = stack_words + levels * BLOCK;
   uint32_t* cursor = PACKED ? valid_rows + ((levels + 3u) >> 2) * BLOCK : reinterpret_cast<uint32_t*>(stack + levels * BLOCK);
-  uint8_t* perm_lut = reinterpret_cast<uint8_t*>(cursor + 12);  // PHX_PERM_LUT: 8 octants x 256 masks (cursor: 12 words)
+  uint8_t* perm_lut = reinterpret_cast<uint8_t*>(cursor + 12);  // PHX_PERM_LUT_BYTES: 8 octants x 256 masks (cursor: 12 words)
   const uint32_t n_closest = do_closest ? pb.counters[q * CNT_STRIDE] : 0u;
   const uint32_t n_shadow = do_shadow ? pb.counters[CNT_SHADOW + sq * CNT_STRIDE] : 0u;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -554,14 +491,10 @@ __global__ void __launch_bounds__(BLOCK, 8) k_trace(DevScene sc, PassBuffers pb,
     unsigned long long* pack = reinterpret_cast<unsigned long long*>(cursor);
     for (uint32_t p = 0; p < 2u; ++p) {
       const uint32_t cwg = p == 0u ? dq.r0 : dq.r1, qn = p == 0u ? n_shadow : n_closest;
-#if PHX_XCD_SEGMENTS
       const uint32_t sgm = blockIdx.x & (CNT_SEGS - 1u), kth = blockIdx.x / CNT_SEGS;  // the kth range of this XCD's segment
       const uint32_t lo_s = (uint32_t)((unsigned long long)qn * sgm / CNT_SEGS), hi_s = (uint32_t)((unsigned long long)qn * (sgm + 1u) / CNT_SEGS);
       const uint32_t lo = (uint32_t)min((unsigned long long)lo_s + (unsigned long long)kth * cwg, (unsigned long long)hi_s), hi = min(lo + cwg, hi_s);
       cursor[8 + p] = sgm;
-#else
-      const uint32_t lo = min(blockIdx.x * cwg, qn), hi = min(lo + cwg, qn);
-#endif
       pack[p] = (unsigned long long)lo | ((unsigned long long)hi << 32);
       cursor[4 + p] = 0u; cursor[6 + p] = 0u;
     }
@@ -570,9 +503,7 @@ __global__ void __launch_bounds__(BLOCK, 8) k_trace(DevScene sc, PassBuffers pb,
   // keeps an 80-byte stride in LDS (PHX_NODE_LDS_BYTES, bvh8.h)
   const uint4* g4 = reinterpret_cast<const uint4*>(sc.pool);
   for (uint32_t i = threadIdx.x; i < ntop * 4u; i += BLOCK) top[(i >> 2) * (PHX_NODE_LDS_BYTES / 16u) + (i & 3u)] = g4[i];
-#if PHX_PERM_LUT
-  for (uint32_t i = threadIdx.x; i < 2048u; i += BLOCK) perm_lut[i] = (uint8_t)perm_xor8(i & 0xffu, i >> 8);
-#endif
+  for (uint32_t i = threadIdx.x; i < PHX_PERM_LUT_BYTES; i += BLOCK) perm_lut[i] = (uint8_t)perm_xor8(i & 0xffu, i >> 8);
   __syncthreads();
   if constexpr (PACKED)
     trace_stream<BLOCK, SPILL, true>(sc, pb, q, cursor, reinterpret_cast<uint2*>(stack_words + threadIdx.x), reinterpret_cast<uint8_t*>(valid_rows + threadIdx.x), levels,
@@ -1040,36 +971,18 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_D) __attribute__((amdgpu_waves
 #define PHX_SHADE_ITEMS_G 8
 #endif
 #define PHX_SHADE_BUCKETS 64  /* sort key = material mod 64; then the misses; slots past the end of the queue go last */
-#ifndef PHX_SHADE_KEY_PROBE
-#define PHX_SHADE_KEY_PROBE 0
-#endif
 // probe builds (-DPHX_SHADE_TIMING=1, scripts/shade_phase_probe.py): s_memtime at the phase boundaries of a shading round, per wave.
 // PHX_PHASE(n) closes phase n: everything the wave has in flight is waited for first, so that a phase is charged the latency of what it
 // asked for (loads issued in a phase and consumed later would otherwise be billed to the consumer).
+#ifndef PHX_SHADE_TIMING
+#define PHX_SHADE_TIMING 0  /* 1: the ticks are summed into DevStats fields the count build uses */
+#endif
 #if PHX_SHADE_TIMING
 #define PHX_PHASE_DECL long long ph_t = clock64(); unsigned long long ph_acc[6] = {0, 0, 0, 0, 0, 0};
 #define PHX_PHASE(n) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const long long now_ = clock64(); ph_acc[n] += (unsigned long long)(now_ - ph_t); ph_t = now_; }
 #else
 #define PHX_PHASE_DECL
 #define PHX_PHASE(n)
-#endif
-#ifndef PHX_SHADE_PREFETCH_PERHIT
-#define PHX_SHADE_PREFETCH_PERHIT 0  /* the same two stages in the per-hit (glass) instantiations: measured worthless in round 5 (profiles/r05_c_shade_prefetch_glass_ab.log) */
-#endif
-#ifndef PHX_SHADE_TRI_LDS
-#define PHX_SHADE_TRI_LDS 1  /* the sort phase keeps each hit's pool index beside the permutation (16 KB of LDS), so that a round requests the hit triangle's shade record (and, where nothing is prefetched, its vertex normals) WITH the hit record and the ray instead of after the hit record has landed */
-#endif
-#ifndef PHX_SHADE_FIRST_SORT
-#define PHX_SHADE_FIRST_SORT 0  /* 1: the camera entries' launch sorts its windows by material like every other.  0: it does not — the 64 lanes of a wave are 64 samples of ONE pixel there, which see one material (two or three on a silhouette) without any sorting */
-#endif
-#ifndef PHX_SCALAR_F_PERHIT
-#define PHX_SCALAR_F_PERHIT 1  /* the per-hit (glass) instantiations read the recipe through the scalar cache too: with the ring append the kernel has the registers (127 / 123 VGPRs, no scratch; round 5: 16 B of scratch): closed showroom -4.4 %, glass showroom -2.9 % shade time (profiles/r06_i_perhit_knobs_ab.log) */
-#endif
-#ifndef PHX_SCALAR_F
-#define PHX_SCALAR_F 1  /* bsdf_f's lobe loop reads the recipe through the scalar cache: -0.6 % shade time, 128 -> 121 VGPRs */
-#endif
-#ifndef PHX_SCALAR_S
-#define PHX_SCALAR_S 0  /* bsdf_sample picks its lobe per lane: through the scalar path it is 2-3 % slower (profiles/r04_j_shade_scalar_ab.log) */
 #endif
 // The lanes that reach a closure evaluation, one distinct material of the wave at a time (after the window's sort by material most
 // waves hold one): the material's index is made wave-uniform (v_readlane), its recipe is addressed in the CONSTANT address space, and
@@ -1098,12 +1011,6 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_D) __attribute__((amdgpu_waves
 // Ordering: the LDS executes the DS instructions of one wave in issue order, so "records, then commit" and "reads, then release" need no
 // fence in hardware; s_waitcnt lgkmcnt(0) + a compiler barrier keep the compiler (and any doubt) out.  NOT __builtin_amdgcn_fence: a
 // workgroup-scope fence also waits for the wave's global loads — the next round's records, requested right before the append.
-#ifndef PHX_SHADE_RING
-#define PHX_SHADE_RING 1
-#endif
-#ifndef PHX_SHADE_DYN_SLICES
-#define PHX_SHADE_DYN_SLICES 1  /* with the ring: a wave takes the next 64 sorted slots of the window from an LDS counter instead of slots [k x BLOCK + 64 w, + 64) of round k (nothing orders the waves inside a window any more, so the fast ones take more) */
-#endif
 #ifndef PHX_RING_BLK
 #define PHX_RING_BLK 256u  /* entries per flush = per global atomic (the counters sustain ~80 returning atomics per us and address: 256 keeps the kernel near 50) */
 #endif
@@ -1195,20 +1102,19 @@ template <bool PERHIT /* some material's closure weights depend on the hit (glas
 __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves_per_eu(PHX_SHADE_WAVES_G, 8))) k_shade_g(DevScene sc, PassBuffers pb, int q, int sq, uint32_t sample0) {
   constexpr int BLOCK = PHX_SHADE_BLOCK_G, ITEMS = PHX_SHADE_ITEMS_G, WINDOW = BLOCK * ITEMS, NB = PHX_SHADE_BUCKETS;
   static_assert(WINDOW <= 65536 && BLOCK >= NB + 2 && NB == 64, "perm holds 16-bit positions; one wave scans the NB material buckets");
-#if PHX_SHADE_RING
   __shared__ float4 ring_a[3 * 2 * PHX_RING_BLK];  // survivors: (o, path | SPECULAR << 31), (d, RNG key), (beta, depth)
   __shared__ float4 ring_b[3 * 2 * PHX_RING_BLK];  // NEE rays: (o, path), (d, tmax), (beta * Li)
   __shared__ RingCtl ring_ctl[2];
-  __shared__ uint32_t slice_next;  // PHX_SHADE_DYN_SLICES: the window's next 64-slot slice
+  // a wave takes the next 64 sorted slots of the window from this counter, not slots [k x BLOCK + 64 w, + 64) of a round k: nothing orders the
+  // waves inside a window since the ring append, so the fast ones take more
+  __shared__ uint32_t slice_next;
   if (threadIdx.x < sizeof(ring_ctl) / 4u) reinterpret_cast<uint32_t*>(ring_ctl)[threadIdx.x] = 0u;  // visible after the first barrier every thread reaches
-#else
-  __shared__ uint32_t lds_sr[2 * ((BLOCK >> 6) + 1)];
-#endif
   __shared__ uint32_t bucket[NB + 2];  // [material mod NB], [NB] misses, [NB + 1] slots past the end of the queue
   __shared__ uint16_t perm[WINDOW];
   if (pb.stats->watchdog | pb.stats->ring_watchdog) return;  // (k_shade above: a step whose trace did not finish is not shaded; the frame fails)
-  constexpr bool TRI_LDS = PHX_SHADE_TRI_LDS != 0;
-  __shared__ uint32_t tri_sorted[TRI_LDS ? WINDOW : 1];  // the hit's pool index (0xffffffff = miss) at its sorted position
+  // the hit's pool index (0xffffffff = miss) at its sorted position, kept beside the permutation (16 KB of LDS): a round requests the hit triangle's
+  // shade record, vertex normals and corner UVs WITH the hit record and the ray instead of after the hit record has landed
+  __shared__ uint32_t tri_sorted[WINDOW];
   const uint32_t count = pb.counters[q * CNT_STRIDE];
   if (blockIdx.x == 0 && threadIdx.x == 0) zero_cursors(pb.counters);  // the next k_trace pulls its chunks from here
   DevTexScene tx{};  // TEX / ENV: the scene's texture tables, pointers in SGPRs (constant address space: s_load)
@@ -1235,30 +1141,22 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
   auto request_keys = [&](const uint32_t (&tri)[ITEMS], uint32_t (&key)[ITEMS]) {
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
-#if PHX_SHADE_KEY_PROBE
-      key[k] = tri[k] == 0xfffffffeu ? NB + 1u : tri[k] != 0xffffffffu ? 0u : (uint32_t)NB;  // probe builds only: what the material gather of the sort phase costs (one-material scenes)
-#else
       key[k] = tri[k] == 0xfffffffeu ? NB + 1u : tri[k] != 0xffffffffu ? (f2u(sc.elem_shade[tri[k]].w) & (NB - 1u)) : (uint32_t)NB;  // the material word of the 16-byte shade record (four to a sector; the shading rounds read the same records)
-#endif
     }
   };
   for (uint32_t base = blockIdx.x * WINDOW; base < count; base += gridDim.x * WINDOW) {
     PHX_PHASE(5)  // (the barrier at the end of the previous window, loop overhead)
     // ---- counting sort of the window by material, through LDS
     if (threadIdx.x < NB + 2) bucket[threadIdx.x] = 0;
-#if PHX_SHADE_RING && PHX_SHADE_DYN_SLICES
     if (threadIdx.x == 0) slice_next = 0u;
-#endif
     __syncthreads();
     uint32_t keys[ITEMS], tri_[ITEMS];
     request_tris(base, tri_);
-    if constexpr (FIRST && !PHX_SHADE_FIRST_SORT) {
+    if constexpr (FIRST) {
       // the camera entries: queue order IS pixel order (a wave = 64 samples of one pixel: one material, a few on a silhouette) — no sort, the
       // identity permutation; the slots past the end of the queue are the window's last ones as they are after a sort
-      if constexpr (TRI_LDS) {
 #pragma unroll
-        for (int k = 0; k < ITEMS; ++k) tri_sorted[k * BLOCK + threadIdx.x] = tri_[k];
-      }
+      for (int k = 0; k < ITEMS; ++k) tri_sorted[k * BLOCK + threadIdx.x] = tri_[k];
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k) perm[k * BLOCK + threadIdx.x] = (uint16_t)(k * BLOCK + threadIdx.x);
     } else {
@@ -1280,7 +1178,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
     for (int k = 0; k < ITEMS; ++k) {
       const uint32_t at = bucket[keys[k]] + ranks[k];
       perm[at] = (uint16_t)(k * BLOCK + threadIdx.x);
-      if constexpr (TRI_LDS) tri_sorted[at] = tri_[k];
+      tri_sorted[at] = tri_[k];
     }
     }
     __syncthreads();
@@ -1288,66 +1186,48 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
 #if PHX_SHADE_TIMING
     ++ph_windows;
 #endif
-    // ---- the window in sorted order: wave w of round k shades sorted positions [k * BLOCK + 64 w, + 64)
-    // The records of round k + 1 — hit, ray — are REQUESTED right before round k's append (PHX_SHADE_PREFETCH): the phase probe of round 5
-    // (profiles/r05_c_shade_phases.md) found a wave waiting 27 % of its time for exactly these loads and 24 % in the append (two barriers
-    // and the round trip of the workgroup's atomics); at the append a thread holds almost nothing but its outputs, so the twelve registers of
-    // the next records cost no occupancy there, and the two waits overlap.  (Round 3 requested them at the START of round k and held them
-    // across the closure code: 5-12 VGPRs where the kernel has none to spare, 1.2 of 42.7 ms: profiles/r03_q_prefetch_ab.log.)
+    // ---- the window in sorted order, in slices of 64 sorted slots handed out by an LDS counter; the live slots are a prefix of the sorted
+    // window, so are the live slices (the slots past the end of the queue sort behind every live one)
+    // The records of the NEXT slice — hit, ray, shade record — are REQUESTED right before this one's append: the phase probe of round 5
+    // (profiles/r05_c_shade_phases.md) found a wave waiting 27 % of its time for exactly these loads and 24 % in the append; at the append a
+    // thread holds almost nothing but its outputs, so the registers of the next records cost no occupancy there, and the two waits overlap.
+    // (Round 3 requested them at the START of a round and held them across the closure code: 5-12 VGPRs where the kernel has none to spare,
+    // 1.2 of 42.7 ms: profiles/r03_q_prefetch_ab.log.)
     uint32_t next_i = 0, next_tri = 0xffffffffu; bool next_live = false;
     float4 next_h = make_float4(0.f, 0.f, 0.f, 0.f), next_a = next_h, next_b = next_h, next_S = next_h;
-    constexpr bool DYN = PHX_SHADE_RING && PHX_SHADE_DYN_SLICES;
-    // DYN: slices of 64 sorted slots, handed out by an LDS counter; the live slots are a prefix of the sorted window, so are the live slices
     const uint32_t nslices = (min((uint32_t)WINDOW, count - base) + 63u) >> 6;
     auto take_slice = [&]() -> uint32_t {
-#if PHX_SHADE_RING && PHX_SHADE_DYN_SLICES
       uint32_t s_ = 0;
       if (__lane_id() == 0) s_ = __hip_atomic_fetch_add(&slice_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       return PHX_UNI(s_);
-#else
-      return 0u;
-#endif
     };
-    auto sorted_slot = [&](uint32_t k) { return DYN ? k * 64u + __lane_id() : k * BLOCK + threadIdx.x; };  // k: slice (DYN) or round
+    auto sorted_slot = [&](uint32_t k) { return k * 64u + __lane_id(); };
     auto request_round = [&](uint32_t k) {
       next_live = false;
-      if (DYN ? k < nslices : (k < (uint32_t)ITEMS && base + k * BLOCK < count)) {
+      if (k < nslices) {
         next_i = base + perm[sorted_slot(k)];
         next_live = next_i < count;
         if (next_live) {
           next_h = pb.hit[next_i];
           if (!FIRST) { next_a = pb.ro[q][next_i]; next_b = pb.rd[q][next_i]; }
-          if constexpr (TRI_LDS) {  // the shade record no longer waits for the hit record: its index is in LDS (four registers across the append)
-            next_tri = tri_sorted[sorted_slot(k)];
-            if (next_tri != 0xffffffffu) next_S = sc.elem_shade[next_tri];
-          }
+          next_tri = tri_sorted[sorted_slot(k)];  // the shade record does not wait for the hit record: its index is in LDS (four registers across the append)
+          if (next_tri != 0xffffffffu) next_S = sc.elem_shade[next_tri];
         }
       }
     };
-    // second stage (PHX_SHADE_PREFETCH 2): requested right after the append, travelling while this round's queue entries are stored: the path
-    // state — since round 6 a queue record like the ray, no longer a gather by path id: four registers that need not live across the append —
-    // and, in builds without PHX_SHADE_TRI_LDS, the shade record, whose index then has to wait for the hit record
+    // second stage, requested right after the append, travelling while this slice's queue entries are stored: the path state — since round 6 a
+    // queue record like the ray, no longer a gather by path id: four registers that need not live across the append
     float4 next_bd = make_float4(1.0f, 1.0f, 1.0f, u2f(0u));  // FIRST: state_t::reset: beta = 1, depth = 0
-    auto request_round_dependents = [&]() {
-      if (next_live) {
-        if (!FIRST) next_bd = pb.qs[q][next_i];
-        const uint32_t tri = f2u(next_h.w);
-        if constexpr (!TRI_LDS) { if (tri != 0xffffffffu) next_S = sc.elem_shade[tri]; }
-      }
-    };
-    // (with per-hit closure weights — glass — either stage costs the kernel 16 B of scratch and buys nothing: 41.7-42.1 ms with, 41.9-42.2
-    // without on the glass showroom, profiles/r05_c_shade_prefetch_glass_ab.log: those instantiations request where they consume)
-    constexpr bool STAGE1 = PHX_SHADE_PREFETCH >= 1 && (!PERHIT || PHX_SHADE_PREFETCH_PERHIT >= 1), STAGE2 = PHX_SHADE_PREFETCH >= 2 && (!PERHIT || PHX_SHADE_PREFETCH_PERHIT >= 2);
-    uint32_t k = DYN ? take_slice() : 0u, k_next = 0u;
-    if constexpr (STAGE1) request_round(k);
-    if constexpr (STAGE2) request_round_dependents();
-    for (;; k = k_next) {
-      // wave-uniform (DYN) / workgroup-uniform: the slots past the end of the queue sort behind every live one
-      if (DYN ? k >= nslices : (k >= (uint32_t)ITEMS || base + k * BLOCK >= count)) break;
-      // (instantiations without a stage request each record where it is consumed, exactly as the round-4 kernel did)
-      if constexpr (STAGE1 && !STAGE2) request_round_dependents();
-      const uint32_t i = STAGE1 ? next_i : base + perm[sorted_slot(k)];
-      const bool live = STAGE1 ? next_live : i < count;
+    auto request_round_dependents = [&]() { if (!FIRST && next_live) next_bd = pb.qs[q][next_i]; };
+    // 35.9 / 35.3 / 34.8 ms for no stage / the first / both (profiles/r05_c_shade_prefetch_ab.log).  With per-hit closure weights — glass — either
+    // stage costs the kernel 16 B of scratch and buys nothing: 41.7-42.1 ms with, 41.9-42.2 without on the glass showroom
+    // (profiles/r05_c_shade_prefetch_glass_ab.log): those instantiations request each record where it is consumed, as the round-4 kernel did
+    constexpr bool PREFETCH = !PERHIT;
+    uint32_t k = take_slice(), k_next = 0u;
+    if constexpr (PREFETCH) { request_round(k); request_round_dependents(); }
+    for (; k < nslices; k = k_next) {  // wave-uniform
+      const uint32_t i = PREFETCH ? next_i : base + perm[sorted_slot(k)];
+      const bool live = PREFETCH ? next_live : i < count;
       // Live ranges are kept short on purpose (the kernel is register-bound: 128 VGPRs as one block of code): radiance and the
       // normals channel are written as soon as the hit is known; the light's record is re-read after the closure evaluation instead
       // of being held across it.
@@ -1359,19 +1239,20 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
       if (live) {
         float4 a, b, bd;
         float4 h;
-        if constexpr (STAGE1) h = next_h; else h = pb.hit[i];
-        // TRI_LDS: the hit's pool index comes from the sort phase (LDS), so its shade record and vertex normals are requested HERE, beside the
-        // hit record and the ray, not after the hit record has landed (one memory round trip less on the critical path of a round)
-        uint32_t tri_early = 0xffffffffu; float4 S_early = make_float4(0.f, 0.f, 0.f, 0.f); VertexNormals VN_early{v3(0.0f), v3(0.0f), v3(0.0f)};
-        CornerUVs UV_early{};  // TEX: the corner UVs travel with the shade record and the normals (the texel gathers then wait on u, v only)
-        if constexpr (TRI_LDS && STAGE1) {
-          tri_early = next_tri; S_early = next_S;
-          if (tri_early != 0xffffffffu) { VN_early = request_vertex_normals(sc, tri_early); if constexpr (TEX) UV_early = request_corner_uvs(tx.elem_uv, tri_early); }
-        } else if constexpr (TRI_LDS) {
-          tri_early = tri_sorted[sorted_slot(k)];
-          if (tri_early != 0xffffffffu) {
-            S_early = sc.elem_shade[tri_early]; VN_early = request_vertex_normals(sc, tri_early);
-            if constexpr (TEX) UV_early = request_corner_uvs(tx.elem_uv, tri_early);
+        if constexpr (PREFETCH) h = next_h; else h = pb.hit[i];
+        // the hit's pool index comes from the sort phase (LDS), so its shade record, vertex normals and corner UVs are requested HERE, beside the
+        // hit record and the ray (one memory round trip less on the critical path of a round; the texel gathers then wait on u, v only)
+        uint32_t tri = 0xffffffffu; float4 S = make_float4(0.f, 0.f, 0.f, 0.f);  // S: (geometric normal, material | smooth << 31), DevScene::elem_shade
+        VertexNormals VN_early{v3(0.0f), v3(0.0f), v3(0.0f)};
+        CornerUVs UV_early{};  // TEX
+        if constexpr (PREFETCH) {
+          tri = next_tri; S = next_S;
+          if (tri != 0xffffffffu) { VN_early = request_vertex_normals(sc, tri); if constexpr (TEX) UV_early = request_corner_uvs(tx.elem_uv, tri); }
+        } else {
+          tri = tri_sorted[sorted_slot(k)];
+          if (tri != 0xffffffffu) {
+            S = sc.elem_shade[tri]; VN_early = request_vertex_normals(sc, tri);
+            if constexpr (TEX) UV_early = request_corner_uvs(tx.elem_uv, tri);
           }
         }
         if (FIRST) {
@@ -1380,7 +1261,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           a = make_float4(co.x, co.y, co.z, u2f(i)); b = make_float4(cd.x, cd.y, cd.z, FLT_MAX);
           bd = make_float4(1.0f, 1.0f, 1.0f, u2f(0u));  // state_t::reset: beta = 1, depth = 0
         } else {
-          if constexpr (STAGE1) { a = next_a; b = next_b; bd = next_bd; } else { a = pb.ro[q][i]; b = pb.rd[q][i]; bd = pb.qs[q][i]; }
+          if constexpr (PREFETCH) { a = next_a; b = next_b; bd = next_bd; } else { a = pb.ro[q][i]; b = pb.rd[q][i]; bd = pb.qs[q][i]; }
         }
         const uint32_t pbits = f2u(a.w);
         path = pbits & 0x7fffffffu;
@@ -1394,19 +1275,13 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
         } else {
           key = f2u(b.w);
         }
-        const uint32_t tri = TRI_LDS ? tri_early : f2u(h.w);
         const v3 o(a.x, a.y, a.z), d(b.x, b.y, b.z);
         v3 add_e(0.0f); bool add_rad = false;
         if (tri != 0xffffffffu) {
           hit_surface = true;
-          VertexNormals VN;
-          float4 S;  // (geometric normal, material | smooth << 31): DevScene::elem_shade
+          VertexNormals VN;  // (these two copies compute nothing, but the register allocation depends on them: EXPERIMENTS.md, "Retired A/B knobs")
           CornerUVs UV{};
-          if constexpr (TRI_LDS) { VN = VN_early; S = S_early; if constexpr (TEX) UV = UV_early; }
-          else {
-            VN = request_vertex_normals(sc, tri); if constexpr (STAGE1) S = next_S; else S = sc.elem_shade[tri];
-            if constexpr (TEX) UV = request_corner_uvs(tx.elem_uv, tri);
-          }
+          VN = VN_early; if constexpr (TEX) UV = UV_early;
           if constexpr (TEX) st = hit_st(UV, h.y, h.z);
           const uint32_t pm = f2u(S.w);
           p = o + d * h.x;            // hits.p = p + wi*d
@@ -1470,15 +1345,15 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           const float oolen = 1.0f / sqrtf(l2);
           sh_d = v3(sh_d.x * oolen, sh_d.y * oolen, sh_d.z * oolen);
           if (sdot(n, sh_d) >= 0.0f) {
-            // li(), spt.hpp:212-255 — evaluated before the occlusion test; k_trace adds it if the ray is unoccluded
+            // li(), spt.hpp:212-255 — evaluated before the occlusion test; k_trace adds it if the ray is unoccluded.  bsdf_f's lobe loop reads the
+            // recipe through the scalar cache: -0.6 % shade time, 128 -> 121 VGPRs; in the per-hit (glass) instantiations too, which have the registers
+            // since the ring append: closed showroom -4.4 %, glass showroom -2.9 % shade time (profiles/r06_i_perhit_knobs_ab.log)
             v3 f(0.0f);
             if constexpr (TEX) {  // the material's lobes with the texels at (s, t); the lookups read the hit's own row of lobe_tex
               const TexHit th{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y};
               PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT, true, MASK>(cm, n, fr, sh_d, wo, th)));
-            } else if constexpr (PHX_SCALAR_F && (!PERHIT || PHX_SCALAR_F_PERHIT)) {
-              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT>(cm, n, fr, sh_d, wo)));
             } else {
-              f = bsdf_f<false, 8, PERHIT>(sc.materials[mat], n, fr, sh_d, wo);
+              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_f<false, 8, PERHIT>(cm, n, fr, sh_d, wo)));
             }
             // the light's record again (L1-resident), behind an empty asm so that the first read is not kept alive across bsdf_f
             asm volatile("" : "+v"(l), "+v"(lt));
@@ -1513,19 +1388,9 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             const uint32_t b1 = (depth - 1u) * DIMS_PER_STEP;
             float pdf; uint32_t fl;
             const float u1 = draw_f32(key, b1 + DIM_BSDF_U), u2 = draw_f32(key, b1 + DIM_BSDF_V);
-#if PHX_SCALAR_S
-            v3 f(0.0f);
-            if constexpr (TEX) {
-              const TexHit th{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y};
-              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT, true, MASK>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl, th)));
-            } else {
-              PHX_FOR_EACH_MATERIAL_OF_THE_WAVE(mat, cm, f = (bsdf_sample<false, 8, PERHIT>(cm, n, fr, u1, u2, wo, nxt_d, pdf, fl)));
-            }
-#else
-            v3 f;
+            v3 f;  // bsdf_sample picks its lobe per lane: through the scalar path it is 2-3 % slower (profiles/r04_j_shade_scalar_ab.log)
             if constexpr (TEX) f = bsdf_sample<false, 8, PERHIT, true, MASK>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl, TexHit{tx.textures, tx.texels, tx.lobe_tex + 8 * (size_t)mat, st.x, st.y});
             else f = bsdf_sample<false, 8, PERHIT>(sc.materials[mat], n, fr, u1, u2, wo, nxt_d, pdf, fl);
-#endif
             if ((f.x == 0.0f && f.y == 0.0f && f.z == 0.0f) || pdf == 0.0f) {
               alive = false;
             } else {
@@ -1536,13 +1401,11 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             }
           }
         }
-        // both queues in one go: two barriers and two concurrent atomics per round (appending the NEE ray before roulette and sampling
-        // — shorter live ranges, four barriers, two atomics in a row — was right while the kernel fought for occupancy; at 4 waves per SIMD
-        // either way, the 10 registers are free and the round trip is not: 43.1 -> 41.5 ms, profiles/r03_zzc_append2_ab.log)
+        // both queues are appended here, after roulette and sampling (appending the NEE ray before them — shorter live ranges — was right
+        // while the kernel fought for occupancy; at 4 waves per SIMD either way the 10 registers are free: 43.1 -> 41.5 ms, profiles/r03_zzc_append2_ab.log)
         PHX_PHASE(3)  // roulette, bsdf_sample
-        k_next = DYN ? take_slice() : k + 1u;
-        if constexpr (STAGE1) request_round(k_next);  // in flight across the append (the append waits for LDS traffic only)
-#if PHX_SHADE_RING
+        k_next = take_slice();
+        if constexpr (PREFETCH) request_round(k_next);  // in flight across the append (the append waits for LDS traffic only)
         {
           const v3 nxt_o = p + n * off;
           ring_append<3>(want_shadow, make_float4(sh_o.x, sh_o.y, sh_o.z, u2f(path)), make_float4(sh_d.x, sh_d.y, sh_d.z, sh_t), make_float4(contrib.x, contrib.y, contrib.z, 0.0f),
@@ -1552,28 +1415,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
                          &ring_ctl[0], ring_a, &pb.counters[(q ^ 1) * CNT_STRIDE], pb.ro[q ^ 1], pb.rd[q ^ 1], pb.qs[q ^ 1], &pb.stats->ring_watchdog);
         }
         PHX_PHASE(4)  // the append: slot reservation, records to LDS, commit; for one wave in BLK / 64 rounds the flush of a block
-        if constexpr (STAGE2) request_round_dependents();
-#else
-        uint32_t no, ns;
-        #if PHX_SHADE_TIMING
-        block_append2<BLOCK>(alive, &pb.counters[(q ^ 1) * CNT_STRIDE], want_shadow, &pb.counters[CNT_SHADOW + sq * CNT_STRIDE], lds_sr, no, ns, &pb.stats->idle_lane_iters);
-#else
-        block_append2<BLOCK>(alive, &pb.counters[(q ^ 1) * CNT_STRIDE], want_shadow, &pb.counters[CNT_SHADOW + sq * CNT_STRIDE], lds_sr, no, ns);
-#endif
-        PHX_PHASE(4)  // the append: two barriers and the workgroup's two atomics on the queue counters
-        if constexpr (STAGE2) request_round_dependents();
-        if (want_shadow) {
-          pb.so[ns] = make_float4(sh_o.x, sh_o.y, sh_o.z, u2f(path));
-          pb.sd[ns] = make_float4(sh_d.x, sh_d.y, sh_d.z, sh_t);
-          pb.sc[ns] = make_float4(contrib.x, contrib.y, contrib.z, 0.0f);
-        }
-        if (alive) {
-          const v3 nxt_o = p + n * off;
-          pb.ro[q ^ 1][no] = make_float4(nxt_o.x, nxt_o.y, nxt_o.z, u2f(path | (next_specular << 31)));
-          pb.rd[q ^ 1][no] = make_float4(nxt_d.x, nxt_d.y, nxt_d.z, u2f(key));
-          pb.qs[q ^ 1][no] = make_float4(beta.x, beta.y, beta.z, u2f(depth));
-        }
-#endif
+        if constexpr (PREFETCH) request_round_dependents();
         PHX_PHASE(5)  // the stores of the two queue entries (waited for: the probe charges them here, the product build does not wait)
 #if PHX_SHADE_TIMING
         ++ph_rounds;
@@ -1582,7 +1424,6 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
     }
     __syncthreads();  // perm and bucket are rewritten by the next window
   }
-#if PHX_SHADE_RING
   // what the workgroup's last windows left in the rings: every complete block has been flushed by the wave that completed it (before that
   // wave reached the barrier above); the open block goes out with its exact count, the survivors' by wave 0, the NEE rays' by wave 1
   __syncthreads();
@@ -1597,7 +1438,6 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
       else ring_flush<3>(ring_b, first, left, &pb.counters[CNT_SHADOW + sq * CNT_STRIDE], pb.so, pb.sd, pb.sc);
     }
   }
-#endif
 #if PHX_SHADE_TIMING
   if ((threadIdx.x & 63u) == 0u) {  // probe build only: s_memtime ticks per phase, summed over the waves (DevStats fields of the count build)
     for (int k = 0; k < 6; ++k) atomicAdd(&pb.stats->stack_pushes[k], ph_acc[k]);
@@ -1751,9 +1591,6 @@ template <typename F>
 void for_each_trace_kernel(F&& f) {
   f(reinterpret_cast<const void*>(&k_trace<256>)); f(reinterpret_cast<const void*>(&k_trace<512>)); f(reinterpret_cast<const void*>(&k_trace<1024>));
   f(reinterpret_cast<const void*>(&k_trace<1024, true>)); f(reinterpret_cast<const void*>(&k_trace<1024, true, true>));
-#if PHX_STACK_PACKED >= 2
-  f(reinterpret_cast<const void*>(&k_trace<256, false, true>)); f(reinterpret_cast<const void*>(&k_trace<512, false, true>)); f(reinterpret_cast<const void*>(&k_trace<1024, false, true>));
-#endif
   f(reinterpret_cast<const void*>(&k_trace_rays<true>)); f(reinterpret_cast<const void*>(&k_trace_rays<false>));
   f(reinterpret_cast<const void*>(&k_trace_primary<1>)); f(reinterpret_cast<const void*>(&k_trace_primary<2>)); f(reinterpret_cast<const void*>(&k_trace_primary<4>));
   f(reinterpret_cast<const void*>(&k_trace_primary<1, true>)); f(reinterpret_cast<const void*>(&k_trace_primary<2, true>)); f(reinterpret_cast<const void*>(&k_trace_primary<4, true>));
@@ -1793,16 +1630,16 @@ TracePlan trace_plan(const DevScene& sc) {
   // nodelets staged in LDS: whatever the per-lane stacks leave of the workgroup's share of the CU's 160 KB at full occupancy
   // (32 waves per CU); 9 (root + one level) when the stacks alone do not fit, and occupancy then follows from the LDS
   // 5-byte stack entries (PHX_STACK_PACKED): for the SPILL plan, when the pool's indices fit 24 bits
-  P.packed = (PHX_STACK_PACKED >= 2 || (PHX_STACK_PACKED == 1 && spill)) && sc.num_elems < (1u << 24) ? 1u : 0u;
+  P.packed = PHX_STACK_PACKED && spill && sc.num_elems < (1u << 24) ? 1u : 0u;
   auto stack_bytes = [&](uint32_t lv, uint32_t blk) { return P.packed ? (lv + ((lv + 3u) >> 2)) * blk * 4u : lv * blk * 8u; };
   auto plan = [&](uint32_t blk, uint32_t& ntop_out, uint32_t& lds_out) {  // -> workgroups per CU for this block size
     uint32_t ntop_req = E.ntop_env;
     if (!ntop_req) {
-      const uint32_t share = 160u * 1024u / (2048u / blk), stacks = stack_bytes(P.lds_levels, blk) + 48u + (PHX_PERM_LUT ? 2048u : 0u);
+      const uint32_t share = 160u * 1024u / (2048u / blk), stacks = stack_bytes(P.lds_levels, blk) + 48u + PHX_PERM_LUT_BYTES;
       ntop_req = share > stacks + 9u * PHX_NODE_LDS_BYTES ? (share - stacks) / PHX_NODE_LDS_BYTES : 9u;
     }
     ntop_out = std::min(ntop_req, sc.num_elems);
-    lds_out = ntop_out * PHX_NODE_LDS_BYTES + stack_bytes(P.lds_levels, blk) + 48u + (PHX_PERM_LUT ? 2048u : 0u);
+    lds_out = ntop_out * PHX_NODE_LDS_BYTES + stack_bytes(P.lds_levels, blk) + 48u + PHX_PERM_LUT_BYTES;
     return std::min(160u * 1024u / lds_out, 2048u / blk);
   };
   // 1024-thread workgroups share one copy of the staged nodelets among 16 waves; a deep tree (levels >= 10: the stacks alone
@@ -1834,11 +1671,6 @@ void launch_trace(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
     hipLaunchKernelGGL(kernel, g, b, lds, stream, sc, pb, q, sq, do_closest, do_shadow, E.refill, ntop, levels, E.min_chunks, E.target_chunks);
   };
   if (P.lds_levels < P.levels) { if (P.packed) go(&k_trace<1024, true, true>); else go(&k_trace<1024, true>); }  // deep tree: 1024-thread workgroups, the stack's deep levels in HBM
-#if PHX_STACK_PACKED >= 2
-  else if (P.packed && block == 256) go(&k_trace<256, false, true>);
-  else if (P.packed && block == 512) go(&k_trace<512, false, true>);
-  else if (P.packed) go(&k_trace<1024, false, true>);
-#endif
   else if (block == 256) go(&k_trace<256>);
   else if (block == 512) go(&k_trace<512>);
   else go(&k_trace<1024>);
@@ -1874,75 +1706,35 @@ static uint64_t shade_g(dim3 g, dim3 b, hipStream_t stream, const DevScene& sc, 
   hipLaunchKernelGGL((k_shade_g<PERHIT, FIRST, LENS, TEX, ENV, MASK>), g, b, 0, stream, sc, pb, q, sq, sample0);
   return 1ull << bit;
 }
+// A run-time flag becomes a template argument in ONE place: f is called with std::true_type or std::false_type.
+template <typename F> static auto with_flag(bool v, F&& f) { if (v) return f(std::true_type{}); else return f(std::false_type{}); }
+// (camera_rays, lens) -> the three legal (FIRST, LENS) pairs: the lens bends camera rays only
+template <typename F> static auto with_pass(bool camera_rays, bool lens, F&& f) {
+  if (camera_rays) return with_flag(lens, [&](auto LENS) { return f(std::true_type{}, LENS); });
+  return f(std::false_type{}, std::false_type{});
+}
 uint64_t launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t capacity, uint32_t sample0, int camera_rays) {
   const bool lens = camera_rays && sc.aperture_radius != 0.0f;  // camera_t::is_pinhole, entities/camera.hpp:37
   if (sc.diffuse_only) {
     const dim3 g((capacity + PHX_SHADE_BLOCK_D - 1) / PHX_SHADE_BLOCK_D), b(PHX_SHADE_BLOCK_D);
-    if (sc.diffuse_only == 2) {
-      if (lens) return shade_d<2, true, true>(g, b, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) return shade_d<2, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-      else return shade_d<2, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    } else {
-      if (lens) return shade_d<1, true, true>(g, b, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) return shade_d<1, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-      else return shade_d<1, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    }
+    return with_flag(sc.diffuse_only == 2, [&](auto ONE_LOBE) {
+      return with_pass(camera_rays != 0, lens, [&](auto FIRST, auto LENS) { return shade_d<decltype(ONE_LOBE)::value ? 2 : 1, decltype(FIRST)::value, decltype(LENS)::value>(g, b, stream, sc, pb, q, sq, sample0); });
+    });
   }
   const dim3 g(shade_grid(sc, capacity, PHX_SHADE_BLOCK_G * PHX_SHADE_ITEMS_G, PHX_SHADE_BLOCK_G)), b(PHX_SHADE_BLOCK_G);
-  if (sc.any_tex & SC_TEX_MASK) {  // image masks on closure mixes: per-hit weights with a texel lookup (PERHIT, TEX and MASK together)
-    if (sc.any_tex & SC_TEX_ENV) {
-      if (lens) return shade_g<true, true, true, true, true, true>(g, b, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) return shade_g<true, true, false, true, true, true>(g, b, stream, sc, pb, q, sq, sample0);
-      else return shade_g<true, false, false, true, true, true>(g, b, stream, sc, pb, q, sq, sample0);
-    } else {
-      if (lens) return shade_g<true, true, true, true, false, true>(g, b, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) return shade_g<true, true, false, true, false, true>(g, b, stream, sc, pb, q, sq, sample0);
-      else return shade_g<true, false, false, true, false, true>(g, b, stream, sc, pb, q, sq, sample0);
-    }
-  }
-  if (sc.any_tex & SC_TEX_ENV) {  // an environment image: the same kernels with the lookup on the miss branch (and the texel lookups of TEX)
-    if (sc.any_tex & SC_TEX_LOBES) {
-      if (sc.any_per_hit) {
-        if (lens) return shade_g<true, true, true, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) return shade_g<true, true, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else return shade_g<true, false, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-      } else {
-        if (lens) return shade_g<false, true, true, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) return shade_g<false, true, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else return shade_g<false, false, false, true, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-      }
-    } else {
-      if (sc.any_per_hit) {
-        if (lens) return shade_g<true, true, true, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) return shade_g<true, true, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else return shade_g<true, false, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-      } else {
-        if (lens) return shade_g<false, true, true, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else if (camera_rays) return shade_g<false, true, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-        else return shade_g<false, false, false, false, true, false>(g, b, stream, sc, pb, q, sq, sample0);
-      }
-    }
-  }
-  if (sc.any_tex) {  // textured scenes: the same kernel with the texel lookups compiled in
-    if (sc.any_per_hit) {
-      if (lens) return shade_g<true, true, true, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) return shade_g<true, true, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-      else return shade_g<true, false, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    } else {
-      if (lens) return shade_g<false, true, true, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-      else if (camera_rays) return shade_g<false, true, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-      else return shade_g<false, false, false, true, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    }
-  }
-  if (sc.any_per_hit) {
-    if (lens) return shade_g<true, true, true, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    else if (camera_rays) return shade_g<true, true, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    else return shade_g<true, false, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-  } else {
-    if (lens) return shade_g<false, true, true, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    else if (camera_rays) return shade_g<false, true, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-    else return shade_g<false, false, false, false, false, false>(g, b, stream, sc, pb, q, sq, sample0);
-  }
+  auto general = [&](auto PERHIT, auto TEX, auto ENV, auto MASK) {
+    return with_pass(camera_rays != 0, lens, [&](auto FIRST, auto LENS) {
+      return shade_g<decltype(PERHIT)::value, decltype(FIRST)::value, decltype(LENS)::value, decltype(TEX)::value, decltype(ENV)::value, decltype(MASK)::value>(g, b, stream, sc, pb, q, sq, sample0);
+    });
+  };
+  const bool env = (sc.any_tex & SC_TEX_ENV) != 0;  // an environment image: the same kernels with the lookup on the miss branch
+  // image masks on closure mixes: per-hit weights with a texel lookup (PERHIT, TEX and MASK together)
+  if (sc.any_tex & SC_TEX_MASK) return with_flag(env, [&](auto ENV) { return general(std::true_type{}, std::true_type{}, ENV, std::true_type{}); });
+  return with_flag(env, [&](auto ENV) {
+    return with_flag((sc.any_tex & SC_TEX_LOBES) != 0, [&](auto TEX) {  // textured scenes: the same kernel with the texel lookups compiled in
+      return with_flag(sc.any_per_hit != 0, [&](auto PERHIT) { return general(PERHIT, TEX, ENV, std::false_type{}); });
+    });
+  });
 }
 void launch_trace_primary(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, uint32_t npaths, uint32_t sample0, int q, int sq) {
   static const int rpl_env = [] { const char* v = getenv("PHX_PRIMARY_RPL"); return v ? atoi(v) : 0; }();  // experiment: 1, 2 or 4 rays per lane
@@ -1953,15 +1745,11 @@ void launch_trace_primary(hipStream_t stream, const DevScene& sc, const PassBuff
   uint32_t rpl = pb.num_samples % 256u == 0 ? 4u : pb.num_samples >= 16u ? 2u : 1u;
   if (rpl_env == 1 || rpl_env == 2 || rpl_env == 4) rpl = (uint32_t)rpl_env;
   const dim3 g((npaths + PHX_PRIMARY_BLOCK * rpl - 1) / (PHX_PRIMARY_BLOCK * rpl)), b(PHX_PRIMARY_BLOCK);
-  if (sc.aperture_radius != 0.0f) {  // thin lens: the rays of a packet leave from a disc, not a point (the packet's bounds know origins apart)
-    if (rpl == 4) hipLaunchKernelGGL((k_trace_primary<4, true>), g, b, lds, stream, sc, pb, npaths, sample0, q, sq);
-    else if (rpl == 2) hipLaunchKernelGGL((k_trace_primary<2, true>), g, b, lds, stream, sc, pb, npaths, sample0, q, sq);
-    else hipLaunchKernelGGL((k_trace_primary<1, true>), g, b, lds, stream, sc, pb, npaths, sample0, q, sq);
-    return;
-  }
-  if (rpl == 4) hipLaunchKernelGGL(k_trace_primary<4>, g, b, lds, stream, sc, pb, npaths, sample0, q, sq);
-  else if (rpl == 2) hipLaunchKernelGGL(k_trace_primary<2>, g, b, lds, stream, sc, pb, npaths, sample0, q, sq);
-  else hipLaunchKernelGGL(k_trace_primary<1>, g, b, lds, stream, sc, pb, npaths, sample0, q, sq);
+  // thin lens: the rays of a packet leave from a disc, not a point (the packet's bounds know origins apart)
+  with_flag(sc.aperture_radius != 0.0f, [&](auto LENS) {
+    auto go = [&](auto RPL) { hipLaunchKernelGGL((k_trace_primary<decltype(RPL)::value, decltype(LENS)::value>), g, b, lds, stream, sc, pb, npaths, sample0, q, sq); };
+    if (rpl == 4) go(std::integral_constant<int, 4>{}); else if (rpl == 2) go(std::integral_constant<int, 2>{}); else go(std::integral_constant<int, 1>{});
+  });
 }
 namespace {
 __global__ void k_build_shade_recs(const TriRec* __restrict__ tris, const uint32_t* __restrict__ elem_of_prim, float4* __restrict__ elem_shade, uint32_t n) {
