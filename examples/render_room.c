@@ -3,7 +3,9 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights]
+ * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
+ * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -62,6 +64,12 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
+  for (int i = 2; i < argc; ++i)
+    if (strcmp(argv[i], "area-lights") == 0) {  /* taken out of the list: the other arguments keep their places */
+      opt.light_sampling = PHX_LIGHTS_BY_AREA;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    }
   if (argc > 2 && strcmp(argv[2], "device-bvh") == 0) opt.bvh_builder = PHX_BVH_DEVICE_LBVH;
   if (argc > 2 && strcmp(argv[2], "host-bvh") == 0) opt.bvh_builder = PHX_BVH_HOST_SAH;
 

@@ -62,7 +62,8 @@ typedef struct phx_options {
   uint32_t samples_in_flight; /* samples of one pixel carried per wavefront pass */
   uint32_t tiles_per_batch;   /* tiles pulled from the queue per pass */
   uint32_t bvh_builder;       /* PHX_BVH_AUTO (default), PHX_BVH_DEVICE_LBVH or PHX_BVH_HOST_SAH: where preprocess builds the tree */
-  uint32_t reserved[5];
+  uint32_t light_sampling;    /* PHX_LIGHTS_REFERENCE (default) or PHX_LIGHTS_BY_AREA: how next-event estimation picks a triangle of the chosen light */
+  uint32_t reserved[4];
 } phx_options;
 /* AUTO = the device builder (LBVH over extended Morton codes + the optimal 8-wide collapse) for every scene with at least 64
  * triangles: 1 M triangles in 12 ms and 10 M in 40 ms against 0.6 s / 7 s of the host's binned-SAH builder, and since round 3 its
@@ -70,6 +71,21 @@ typedef struct phx_options {
  * on every call (src/xpu/cpu.cpp:35-44), so the build time is part of the interface's cost.  HOST_SAH stays selectable, and AUTO falls back to it
  * when the device build fails (phx_stats.bvh_built_on_device = 0); an explicit DEVICE_LBVH request fails with PHX_ERR_DEVICE instead. */
 enum { PHX_BVH_AUTO = 0, PHX_BVH_DEVICE_LBVH = 1, PHX_BVH_HOST_SAH = 2 };
+/* light_sampling.  Next-event estimation chooses a light uniformly (l = floor(pick * nlights), clamped) and a triangle inside it from the
+ * draw lu, and reports the density lpdf = (1 / area of the light's face set) / nlights.  Any other value is PHX_ERR_ARG at phx_dev_preprocess.
+ *   PHX_LIGHTS_REFERENCE: the triangle by index, ti = floor(lu * num_tris) (clamped), remapped = min(lu * num_tris - ti, 1 - FLT_EPSILON), as
+ *     light.cpp:55-67 does with its search commented out (light.cpp:30-53).  The reported density is the true one only when every triangle of
+ *     the light has the same area (SURVEY A-12; tests/integrator64.py: uniform_triangle_pick).  Bit for bit the reference's films.
+ *   PHX_LIGHTS_BY_AREA: the triangle by area, all in fp32.  Per light, in the face order of its face set,
+ *       acc_i = acc_{i-1} + area_i        (the running sum whose last value is the light's area)
+ *       cdf[i] = acc_i / area             (the last entry is area / area = 1)
+ *     ti is the smallest i with lu < cdf[i], or num_tris - 1 when there is none (binary search on the monotone table);
+ *       lo = ti ? cdf[ti - 1] : 0         remapped = min((lu - lo) / (cdf[ti] - lo), 1 - FLT_EPSILON)
+ *     and everything behind the pick is unchanged: triangle_t::sample(remapped, lv), P, lpdf, which is now the true density.  A triangle
+ *     of zero area has cdf[i] == lo and is never chosen.  A light of one triangle, or of two whose fp32 areas are bit-equal (cdf = {0.5, 1}),
+ *     is sampled bit for bit as under PHX_LIGHTS_REFERENCE; three or more equal triangles are not (3 * a rounds).  The scene is shaded by
+ *     k_shade_g (phx_stats.shade_general = 1) whatever its closures.  Lights are still chosen uniformly, not by power. */
+enum { PHX_LIGHTS_REFERENCE = 0, PHX_LIGHTS_BY_AREA = 1 };
 
 /* ---- scene: what the device reads through scene_t (src/scene.hpp:14-50) --------------- */
 
@@ -381,6 +397,12 @@ int phx_dev_lobe_weights(phx_device* dev, uint32_t material, uint32_t n_items, c
  * the device for n directions dirs (x, y, z per item) against the preprocessed scene's environment: rgb per item.  A parity hook.
  * PHX_ERR_STATE before preprocess; PHX_ERR_ARG when the scene's environment has no image. */
 int phx_dev_environment_lookup(phx_device* dev, uint32_t n, const float* dirs, float* rgb);
+
+/* The light sample of next-event estimation as the shade kernel draws it, in the light_sampling mode the device was made with: for n triples
+ * u3 (pick, lu, lv per item) the chosen light (index into the scene's emissive face sets in mesh x face-set order), the triangle inside it (face
+ * order of the set), the barycentrics (bu, bv) of triangle_t::sample, the point P = bu * a + bv * b + (1 - bu - bv) * c and the light's lpdf.
+ * A parity hook: it runs the device function k_shade_g runs.  PHX_ERR_STATE before preprocess. */
+int phx_dev_light_sample(phx_device* dev, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -30,6 +30,7 @@ def fac_texture(word):
 
 
 BVH_AUTO, BVH_DEVICE_LBVH, BVH_HOST_SAH = 0, 1, 2
+LIGHTS_REFERENCE, LIGHTS_BY_AREA = 0, 1  # Options.light_sampling: a light's triangle by index (the reference) or by area
 MESH_UV_PER_VERTEX, MESH_NORMALS_PER_VERTEX = 1, 2
 TEX_LINEAR, TEX_CLOSEST = 0, 1
 WRAP_PERIODIC, WRAP_CLAMP, WRAP_BLACK = 0, 1, 2
@@ -79,7 +80,7 @@ class Options(C.Structure):
         ("samples_per_pixel", C.c_uint32), ("paths_per_sample", C.c_uint32), ("path_depth", C.c_uint32),
         ("single_threaded", C.c_uint32), ("host_only", C.c_uint32), ("render_normals", C.c_uint32),
         ("verbose", C.c_uint32), ("device_ordinal", C.c_int32), ("samples_in_flight", C.c_uint32),
-        ("tiles_per_batch", C.c_uint32), ("bvh_builder", C.c_uint32), ("reserved", C.c_uint32 * 5),
+        ("tiles_per_batch", C.c_uint32), ("bvh_builder", C.c_uint32), ("light_sampling", C.c_uint32), ("reserved", C.c_uint32 * 4),
     ]
 
 
@@ -173,6 +174,7 @@ EXPORTS = [
     "phx_last_error", "phx_dev_get_stats", "phx_tiles_make", "phx_tiles_next", "phx_tiles_count", "phx_tiles_reset",
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
     "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
+    "phx_dev_light_sample",
 ]
 
 
@@ -200,5 +202,6 @@ def declare(lib):
     lib.phx_dev_texture_lookup.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p]; lib.phx_dev_texture_lookup.restype = C.c_int
     lib.phx_dev_environment_lookup.argtypes = [vp, C.c_uint32, f32p, f32p]; lib.phx_dev_environment_lookup.restype = C.c_int
     lib.phx_dev_lobe_weights.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, u32p]; lib.phx_dev_lobe_weights.restype = C.c_int
+    lib.phx_dev_light_sample.argtypes = [vp, C.c_uint32, f32p, u32p, u32p, f32p, f32p, f32p]; lib.phx_dev_light_sample.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

@@ -327,6 +327,8 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   if (s->camera.film_width == 0 || s->camera.film_height == 0 || s->camera.film_width > 65535 || s->camera.film_height > 65535)
     return fail(PHX_ERR_ARG, "film size out of range");
   if (s->environment_material >= (int32_t)s->num_materials) return fail(PHX_ERR_ARG, "environment material out of range");
+  if (d->opt.light_sampling > PHX_LIGHTS_BY_AREA) return fail(PHX_ERR_ARG, "unknown light_sampling");
+  const bool lights_by_area = d->opt.light_sampling == PHX_LIGHTS_BY_AREA;
   DeviceScope on(d->hip_device);
   if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
   const auto t_pre0 = std::chrono::steady_clock::now();
@@ -380,6 +382,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   std::vector<float> abc; std::vector<uint32_t> prim_material; std::vector<float> prim_normals;
   std::vector<float2> prim_uv;  // any_tex: 3 corner UVs per primitive
   std::vector<DevLight> lights; std::vector<DevLightTri> light_tris;
+  std::vector<float> light_cdf;  // PHX_LIGHTS_BY_AREA: per light triangle, the light's running area up to and including it; divided by the light's area below
   bool any_smooth = false;
   for (uint32_t mi = 0; mi < s->num_meshes; ++mi) {
     const phx_mesh& m = s->meshes[mi];
@@ -432,9 +435,13 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
           light_tris.push_back(T);
           L.area += 0.5f * length(cross(ab, ac));  // triangle_t::area, mesh.cpp:293-300; summed in face order (light.cpp:36-39)
           L.num_tris++;
+          if (lights_by_area) light_cdf.push_back(L.area);  // acc_i
         }
       }
-      if (emitter && L.num_tris) lights.push_back(L);
+      if (emitter && L.num_tris) {
+        lights.push_back(L);
+        for (uint32_t k = 0; k < (lights_by_area ? L.num_tris : 0u); ++k) light_cdf[L.first_tri + k] = light_cdf[L.first_tri + k] / L.area;  // cdf[i] = acc_i / area; the last is 1
+      }
     }
   }
   if (prim_material.empty()) return fail(PHX_ERR_ARG, "scene has no triangles");
@@ -521,7 +528,14 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   if (bvh_depth > PHX_MAX_BVH_DEPTH)
     return fail(PHX_ERR_ARG, "tree too deep: " + std::to_string(bvh_depth) + " levels, the traversal stack in LDS holds " + std::to_string(PHX_MAX_BVH_DEPTH));
   if ((rc = d->d_materials.upload(mats))) return rc;
-  if ((rc = d->d_lights.upload(lights))) return rc;
+  if (lights_by_area) {  // the CDF rides behind the light table (kernels.hip: light_cdf): one float per light triangle, in records of the table's size
+    const size_t nl = lights.size();
+    lights.resize(nl + (light_cdf.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
+    std::memcpy(static_cast<void*>(lights.data() + nl), light_cdf.data(), light_cdf.size() * sizeof(float));
+    rc = d->d_lights.upload(lights);
+    lights.resize(nl);
+    if (rc) return rc;
+  } else if ((rc = d->d_lights.upload(lights))) return rc;
   if ((rc = d->d_light_tris.upload(light_tris))) return rc;
   // what shading reads of a hit triangle, 16 bytes per POOL ELEMENT: geometric normal + material word
   if ((rc = d->d_elem_shade.alloc(bvh_elems))) return rc;
@@ -587,8 +601,8 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   sc.ratio = (float)s->camera.film_width / (float)s->camera.film_height;
   sc.width = s->camera.film_width; sc.height = s->camera.film_height;
   sc.aperture_radius = s->camera.aperture_radius; sc.focal_distance = s->camera.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
-  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u);
-  sc.tex = sc.any_tex ? d->d_tex_scene.p : nullptr;
+  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u) | (lights_by_area ? SC_LIGHTS_BY_AREA : 0u);
+  sc.tex = (sc.any_tex & SC_TEX_ANY) ? d->d_tex_scene.p : nullptr;
   sc.max_depth = d->opt.path_depth;
   sc.stack_levels = bvh_depth;
   sc.num_elems = (uint32_t)bvh_elems;
@@ -596,7 +610,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
     hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, d->hip_device));
     sc.num_cus = (uint32_t)prop.multiProcessorCount;
   }
-  sc.diffuse_only = sc.any_tex ? 0 : 1;  // textured lobes and environment maps are shaded by k_shade_g<.., TEX, ENV> only
+  sc.diffuse_only = sc.any_tex ? 0 : 1;  // textured lobes and environment maps are shaded by k_shade_g<.., TEX, ENV> only, and so is the pick by area
   for (auto& m : mats) { if (m.per_hit) sc.diffuse_only = 0; for (uint32_t k = 0; k < m.num_lobes; ++k) if (m.lobes[k].type != L_DIFFUSE) sc.diffuse_only = 0; }
   sc.mat_lite = nullptr;
   sc.any_per_hit = 0;
@@ -620,7 +634,7 @@ static int preprocess_impl(phx_device* d, const phx_scene* s) {
   d->mat_masked.assign(s->num_materials, 0);
   for (uint32_t i = 0; i < s->num_materials; ++i)
     for (uint32_t k = 0; k < mats[i].num_lobes; ++k) if (mats[i].lobes[k].fac_mode >= PHX_FAC_TEX_B) d->mat_masked[i] = 1;
-  d->num_textures = sc.any_tex ? s->num_textures : 0;
+  d->num_textures = (sc.any_tex & SC_TEX_ANY) ? s->num_textures : 0;
   d->env_tex = env_tex;
   d->env_mapping = env_tex ? s->materials[s->environment_material].emission_mapping : 0u;
   for (int c = 0; c < 3; ++c) d->env_e[c] = env_tex ? s->materials[s->environment_material].emission[c] : 0.0f;
@@ -875,6 +889,29 @@ static int dev_environment_lookup_impl(phx_device* d, uint32_t n, const float* d
   return PHX_OK;
 }
 int phx_dev_environment_lookup(phx_device* d, uint32_t n, const float* dirs, float* rgb) { return guarded([&]() { return dev_environment_lookup_impl(d, n, dirs, rgb); }); }
+
+static int dev_light_sample_impl(phx_device* d, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf) {
+  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "light_sample before preprocess");
+  if (n == 0) return PHX_OK;
+  if (!u3 || !light || !tri || !bary || !P || !pdf) return fail(PHX_ERR_ARG, "light_sample: null argument");
+  DeviceScope on(d->hip_device);
+  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+  DevBuf<float> a, ob, oP, op; DevBuf<uint32_t> ol, ot; int rc;
+  if ((rc = kat_upload(u3, 3 * (size_t)n, a)) || (rc = ol.alloc(n)) || (rc = ot.alloc(n)) || (rc = ob.alloc(2 * (size_t)n)) || (rc = oP.alloc(3 * (size_t)n)) ||
+      (rc = op.alloc(n))) return rc;
+  launch_light_sample(d->stream, d->scene, n, a.p, ol.p, ot.p, ob.p, oP.p, op.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(light, ol.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tri, ot.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bary, ob.p, 2 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(P, oP.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(pdf, op.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return PHX_OK;
+}
+int phx_dev_light_sample(phx_device* d, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf) {
+  return guarded([&]() { return dev_light_sample_impl(d, n, u3, light, tri, bary, P, pdf); });
+}
 
 int phx_dev_copy_bvh(phx_device* d, void* out, uint64_t capacity, uint64_t* bytes, float* grid6) {
   if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "copy_bvh before preprocess");

@@ -38,7 +38,11 @@ struct DevTexScene {
 };
 // DevScene::any_tex bits: which image lookups the shade kernels compile in
 enum { SC_TEX_LOBES = 1u /* some lobe is textured or masked: TEX */, SC_TEX_ENV = 2u /* the environment has an image: ENV */,
-       SC_TEX_MASK = 4u /* some lobe's mix factor is an image (PHX_FAC_TEX_*): MASK, always with SC_TEX_LOBES and any_per_hit */ };
+       SC_TEX_MASK = 4u /* some lobe's mix factor is an image (PHX_FAC_TEX_*): MASK, always with SC_TEX_LOBES and any_per_hit */,
+       SC_TEX_ANY = 7u,
+       // not an image bit: PHX_LIGHTS_BY_AREA.  k_shade_g picks a light's triangle by the area CDF (light_pick); the scene then runs k_shade_g
+       // (diffuse_only = 0) and `lights` has the CDF behind it
+       SC_LIGHTS_BY_AREA = 8u };
 
 struct DevScene {
   const uint32_t* pool;           // the BVH8 pool: 16 words per element, element 0 = root nodelet (bvh8.h)
@@ -52,7 +56,8 @@ struct DevScene {
                                   // WITH the triangle record, not after it (round 6; entries of nodelets are never read) — or nullptr when no face is smooth
   const DevMaterial* materials;
   const DevMatLite* mat_lite;     // diffuse_only == 2: the same table, 32 B per material
-  const DevLight* lights;
+  const DevLight* lights;         // num_lights records; under SC_LIGHTS_BY_AREA the area CDF follows them in the same allocation: one float per light
+                                  // triangle, indexed like light_tris (light_cdf)
   const DevLightTri* light_tris;
   uint32_t num_lights;
   int32_t env_material;
@@ -148,6 +153,8 @@ void launch_remap_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32
 void launch_scatter_film(hipStream_t stream, const PassBuffers& pb, float* device_film, uint32_t film_width);
 
 // stage-level entry points (synchronous helpers for the parity tests)
+// light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf
+void launch_light_sample(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf);
 void launch_trace_rays(hipStream_t stream, const DevScene& sc, uint32_t n, const float4* ro, const float4* rd, float4* hit, int any);
 void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3);
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,

@@ -955,6 +955,37 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_D) __attribute__((amdgpu_waves
   (void)masked;  // rays_masked = rays_closest - rays_shadow: every shaded slot yields a shadow ray or a masked slot
 }
 
+// ---- next-event estimation's pick (light_sampler_t, spt.hpp:95-149; area_light_t::sample, light.cpp:55-67) ---------------------------------
+// The light uniformly, then a triangle inside it and the draw remapped into that triangle.  PHX_LIGHTS_REFERENCE: the triangle by index, as
+// the reference does with its search commented out (light.cpp:30-53) -- the pdf 1/area it reports is then the true density only for lights of
+// equal triangles.  PHX_LIGHTS_BY_AREA (SC_LIGHTS_BY_AREA, a wave-uniform branch on a kernel argument): by the area CDF that follows the light
+// table, the rule of include/phx_xpu.h.  Used by k_shade_g and by phx_dev_light_sample; k_shade<1/2> keep their own copy of the reference
+// pick (a BY_AREA scene never runs them).
+__device__ __forceinline__ const float* light_cdf(const DevScene& sc) { return reinterpret_cast<const float*>(sc.lights + sc.num_lights); }
+__device__ __forceinline__ void light_pick(const DevScene& sc, float pick, float lu, uint32_t& l, uint32_t& ti, uint32_t& lt, float& remapped) {
+  const float nlf = (float)sc.num_lights;
+  l = (uint32_t)floorf(pick * nlf);
+  if (l > sc.num_lights - 1) l = sc.num_lights - 1;
+  const uint32_t ltris = sc.lights[l].num_tris;
+  if (sc.any_tex & SC_LIGHTS_BY_AREA) {
+    const float* cdf = light_cdf(sc) + sc.lights[l].first_tri;  // cdf[i] = (area_0 + ... + area_i) / area, monotone, cdf[ltris - 1] == 1
+    uint32_t lo = 0, hi = ltris - 1;                             // the smallest i with lu < cdf[i], or ltris - 1
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (lu < cdf[mid]) hi = mid; else lo = mid + 1;
+    }
+    ti = lo;
+    const float below = ti ? cdf[ti - 1] : 0.0f;
+    remapped = fminf((lu - below) / (cdf[ti] - below), 1.0f - FLT_EPSILON);
+  } else {
+    const float numf = (float)ltris;
+    ti = (uint32_t)floorf(lu * numf);  // uniform by index (light.cpp:55), pdf = 1/area
+    if (ti > ltris - 1) ti = ltris - 1;
+    remapped = fminf(lu * numf - (float)ti, 1.0f - FLT_EPSILON);
+  }
+  lt = sc.lights[l].first_tri + ti;
+}
+
 // ---- general closures: shade + NEE + integrate with the hits of a workgroup sorted by material ----------------------------------
 // k_shade_g replaces the round-2 k_shade<0/3> (128 VGPRs, 160-700 B of scratch per lane, 4 waves per SIMD: the weakest kernel of the
 // repo).  What changed, and why:
@@ -1322,15 +1353,8 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
         if (hit_surface) {
           const uint32_t b0 = depth * DIMS_PER_STEP;
           const float pick = draw_f32(key, b0 + DIM_LIGHT_PICK), lu = draw_f32(key, b0 + DIM_LIGHT_U), lv = draw_f32(key, b0 + DIM_LIGHT_V);
-          const float nlf = (float)sc.num_lights;
-          uint32_t l = (uint32_t)floorf(pick * nlf);
-          if (l > sc.num_lights - 1) l = sc.num_lights - 1;
-          const uint32_t ltris = sc.lights[l].num_tris;
-          const float numf = (float)ltris;
-          uint32_t ti = (uint32_t)floorf(lu * numf);  // uniform by index (light.cpp:55), pdf = 1/area
-          if (ti > ltris - 1) ti = ltris - 1;
-          const float remapped = fminf(lu * numf - (float)ti, 1.0f - FLT_EPSILON);
-          uint32_t lt = sc.lights[l].first_tri + ti;
+          uint32_t l, ti, lt; float remapped;
+          light_pick(sc, pick, lu, l, ti, lt, remapped);  // the triangle by index (the reference) or by area (PHX_LIGHTS_BY_AREA)
           const float x = sqrtf(remapped);
           const float bu = 1 - x, bv = lv * x;     // triangle_t::sample, mesh.cpp:318-324
           {
@@ -1532,6 +1556,23 @@ __global__ void __launch_bounds__(64) k_texture_lookup(const DevTexture* texture
   if (i >= n) return;
   const v3 c = tex_lookup(textures, texels, tex, st[2 * i], st[2 * i + 1]);
   rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
+}
+
+// phx_dev_light_sample: the light sample of k_shade_g's next-event block (light_pick, triangle_t::sample, P)
+__global__ void __launch_bounds__(64) k_light_sample(DevScene sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P3, float* pdf) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float pick = u3[3 * i], lu = u3[3 * i + 1], lv = u3[3 * i + 2];
+  uint32_t l, ti, lt; float remapped;
+  light_pick(sc, pick, lu, l, ti, lt, remapped);
+  const float x = sqrtf(remapped);
+  const float bu = 1 - x, bv = lv * x;     // triangle_t::sample, mesh.cpp:318-324
+  const DevLightTri& LT = sc.light_tris[lt];
+  const v3 la(LT.ax, LT.ay, LT.az), lb(LT.bx, LT.by, LT.bz), lc(LT.cx, LT.cy, LT.cz);
+  const v3 P = bu * la + bv * lb + (1 - bu - bv) * lc;
+  light[i] = l; tri[i] = ti; bary[2 * i] = bu; bary[2 * i + 1] = bv;
+  P3[3 * i] = P.x; P3[3 * i + 1] = P.y; P3[3 * i + 2] = P.z;
+  pdf[i] = sc.lights[l].lpdf;
 }
 
 // phx_dev_lobe_weights: lobe_weight_of as k_shade_g<.., TEX, ., MASK> (TEXTURED) or k_shade_g<PERHIT> (scenes without a texture table) resolves it
@@ -1821,6 +1862,9 @@ void launch_lobe_weights(hipStream_t stream, const DevMaterial* mat, const DevTe
                          const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
   if (textures) hipLaunchKernelGGL(k_lobe_weights<true>, dim3((n + 63) / 64), dim3(64), 0, stream, mat, textures, texels, lobe_tex, n, n3, wi3, st, w, kept);
   else hipLaunchKernelGGL(k_lobe_weights<false>, dim3((n + 63) / 64), dim3(64), 0, stream, mat, textures, texels, lobe_tex, n, n3, wi3, st, w, kept);
+}
+void launch_light_sample(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf) {
+  hipLaunchKernelGGL(k_light_sample, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, light, tri, bary, P, pdf);
 }
 void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
   hipLaunchKernelGGL(k_texture_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, n, st, rgb);

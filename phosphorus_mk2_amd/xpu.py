@@ -54,7 +54,8 @@ class Options:
     """parsed_options_t (src/options.hpp:6-43) plus the device knobs."""
 
     def __init__(self, samples_per_pixel=16, paths_per_sample=16, path_depth=9, single_threaded=False, host_only=False,
-                 render_normals=False, verbose=False, device_ordinal=-1, samples_in_flight=0, tiles_per_batch=0, bvh_builder="auto"):
+                 render_normals=False, verbose=False, device_ordinal=-1, samples_in_flight=0, tiles_per_batch=0, bvh_builder="auto",
+                 light_sampling="reference"):
         self.samples_per_pixel = samples_per_pixel
         self.paths_per_sample = paths_per_sample
         self.path_depth = path_depth
@@ -66,6 +67,9 @@ class Options:
         self.samples_in_flight = samples_in_flight
         self.tiles_per_batch = tiles_per_batch
         self.bvh_builder = bvh_builder  # "host": binned SAH on the host cores; "device": LBVH built on the GPU; "auto": by scene size
+        # "reference": next-event estimation picks a light's triangle by index, as the reference does (biased for lights of unequal triangles);
+        # "area": by the light's area CDF (unbiased; the scene is shaded by k_shade_g).  An int is passed through as it is.
+        self.light_sampling = light_sampling
 
     def pack(self):
         o = abi.Options()
@@ -74,6 +78,8 @@ class Options:
         o.render_normals, o.verbose = int(self.render_normals), int(self.verbose)
         o.device_ordinal, o.samples_in_flight, o.tiles_per_batch = self.device_ordinal, self.samples_in_flight, self.tiles_per_batch
         o.bvh_builder = {"auto": abi.BVH_AUTO, "host": abi.BVH_HOST_SAH, "device": abi.BVH_DEVICE_LBVH}[self.bvh_builder]
+        ls = self.light_sampling
+        o.light_sampling = ls if isinstance(ls, int) else {"reference": abi.LIGHTS_REFERENCE, "area": abi.LIGHTS_BY_AREA}[ls]
         return o
 
 
@@ -314,6 +320,19 @@ class HipDevice:
                "phx_dev_lobe_weights")
         return w, kept
 
+    def light_sample(self, u3):
+        """Next-event estimation's light sample as the shade kernel draws it, in this device's light_sampling mode: u3 (n, 3) = (pick, lu,
+        lv) per item -> dict of light (n,) u32, tri (n,) u32 (index inside the light, face order), bary (n, 2) f32 (bu, bv), P (n, 3) f32 and
+        pdf (n,) f32 (the light's lpdf).  phx_dev_light_sample."""
+        u3 = np.ascontiguousarray(u3, np.float32).reshape(-1, 3)
+        k = len(u3)
+        light = np.zeros(k, np.uint32); tri = np.zeros(k, np.uint32)
+        bary = np.zeros((k, 2), np.float32); P = np.zeros((k, 3), np.float32); pdf = np.zeros(k, np.float32)
+        fp = lambda a: a.ctypes.data_as(abi.f32p)
+        up = lambda a: a.ctypes.data_as(abi.u32p)
+        _check(self._lib, self._lib.phx_dev_light_sample(self._h, k, fp(u3), up(light), up(tri), fp(bary), fp(P), fp(pdf)), "phx_dev_light_sample")
+        return {"light": light, "tri": tri, "bary": bary, "P": P, "pdf": pdf}
+
     def texture_lookup(self, texture, st):
         """The shade kernel's image lookup on the device: texture `texture` (0-based index into SceneDesc.textures of the preprocessed
         scene, which must have a textured lobe) at st (n, 2) -> rgb (n, 3) f32."""
@@ -369,11 +388,11 @@ def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_s
 
 
 def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=32, rank=0, world=1, callback_tiles=False,
-           samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto"):
+           samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference"):
     """Convenience: the call sequence of session_t::render (plugins/blender/session.cpp:73-94):
     make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats)."""
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
-                   tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder)
+                   tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling)
     # ONE device, on the caller's current GPU (device_ordinal -1): discover() is for hosts that drive every GPU (render_on) and
     # would build a context, a stream and the kernel attributes on each of them only to use the first
     dev = HipDevice.make(opts)

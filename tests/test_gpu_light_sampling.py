@@ -1,0 +1,264 @@
+"""Picking a mesh light's triangle by area on the device (phx_options.light_sampling = PHX_LIGHTS_BY_AREA: light_pick in kernels.hip, run by
+k_shade_g and by phx_dev_light_sample).  The oracle knows the reference's pick only, so the new mode is held to three things: the numpy
+restatement of tests/test_light_sampling.py, bit for bit, through the parity hook; closed forms of direct lighting under lamps of unequal
+triangles, which the reference's pick misses and this one must meet; and the oracle's own films, bit for bit, on every scene whose lights
+the two picks sample alike (one triangle, or two of bit-equal area) -- which takes the new branch through all 30 k_shade_g instantiations."""
+import math
+
+import numpy as np
+import pytest
+
+from conftest import bits_equal
+from phosphorus_mk2_amd import abi, scenes
+from test_analytic_direct_light import H_LAMP, LE, RHO, SPP, W
+from test_gpu_shade_kernels import CASES, DEPTH as T_DEPTH, FAMILIES, SEED as T_SEED, SPP as T_SPP, build, expected_kernels
+from test_light_sampling import (LE2, QUAD, TWO_LAMPS, LightTable, _camera, _floor, edge_draws, film_of, light_sample, meets, moments, rects_mesh, striped_G,
+                                 striped_scene, two_lamp_scene)
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+COUNTERS = ("camera_samples", "rays_closest", "rays_shadow", "rays_masked")
+
+
+@pytest.fixture(scope="module")
+def xpu():
+    from phosphorus_mk2_amd import xpu
+    xpu.load_library()
+    return xpu
+
+
+# ---- 4. the hook is the restatement, bit for bit, in both modes ----------------------------------------------------------------------------
+def three_lights_scene():
+    """lights of 1, 2 and 37 triangles in that order: the second and third lights' tables start at first_tri 1 and 3"""
+    rng = np.random.default_rng(21)
+    mats = [scenes.diffuse(RHO, RHO, RHO), scenes.emitter(*LE), scenes.emitter(*LE2), scenes.emitter(1.0, 1.0, 1.0)]
+    one = scenes.MeshDesc(vertices=np.array([(-0.9, 1.0, 0.1), (-0.9, 1.0, -0.6), (-0.3, 1.0, -0.4)], F), faces=np.array([[0, 1, 2]], np.uint32),
+                          sets=[(1, np.array([0], np.uint32))])
+    two = rects_mesh([QUAD], 2)
+    c = rng.uniform(-0.8, 0.8, (37, 1, 3)) + np.array([0.3, 1.6, 0.0])
+    v = (c + rng.uniform(-1.0, 1.0, (37, 3, 3)) * (10.0 ** rng.uniform(-2.0, -0.5, (37, 1, 1)))).astype(F)
+    many = scenes.MeshDesc(vertices=v.reshape(-1, 3), faces=np.arange(111, dtype=np.uint32).reshape(37, 3), sets=[(3, np.arange(37, dtype=np.uint32))])
+    return scenes.SceneDesc(_floor() + [one, two, many], mats, _camera(), name="three_lights")
+
+
+def fan_scene():
+    """a fan lamp: 12 triangles about one apex whose areas span three decades, one of them of zero area (two rim vertices coincide)"""
+    steps = np.array([1.0, 5e-4, 0.3, 0.0, 3e-3, 0.7, 1e-2, 0.1, 3e-2, 0.5, 2e-3, 0.05])
+    ang = np.concatenate([[0.0], np.cumsum(steps)])
+    rim = np.stack([0.5 * np.cos(ang), np.full(len(ang), H_LAMP), 0.5 * np.sin(ang)], -1)
+    v = np.concatenate([[(0.0, H_LAMP, 0.0)], rim]).astype(F)
+    f = np.array([(0, k + 1, k + 2) for k in range(12)], np.uint32)  # (apex, rim k, rim k + 1): n = -y
+    lamp = scenes.MeshDesc(vertices=v, faces=f, sets=[(1, np.arange(12, dtype=np.uint32))])
+    return scenes.SceneDesc(_floor() + [lamp], [scenes.diffuse(RHO, RHO, RHO), scenes.emitter(*LE)], _camera(), name="fan_lamp")
+
+
+def test_the_hook_scenes_are_what_they_claim():
+    t = LightTable(three_lights_scene())
+    assert [len(a) for a in t.areas] == [1, 2, 37]
+    f = LightTable(fan_scene())
+    a = f.areas[0]
+    assert f.n == 1 and len(a) == 12 and (a == 0).sum() == 1 and a[a > 0].max() / a[a > 0].min() > 1000.0
+    assert f.cdf[0][-1] == 1.0 and (np.diff(f.cdf[0]) >= 0).all()
+
+
+@pytest.mark.parametrize("make", [striped_scene, three_lights_scene, fan_scene], ids=["striped", "three_lights", "fan"])
+@pytest.mark.parametrize("mode", ["reference", "area"])
+def test_hook_is_the_restatement_bit_for_bit(xpu, make, mode):
+    sc = make()
+    t = LightTable(sc)
+    rng = np.random.default_rng(31)
+    u3 = [rng.random((1 << 16, 3), dtype=F)]
+    for k in range(t.n):  # every light: lu at each cdf[i] and its two neighbours, 0 and 1 - 2^-24
+        lu = edge_draws(t.cdf[k])
+        u3.append(np.stack([np.full(len(lu), F((k + 0.5) / t.n)), lu, rng.random(len(lu), dtype=F)], -1))
+    u3.append(np.array([[0.0, 0.0, 0.0], [1 - 2.0 ** -24, 1 - 2.0 ** -24, 1 - 2.0 ** -24], [1 - 2.0 ** -24, 0.0, 0.5]], F))
+    u3 = np.concatenate(u3).astype(F)
+    dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=1, paths_per_sample=1, path_depth=1, light_sampling=mode))
+    try:
+        dev.preprocess(sc)
+        got = dev.light_sample(u3)
+    finally:
+        dev.close()
+    want = light_sample(t, u3, mode == "area")
+    assert set(np.unique(want["light"])) == set(range(t.n))
+    if mode == "area":  # a triangle of zero area is never chosen; every other one is
+        for k in range(t.n):
+            seen = np.unique(want["tri"][want["light"] == k])
+            assert set(seen) == set(np.flatnonzero(t.areas[k] > 0)), (k, seen)
+    failed = [f"{key}: {(np.asarray(got[key]).reshape(len(u3), -1).view(np.uint32) != np.asarray(want[key]).reshape(len(u3), -1).view(np.uint32)).any(1).sum()} of {len(u3)} differ"
+              for key in ("light", "tri", "bary", "P", "pdf") if not bits_equal(got[key], want[key])]
+    assert not failed, "\n".join(failed)
+
+
+# ---- 5. the striped lamp on the device --------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def striped_films(xpu, orc):
+    sc = striped_scene()
+    ref = orc.Oracle(sc, spp=SPP, pps=1, depth=1).render(rng=orc.RNG_COUNTER, seed=3, threads=4)
+    return ref, xpu.render(sc, spp=SPP, pps=1, depth=1, seed=3), xpu.render(sc, spp=SPP, pps=1, depth=1, seed=3, light_sampling="area")
+
+
+def test_reference_mode_keeps_the_quirk_on_the_striped_lamp(striped_films):
+    (ref, ost), (film, st), _ = striped_films
+    assert st["rays_shadow"] == st["rays_closest"] == W * W * SPP == ost["rays_closest"]
+    assert bits_equal(film[..., :3], ref[..., :3])
+    assert meets(film, film_of(striped_G(True))) and not meets(film, film_of(striped_G(False)))
+    assert st["shade_general"] == 0
+
+
+def test_by_area_meets_the_true_closed_form_on_the_striped_lamp(striped_films):
+    """THE test that fails without the feature: with the pick by area the estimator is uniform over the lamp's area, as it is for the
+    two-triangle lamp of test_analytic_direct_light at this size, spp and geometry, so that file's three tolerances apply unchanged."""
+    _, (film_ref, _), (film, st) = striped_films
+    assert st["rays_shadow"] == st["rays_closest"] == W * W * SPP
+    assert meets(film, film_of(striped_G(False)))
+    assert not bits_equal(film[..., :3], film_ref[..., :3])
+    assert not meets(film, film_of(striped_G(True)))
+    assert st["shade_general"] == 1
+    got = film[..., :3].astype(np.float64)
+    assert np.allclose(got[..., 0] / LE[0], got[..., 2] / LE[2], rtol=1e-5)  # the three channels are one estimate scaled by L_e
+
+
+# ---- 6. two lamps at once ---------------------------------------------------------------------------------------------------------------------
+def test_by_area_meets_the_sum_of_the_closed_forms_under_two_lamps(xpu):
+    """The striped lamp plus a two-triangle quad of another emission.  Tolerances: 4 standard errors of the film mean, 5 of a pixel, the
+    variance m2 - mean^2 of one sample from test_light_sampling.moments (no render enters it;
+    test_the_standard_error_model_holds_where_the_reference_pick_is_unbiased checks the model itself on the oracle).  The pixel centre stands for the pixel: the film's
+    jitter moves a sample by at most half a pixel (0.015 on the floor), which changes the mean by the integrand's curvature, about 1e-4
+    of it, and adds 1e-4 of the variance -- both far inside the bounds (the film mean's standard error is about 1.5e-3 of it)."""
+    sc = two_lamp_scene()
+    mean, m2 = moments(TWO_LAMPS)
+    var = m2 - mean * mean
+    assert (var > 0).all()
+    se_pixel = np.sqrt(var / SPP)
+    se_mean = np.sqrt(var.sum((0, 1)) / SPP) / (W * W)
+    film, st = xpu.render(sc, spp=SPP, pps=1, depth=1, seed=3, light_sampling="area")
+    assert st["rays_shadow"] == st["rays_closest"] == W * W * SPP
+    got = film[..., :3].astype(np.float64)
+    z_pixel = np.abs(got - mean) / se_pixel
+    z_mean = np.abs(got.mean((0, 1)) - mean.mean((0, 1))) / se_mean
+    print(f"two lamps, by area: film mean off by {z_mean} standard errors (relative se {se_mean / mean.mean((0, 1))}), worst pixel {z_pixel.max():.2f} "
+          f"standard errors, rms {np.sqrt((z_pixel ** 2).mean()):.3f}")
+    assert (z_mean < 4.0).all() and z_pixel.max() < 5.0
+    assert 0.9 < np.sqrt((z_pixel ** 2).mean()) < 1.1  # the model's variance is the film's: the z scores have unit spread
+    # the reference's pick misses the same bound: the film mean is off by the quirk
+    ref, _ = xpu.render(sc, spp=SPP, pps=1, depth=1, seed=3)
+    zr = np.abs(ref[..., :3].astype(np.float64).mean((0, 1)) - mean.mean((0, 1))) / se_mean
+    print(f"two lamps, reference pick: film mean off by {zr} standard errors")
+    assert (zr > 4.0).any()
+
+
+# ---- 7. parity link to the oracle ----------------------------------------------------------------------------------------------------------
+G_CASES = [(n, l) for n, l in CASES if FAMILIES[n][0] >= abi.SHADE_FAMILY_GENERAL]
+LEFT_OUT = ()  # k_shade_g cases whose lamp is not a pair of bit-equal triangles (at most two may be): none, because ...
+# ... glass_blobs (the perhit and env_perhit families, pinhole and lens: four cases, six instantiations) has a second lamp of FOUR triangles, which
+# fails the precondition.  Rather than lose those kernels the lamp is cut to its first two triangles, in the device's and the oracle's scene alike:
+# the closures, and with them the family, stay the table's.
+CUT_LAMP = ("perhit", "env_perhit")
+
+
+def _cut_lamps_to_pairs(sc):
+    cut = 0
+    for m in sc.meshes:
+        for k, (mat, faces) in enumerate(m.sets):
+            if sc.materials[mat].is_emitter and len(faces) > 2:
+                m.sets[k] = (mat, faces[:2].copy()); cut += 1
+    assert cut == 1
+    return sc
+
+
+def _parity_scenes(name, lens):
+    if name == "cornell":
+        sc = scenes.cornell(64, 48)
+        return sc, sc, abi.SHADE_FAMILY_GENERAL
+    if name == "soup1k":
+        sc = scenes.soup(1000, width=64, height=48)
+        return sc, sc, abi.SHADE_FAMILY_GENERAL
+    st, sb = build(name, lens)
+    if name in CUT_LAMP:
+        assert st is not sb and not LightTable(st).equal_pairs_only()
+        _cut_lamps_to_pairs(st); _cut_lamps_to_pairs(sb)
+    return st, sb, FAMILIES[name][0]
+
+
+PARITY = [("cornell", False), ("soup1k", False)] + [c for c in G_CASES if c not in LEFT_OUT]
+
+
+def test_parity_cases_cover_every_k_shade_g_instantiation():
+    assert len(G_CASES) == 20 and len(LEFT_OUT) <= 2
+    union = 0
+    for name, lens in PARITY[2:]:
+        union |= expected_kernels(FAMILIES[name][0], lens)
+    want = sum(1 << b for b in range(abi.SHADE_KERNELS) if b // abi.SHADE_PASSES >= abi.SHADE_FAMILY_GENERAL)
+    if not LEFT_OUT:
+        assert union == want and bin(want).count("1") == 30
+
+
+@pytest.mark.parametrize("name,lens", PARITY, ids=[f"{n}-{'lens' if l else 'pinhole'}" for n, l in PARITY])
+def test_by_area_is_the_oracle_where_the_two_picks_agree(xpu, orc, name, lens):
+    """lights of one triangle or of two bit-equal ones: cdf = {1} or {0.5, 1}, both picks return the same triangle and the same remapped
+    draw, so the BY_AREA film and ray counters are the oracle's, bit for bit (lowest-primitive tie rule)"""
+    st_scene, sb_scene, family = _parity_scenes(name, lens)
+    assert LightTable(st_scene).equal_pairs_only() and LightTable(sb_scene).equal_pairs_only(), "the case's lamp is not a pair of bit-equal triangles"
+    film, st = xpu.render(st_scene, spp=T_SPP, pps=1, depth=T_DEPTH, seed=T_SEED, light_sampling="area")
+    orc.set_tie_rule(1)
+    try:
+        ref, ost = orc.Oracle(sb_scene, spp=T_SPP, pps=1, depth=T_DEPTH).render(rng=orc.RNG_COUNTER, seed=T_SEED, threads=8)
+    finally:
+        orc.set_tie_rule(0)
+    failed = [f"{k}: {st[k]}, the oracle's {ost[k]}" for k in COUNTERS if st[k] != ost[k]]
+    if st["shade_kernels"] != expected_kernels(family, lens):
+        failed.append(f"launched {abi.shade_kernel_names(st['shade_kernels'])}, expected {abi.shade_kernel_names(expected_kernels(family, lens))}")
+    if not film[..., :3].max() > 0.05:
+        failed.append("the film is dark")
+    if not bits_equal(film[..., :3], ref[..., :3]):
+        failed.append(f"the film differs from the oracle's in {(film[..., :3].view(np.uint32) != ref[..., :3].view(np.uint32)).any(-1).mean():.1%} of the pixels")
+    assert not failed, "\n".join(failed)
+
+
+# ---- 8. dispatch ---------------------------------------------------------------------------------------------------------------------------
+def test_by_area_runs_the_general_kernels_and_counts_its_table(xpu):
+    sc = scenes.cornell(32, 32)  # Lambert only, one lobe per material
+    _, st0 = xpu.render(sc, spp=4, pps=1, depth=9, seed=1)
+    _, st0b = xpu.render(sc, spp=4, pps=1, depth=9, seed=1, light_sampling="reference")
+    _, st1 = xpu.render(sc, spp=4, pps=1, depth=9, seed=1, light_sampling="area")
+    assert st0["shade_kernels"] == expected_kernels(abi.SHADE_FAMILY_LAMBERT1, False) and st0["shade_general"] == 0
+    assert st1["shade_kernels"] == expected_kernels(abi.SHADE_FAMILY_GENERAL, False) and st1["shade_general"] == 1
+    assert st0b["shade_kernels"] == st0["shade_kernels"] and st0b["device_bytes"] == st0["device_bytes"]
+    # the Lambert scene gives up its 32-byte-per-material table of k_shade<2> and gains the CDF, in records of the light table (32 bytes)
+    cdf_bytes = 4 * 2
+    assert st1["device_bytes"] - st0["device_bytes"] == 32 * math.ceil(cdf_bytes / 32) - 32 * len(sc.materials)
+    # a scene k_shade_g shades either way: the CDF is all that is added
+    zoo = scenes.multi_material_soup(3000, width=32, height=32)
+    fan = fan_scene()
+    zoo.meshes.append(fan.meshes[-1]); zoo.materials.append(scenes.emitter(1.0, 1.0, 1.0)); zoo.meshes[-1].sets = [(len(zoo.materials) - 1, zoo.meshes[-1].sets[0][1])]
+    ntris = sum(len(a) for a in LightTable(zoo).areas)
+    assert ntris >= 14
+    _, z0 = xpu.render(zoo, spp=4, pps=1, depth=9, seed=1)
+    _, z1 = xpu.render(zoo, spp=4, pps=1, depth=9, seed=1, light_sampling="area")
+    assert z0["shade_general"] == z1["shade_general"] == 1 and z0["shade_kernels"] == z1["shade_kernels"]
+    assert 4 * ntris <= z1["device_bytes"] - z0["device_bytes"] == 32 * math.ceil(4 * ntris / 32)
+
+
+# ---- 9. refusal ----------------------------------------------------------------------------------------------------------------------------
+def test_an_unknown_mode_is_refused_at_preprocess(xpu):
+    """light_sampling is a device option like bvh_builder: fixed at phx_dev_make, checked at phx_dev_preprocess.  A device made with an
+    unknown value refuses every scene with PHX_ERR_ARG before it touches anything and stays a well-formed device: the hooks still answer
+    PHX_ERR_STATE, the refusal repeats, it closes; a device made next renders the film rendered before."""
+    good = scenes.cornell(32, 32)
+    ref, st = xpu.render(good, spp=4, pps=1, depth=9, seed=1, light_sampling="area")
+    assert ref[..., :3].max() > 0.05
+    dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=4, paths_per_sample=1, path_depth=9, light_sampling=2))
+    try:
+        for _ in range(2):
+            with pytest.raises(xpu.DeviceError) as e:
+                dev.light_sample(np.zeros((1, 3), F))
+            assert "(4)" in str(e.value)  # PHX_ERR_STATE before preprocess
+            with pytest.raises(xpu.DeviceError) as e:
+                dev.preprocess(good)
+            assert "(1)" in str(e.value) and "light_sampling" in str(e.value)  # PHX_ERR_ARG with a message
+    finally:
+        dev.close()
+    again, st2 = xpu.render(good, spp=4, pps=1, depth=9, seed=1, light_sampling="area")
+    assert bits_equal(again, ref) and all(st[k] == st2[k] for k in COUNTERS)
