@@ -336,7 +336,10 @@ typedef struct phx_device phx_device; /* opaque */
 int         phx_discover(const phx_options* options, int* num_devices);
 /* T::make(const parsed_options_t&) (src/xpu/cpu.hpp:35).  NULL on failure (see phx_last_error). */
 phx_device* phx_dev_make(const phx_options* options);
-/* xpu_t::preprocess (src/xpu.hpp:20; cpu.cpp:219 -> details_t::reset :35): flatten + upload scene, build BVH. */
+/* xpu_t::preprocess (src/xpu.hpp:20; cpu.cpp:219 -> details_t::reset :35): flatten + upload scene, build BVH.
+ * A call refused before anything is uploaded (PHX_ERR_STATE, a malformed scene) keeps the previous scene renderable; one that fails later
+ * (the device builder's fatal error, a tree too deep, out of memory) leaves the device WITHOUT a scene: phx_dev_start and the stage-level
+ * entry points answer PHX_ERR_STATE until a phx_dev_preprocess succeeds. */
 int         phx_dev_preprocess(phx_device* dev, const phx_scene* scene);
 /* xpu_t::start (src/xpu.hpp:26; cpu.cpp:223-238): non-blocking; spawns the driver thread. */
 int         phx_dev_start(phx_device* dev, const phx_frame* frame);

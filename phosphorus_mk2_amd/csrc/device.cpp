@@ -9,18 +9,20 @@
 #include "bvh_build.h"
 #include "bvh_gpu.h"
 #include "kernels.h"
+#include "scene_flatten.h"
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cfloat>
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -78,6 +80,33 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
+// Queues + state of the paths in flight, 16 bytes per path each (kernels.h: PassBuffers): ray queues 2 x 32, path state travelling with them
+// 2 x 16, hit 16, shadow queue 48, radiance 16, and the primary normal 16 when the frame has a normals channel.
+struct PathQueues {
+  enum { RO, RD, QS, RO1, RD1, QS1, HIT, SO, SD, SC, PR, PN, COUNT };  // PN last: allocated only for a frame with a normals channel
+  DevBuf<float4> q[COUNT];
+  static constexpr size_t bytes_per_path(bool normals) { return (COUNT - (normals ? 0 : 1)) * sizeof(float4); }
+  int alloc(size_t npaths, bool normals) {
+    for (int i = 0; i < COUNT - (normals ? 0 : 1); ++i) if (const int rc = q[i].alloc(npaths)) return rc;
+    return PHX_OK;
+  }
+  void release() { for (auto& b : q) b.release(); }
+  size_t bytes() const { size_t n = 0; for (auto& b : q) n += b.bytes(); return n; }
+  size_t capacity() const { return q[HIT].n; }  // paths the queues hold
+  void fill(PassBuffers& B, bool normals) const {
+    for (int k = 0; k < 2; ++k) { B.ro[k] = q[RO + 3 * k].p; B.rd[k] = q[RD + 3 * k].p; B.qs[k] = q[QS + 3 * k].p; }
+    B.hit = q[HIT].p; B.so = q[SO].p; B.sd = q[SD].p; B.sc = q[SC].p; B.pr = q[PR].p; B.pn = normals ? q[PN].p : nullptr;
+  }
+};
+static_assert(PathQueues::bytes_per_path(false) == 176 && PathQueues::bytes_per_path(true) == 192, "what path_budget divides the device's memory by");
+
+bool host_timing() {  // PHX_HOST_TIMING, read at the first frame: where a frame's and a batch's host time goes, on stderr (probe)
+  static const bool on = std::getenv("PHX_HOST_TIMING") != nullptr;
+  return on;
+}
+using Clock = std::chrono::steady_clock;
+double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
 }  // namespace
 
 struct phx_tiles {
@@ -104,7 +133,7 @@ struct phx_device {
   double preprocess_ms = 0, bvh_build_ms = 0;
 
   // pass buffers
-  DevBuf<float4> ro[2], rd[2], qs[2], hit, so, sd, sc, pr, pn;
+  PathQueues queues;
   DevBuf<uint32_t> counters; DevBuf<DevStats> dstats; DevBuf<uint32_t> pix_xy; DevBuf<float2> jitter; DevBuf<float> acc;
   uint64_t jitter_seed = 0; uint32_t jitter_spp = 0;  // what the jitter table on the device was made for
   float* h_acc = nullptr; size_t h_acc_n = 0;  // pinned staging for add_tile
@@ -125,7 +154,8 @@ struct phx_device {
   TracePlan plan{};
   uint64_t paths_in_flight = 0;
   double bvh_cost_model = 0; uint32_t bvh_built_on_device = 0;
-  struct Timed { size_t begin, end; int kind; };  // (event before, event behind, kind 0 k_trace / 2 begin-pass, film / 3 shade / 4 k_trace_primary)
+  enum class Launch { Trace, Primary, Shade, Pass /* begin-pass, film */ };
+  struct Timed { size_t begin, end; Launch kind; };  // (event before, event behind, what ran between them)
   // The launches of a batch and the HIP events between them.  (Round 5 captured a batch's launches — memset, [begin-pass, camera rays,
   // shade, (trace, shade) x (depth - 1), trace, film] per pass, film scatter — as ONE hipGraph, cached by a hash of the kernel arguments:
   // rank 0 of 8 of the bench frame 9.12-9.27 ms with direct launches and events, 9.08-9.37 without events, 9.14-9.16 as a graph — nothing,
@@ -137,7 +167,7 @@ struct phx_device {
   };
   BatchLaunches direct;
   bool kernel_timing = true;        // per-kernel HIP events (phx_stats::closest_ms ...); PHX_KERNEL_TIMING=0 launches without them (probe)
-  std::chrono::steady_clock::time_point t_start, t_enq, t_sync;  // host timing probe (PHX_HOST_TIMING)
+  Clock::time_point t_start, t_enq, t_sync;  // host timing probe (PHX_HOST_TIMING)
 
   ~phx_device() {
     {
@@ -162,12 +192,9 @@ struct phx_device {
   }
   // HBM held by this device object (phx_stats::device_bytes)
   uint64_t device_bytes() const {
-    uint64_t b = d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
-                 d_lights.bytes() + d_light_tris.bytes() + hit.bytes() + so.bytes() + sd.bytes() + sc.bytes() + pr.bytes() + pn.bytes() +
-                 counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
-                 d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes();
-    for (int q = 0; q < 2; ++q) b += ro[q].bytes() + rd[q].bytes() + qs[q].bytes();
-    return b;
+    return d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
+           d_lights.bytes() + d_light_tris.bytes() + queues.bytes() + counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
+           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes();
   }
   // paths in flight this device may carry: up to 512 M (about 95 GB of queues + state: sized for 288 GB of HBM), but never more than 60 % of
   // what the device has free right now plus what this object already holds for queues (another device object, torch or RCCL may share the GPU)
@@ -177,77 +204,20 @@ struct phx_device {
     if (!budget_bytes) {
       budget_bytes = ~0ull;
       size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        size_t held = 0;
-        for (int q = 0; q < 2; ++q) held += (ro[q].n + rd[q].n + qs[q].n) * sizeof(float4);
-        held += (hit.n + so.n + sd.n + sc.n + pr.n + pn.n) * sizeof(float4);
-        budget_bytes = (uint64_t)((double)(free_b + held) * 0.6);
-      }
+      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget_bytes = (uint64_t)((double)(free_b + queues.bytes()) * 0.6);
     }
     return std::min<uint64_t>(cap_m << 20, budget_bytes / path_bytes);
   }
   void driver_loop();
   int run_frame();
   int enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, uint32_t S, uint32_t xs);
-  int render_batch(const std::vector<phx_tile>& tiles, const std::vector<float2>& jit);
+  int render_batch(const std::vector<phx_tile>& tiles);
 };
 
-// ---- scene flattening --------------------------------------------------------------------------------
+// ---- preprocess ---------------------------------------------------------------------------------------
+// Three stages: the state checks, flatten_scene (scene_flatten.cpp: validation and everything derived on the host — a refusal leaves the
+// device and its previous scene untouched), and commit_scene, which builds the tree and replaces the device's tables.
 namespace {
-
-// microfacet_t::roughness_to_alpha + precompute (src/bsdf/params.hpp:86-99), with the device's logf_
-float roughness_to_alpha(float roughness) {
-  roughness = std::max(roughness, (float)1e-5);
-  float x = logf_(roughness);
-  return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
-}
-
-int bake_material(const phx_material& m, float sheen_L5, DevMaterial& out, uint32_t* lobe_tex /* 8: texture + 1 per baked lobe */) {
-  std::memset(&out, 0, sizeof(out));
-  for (int k = 0; k < PHX_MAX_LOBES; ++k) lobe_tex[k] = 0;
-  out.is_emitter = m.is_emitter; out.ex = m.emission[0]; out.ey = m.emission[1]; out.ez = m.emission[2];
-  out.sheen_L5 = sheen_L5;
-  if (m.num_lobes > PHX_MAX_LOBES) return 1;
-  uint32_t k = 0;
-  for (uint32_t i = 0; i < m.num_lobes; ++i) {
-    const phx_lobe& s = m.lobes[i];
-    DevLobe& l = out.lobes[k];
-    l.type = s.type; l.wx = s.weight[0]; l.wy = s.weight[1]; l.wz = s.weight[2];
-    // the device lobe holds the mode byte alone; an image mode has no ior and keeps its mask's texture + 1 in that word's bits (validated by the caller)
-    const uint32_t mode = PHX_FAC_MODE(s.fac_mode);
-    l.fac_mode = mode; l.fac_ior = mode >= PHX_FAC_TEX_B ? float_of_bits(PHX_FAC_TEXTURE(s.fac_mode)) : s.fac_ior;
-    l.px = s.pre_weight[0]; l.py = s.pre_weight[1]; l.pz = s.pre_weight[2];
-    if (mode > PHX_FAC_TEX_A) return 1;
-    if (mode != PHX_FAC_NONE) out.per_hit = 1;
-    if (s.texture) { out.tex_lobes |= 1u << k; lobe_tex[k] = s.texture; }  // (validated by the caller)
-    switch (s.type) {
-      case PHX_LOBE_DIFFUSE: l.flags = B_REFLECT | B_DIFFUSE; break;
-      case PHX_LOBE_OREN_NAYAR: {  // oren_nayar_t::precompute, params.hpp:36-43
-        l.flags = B_REFLECT | B_DIFFUSE;
-        const float sg = (float)((double)s.alpha * (kPiD / (double)180.0f));
-        const float s2 = sg * sg;
-        l.a = 1.0f - (s2 / (2.0f * (s2 + 0.33f)));
-        l.b = 0.45f * s2 / (s2 + 0.09f);
-        break;
-      }
-      case PHX_LOBE_REFLECTION: l.flags = B_REFLECT | B_SPECULAR; l.eta = s.eta; break;
-      case PHX_LOBE_REFRACTION: l.flags = B_TRANSMIT | B_SPECULAR; l.eta = s.eta; break;
-      case PHX_LOBE_MICROFACET:
-        l.flags = s.refract ? B_TRANSMIT : B_REFLECT;  // src/bsdf.hpp:70-72
-        l.eta = s.eta; l.refract = s.refract;
-        l.xalpha = std::min(1.0f, std::max(0.0001f, roughness_to_alpha(s.xalpha)));
-        l.yalpha = std::min(1.0f, std::max(0.0001f, roughness_to_alpha(s.yalpha)));
-        break;
-      case PHX_LOBE_SHEEN: l.flags = B_REFLECT | B_GLOSSY; l.r = s.r; break;
-      case PHX_LOBE_TRANSPARENT: l.flags = B_TRANSMIT; break;  // src/material.cpp:98-103
-      case PHX_LOBE_EMISSIVE: case PHX_LOBE_BACKGROUND: continue;  // not lobes (material.cpp:240-245)
-      default: return 1;
-    }
-    ++k;
-  }
-  out.num_lobes = k;
-  return 0;
-}
 
 // No C++ exception may cross the C ABI (the reference's own std::runtime_error cases become status codes): every entry
 // point that allocates or spawns runs its body through guarded().
@@ -257,6 +227,151 @@ int guarded(F&& body) {
   catch (const std::bad_alloc&) { return fail(PHX_ERR_OOM, "host memory allocation failed"); }
   catch (const std::exception& e) { return fail(PHX_ERR_DEVICE, std::string("unexpected exception: ") + e.what()); }
   catch (...) { return fail(PHX_ERR_DEVICE, "unexpected exception"); }
+}
+
+// PHX_BVH_AUTO: the device builder (bvh_gpu.hip) unless the scene is tiny.  Round 2 kept the host's binned SAH for scenes up to 2 M
+// triangles because its trees traced 3-5 % faster on mesh-like scenes; with extended Morton codes (the size of a primitive as a
+// fourth coordinate) the device trees are as fast or faster everywhere measured — soups -2 ... -7 % k_trace time, the showroom
+// -3 % — and they are built in milliseconds (profiles/r03_z_emc_probe.log, r03_za_builder_ab.log).
+// Fills d_pool, the tree's words of d->scene and of the statistics, and elem_of_prim: the pool index of every primitive's triangle record (the
+// shade records and the normals table are laid out by it).  d_prim_material holds the scene's material words already.
+int build_tree(phx_device* d, const FlatScene& fs, DevBuf<uint32_t>& elem_of_prim) {
+  int rc;
+  const uint32_t builder = d->opt.bvh_builder;
+  const uint32_t ntri = (uint32_t)fs.prim_material.size();
+  bool want_host = builder == PHX_BVH_HOST_SAH || (builder == PHX_BVH_AUTO && ntri < 64u);
+  GpuBvh g{};
+  if (!want_host) {
+    // the triangles go up once (36 B each); the tree is built and stays in HBM (bvh_gpu.hip)
+    DevBuf<float> d_abc;
+    char msg[256] = {0};
+    rc = d_abc.upload(fs.abc);
+    int brc = rc ? (rc == PHX_ERR_OOM ? (int)BVH_GPU_RECOVERABLE : 1) : 0;
+    if (rc) std::snprintf(msg, sizeof(msg), "%s", g_error.c_str());
+#if PHX_TEST_HOOKS
+    // test hook, compiled into the twin library libphx_hip_hooks.so only (tests/test_gpu_parity.py): makes the device build report a
+    // recoverable or a fatal failure
+    if (const char* how = std::getenv("PHX_TEST_FAIL_DEVICE_BUILD")) {
+      brc = std::strcmp(how, "fatal") == 0 ? 1 : (int)BVH_GPU_RECOVERABLE;
+      std::snprintf(msg, sizeof(msg), "forced %s failure (PHX_TEST_FAIL_DEVICE_BUILD)", brc == 1 ? "fatal" : "recoverable");
+    }
+#endif
+    if (!brc && elem_of_prim.alloc(ntri)) brc = (int)BVH_GPU_RECOVERABLE, std::snprintf(msg, sizeof(msg), "%s", g_error.c_str());
+    if (!brc) brc = build_bvh8_gpu(d->stream, d_abc.p, d->d_prim_material.p, ntri, &g, msg, sizeof(msg), elem_of_prim.p);
+    if (brc) {
+      // An explicit DEVICE_LBVH request fails loudly, and so does AUTO when the device builder reports anything but a RECOVERABLE cause
+      // (a HIP error from a launch or a sync, lost triangles: bugs that a silent 0.6-7 s host build would hide).  Under AUTO a device
+      // build that cannot get its scratch memory, or meets a tree deeper than its tables, falls back to the host's binned-SAH builder
+      // — which handled every scene before the device builder became the default — and says so: on stderr, in phx_last_error of this
+      // thread (a successful call leaves the text in place) and in phx_stats::bvh_built_on_device.
+      if (builder != PHX_BVH_AUTO || brc != (int)BVH_GPU_RECOVERABLE) return fail(rc ? rc : PHX_ERR_DEVICE, std::string("device BVH build: ") + msg);
+      (void)hipGetLastError();  // a failed hipMalloc leaves its error behind
+      g_error = std::string("device BVH build fell back to the host builder: ") + msg;
+      std::fprintf(stderr, "libphx_hip: %s\n", g_error.c_str());
+      want_host = true;
+    }
+  }
+  DevScene& sc = d->scene;
+  if (want_host) {
+    Bvh8 bvh;
+    const int threads = (int)std::max(1u, std::thread::hardware_concurrency());
+    build_bvh8(fs.abc.data(), ntri, bvh, threads, fs.prim_material.data());
+    if ((rc = d->d_pool.upload(bvh.pool))) return rc;
+    if ((rc = elem_of_prim.upload(bvh.elem_of_prim))) return rc;
+    sc.stack_levels = bvh.depth; sc.num_elems = (uint32_t)bvh.pool.size(); sc.grid = bvh.grid;
+    d->bvh_nodes = bvh.num_nodes; d->bvh_cost_model = bvh.cost; d->bvh_built_on_device = 0;
+  } else {
+    d->d_pool.adopt(g.pool, g.num_elems);
+    sc.stack_levels = g.depth; sc.num_elems = g.num_elems; sc.grid = g.grid;
+    d->bvh_nodes = g.num_nodes; d->bvh_cost_model = g.cost; d->bvh_built_on_device = 1;
+  }
+  sc.pool = reinterpret_cast<const uint32_t*>(d->d_pool.p);
+  sc.tris = reinterpret_cast<const TriRec*>(d->d_pool.p);
+  d->bvh_bytes = (uint64_t)sc.num_elems * sizeof(PoolElem);
+  return PHX_OK;
+}
+
+// Replaces the device's scene by `fs`.  From its first line to its last the device has NO scene (preprocessed == false): a failure on the
+// way — the device builder's fatal error, a tree too deep, a hipMalloc that fails — leaves buffers of the old and the new scene mixed, and
+// start / the stage hooks answer PHX_ERR_STATE until a preprocess succeeds.
+int commit_scene(phx_device* d, FlatScene& fs) {
+  int rc;
+  d->preprocessed = false;
+  DevScene& sc = d->scene = fs.scene;
+  const uint32_t ntri = (uint32_t)fs.prim_material.size();
+  const bool any_tex = (sc.any_tex & SC_TEX_LOBES) != 0, any_image = (sc.any_tex & SC_TEX_ANY) != 0;
+  if ((rc = d->d_prim_material.upload(fs.prim_material))) return rc;
+  const auto t_bvh0 = Clock::now();
+  DevBuf<uint32_t> d_elem_of_prim;
+  if ((rc = build_tree(d, fs, d_elem_of_prim))) return rc;
+  d->bvh_build_ms = ms_between(t_bvh0, Clock::now());
+  // k_trace / k_trace_rays keep one pending sibling group per level and lane in LDS (bvh8.h: PHX_MAX_BVH_DEPTH)
+  if (sc.stack_levels > PHX_MAX_BVH_DEPTH)
+    return fail(PHX_ERR_ARG, "tree too deep: " + std::to_string(sc.stack_levels) + " levels, the traversal stack in LDS holds " + std::to_string(PHX_MAX_BVH_DEPTH));
+  if ((rc = d->d_materials.upload(fs.materials))) return rc;
+  if (sc.any_tex & SC_LIGHTS_BY_AREA) {  // the CDF rides behind the light table (kernels.hip: light_cdf): one float per light triangle, in records of the table's size
+    const size_t nl = fs.lights.size();
+    fs.lights.resize(nl + (fs.light_cdf.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
+    std::memcpy(static_cast<void*>(fs.lights.data() + nl), fs.light_cdf.data(), fs.light_cdf.size() * sizeof(float));
+  }
+  if ((rc = d->d_lights.upload(fs.lights)) || (rc = d->d_light_tris.upload(fs.light_tris))) return rc;
+  // what shading reads of a hit triangle, 16 bytes per POOL ELEMENT: geometric normal + material word
+  if ((rc = d->d_elem_shade.alloc(sc.num_elems))) return rc;
+  launch_build_shade_recs(d->stream, sc.tris, d_elem_of_prim.p, d->d_elem_shade.p, ntri);
+  HIPCHK(hipGetLastError());
+  // Vertex normals by POOL ELEMENT (the index a hit record carries), so that the shade kernels request them with the triangle record and not
+  // after it; the smooth light triangles' `prim` becomes a pool index too (shading_normal on the light's face, spt.hpp:212-255).  Corner UVs
+  // likewise (textured lobes only).  The tables in primitive order live until the stream has been synchronised below.
+  DevBuf<float> d_prim_normals; DevBuf<float2> d_prim_uv;
+  if (fs.any_smooth) {
+    if ((rc = d_prim_normals.upload(fs.prim_normals)) || (rc = d->d_elem_normals.alloc(9 * (size_t)sc.num_elems))) return rc;
+    launch_permute_normals(d->stream, d_prim_normals.p, d_elem_of_prim.p, d->d_elem_normals.p, ntri);
+    launch_remap_light_tris(d->stream, d->d_light_tris.p, (uint32_t)fs.light_tris.size(), d_elem_of_prim.p);
+  } else {
+    d->d_elem_normals.release();
+  }
+  if (any_tex) {
+    if ((rc = d_prim_uv.upload(fs.prim_uv)) || (rc = d->d_elem_uv.alloc(3 * (size_t)sc.num_elems)) || (rc = d->d_lobe_tex.upload(fs.lobe_tex))) return rc;
+    launch_permute_uvs(d->stream, d_prim_uv.p, d_elem_of_prim.p, d->d_elem_uv.p, ntri);
+  } else {
+    d->d_elem_uv.release(); d->d_lobe_tex.release();
+  }
+  HIPCHK(hipGetLastError());
+  if (any_image) {  // the texture table and the texels, and the one record through which the shade kernels find them
+    if ((rc = d->d_textures.upload(fs.textures)) || (rc = d->d_texels.upload(fs.texels))) return rc;
+    const std::vector<DevTexScene> ts{DevTexScene{any_tex ? d->d_elem_uv.p : nullptr, d->d_textures.p, d->d_texels.p, any_tex ? d->d_lobe_tex.p : nullptr,
+                                                  fs.env_tex ? fs.env_tex - 1u : 0u, fs.env_mapping}};
+    if ((rc = d->d_tex_scene.upload(ts))) return rc;
+  } else {
+    d->d_textures.release(); d->d_texels.release(); d->d_tex_scene.release();
+  }
+  if (sc.diffuse_only == 2 && (rc = d->d_mat_lite.upload(fs.mat_lite))) return rc;
+  HIPCHK(hipStreamSynchronize(d->stream));  // d_elem_of_prim and the tables in primitive order go out of scope below
+
+  sc.elem_normals = fs.any_smooth ? d->d_elem_normals.p : nullptr;
+  sc.elem_shade = d->d_elem_shade.p;
+  sc.materials = d->d_materials.p;
+  sc.mat_lite = sc.diffuse_only == 2 ? d->d_mat_lite.p : nullptr;
+  sc.lights = d->d_lights.p; sc.light_tris = d->d_light_tris.p;
+  sc.tex = any_image ? d->d_tex_scene.p : nullptr;
+  {
+    hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, d->hip_device));
+    sc.num_cus = (uint32_t)prop.multiProcessorCount;
+  }
+  d->plan = trace_plan(sc);
+  if (d->plan.spill_threads) {  // stack levels below the ones k_trace keeps in LDS (kernels.hip: trace_plan)
+    if ((rc = d->d_spill.alloc((size_t)d->plan.spill_threads * (d->plan.levels - d->plan.lds_levels)))) return rc;
+    sc.stack_spill = d->d_spill.p; sc.spill_stride = d->plan.spill_threads;
+  }
+  d->num_materials = (uint32_t)fs.materials.size();
+  d->mat_masked = std::move(fs.mat_masked);
+  d->num_textures = any_image ? (uint32_t)fs.textures.size() : 0;
+  d->env_tex = fs.env_tex; d->env_mapping = fs.env_mapping;
+  for (int c = 0; c < 3; ++c) d->env_e[c] = fs.env_e[c];
+  d->num_triangles = ntri;
+  d->budget_bytes = 0;  // the next frame asks the device again how much memory is free
+  d->preprocessed = true;
+  return PHX_OK;
 }
 
 }  // namespace
@@ -315,343 +430,20 @@ void phx_dev_destroy(phx_device* dev) {
   delete dev;
 }
 
-static int preprocess_impl(phx_device* d, const phx_scene* s);
-int phx_dev_preprocess(phx_device* d, const phx_scene* s) { return guarded([&]() { return preprocess_impl(d, s); }); }
-static int preprocess_impl(phx_device* d, const phx_scene* s) {
-  if (!d || !s) return fail(PHX_ERR_ARG, "preprocess: null argument");
-  if (d->running) return fail(PHX_ERR_STATE, "preprocess while a frame is running");
-  if (!s->meshes || !s->materials || s->num_materials == 0) return fail(PHX_ERR_ARG, "scene without meshes/materials");
-  // (camera_t's constructor leaves focal_distance uninitialised, entities/camera.hpp:31-36: it means something only behind a lens)
-  if (!(std::fabs(s->camera.aperture_radius) <= FLT_MAX) || (s->camera.aperture_radius != 0.0f && !(std::fabs(s->camera.focal_distance) <= FLT_MAX)))
-    return fail(PHX_ERR_ARG, "camera: aperture radius / focal distance not finite");
-  if (s->camera.film_width == 0 || s->camera.film_height == 0 || s->camera.film_width > 65535 || s->camera.film_height > 65535)
-    return fail(PHX_ERR_ARG, "film size out of range");
-  if (s->environment_material >= (int32_t)s->num_materials) return fail(PHX_ERR_ARG, "environment material out of range");
-  if (d->opt.light_sampling > PHX_LIGHTS_BY_AREA) return fail(PHX_ERR_ARG, "unknown light_sampling");
-  const bool lights_by_area = d->opt.light_sampling == PHX_LIGHTS_BY_AREA;
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  const auto t_pre0 = std::chrono::steady_clock::now();
-
-  // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
-  // non-emitting materials may carry one (textured emission is not supported)
-  if (s->num_textures && !s->textures) return fail(PHX_ERR_ARG, "scene with textures but a null texture table");
-  uint64_t total_texels = 0;
-  for (uint32_t t = 0; t < s->num_textures; ++t) {
-    const phx_texture& T = s->textures[t];
-    if (T.width == 0 || T.height == 0) return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " has zero size");
-    if (T.width > 65536u || T.height > 65536u || (uint64_t)T.width * T.height > (1ull << 26))
-      return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " too large (at most 65536 x 65536 and 2^26 texels)");
-    if (!T.texels) return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " without texels");
-    if (T.filter > PHX_TEX_CLOSEST || T.swrap > PHX_WRAP_BLACK || T.twrap > PHX_WRAP_BLACK) return fail(PHX_ERR_ARG, "texture " + std::to_string(t) + " with an unknown filter or wrap mode");
-    total_texels += (uint64_t)T.width * T.height;
-  }
-  if (total_texels > (1ull << 30)) return fail(PHX_ERR_ARG, "textures too large (at most 2^30 texels in all)");
-  bool any_tex = false, any_mask = false;  // any_tex: some lobe reads an image at the hit's UV (colour texture or mask)
-  for (uint32_t i = 0; i < s->num_materials; ++i) {
-    const phx_material& m = s->materials[i];
-    for (uint32_t k = 0; k < m.num_lobes && k < PHX_MAX_LOBES; ++k) {
-      // an image mask on the closure's mix factor (fac_mode: mode byte + the mask's texture): the same rules as a colour texture
-      const uint32_t mode = PHX_FAC_MODE(m.lobes[k].fac_mode), mask = PHX_FAC_TEXTURE(m.lobes[k].fac_mode);
-      if (mode > PHX_FAC_TEX_A) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": unknown fac_mode");
-      if (mode < PHX_FAC_TEX_B && mask) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": fac_mode names a mask texture but its mode is not PHX_FAC_TEX_*");
-      if (mode >= PHX_FAC_TEX_B) {
-        if (mask == 0 || mask > s->num_textures) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": mask texture index out of range");
-        if (m.is_emitter || (int32_t)i == s->environment_material || m.lobes[k].type == PHX_LOBE_EMISSIVE || m.lobes[k].type == PHX_LOBE_BACKGROUND)
-          return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": masks on emitters / the environment are not supported");
-        any_tex = any_mask = true;
-      }
-      const uint32_t t = m.lobes[k].texture;
-      if (!t) continue;
-      if (t > s->num_textures) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": lobe texture index out of range");
-      if (m.is_emitter || (int32_t)i == s->environment_material || m.lobes[k].type == PHX_LOBE_EMISSIVE || m.lobes[k].type == PHX_LOBE_BACKGROUND)
-        return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": textures on emitters / the environment are not supported");
-      any_tex = true;
-    }
-    // an environment map: only on the environment material (textured surface emission would need UVs at NEE's light samples)
-    if (m.emission_mapping > PHX_ENV_LATLONG_Z_UP) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": unknown emission_mapping");
-    if (m.emission_texture) {
-      if ((int32_t)i != s->environment_material)
-        return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": emission_texture is allowed only on the environment material");
-      if (m.emission_texture > s->num_textures) return fail(PHX_ERR_ARG, "material " + std::to_string(i) + ": emission_texture index out of range");
-    }
-  }
-  const uint32_t env_tex = s->environment_material >= 0 ? s->materials[s->environment_material].emission_texture : 0u;  // texture + 1, 0 = none
-
-  // triangles in scene_t::triangles() order: mesh order x face-set order (scene.cpp:58-62, mesh.cpp:118-128)
-  std::vector<float> abc; std::vector<uint32_t> prim_material; std::vector<float> prim_normals;
-  std::vector<float2> prim_uv;  // any_tex: 3 corner UVs per primitive
-  std::vector<DevLight> lights; std::vector<DevLightTri> light_tris;
-  std::vector<float> light_cdf;  // PHX_LIGHTS_BY_AREA: per light triangle, the light's running area up to and including it; divided by the light's area below
-  bool any_smooth = false;
-  for (uint32_t mi = 0; mi < s->num_meshes; ++mi) {
-    const phx_mesh& m = s->meshes[mi];
-    for (uint32_t f = 0; f < m.num_faces; ++f) if (m.smooth && m.smooth[f]) any_smooth = true;
-  }
-  for (uint32_t mi = 0; mi < s->num_meshes; ++mi) {
-    const phx_mesh& m = s->meshes[mi];
-    if (!m.vertices || !m.faces || (m.num_sets && !m.sets) || (any_tex && m.num_uvs && !m.uvs)) return fail(PHX_ERR_ARG, "mesh with null arrays");
-    for (uint32_t si = 0; si < m.num_sets; ++si) {
-      const phx_face_set& fs = m.sets[si];
-      if (fs.material >= s->num_materials) return fail(PHX_ERR_ARG, "face set material out of range");
-      const bool emitter = s->materials[fs.material].is_emitter != 0;
-      DevLight L{(uint32_t)light_tris.size(), 0, 0.0f, fs.material, 0.0f, 0.0f, 0.0f, 0.0f};
-      for (uint32_t k = 0; k < fs.num_faces; ++k) {
-        const uint32_t f = fs.faces[k];
-        if (f >= m.num_faces) return fail(PHX_ERR_ARG, "face index out of range");
-        const uint32_t ia = m.faces[3 * f], ib = m.faces[3 * f + 1], ic = m.faces[3 * f + 2];
-        if (ia >= m.num_vertices || ib >= m.num_vertices || ic >= m.num_vertices) return fail(PHX_ERR_ARG, "vertex index out of range");
-        const uint32_t prim = (uint32_t)prim_material.size();
-        const float* a = m.vertices + 3 * (size_t)ia; const float* b = m.vertices + 3 * (size_t)ib; const float* c = m.vertices + 3 * (size_t)ic;
-        abc.insert(abc.end(), a, a + 3); abc.insert(abc.end(), b, b + 3); abc.insert(abc.end(), c, c + 3);
-        const bool smooth = m.smooth && m.smooth[f];
-        prim_material.push_back(fs.material | (smooth ? 0x80000000u : 0u));
-        if (any_smooth) {
-          uint32_t na = ia, nb = ib, nc = ic;
-          if (!(m.flags & PHX_MESH_NORMALS_PER_VERTEX)) { na = 3 * f; nb = 3 * f + 1; nc = 3 * f + 2; }  // mesh.cpp:188-192
-          float nn[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-          if (smooth) {
-            if (!m.normals || na >= m.num_normals || nb >= m.num_normals || nc >= m.num_normals) return fail(PHX_ERR_ARG, "normal index out of range");
-            std::memcpy(nn, m.normals + 3 * (size_t)na, 12); std::memcpy(nn + 3, m.normals + 3 * (size_t)nb, 12); std::memcpy(nn + 6, m.normals + 3 * (size_t)nc, 12);
-          }
-          prim_normals.insert(prim_normals.end(), nn, nn + 9);
-        }
-        if (any_tex) {  // mesh_t::shading_parameters (mesh.cpp:239-257): UV indices per vertex or per face corner, like the normals; no UVs: (0, 0)
-          float2 uv[3] = {make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)};
-          if (m.num_uvs) {
-            const bool per_vertex = (m.flags & PHX_MESH_UV_PER_VERTEX) != 0;
-            const uint32_t ui[3] = {per_vertex ? ia : 3 * f, per_vertex ? ib : 3 * f + 1, per_vertex ? ic : 3 * f + 2};
-            for (int c = 0; c < 3; ++c) {
-              if (ui[c] >= m.num_uvs) return fail(PHX_ERR_ARG, "uv index out of range");
-              uv[c] = make_float2(m.uvs[2 * (size_t)ui[c]], m.uvs[2 * (size_t)ui[c] + 1]);
-            }
-          }
-          prim_uv.insert(prim_uv.end(), uv, uv + 3);
-        }
-        if (emitter) {  // mesh_t::preprocess -> light_t::make_area (mesh.cpp:108-116), area_light_t (light.cpp:10-45)
-          const v3 ab(b[0] - a[0], b[1] - a[1], b[2] - a[2]), ac(c[0] - a[0], c[1] - a[1], c[2] - a[2]);
-          const v3 gn = normalize_inplace(cross(ab, ac));  // the flat face's normal as k_shade's shading_normal would compute it per sample
-          DevLightTri T{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2], gn.x, gn.y, gn.z, prim, smooth ? 1u : 0u, mi | (fs.material << 16), 3 * f};
-          light_tris.push_back(T);
-          L.area += 0.5f * length(cross(ab, ac));  // triangle_t::area, mesh.cpp:293-300; summed in face order (light.cpp:36-39)
-          L.num_tris++;
-          if (lights_by_area) light_cdf.push_back(L.area);  // acc_i
-        }
-      }
-      if (emitter && L.num_tris) {
-        lights.push_back(L);
-        for (uint32_t k = 0; k < (lights_by_area ? L.num_tris : 0u); ++k) light_cdf[L.first_tri + k] = light_cdf[L.first_tri + k] / L.area;  // cdf[i] = acc_i / area; the last is 1
-      }
-    }
-  }
-  if (prim_material.empty()) return fail(PHX_ERR_ARG, "scene has no triangles");
-  if (lights.empty()) return fail(PHX_ERR_ARG, "scene has no emissive face set (reference underflows nlights-1, SURVEY A-19)");
-
-  // sheen_L5: the first sheen lobe of the material table (bsdf.h)
-  float L5 = 0.0f; bool have = false;
-  for (uint32_t i = 0; i < s->num_materials && !have; ++i)
-    for (uint32_t k = 0; k < s->materials[i].num_lobes && k < PHX_MAX_LOBES; ++k)
-      if (s->materials[i].lobes[k].type == PHX_LOBE_SHEEN) { L5 = sheen_L(0.5f, s->materials[i].lobes[k].r); have = true; break; }
-  std::vector<DevMaterial> mats(s->num_materials);
-  std::vector<uint32_t> lobe_tex(8 * (size_t)s->num_materials);
-  for (uint32_t i = 0; i < s->num_materials; ++i)
-    if (bake_material(s->materials[i], L5, mats[i], lobe_tex.data() + 8 * (size_t)i)) return fail(PHX_ERR_ARG, "material with an unknown closure id");
-
-  {  // per light: the pick pdf and the emission of its material, as k_shade evaluated them per sample until round 2
-    const float nlf = (float)lights.size();
-    for (auto& L : lights) {
-      L.lpdf = (1.0f / L.area) / nlf;
-      if (L.material >= s->num_materials) return fail(PHX_ERR_ARG, "light with a material index out of range");
-      L.ex = mats[L.material].ex; L.ey = mats[L.material].ey; L.ez = mats[L.material].ez;
-    }
-  }
-  int rc;
-  if ((rc = d->d_prim_material.upload(prim_material))) return rc;
-  const auto t_bvh0 = std::chrono::steady_clock::now();
-  // PHX_BVH_AUTO: the device builder (bvh_gpu.hip) unless the scene is tiny.  Round 2 kept the host's binned SAH for scenes up to 2 M
-  // triangles because its trees traced 3-5 % faster on mesh-like scenes; with extended Morton codes (the size of a primitive as a
-  // fourth coordinate) the device trees are as fast or faster everywhere measured — soups -2 ... -7 % k_trace time, the showroom
-  // -3 % — and they are built in milliseconds (profiles/r03_z_emc_probe.log, r03_za_builder_ab.log).
-  const uint32_t builder = d->opt.bvh_builder;
-  const uint32_t ntri = (uint32_t)prim_material.size();
-  if (builder > PHX_BVH_HOST_SAH) return fail(PHX_ERR_ARG, "unknown bvh_builder");
-  bool want_host = builder == PHX_BVH_HOST_SAH || (builder == PHX_BVH_AUTO && ntri < 64u);
-  GpuBvh g{};
-  DevBuf<uint32_t> d_elem_of_prim;  // pool index of every primitive's triangle record (the shade records and the normals table are laid out by it)
-  if (!want_host) {
-    // the triangles go up once (36 B each); the tree is built and stays in HBM (bvh_gpu.hip)
-    DevBuf<float> d_abc;
-    char msg[256] = {0};
-    rc = d_abc.upload(abc);
-    int brc = rc ? (rc == PHX_ERR_OOM ? (int)BVH_GPU_RECOVERABLE : 1) : 0;
-    if (rc) std::snprintf(msg, sizeof(msg), "%s", g_error.c_str());
-#if PHX_TEST_HOOKS
-    // test hook, compiled into the twin library libphx_hip_hooks.so only (tests/test_gpu_parity.py): makes the device build report a
-    // recoverable or a fatal failure
-    if (const char* how = std::getenv("PHX_TEST_FAIL_DEVICE_BUILD")) {
-      brc = std::strcmp(how, "fatal") == 0 ? 1 : (int)BVH_GPU_RECOVERABLE;
-      std::snprintf(msg, sizeof(msg), "forced %s failure (PHX_TEST_FAIL_DEVICE_BUILD)", brc == 1 ? "fatal" : "recoverable");
-    }
-#endif
-    if (!brc && d_elem_of_prim.alloc(ntri)) brc = (int)BVH_GPU_RECOVERABLE, std::snprintf(msg, sizeof(msg), "%s", g_error.c_str());
-    if (!brc) brc = build_bvh8_gpu(d->stream, d_abc.p, d->d_prim_material.p, ntri, &g, msg, sizeof(msg), d_elem_of_prim.p);
-    if (brc) {
-      // An explicit DEVICE_LBVH request fails loudly, and so does AUTO when the device builder reports anything but a RECOVERABLE cause
-      // (a HIP error from a launch or a sync, lost triangles: bugs that a silent 0.6-7 s host build would hide).  Under AUTO a device
-      // build that cannot get its scratch memory, or meets a tree deeper than its tables, falls back to the host's binned-SAH builder
-      // — which handled every scene before the device builder became the default — and says so: on stderr, in phx_last_error of this
-      // thread (a successful call leaves the text in place) and in phx_stats::bvh_built_on_device.
-      if (builder != PHX_BVH_AUTO || brc != (int)BVH_GPU_RECOVERABLE) return fail(rc ? rc : PHX_ERR_DEVICE, std::string("device BVH build: ") + msg);
-      (void)hipGetLastError();  // a failed hipMalloc leaves its error behind
-      g_error = std::string("device BVH build fell back to the host builder: ") + msg;
-      std::fprintf(stderr, "libphx_hip: %s\n", g_error.c_str());
-      want_host = true;
-    }
-  }
-  uint32_t bvh_depth = 0; size_t bvh_node_count = 0, bvh_elems = 0;
-  SceneGrid bvh_grid{};
-  if (want_host) {
-    Bvh8 bvh;
-    const int threads = (int)std::max(1u, std::thread::hardware_concurrency());
-    build_bvh8(abc.data(), ntri, bvh, threads, prim_material.data());
-    if ((rc = d->d_pool.upload(bvh.pool))) return rc;
-    if ((rc = d_elem_of_prim.upload(bvh.elem_of_prim))) return rc;
-    bvh_depth = bvh.depth; bvh_node_count = bvh.num_nodes; bvh_elems = bvh.pool.size(); bvh_grid = bvh.grid;
-    d->bvh_cost_model = bvh.cost; d->bvh_built_on_device = 0;
-  } else {
-    d->d_pool.adopt(g.pool, g.num_elems);
-    bvh_depth = g.depth; bvh_node_count = g.num_nodes; bvh_elems = g.num_elems; bvh_grid = g.grid;
-    d->bvh_cost_model = g.cost; d->bvh_built_on_device = 1;
-  }
-  const auto t_bvh1 = std::chrono::steady_clock::now();
-  // k_trace / k_trace_rays keep one pending sibling group per level and lane in LDS (bvh8.h: PHX_MAX_BVH_DEPTH)
-  if (bvh_depth > PHX_MAX_BVH_DEPTH)
-    return fail(PHX_ERR_ARG, "tree too deep: " + std::to_string(bvh_depth) + " levels, the traversal stack in LDS holds " + std::to_string(PHX_MAX_BVH_DEPTH));
-  if ((rc = d->d_materials.upload(mats))) return rc;
-  if (lights_by_area) {  // the CDF rides behind the light table (kernels.hip: light_cdf): one float per light triangle, in records of the table's size
-    const size_t nl = lights.size();
-    lights.resize(nl + (light_cdf.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
-    std::memcpy(static_cast<void*>(lights.data() + nl), light_cdf.data(), light_cdf.size() * sizeof(float));
-    rc = d->d_lights.upload(lights);
-    lights.resize(nl);
-    if (rc) return rc;
-  } else if ((rc = d->d_lights.upload(lights))) return rc;
-  if ((rc = d->d_light_tris.upload(light_tris))) return rc;
-  // what shading reads of a hit triangle, 16 bytes per POOL ELEMENT: geometric normal + material word
-  if ((rc = d->d_elem_shade.alloc(bvh_elems))) return rc;
-  launch_build_shade_recs(d->stream, reinterpret_cast<const TriRec*>(d->d_pool.p), d_elem_of_prim.p, d->d_elem_shade.p, ntri);
-  HIPCHK(hipGetLastError());
-  if (any_smooth) {
-    // vertex normals by POOL ELEMENT (the index a hit record carries), so that the shade kernels request them with the triangle record and not
-    // after it; the smooth light triangles' `prim` becomes a pool index too (shading_normal on the light's face, spt.hpp:212-255)
-    DevBuf<float> d_prim_normals;
-    if ((rc = d_prim_normals.upload(prim_normals))) return rc;
-    if ((rc = d->d_elem_normals.alloc(9 * bvh_elems))) return rc;
-    launch_permute_normals(d->stream, d_prim_normals.p, d_elem_of_prim.p, d->d_elem_normals.p, ntri);
-    launch_remap_light_tris(d->stream, d->d_light_tris.p, (uint32_t)light_tris.size(), d_elem_of_prim.p);
-    HIPCHK(hipGetLastError());
-  } else {
-    d->d_elem_normals.release();
-  }
-  if (any_tex || env_tex) {
-    // corner UVs by POOL ELEMENT, like the normals (textured lobes only); every texture's texels as float4 (one 16-byte load per texel)
-    // behind a small table
-    DevBuf<float2> d_prim_uv;
-    if (any_tex) {
-      if ((rc = d_prim_uv.upload(prim_uv))) return rc;
-      if ((rc = d->d_elem_uv.alloc(3 * bvh_elems))) return rc;
-      launch_permute_uvs(d->stream, d_prim_uv.p, d_elem_of_prim.p, d->d_elem_uv.p, ntri);
-      HIPCHK(hipGetLastError());
-    } else {
-      d->d_elem_uv.release(); d->d_lobe_tex.release();
-    }
-    std::vector<DevTexture> tabs(s->num_textures);
-    std::vector<float4> texels((size_t)total_texels);
-    uint32_t off = 0;
-    for (uint32_t t = 0; t < s->num_textures; ++t) {
-      const phx_texture& T = s->textures[t];
-      const uint32_t nt = T.width * T.height;
-      tabs[t] = DevTexture{off, T.width, T.height, T.filter | (T.swrap << 8) | (T.twrap << 16)};
-      for (uint32_t k = 0; k < nt; ++k) texels[off + k] = make_float4(T.texels[3 * (size_t)k], T.texels[3 * (size_t)k + 1], T.texels[3 * (size_t)k + 2], 0.0f);
-      off += nt;
-    }
-    if ((rc = d->d_textures.upload(tabs)) || (rc = d->d_texels.upload(texels)) || (any_tex && (rc = d->d_lobe_tex.upload(lobe_tex)))) return rc;
-    const uint32_t env_mapping = env_tex ? s->materials[s->environment_material].emission_mapping : 0u;
-    const std::vector<DevTexScene> ts{DevTexScene{any_tex ? d->d_elem_uv.p : nullptr, d->d_textures.p, d->d_texels.p, any_tex ? d->d_lobe_tex.p : nullptr,
-                                                  env_tex ? env_tex - 1u : 0u, env_mapping}};
-    if ((rc = d->d_tex_scene.upload(ts))) return rc;
-    HIPCHK(hipStreamSynchronize(d->stream));  // d_prim_uv goes out of scope
-  } else {
-    d->d_elem_uv.release(); d->d_textures.release(); d->d_texels.release(); d->d_lobe_tex.release(); d->d_tex_scene.release();
-  }
-  HIPCHK(hipStreamSynchronize(d->stream));  // d_elem_of_prim (and the normals in primitive order) go out of scope below
-
-  DevScene& sc = d->scene;
-  sc.pool = reinterpret_cast<const uint32_t*>(d->d_pool.p);
-  sc.tris = reinterpret_cast<const TriRec*>(d->d_pool.p);
-  sc.grid = bvh_grid;
-  sc.elem_normals = any_smooth ? d->d_elem_normals.p : nullptr;
-  sc.elem_shade = d->d_elem_shade.p;
-  sc.materials = d->d_materials.p;
-  sc.lights = d->d_lights.p; sc.light_tris = d->d_light_tris.p; sc.num_lights = (uint32_t)lights.size();
-  sc.env_material = s->environment_material;
-  std::memcpy(sc.cam_m, s->camera.to_world, sizeof(sc.cam_m));
-  sc.zoom = 1.12f * std::tan(s->camera.fov * 0.5f);  // camera.hpp:113
-  sc.stepx = 1.0f / (float)s->camera.film_width; sc.stepy = 1.0f / (float)s->camera.film_height;
-  sc.ratio = (float)s->camera.film_width / (float)s->camera.film_height;
-  sc.width = s->camera.film_width; sc.height = s->camera.film_height;
-  sc.aperture_radius = s->camera.aperture_radius; sc.focal_distance = s->camera.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
-  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u) | (lights_by_area ? SC_LIGHTS_BY_AREA : 0u);
-  sc.tex = (sc.any_tex & SC_TEX_ANY) ? d->d_tex_scene.p : nullptr;
-  sc.max_depth = d->opt.path_depth;
-  sc.stack_levels = bvh_depth;
-  sc.num_elems = (uint32_t)bvh_elems;
-  {
-    hipDeviceProp_t prop; HIPCHK(hipGetDeviceProperties(&prop, d->hip_device));
-    sc.num_cus = (uint32_t)prop.multiProcessorCount;
-  }
-  sc.diffuse_only = sc.any_tex ? 0 : 1;  // textured lobes and environment maps are shaded by k_shade_g<.., TEX, ENV> only, and so is the pick by area
-  for (auto& m : mats) { if (m.per_hit) sc.diffuse_only = 0; for (uint32_t k = 0; k < m.num_lobes; ++k) if (m.lobes[k].type != L_DIFFUSE) sc.diffuse_only = 0; }
-  sc.mat_lite = nullptr;
-  sc.any_per_hit = 0;
-  for (auto& m : mats) if (m.per_hit) sc.any_per_hit = 1;
-  if (sc.diffuse_only) {  // at most one Lambert lobe everywhere (the soups, the Cornell box): a 32-byte material table for k_shade<2>
-    bool single = true;
-    for (auto& m : mats) single = single && m.num_lobes <= 1;
-    if (single) {
-      std::vector<DevMatLite> lite(mats.size());
-      for (size_t i = 0; i < mats.size(); ++i) {
-        const DevMaterial& m = mats[i];
-        lite[i] = DevMatLite{m.lobes[0].wx, m.lobes[0].wy, m.lobes[0].wz, m.num_lobes | (m.lobes[0].flags << 8), m.ex, m.ey, m.ez, 0u};
-        if (m.num_lobes == 0) { lite[i].wx = lite[i].wy = lite[i].wz = 0.0f; lite[i].lobes_flags = 0; }
-      }
-      if ((rc = d->d_mat_lite.upload(lite))) return rc;
-      sc.mat_lite = d->d_mat_lite.p;
-      sc.diffuse_only = 2;
-    }
-  }
-  d->num_materials = s->num_materials;
-  d->mat_masked.assign(s->num_materials, 0);
-  for (uint32_t i = 0; i < s->num_materials; ++i)
-    for (uint32_t k = 0; k < mats[i].num_lobes; ++k) if (mats[i].lobes[k].fac_mode >= PHX_FAC_TEX_B) d->mat_masked[i] = 1;
-  d->num_textures = (sc.any_tex & SC_TEX_ANY) ? s->num_textures : 0;
-  d->env_tex = env_tex;
-  d->env_mapping = env_tex ? s->materials[s->environment_material].emission_mapping : 0u;
-  for (int c = 0; c < 3; ++c) d->env_e[c] = env_tex ? s->materials[s->environment_material].emission[c] : 0.0f;
-  d->bvh_nodes = bvh_node_count;
-  d->bvh_bytes = bvh_elems * sizeof(PoolElem);
-  d->bvh_build_ms = std::chrono::duration<double, std::milli>(t_bvh1 - t_bvh0).count();
-  d->preprocess_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_pre0).count();
-  d->num_triangles = prim_material.size();
-  sc.stack_spill = nullptr; sc.spill_stride = 0;
-  d->plan = trace_plan(sc);
-  if (d->plan.spill_threads) {  // stack levels below the ones k_trace keeps in LDS (kernels.hip: trace_plan)
-    if ((rc = d->d_spill.alloc((size_t)d->plan.spill_threads * (d->plan.levels - d->plan.lds_levels)))) return rc;
-    sc.stack_spill = d->d_spill.p; sc.spill_stride = d->plan.spill_threads;
-  }
-  d->budget_bytes = 0;  // the next frame asks the device again how much memory is free
-  d->preprocessed = true;
-  return PHX_OK;
+int phx_dev_preprocess(phx_device* d, const phx_scene* s) {
+  return guarded([&]() -> int {
+    if (!d || !s) return fail(PHX_ERR_ARG, "preprocess: null argument");
+    if (d->running) return fail(PHX_ERR_STATE, "preprocess while a frame is running");
+    const auto t0 = Clock::now();
+    FlatScene fs; std::string why;
+    if (const int rc = flatten_scene(*s, d->opt, fs, why)) return fail(rc, why);
+    if (d->opt.bvh_builder > PHX_BVH_HOST_SAH) return fail(PHX_ERR_ARG, "unknown bvh_builder");
+    DeviceScope on(d->hip_device);
+    if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+    if (const int rc = commit_scene(d, fs)) return rc;
+    d->preprocess_ms = ms_between(t0, Clock::now());
+    return PHX_OK;
+  });
 }
 
 int phx_dev_start(phx_device* d, const phx_frame* f) {
@@ -666,7 +458,7 @@ int phx_dev_start(phx_device* d, const phx_frame* f) {
     static const int timing_env = [] { const char* v = std::getenv("PHX_KERNEL_TIMING"); return v ? std::atoi(v) : -1; }();
     d->kernel_timing = timing_env >= 0 ? timing_env != 0 : true;
   }
-  d->t_start = std::chrono::steady_clock::now();
+  d->t_start = Clock::now();
   const int rc = guarded([&]() {
     if (!d->driver.joinable()) d->driver = std::thread([d]() { d->driver_loop(); });  // the first frame of this device starts its driver
     return (int)PHX_OK;
@@ -752,165 +544,145 @@ void phx_tiles_reset(phx_tiles* q) { if (q) q->cursor = 0; }
 void phx_tiles_free(phx_tiles* q) { delete q; }
 
 // ---- stage-level entry points ----------------------------------------------------------------------------
-static int dev_trace_impl(phx_device* d, uint32_t n, const float* o, const float* dir, const float* tmax, int shadow,
-                  float* t, float* u, float* v, uint32_t* prim, uint8_t* hit);
+}  // extern "C"
+
+namespace {
+
+// Device copies of a stage hook's arrays.  in() uploads, out() allocates and remembers where the result goes, run() launches, waits and copies
+// back.  The first array enters the hook's device (after the hook's own argument checks, as ever), and the caller's device comes back when the
+// hook returns.  The first failure sticks (rc), and run() returns it without launching.
+struct Staging {
+  phx_device* d; int rc = PHX_OK;
+  std::optional<DeviceScope> on;
+  std::deque<DevBuf<uint32_t>> bufs;
+  struct Back { void* host; const void* dev; size_t bytes; };
+  std::vector<Back> back;
+  template <typename T> T* out(T* host, size_t n) {  // host == nullptr: nothing to copy back
+    static_assert(sizeof(T) % 4 == 0, "arrays of 32-bit words");
+    if (!rc && !on && !on.emplace(d->hip_device).ok) rc = fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+    if (rc) return nullptr;
+    bufs.emplace_back();
+    if ((rc = bufs.back().alloc(n * (sizeof(T) / 4)))) return nullptr;
+    if (host) back.push_back({host, bufs.back().p, n * sizeof(T)});
+    return reinterpret_cast<T*>(bufs.back().p);
+  }
+  template <typename T> const T* in(const T* src, size_t n) {
+    T* p = out<T>(nullptr, n);
+    const hipError_t e = p ? hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) rc = fail(PHX_ERR_DEVICE, std::string("hipMemcpy(dst.p, src, n * sizeof(float), hipMemcpyHostToDevice): ") + hipGetErrorString(e));  // (the text these hooks have always given)
+    return p;
+  }
+  template <typename F> int run(F&& launch) {
+    if (rc) return rc;
+    launch();
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(d->stream));
+    for (const Back& b : back) HIPCHK(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+    return PHX_OK;
+  }
+};
+
+// A stage hook: no exception leaves it, and it needs a preprocessed scene.  `body` does the hook's own argument checks, stages its arrays and runs its launch.
+template <typename F>
+int stage_hook(phx_device* d, const char* name, F&& body) {
+  return guarded([&]() -> int {
+    if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, std::string(name) + " before preprocess");
+    Staging s{d};
+    return body(s);
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
 int phx_dev_trace(phx_device* d, uint32_t n, const float* o, const float* dir, const float* tmax, int shadow,
-                  float* t, float* u, float* v, uint32_t* prim, uint8_t* hit) { return guarded([&]() { return dev_trace_impl(d, n, o, dir, tmax, shadow, t, u, v, prim, hit); }); }
-static int dev_trace_impl(phx_device* d, uint32_t n, const float* o, const float* dir, const float* tmax, int shadow,
                   float* t, float* u, float* v, uint32_t* prim, uint8_t* hit) {
-  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "trace before preprocess");
-  if (n == 0) return PHX_OK;
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  std::vector<float4> ro(n), rd(n), hh(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    ro[i] = make_float4(o[3 * i], o[3 * i + 1], o[3 * i + 2], 0.0f);
-    rd[i] = make_float4(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2], tmax[i]);
-  }
-  DevBuf<float4> a, b, c; int rc;
-  if ((rc = a.upload(ro)) || (rc = b.upload(rd)) || (rc = c.alloc(n))) return rc;
-  launch_trace_rays(d->stream, d->scene, n, a.p, b.p, c.p, shadow);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  HIPCHK(hipMemcpy(hh.data(), c.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < n; ++i) {
-    uint32_t tri; std::memcpy(&tri, &hh[i].w, 4);
-    if (t) t[i] = hh[i].x;
-    if (u) u[i] = hh[i].y;
-    if (v) v[i] = hh[i].z;
-    if (prim) prim[i] = tri;  // k_trace_rays stores the primitive id (scene_t::triangles() order), 0xffffffff on a miss
-    if (hit) hit[i] = tri != 0xffffffffu;
-  }
-  return PHX_OK;
+  return stage_hook(d, "trace", [&](Staging& s) -> int {
+    if (n == 0) return PHX_OK;
+    std::vector<float4> ro(n), rd(n), hh(n);
+    for (uint32_t i = 0; i < n; ++i) { ro[i] = make_float4(o[3 * i], o[3 * i + 1], o[3 * i + 2], 0.0f); rd[i] = make_float4(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2], tmax[i]); }
+    const float4 *a = s.in(ro.data(), n), *b = s.in(rd.data(), n); float4* c = s.out(hh.data(), n);
+    if (const int rc = s.run([&] { launch_trace_rays(d->stream, d->scene, n, a, b, c, shadow); })) return rc;
+    for (uint32_t i = 0; i < n; ++i) {  // k_trace_rays stores the primitive id (scene_t::triangles() order) in w, 0xffffffff on a miss
+      const uint32_t tri = bits_of(hh[i].w);
+      if (t) t[i] = hh[i].x;
+      if (u) u[i] = hh[i].y;
+      if (v) v[i] = hh[i].z;
+      if (prim) prim[i] = tri;
+      if (hit) hit[i] = tri != 0xffffffffu;
+    }
+    return PHX_OK;
+  });
 }
 
-static int kat_upload(const float* src, size_t n, DevBuf<float>& dst) {
-  int rc = dst.alloc(n); if (rc) return rc;
-  HIPCHK(hipMemcpy(dst.p, src, n * sizeof(float), hipMemcpyHostToDevice));
-  return PHX_OK;
+int phx_dev_bsdf_f(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3) {
+  return stage_hook(d, "bsdf_f", [&](Staging& s) -> int {
+    if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
+    if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_f: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
+    if (n == 0) return PHX_OK;
+    const size_t n3s = 3 * (size_t)n;
+    const float *a = s.in(n3, n3s), *b = s.in(wi3, n3s), *c = s.in(wo3, n3s); float* f = s.out(f3, n3s);
+    return s.run([&] { launch_bsdf_f(d->stream, d->d_materials.p + material, n, a, b, c, f); });
+  });
 }
 
-static int dev_bsdf_f_impl(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3);
-int phx_dev_bsdf_f(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3) { return guarded([&]() { return dev_bsdf_f_impl(d, material, n, n3, wi3, wo3, f3); }); }
-static int dev_bsdf_f_impl(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3) {
-  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "bsdf_f before preprocess");
-  if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
-  if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_f: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
-  if (n == 0) return PHX_OK;
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  DevBuf<float> a, b, c, o; int rc;
-  if ((rc = kat_upload(n3, 3 * (size_t)n, a)) || (rc = kat_upload(wi3, 3 * (size_t)n, b)) || (rc = kat_upload(wo3, 3 * (size_t)n, c)) || (rc = o.alloc(3 * (size_t)n))) return rc;
-  launch_bsdf_f(d->stream, d->d_materials.p + material, n, a.p, b.p, c.p, o.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  HIPCHK(hipMemcpy(f3, o.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  return PHX_OK;
-}
-
-static int dev_bsdf_sample_impl(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* u2,
-                        float* wo3, float* f3, float* pdf, uint32_t* flags);
 int phx_dev_bsdf_sample(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* u2,
-                        float* wo3, float* f3, float* pdf, uint32_t* flags) { return guarded([&]() { return dev_bsdf_sample_impl(d, material, n, n3, wi3, u2, wo3, f3, pdf, flags); }); }
-static int dev_bsdf_sample_impl(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags) {
-  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "bsdf_sample before preprocess");
-  if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
-  if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_sample: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
-  if (n == 0) return PHX_OK;
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  DevBuf<float> a, b, c, wo, f, p; DevBuf<uint32_t> fl; int rc;
-  if ((rc = kat_upload(n3, 3 * (size_t)n, a)) || (rc = kat_upload(wi3, 3 * (size_t)n, b)) || (rc = kat_upload(u2, 2 * (size_t)n, c)) ||
-      (rc = wo.alloc(3 * (size_t)n)) || (rc = f.alloc(3 * (size_t)n)) || (rc = p.alloc(n)) || (rc = fl.alloc(n))) return rc;
-  launch_bsdf_sample(d->stream, d->d_materials.p + material, n, a.p, b.p, c.p, wo.p, f.p, p.p, fl.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  HIPCHK(hipMemcpy(wo3, wo.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(f3, f.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(pdf, p.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(flags, fl.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return PHX_OK;
+  return stage_hook(d, "bsdf_sample", [&](Staging& s) -> int {
+    if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
+    if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_sample: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
+    if (n == 0) return PHX_OK;
+    const size_t n3s = 3 * (size_t)n;
+    const float *a = s.in(n3, n3s), *b = s.in(wi3, n3s), *c = s.in(u2, 2 * (size_t)n);
+    float *wo = s.out(wo3, n3s), *f = s.out(f3, n3s), *p = s.out(pdf, n); uint32_t* fl = s.out(flags, n);
+    return s.run([&] { launch_bsdf_sample(d->stream, d->d_materials.p + material, n, a, b, c, wo, f, p, fl); });
+  });
 }
 
-static int dev_texture_lookup_impl(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) {
-  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "texture_lookup before preprocess");
-  if (texture >= d->num_textures) return fail(PHX_ERR_ARG, "texture out of range (textures are kept only for scenes with a textured lobe)");
-  if (n == 0) return PHX_OK;
-  if (!st || !rgb) return fail(PHX_ERR_ARG, "texture_lookup: null argument");
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  DevBuf<float> a, o; int rc;
-  if ((rc = kat_upload(st, 2 * (size_t)n, a)) || (rc = o.alloc(3 * (size_t)n))) return rc;
-  launch_texture_lookup(d->stream, d->d_textures.p, d->d_texels.p, texture, n, a.p, o.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  HIPCHK(hipMemcpy(rgb, o.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  return PHX_OK;
+int phx_dev_texture_lookup(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) {
+  return stage_hook(d, "texture_lookup", [&](Staging& s) -> int {
+    if (texture >= d->num_textures) return fail(PHX_ERR_ARG, "texture out of range (textures are kept only for scenes with a textured lobe)");
+    if (n == 0) return PHX_OK;
+    if (!st || !rgb) return fail(PHX_ERR_ARG, "texture_lookup: null argument");
+    const float* a = s.in(st, 2 * (size_t)n); float* o = s.out(rgb, 3 * (size_t)n);
+    return s.run([&] { launch_texture_lookup(d->stream, d->d_textures.p, d->d_texels.p, texture, n, a, o); });
+  });
 }
-int phx_dev_texture_lookup(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) { return guarded([&]() { return dev_texture_lookup_impl(d, texture, n, st, rgb); }); }
 
-static int dev_lobe_weights_impl(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
-  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "lobe_weights before preprocess");
-  if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
-  if (n == 0) return PHX_OK;
-  const bool tex = (d->scene.any_tex & SC_TEX_LOBES) != 0;  // the scene's lobes read images: st is needed
-  if (!n3 || !wi3 || !w || !kept || (tex && !st)) return fail(PHX_ERR_ARG, "lobe_weights: null argument");
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  DevBuf<float> a, b, c, o; DevBuf<uint32_t> k; int rc;
-  if ((rc = kat_upload(n3, 3 * (size_t)n, a)) || (rc = kat_upload(wi3, 3 * (size_t)n, b)) || (tex && (rc = kat_upload(st, 2 * (size_t)n, c))) ||
-      (rc = o.alloc(3 * PHX_MAX_LOBES * (size_t)n)) || (rc = k.alloc((size_t)n))) return rc;
-  launch_lobe_weights(d->stream, d->d_materials.p + material, tex ? d->d_textures.p : nullptr, d->d_texels.p, tex ? d->d_lobe_tex.p + 8 * (size_t)material : nullptr,
-                      n, a.p, b.p, c.p, o.p, k.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  HIPCHK(hipMemcpy(w, o.p, 3 * PHX_MAX_LOBES * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(kept, k.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return PHX_OK;
-}
 int phx_dev_lobe_weights(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
-  return guarded([&]() { return dev_lobe_weights_impl(d, material, n, n3, wi3, st, w, kept); });
+  return stage_hook(d, "lobe_weights", [&](Staging& s) -> int {
+    if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
+    if (n == 0) return PHX_OK;
+    const bool tex = (d->scene.any_tex & SC_TEX_LOBES) != 0;  // the scene's lobes read images: st is needed
+    if (!n3 || !wi3 || !w || !kept || (tex && !st)) return fail(PHX_ERR_ARG, "lobe_weights: null argument");
+    const float *a = s.in(n3, 3 * (size_t)n), *b = s.in(wi3, 3 * (size_t)n), *c = tex ? s.in(st, 2 * (size_t)n) : nullptr;
+    float* o = s.out(w, 3 * PHX_MAX_LOBES * (size_t)n); uint32_t* k = s.out(kept, n);
+    return s.run([&] {
+      launch_lobe_weights(d->stream, d->d_materials.p + material, tex ? d->d_textures.p : nullptr, d->d_texels.p, tex ? d->d_lobe_tex.p + 8 * (size_t)material : nullptr,
+                          n, a, b, c, o, k);
+    });
+  });
 }
 
-static int dev_environment_lookup_impl(phx_device* d, uint32_t n, const float* dirs, float* rgb) {
-  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "environment_lookup before preprocess");
-  if (!d->env_tex) return fail(PHX_ERR_ARG, "environment_lookup: the scene's environment has no image");
-  if (n == 0) return PHX_OK;
-  if (!dirs || !rgb) return fail(PHX_ERR_ARG, "environment_lookup: null argument");
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  DevBuf<float> a, o; int rc;
-  if ((rc = kat_upload(dirs, 3 * (size_t)n, a)) || (rc = o.alloc(3 * (size_t)n))) return rc;
-  launch_environment_lookup(d->stream, d->d_textures.p, d->d_texels.p, d->env_tex - 1u, d->env_mapping, d->env_e[0], d->env_e[1], d->env_e[2], n, a.p, o.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  HIPCHK(hipMemcpy(rgb, o.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  return PHX_OK;
+int phx_dev_environment_lookup(phx_device* d, uint32_t n, const float* dirs, float* rgb) {
+  return stage_hook(d, "environment_lookup", [&](Staging& s) -> int {
+    if (!d->env_tex) return fail(PHX_ERR_ARG, "environment_lookup: the scene's environment has no image");
+    if (n == 0) return PHX_OK;
+    if (!dirs || !rgb) return fail(PHX_ERR_ARG, "environment_lookup: null argument");
+    const float* a = s.in(dirs, 3 * (size_t)n); float* o = s.out(rgb, 3 * (size_t)n);
+    return s.run([&] { launch_environment_lookup(d->stream, d->d_textures.p, d->d_texels.p, d->env_tex - 1u, d->env_mapping, d->env_e[0], d->env_e[1], d->env_e[2], n, a, o); });
+  });
 }
-int phx_dev_environment_lookup(phx_device* d, uint32_t n, const float* dirs, float* rgb) { return guarded([&]() { return dev_environment_lookup_impl(d, n, dirs, rgb); }); }
 
-static int dev_light_sample_impl(phx_device* d, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf) {
-  if (!d || !d->preprocessed) return fail(PHX_ERR_STATE, "light_sample before preprocess");
-  if (n == 0) return PHX_OK;
-  if (!u3 || !light || !tri || !bary || !P || !pdf) return fail(PHX_ERR_ARG, "light_sample: null argument");
-  DeviceScope on(d->hip_device);
-  if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
-  DevBuf<float> a, ob, oP, op; DevBuf<uint32_t> ol, ot; int rc;
-  if ((rc = kat_upload(u3, 3 * (size_t)n, a)) || (rc = ol.alloc(n)) || (rc = ot.alloc(n)) || (rc = ob.alloc(2 * (size_t)n)) || (rc = oP.alloc(3 * (size_t)n)) ||
-      (rc = op.alloc(n))) return rc;
-  launch_light_sample(d->stream, d->scene, n, a.p, ol.p, ot.p, ob.p, oP.p, op.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  HIPCHK(hipMemcpy(light, ol.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(tri, ot.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(bary, ob.p, 2 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(P, oP.p, 3 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(pdf, op.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  return PHX_OK;
-}
 int phx_dev_light_sample(phx_device* d, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf) {
-  return guarded([&]() { return dev_light_sample_impl(d, n, u3, light, tri, bary, P, pdf); });
+  return stage_hook(d, "light_sample", [&](Staging& s) -> int {
+    if (n == 0) return PHX_OK;
+    if (!u3 || !light || !tri || !bary || !P || !pdf) return fail(PHX_ERR_ARG, "light_sample: null argument");
+    const float* a = s.in(u3, 3 * (size_t)n);
+    uint32_t *ol = s.out(light, n), *ot = s.out(tri, n); float *ob = s.out(bary, 2 * (size_t)n), *oP = s.out(P, 3 * (size_t)n), *op = s.out(pdf, n);
+    return s.run([&] { launch_light_sample(d->stream, d->scene, n, a, ol, ot, ob, oP, op); });
+  });
 }
 
 int phx_dev_copy_bvh(phx_device* d, void* out, uint64_t capacity, uint64_t* bytes, float* grid6) {
@@ -928,6 +700,23 @@ int phx_dev_copy_bvh(phx_device* d, void* out, uint64_t capacity, uint64_t* byte
 }  // extern "C"
 
 // ---- the frame driver ------------------------------------------------------------------------------------
+namespace {
+
+void copy_stats(const DevStats& ds, phx_stats& stats) {  // what the kernels counted, into the frame's phx_stats
+  stats.camera_samples = ds.camera_samples; stats.rays_closest = ds.rays_closest; stats.rays_shadow = ds.rays_shadow;
+  stats.rays_masked = ds.rays_closest - ds.rays_shadow;  // every shaded slot is a shadow ray or a masked slot (spt.hpp:138-141)
+  for (int k = 0; k < 2; ++k) { stats.node_visits_lds[k] = ds.node_visits_lds[k]; stats.node_visits_mem[k] = ds.node_visits_mem[k]; stats.tri_tests[k] = ds.tri_tests[k]; }
+  stats.instrumented = launch_counts_traversal_work() ? 1 : 0;
+  stats.wave_iters = ds.wave_iters; stats.node_block_execs = ds.node_block_execs; stats.tri_block_execs = ds.tri_block_execs; stats.refills = ds.refills;
+  stats.idle_lane_iters = ds.idle_lane_iters; stats.tri_pending_lane_iters = ds.tri_pending_lane_iters;
+  for (int k = 0; k < 8; ++k) { stats.stack_pushes[k] = ds.stack_pushes[k]; stats.tri_pairs_hist[k] = ds.tri_pairs_hist[k]; }
+  stats.tri_pairs_pending = ds.tri_pairs_pending;
+  stats.primary_packets = ds.primary_packets; stats.primary_fallbacks = ds.primary_fallbacks; stats.primary_node_tests = ds.primary_node_tests;
+  stats.primary_tri_tests = ds.primary_tri_tests; stats.primary_tri_lanes_hit = ds.primary_tri_lanes_hit;
+}
+
+}  // namespace
+
 void phx_device::driver_loop() {
   (void)hipSetDevice(hip_device);
   for (;;) {
@@ -950,7 +739,7 @@ void phx_device::driver_loop() {
 
 int phx_device::run_frame() {
   HIPCHK(hipSetDevice(hip_device));
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = Clock::now();
   std::memset(&stats, 0, sizeof(stats));
   int rc;
   if ((rc = dstats.alloc(1)) || (rc = counters.alloc(CNT_WORDS))) return rc;
@@ -986,7 +775,7 @@ int phx_device::run_frame() {
   // pixel keeps the 64 lanes of a wave — and the 256 rays of a camera-ray packet — on ONE pixel.  (Round 3 took 8 M pixels whatever the spp:
   // the 3840x2160, 256-spp frame of BASELINE config 4 went through as 8 passes of 32 samples; as 8 batches of 256 samples it is 6.8 %
   // faster — camera rays 67.9 -> 36.0 ms, k_trace -4 %: profiles/r04_v_batch_probe.log.)
-  const size_t path_bytes = 176u + (frame.normals_channel ? 16u : 0u);
+  const size_t path_bytes = PathQueues::bytes_per_path(frame.normals_channel != 0);
   // (divided by the samples a pass will really carry: with an explicit samples_in_flight only P x S paths are ever in flight)
   const uint32_t pass_samples = std::max(1u, std::min(opt.samples_per_pixel, opt.samples_in_flight ? opt.samples_in_flight : opt.samples_per_pixel));
   const uint64_t pixel_cap = std::min<uint64_t>(8u << 20, std::max<uint64_t>(path_budget(path_bytes) / pass_samples, 64u << 10));
@@ -1009,56 +798,42 @@ int phx_device::run_frame() {
     {
       // the batch's tiles in Morton order of their film position: path ids are pixel-major, so the batch's queue — and with it each
       // XCD's eighth of it (k_trace's segments) — covers a compact block of the film instead of a row of tiles 3840 pixels wide
-      static const bool morton = [] { const char* v = std::getenv("PHX_TILE_MORTON"); return v ? std::atoi(v) != 0 : true; }();
-      if (morton) {
-        auto spread = [](uint32_t v) { v &= 0xffffu; v = (v | (v << 8)) & 0x00ff00ffu; v = (v | (v << 4)) & 0x0f0f0f0fu; v = (v | (v << 2)) & 0x33333333u; v = (v | (v << 1)) & 0x55555555u; return v; };
-        auto key = [&](const phx_tile& t) { return spread(t.x >> 5) | (spread(t.y >> 5) << 1); };
-        std::stable_sort(tiles.begin(), tiles.end(), [&](const phx_tile& a, const phx_tile& b) { return key(a) < key(b); });
-      }
+      // (1 M soup + 2.3 % against queue order, 100 k soup and config 4 unchanged, films bit-identical: profiles/r04_y_morton.log)
+      auto spread = [](uint32_t v) { v &= 0xffffu; v = (v | (v << 8)) & 0x00ff00ffu; v = (v | (v << 4)) & 0x0f0f0f0fu; v = (v | (v << 2)) & 0x33333333u; v = (v | (v << 1)) & 0x55555555u; return v; };
+      auto key = [&](const phx_tile& t) { return spread(t.x >> 5) | (spread(t.y >> 5) << 1); };
+      std::stable_sort(tiles.begin(), tiles.end(), [&](const phx_tile& a, const phx_tile& b) { return key(a) < key(b); });
     }
-    if ((rc = render_batch(tiles, jit))) return rc;
+    if ((rc = render_batch(tiles))) return rc;
     stats.tiles += tiles.size();
   }
-  t_enq = std::chrono::steady_clock::now();
+  t_enq = Clock::now();
   HIPCHK(hipStreamSynchronize(stream));
-  t_sync = std::chrono::steady_clock::now();
+  t_sync = Clock::now();
   DevStats ds;
   HIPCHK(hipMemcpy(&ds, dstats.p, sizeof(ds), hipMemcpyDeviceToHost));
-  stats.camera_samples = ds.camera_samples; stats.rays_closest = ds.rays_closest; stats.rays_shadow = ds.rays_shadow;
-  stats.rays_masked = ds.rays_closest - ds.rays_shadow;  // every shaded slot is a shadow ray or a masked slot (spt.hpp:138-141)
-  for (int k = 0; k < 2; ++k) { stats.node_visits_lds[k] = ds.node_visits_lds[k]; stats.node_visits_mem[k] = ds.node_visits_mem[k]; stats.tri_tests[k] = ds.tri_tests[k]; }
-  stats.instrumented = launch_counts_traversal_work() ? 1 : 0;
-  stats.wave_iters = ds.wave_iters; stats.node_block_execs = ds.node_block_execs; stats.tri_block_execs = ds.tri_block_execs; stats.refills = ds.refills;
-  stats.idle_lane_iters = ds.idle_lane_iters; stats.tri_pending_lane_iters = ds.tri_pending_lane_iters;
-  for (int k = 0; k < 8; ++k) { stats.stack_pushes[k] = ds.stack_pushes[k]; stats.tri_pairs_hist[k] = ds.tri_pairs_hist[k]; }
-  stats.tri_pairs_pending = ds.tri_pairs_pending;
-  stats.primary_packets = ds.primary_packets; stats.primary_fallbacks = ds.primary_fallbacks; stats.primary_node_tests = ds.primary_node_tests;
-  stats.primary_tri_tests = ds.primary_tri_tests; stats.primary_tri_lanes_hit = ds.primary_tri_lanes_hit;
+  copy_stats(ds, stats);
   if (ds.watchdog) return fail(PHX_ERR_DEVICE, "k_trace: " + std::to_string(ds.watchdog) + " wave(s) hit the iteration watchdog: the frame is incomplete");
   if (ds.ring_watchdog) return fail(PHX_ERR_DEVICE, "k_shade_g: " + std::to_string(ds.ring_watchdog) + " wave(s) timed out waiting for a block of the append ring: the frame is incomplete");
   stats.trace_ms = stats.closest_ms + stats.shadow_ms + stats.primary_ms;
-  stats.frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  static const bool host_timing = std::getenv("PHX_HOST_TIMING") != nullptr;
-  if (host_timing) {
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  stats.frame_ms = ms_between(t0, Clock::now());
+  if (host_timing()) {
+    auto ms = ms_between;
     std::fprintf(stderr, "host timing: start->thread %.3f  thread->sync-begin (enqueue etc.) %.3f  sync wait %.3f  stats %.3f | kernels on the GPU %.3f ms | start->done %.3f\n",
-                 ms(t_start, t0), ms(t0, t_enq), ms(t_enq, t_sync), ms(t_sync, std::chrono::steady_clock::now()), stats.trace_ms + stats.shade_ms, ms(t_start, std::chrono::steady_clock::now()));
+                 ms(t_start, t0), ms(t0, t_enq), ms(t_enq, t_sync), ms(t_sync, Clock::now()), stats.trace_ms + stats.shade_ms, ms(t_start, Clock::now()));
   }
   return PHX_OK;
 }
 
-int phx_device::render_batch(const std::vector<phx_tile>& tiles, const std::vector<float2>& jit) {
-  (void)jit;
+int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   int rc;
-  static const bool host_timing = std::getenv("PHX_HOST_TIMING") != nullptr;  // probe: where a batch's host time goes
-  const auto tb0 = std::chrono::steady_clock::now();
+  const auto tb0 = Clock::now();
   auto tb_alloc = tb0, tb_enq = tb0;
   uint32_t P = 0;
   for (auto& t : tiles) P += t.w * t.h;
   const uint32_t spp = opt.samples_per_pixel;
   const uint32_t xs = frame.primary_components + (frame.normals_channel ? 3u : 0u);
-  // bytes of queues + state per path in flight: ray queues 2 x 32, hit 16, shadow queue 48, path state 32 (+ 16 with normals)
-  const size_t path_bytes = 176u + (frame.normals_channel ? 16u : 0u);
+  const bool normals = frame.normals_channel != 0;
+  const size_t path_bytes = PathQueues::bytes_per_path(normals);
   // paths in flight: the device's budget (path_budget: up to 512 M paths).  Deep bounces keep only a few percent of the paths alive, so
   // many paths per pass are what keeps late launches full; a batch that cannot carry all its samples at once splits the spp range
   // into equal passes.
@@ -1075,7 +850,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles, const std::vect
   // The budget is a cached reading of the device's free memory (hipMemGetInfo costs ~0.1 ms).  It is only trusted while the queues this
   // object already holds are large enough: a batch that has to GROW them asks the device again — another device object, torch films or
   // RCCL buffers may have taken memory since the reading was made.
-  if ((size_t)P * S > hit.n && !opt.samples_in_flight) { budget_bytes = 0; S = std::min(pick_samples(), spp); }
+  if ((size_t)P * S > queues.capacity() && !opt.samples_in_flight) { budget_bytes = 0; S = std::min(pick_samples(), spp); }
   if ((size_t)P * S >= 0x7fffffffull) return fail(PHX_ERR_ARG, "too many paths in flight");
 
   // pixel table of the batch; a frame loop presents the same tiles again and again, so the upload is skipped when nothing changed
@@ -1094,33 +869,25 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles, const std::vect
   size_t npaths = 0;
   for (;;) {
     npaths = (size_t)P * S;
-    rc = PHX_OK;
-    for (int q = 0; q < 2 && !rc; ++q) if ((rc = ro[q].alloc(npaths)) || (rc = rd[q].alloc(npaths)) || (rc = qs[q].alloc(npaths))) break;
-    if (!rc) (void)((rc = hit.alloc(npaths)) || (rc = so.alloc(npaths)) || (rc = sd.alloc(npaths)) || (rc = sc.alloc(npaths)) ||
-                    (rc = pr.alloc(npaths)) || (frame.normals_channel && (rc = pn.alloc(npaths))));
-    if (!rc) break;
+    if (!(rc = queues.alloc(npaths, normals))) break;
     if (rc != PHX_ERR_OOM || S == 1) return rc;
     (void)hipGetLastError();
-    for (int q = 0; q < 2; ++q) { ro[q].release(); rd[q].release(); qs[q].release(); }
-    hit.release(); so.release(); sd.release(); sc.release(); pr.release(); pn.release();
+    queues.release();
     budget_bytes = 0;  // the reading was stale: the next path_budget() — of this batch, of the next one, of the next frame — asks the device again
     S = std::min((S + 1) / 2, std::min(pick_samples(), spp));
   }
   paths_in_flight = npaths;
-  tb_alloc = std::chrono::steady_clock::now();
+  tb_alloc = Clock::now();
 
   PassBuffers B{};
-  for (int q = 0; q < 2; ++q) { B.ro[q] = ro[q].p; B.rd[q] = rd[q].p; B.qs[q] = qs[q].p; }
-  B.hit = hit.p; B.so = so.p; B.sd = sd.p; B.sc = sc.p; B.pr = pr.p;
-  B.pn = frame.normals_channel ? pn.p : nullptr;
+  queues.fill(B, normals);
   B.counters = counters.p; B.stats = dstats.p; B.pix_xy = pix_xy.p; B.jitter = jitter.p; B.acc = acc.p;
   B.num_pixels = P; B.xstride = xs; B.normals_offset = frame.normals_channel ? frame.primary_components : 0;
   B.seed = frame.sampler_seed;
 
-  BatchLaunches* G = &direct;
   direct.events_used = 0; direct.timed.clear();
   if ((rc = enqueue_batch(direct, B, P, S, xs))) return rc;
-  tb_enq = std::chrono::steady_clock::now();
+  tb_enq = Clock::now();
   if (frame.add_tile || frame.host_film) {
     const size_t nfl = (size_t)P * xs;
     if (nfl > h_acc_n) {
@@ -1156,19 +923,21 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles, const std::vect
   } else {
     HIPCHK(hipStreamSynchronize(stream));
   }
-  if (host_timing) {
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  if (host_timing()) {
+    auto ms = ms_between;
     std::fprintf(stderr, "batch of %u px x %u samples: tables + allocation %.3f ms, enqueue %.3f, wait + sink %.3f\n", P, S, ms(tb0, tb_alloc), ms(tb_alloc, tb_enq),
-                 ms(tb_enq, std::chrono::steady_clock::now()));
+                 ms(tb_enq, Clock::now()));
   }
   // the batch is complete: its launches' HIP-event times (the next batch records the same events again)
-  for (auto& te : G->timed) {
+  for (auto& te : direct.timed) {
     float ms = 0.0f;
-    HIPCHK(hipEventElapsedTime(&ms, G->events[te.begin], G->events[te.end]));
-    if (te.kind == 0) { stats.closest_ms += ms; stats.trace_launches++; }  // k_trace: closest + shadow rays in one launch
-    else if (te.kind == 4) { stats.primary_ms += ms; stats.primary_launches++; }  // k_trace_primary: the camera rays of a pass
-    else stats.shade_ms += ms;
-    if (te.kind == 3) { stats.shade_kernel_ms += ms; stats.shade_launches++; }
+    HIPCHK(hipEventElapsedTime(&ms, direct.events[te.begin], direct.events[te.end]));
+    switch (te.kind) {
+      case Launch::Trace: stats.closest_ms += ms; stats.trace_launches++; break;      // k_trace: closest + shadow rays in one launch
+      case Launch::Primary: stats.primary_ms += ms; stats.primary_launches++; break;  // k_trace_primary: the camera rays of a pass
+      case Launch::Shade: stats.shade_ms += ms; stats.shade_kernel_ms += ms; stats.shade_launches++; break;
+      case Launch::Pass: stats.shade_ms += ms; break;  // begin-pass and film count as shading time
+    }
   }
   return PHX_OK;
 }
@@ -1184,7 +953,7 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
   // the queue: 42 of them per pass made the gaps between the 21 launches longer than the launches need).  A launch's time then includes
   // the few microseconds since the previous kernel ended.
   long last_end = -1;  // index of the event recorded behind the previous timed launch of this batch
-  auto timed_launch = [&](int kind, auto&& fn) -> int {
+  auto timed_launch = [&](Launch kind, auto&& fn) -> int {
     hipEvent_t e; int r;
     if (!kernel_timing) { fn(); return PHX_OK; }
     if (last_end < 0) { if ((r = next_event(g, &e))) return r; HIPCHK(hipEventRecord(e, stream)); last_end = (long)g.events_used - 1; }
@@ -1217,12 +986,12 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
   }
   auto queue_bound = [&](uint32_t pass, uint32_t step, uint32_t cap) -> uint32_t {  // length of the ray queue k_trace(step) of this pass traced, once it has started
     const volatile uint32_t* w = &h_qlen[(size_t)pass * depth + step];
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     for (uint32_t spins = 0;; ++spins) {
       const uint32_t v = __atomic_load_n(const_cast<const uint32_t*>(w), __ATOMIC_ACQUIRE);
       if (v != 0xffffffffu) return std::min(v, cap);
       // never for ever: a device that has stopped (fault, watchdog) is found by the synchronisation behind the batch — size for the capacity and go on
-      if ((spins & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) return cap;
+      if ((spins & 1023u) == 1023u && Clock::now() - t0 > std::chrono::seconds(2)) return cap;
     }
   };
   uint32_t pass = 0;
@@ -1231,26 +1000,26 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
     const uint32_t cap = P * ns;
     B.num_samples = ns;
     B.qlen_out = nullptr;
-    if ((rc = timed_launch(2, [&]() { launch_begin_pass(stream, B, ns); }))) return rc;
+    if ((rc = timed_launch(Launch::Pass, [&]() { launch_begin_pass(stream, B, ns); }))) return rc;
     int q = 0;
     for (uint32_t bounce = 0; bounce < opt.path_depth; ++bounce) {  // a path takes at most path_depth steps (spt.hpp:314)
       // step `bounce`: closest-hit rays of this step + the shadow rays k_shade produced in the previous step
       const int sq_read = (int)((bounce + 1) & 1), sq_write = (int)(bounce & 1);
       if (bounce == 0) {  // the camera rays: one packet walk per 64 x n of them
-        if ((rc = timed_launch(4, [&]() { launch_trace_primary(stream, scene, B, cap, s0, q, sq_read); }))) return rc;
+        if ((rc = timed_launch(Launch::Primary, [&]() { launch_trace_primary(stream, scene, B, cap, s0, q, sq_read); }))) return rc;
       } else {
         B.qlen_out = grid_by_queue ? h_qlen + (size_t)pass * depth + bounce : nullptr;
-        if ((rc = timed_launch(0, [&]() { launch_trace(stream, scene, B, q, sq_read, 1, 1, cap); }))) return rc;
+        if ((rc = timed_launch(Launch::Trace, [&]() { launch_trace(stream, scene, B, q, sq_read, 1, 1, cap); }))) return rc;
         B.qlen_out = nullptr;
       }
       // step 0: the capacity.  Step 1: the length k_trace(1) — the longest launch of a pass, enqueued just above — publishes as it starts.
       // Later steps: the length published one step earlier (the device then still has two launches queued while the host waits).
       const uint32_t shade_cap = (grid_by_queue && bounce >= 1) ? std::max(queue_bound(pass, bounce == 1 ? 1u : bounce - 1, cap), 1u) : cap;
-      if ((rc = timed_launch(3, [&]() { stats.shade_kernels |= launch_shade(stream, scene, B, q, sq_write, shade_cap, s0, bounce == 0); }))) return rc;
+      if ((rc = timed_launch(Launch::Shade, [&]() { stats.shade_kernels |= launch_shade(stream, scene, B, q, sq_write, shade_cap, s0, bounce == 0); }))) return rc;
       q ^= 1;
     }
-    if ((rc = timed_launch(0, [&]() { launch_trace(stream, scene, B, q, (int)((opt.path_depth - 1) & 1), 0, 1, cap); }))) return rc;
-    if ((rc = timed_launch(2, [&]() { launch_film(stream, B, ns, inv); }))) return rc;
+    if ((rc = timed_launch(Launch::Trace, [&]() { launch_trace(stream, scene, B, q, (int)((opt.path_depth - 1) & 1), 0, 1, cap); }))) return rc;
+    if ((rc = timed_launch(Launch::Pass, [&]() { launch_film(stream, B, ns, inv); }))) return rc;
     HIPCHK(hipGetLastError());
   }
   // film_t<>::add_tile (film.hpp:12-15)

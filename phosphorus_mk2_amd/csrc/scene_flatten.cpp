@@ -1,0 +1,260 @@
+// scene_flatten.cpp — phx_scene -> FlatScene (scene_flatten.h): validation, primitive-order arrays, baked materials and lights.
+// Host code only: no HIP call, no device, no global state.
+#include "scene_flatten.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+
+namespace phx {
+namespace {
+
+// microfacet_t::roughness_to_alpha + precompute (src/bsdf/params.hpp:86-99), with the device's logf_
+float roughness_to_alpha(float roughness) {
+  roughness = std::max(roughness, (float)1e-5);
+  float x = logf_(roughness);
+  return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
+}
+
+// -> false: more than 8 lobes or an unknown closure id (fac_mode, textures and masks were validated by the caller)
+bool bake_material(const phx_material& m, float sheen_L5, DevMaterial& out, uint32_t* lobe_tex /* 8: texture + 1 per baked lobe */) {
+  std::memset(&out, 0, sizeof(out));
+  for (int k = 0; k < PHX_MAX_LOBES; ++k) lobe_tex[k] = 0;
+  out.is_emitter = m.is_emitter; out.ex = m.emission[0]; out.ey = m.emission[1]; out.ez = m.emission[2];
+  out.sheen_L5 = sheen_L5;
+  if (m.num_lobes > PHX_MAX_LOBES) return false;
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < m.num_lobes; ++i) {
+    const phx_lobe& s = m.lobes[i];
+    DevLobe& l = out.lobes[k];
+    l.type = s.type; l.wx = s.weight[0]; l.wy = s.weight[1]; l.wz = s.weight[2];
+    // the device lobe holds the mode byte alone; an image mode has no ior and keeps its mask's texture + 1 in that word's bits
+    const uint32_t mode = PHX_FAC_MODE(s.fac_mode);
+    l.fac_mode = mode; l.fac_ior = mode >= PHX_FAC_TEX_B ? float_of_bits(PHX_FAC_TEXTURE(s.fac_mode)) : s.fac_ior;
+    l.px = s.pre_weight[0]; l.py = s.pre_weight[1]; l.pz = s.pre_weight[2];
+    if (mode != PHX_FAC_NONE) out.per_hit = 1;
+    if (s.texture) { out.tex_lobes |= 1u << k; lobe_tex[k] = s.texture; }
+    switch (s.type) {
+      case PHX_LOBE_DIFFUSE: l.flags = B_REFLECT | B_DIFFUSE; break;
+      case PHX_LOBE_OREN_NAYAR: {  // oren_nayar_t::precompute, params.hpp:36-43
+        l.flags = B_REFLECT | B_DIFFUSE;
+        const float sg = (float)((double)s.alpha * (kPiD / (double)180.0f));
+        const float s2 = sg * sg;
+        l.a = 1.0f - (s2 / (2.0f * (s2 + 0.33f)));
+        l.b = 0.45f * s2 / (s2 + 0.09f);
+        break;
+      }
+      case PHX_LOBE_REFLECTION: l.flags = B_REFLECT | B_SPECULAR; l.eta = s.eta; break;
+      case PHX_LOBE_REFRACTION: l.flags = B_TRANSMIT | B_SPECULAR; l.eta = s.eta; break;
+      case PHX_LOBE_MICROFACET:
+        l.flags = s.refract ? B_TRANSMIT : B_REFLECT;  // src/bsdf.hpp:70-72
+        l.eta = s.eta; l.refract = s.refract;
+        l.xalpha = std::min(1.0f, std::max(0.0001f, roughness_to_alpha(s.xalpha)));
+        l.yalpha = std::min(1.0f, std::max(0.0001f, roughness_to_alpha(s.yalpha)));
+        break;
+      case PHX_LOBE_SHEEN: l.flags = B_REFLECT | B_GLOSSY; l.r = s.r; break;
+      case PHX_LOBE_TRANSPARENT: l.flags = B_TRANSMIT; break;  // src/material.cpp:98-103
+      case PHX_LOBE_EMISSIVE: case PHX_LOBE_BACKGROUND: continue;  // not lobes (material.cpp:240-245)
+      default: return false;
+    }
+    ++k;
+  }
+  out.num_lobes = k;
+  return true;
+}
+
+}  // namespace
+
+int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err) {
+  auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
+  auto material = [](uint32_t i) { return "material " + std::to_string(i); };
+  if (!s.meshes || !s.materials || s.num_materials == 0) return refuse("scene without meshes/materials");
+  // (camera_t's constructor leaves focal_distance uninitialised, entities/camera.hpp:31-36: it means something only behind a lens)
+  if (!(std::fabs(s.camera.aperture_radius) <= FLT_MAX) || (s.camera.aperture_radius != 0.0f && !(std::fabs(s.camera.focal_distance) <= FLT_MAX)))
+    return refuse("camera: aperture radius / focal distance not finite");
+  if (s.camera.film_width == 0 || s.camera.film_height == 0 || s.camera.film_width > 65535 || s.camera.film_height > 65535)
+    return refuse("film size out of range");
+  if (s.environment_material >= (int32_t)s.num_materials) return refuse("environment material out of range");
+  if (opt.light_sampling > PHX_LIGHTS_BY_AREA) return refuse("unknown light_sampling");
+  const bool lights_by_area = opt.light_sampling == PHX_LIGHTS_BY_AREA;
+
+  // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
+  // non-emitting materials may carry one (textured emission is not supported)
+  if (s.num_textures && !s.textures) return refuse("scene with textures but a null texture table");
+  uint64_t total_texels = 0;
+  for (uint32_t t = 0; t < s.num_textures; ++t) {
+    const phx_texture& T = s.textures[t];
+    const std::string texture = "texture " + std::to_string(t);
+    if (T.width == 0 || T.height == 0) return refuse(texture + " has zero size");
+    if (T.width > 65536u || T.height > 65536u || (uint64_t)T.width * T.height > (1ull << 26))
+      return refuse(texture + " too large (at most 65536 x 65536 and 2^26 texels)");
+    if (!T.texels) return refuse(texture + " without texels");
+    if (T.filter > PHX_TEX_CLOSEST || T.swrap > PHX_WRAP_BLACK || T.twrap > PHX_WRAP_BLACK) return refuse(texture + " with an unknown filter or wrap mode");
+    total_texels += (uint64_t)T.width * T.height;
+  }
+  if (total_texels > (1ull << 30)) return refuse("textures too large (at most 2^30 texels in all)");
+  bool any_tex = false, any_mask = false;  // any_tex: some lobe reads an image at the hit's UV (colour texture or mask)
+  for (uint32_t i = 0; i < s.num_materials; ++i) {
+    const phx_material& m = s.materials[i];
+    for (uint32_t k = 0; k < m.num_lobes && k < PHX_MAX_LOBES; ++k) {
+      const bool emits = m.is_emitter || (int32_t)i == s.environment_material || m.lobes[k].type == PHX_LOBE_EMISSIVE || m.lobes[k].type == PHX_LOBE_BACKGROUND;
+      // an image mask on the closure's mix factor (fac_mode: mode byte + the mask's texture): the same rules as a colour texture
+      const uint32_t mode = PHX_FAC_MODE(m.lobes[k].fac_mode), mask = PHX_FAC_TEXTURE(m.lobes[k].fac_mode);
+      if (mode > PHX_FAC_TEX_A) return refuse(material(i) + ": unknown fac_mode");
+      if (mode < PHX_FAC_TEX_B && mask) return refuse(material(i) + ": fac_mode names a mask texture but its mode is not PHX_FAC_TEX_*");
+      if (mode >= PHX_FAC_TEX_B) {
+        if (mask == 0 || mask > s.num_textures) return refuse(material(i) + ": mask texture index out of range");
+        if (emits) return refuse(material(i) + ": masks on emitters / the environment are not supported");
+        any_tex = any_mask = true;
+      }
+      const uint32_t t = m.lobes[k].texture;
+      if (!t) continue;
+      if (t > s.num_textures) return refuse(material(i) + ": lobe texture index out of range");
+      if (emits) return refuse(material(i) + ": textures on emitters / the environment are not supported");
+      any_tex = true;
+    }
+    // an environment map: only on the environment material (textured surface emission would need UVs at NEE's light samples)
+    if (m.emission_mapping > PHX_ENV_LATLONG_Z_UP) return refuse(material(i) + ": unknown emission_mapping");
+    if (m.emission_texture) {
+      if ((int32_t)i != s.environment_material) return refuse(material(i) + ": emission_texture is allowed only on the environment material");
+      if (m.emission_texture > s.num_textures) return refuse(material(i) + ": emission_texture index out of range");
+    }
+  }
+
+  out = FlatScene{};
+  for (uint32_t mi = 0; mi < s.num_meshes; ++mi) {
+    const phx_mesh& m = s.meshes[mi];
+    for (uint32_t f = 0; f < m.num_faces; ++f) if (m.smooth && m.smooth[f]) out.any_smooth = true;
+  }
+  for (uint32_t mi = 0; mi < s.num_meshes; ++mi) {
+    const phx_mesh& m = s.meshes[mi];
+    if (!m.vertices || !m.faces || (m.num_sets && !m.sets) || (any_tex && m.num_uvs && !m.uvs)) return refuse("mesh with null arrays");
+    for (uint32_t si = 0; si < m.num_sets; ++si) {
+      const phx_face_set& fs = m.sets[si];
+      if (fs.material >= s.num_materials) return refuse("face set material out of range");
+      const bool emitter = s.materials[fs.material].is_emitter != 0;
+      DevLight L{(uint32_t)out.light_tris.size(), 0, 0.0f, fs.material, 0.0f, 0.0f, 0.0f, 0.0f};
+      for (uint32_t k = 0; k < fs.num_faces; ++k) {
+        const uint32_t f = fs.faces[k];
+        if (f >= m.num_faces) return refuse("face index out of range");
+        const uint32_t ia = m.faces[3 * f], ib = m.faces[3 * f + 1], ic = m.faces[3 * f + 2];
+        if (ia >= m.num_vertices || ib >= m.num_vertices || ic >= m.num_vertices) return refuse("vertex index out of range");
+        const uint32_t prim = (uint32_t)out.prim_material.size();
+        const float* a = m.vertices + 3 * (size_t)ia; const float* b = m.vertices + 3 * (size_t)ib; const float* c = m.vertices + 3 * (size_t)ic;
+        out.abc.insert(out.abc.end(), a, a + 3); out.abc.insert(out.abc.end(), b, b + 3); out.abc.insert(out.abc.end(), c, c + 3);
+        const bool smooth = m.smooth && m.smooth[f];
+        out.prim_material.push_back(fs.material | (smooth ? 0x80000000u : 0u));
+        if (out.any_smooth) {
+          uint32_t na = ia, nb = ib, nc = ic;
+          if (!(m.flags & PHX_MESH_NORMALS_PER_VERTEX)) { na = 3 * f; nb = 3 * f + 1; nc = 3 * f + 2; }  // mesh.cpp:188-192
+          float nn[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+          if (smooth) {
+            if (!m.normals || na >= m.num_normals || nb >= m.num_normals || nc >= m.num_normals) return refuse("normal index out of range");
+            std::memcpy(nn, m.normals + 3 * (size_t)na, 12); std::memcpy(nn + 3, m.normals + 3 * (size_t)nb, 12); std::memcpy(nn + 6, m.normals + 3 * (size_t)nc, 12);
+          }
+          out.prim_normals.insert(out.prim_normals.end(), nn, nn + 9);
+        }
+        if (any_tex) {  // mesh_t::shading_parameters (mesh.cpp:239-257): UV indices per vertex or per face corner, like the normals; no UVs: (0, 0)
+          float2 uv[3] = {make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)};
+          if (m.num_uvs) {
+            const bool per_vertex = (m.flags & PHX_MESH_UV_PER_VERTEX) != 0;
+            const uint32_t ui[3] = {per_vertex ? ia : 3 * f, per_vertex ? ib : 3 * f + 1, per_vertex ? ic : 3 * f + 2};
+            for (int c = 0; c < 3; ++c) {
+              if (ui[c] >= m.num_uvs) return refuse("uv index out of range");
+              uv[c] = make_float2(m.uvs[2 * (size_t)ui[c]], m.uvs[2 * (size_t)ui[c] + 1]);
+            }
+          }
+          out.prim_uv.insert(out.prim_uv.end(), uv, uv + 3);
+        }
+        if (emitter) {  // mesh_t::preprocess -> light_t::make_area (mesh.cpp:108-116), area_light_t (light.cpp:10-45)
+          const v3 ab(b[0] - a[0], b[1] - a[1], b[2] - a[2]), ac(c[0] - a[0], c[1] - a[1], c[2] - a[2]);
+          const v3 gn = normalize_inplace(cross(ab, ac));  // the flat face's normal as k_shade's shading_normal would compute it per sample
+          DevLightTri T{a[0], a[1], a[2], b[0], b[1], b[2], c[0], c[1], c[2], gn.x, gn.y, gn.z, prim, smooth ? 1u : 0u, mi | (fs.material << 16), 3 * f};
+          out.light_tris.push_back(T);
+          L.area += 0.5f * length(cross(ab, ac));  // triangle_t::area, mesh.cpp:293-300; summed in face order (light.cpp:36-39)
+          L.num_tris++;
+          if (lights_by_area) out.light_cdf.push_back(L.area);  // acc_i
+        }
+      }
+      if (emitter && L.num_tris) {
+        out.lights.push_back(L);
+        for (uint32_t k = 0; k < (lights_by_area ? L.num_tris : 0u); ++k) out.light_cdf[L.first_tri + k] = out.light_cdf[L.first_tri + k] / L.area;  // cdf[i] = acc_i / area; the last is 1
+      }
+    }
+  }
+  if (out.prim_material.empty()) return refuse("scene has no triangles");
+  if (out.lights.empty()) return refuse("scene has no emissive face set (reference underflows nlights-1, SURVEY A-19)");
+
+  // sheen_L5: the first sheen lobe of the material table (bsdf.h)
+  float L5 = 0.0f; bool have = false;
+  for (uint32_t i = 0; i < s.num_materials && !have; ++i)
+    for (uint32_t k = 0; k < s.materials[i].num_lobes && k < PHX_MAX_LOBES; ++k)
+      if (s.materials[i].lobes[k].type == PHX_LOBE_SHEEN) { L5 = sheen_L(0.5f, s.materials[i].lobes[k].r); have = true; break; }
+  std::vector<DevMaterial>& mats = out.materials;
+  mats.resize(s.num_materials);
+  out.lobe_tex.resize(8 * (size_t)s.num_materials);
+  for (uint32_t i = 0; i < s.num_materials; ++i)
+    if (!bake_material(s.materials[i], L5, mats[i], out.lobe_tex.data() + 8 * (size_t)i)) return refuse("material with an unknown closure id");
+  out.mat_masked.assign(s.num_materials, 0);
+  for (uint32_t i = 0; i < s.num_materials; ++i)
+    for (uint32_t k = 0; k < mats[i].num_lobes; ++k) if (mats[i].lobes[k].fac_mode >= PHX_FAC_TEX_B) out.mat_masked[i] = 1;
+
+  {  // per light: the pick pdf and the emission of its material, as k_shade evaluated them per sample until round 2
+    const float nlf = (float)out.lights.size();
+    for (auto& L : out.lights) {
+      L.lpdf = (1.0f / L.area) / nlf;
+      L.ex = mats[L.material].ex; L.ey = mats[L.material].ey; L.ez = mats[L.material].ez;
+    }
+  }
+
+  // the environment's image, and every texture's texels as float4 (one 16-byte load per texel) behind a small table
+  DevScene& sc = out.scene;
+  sc.env_material = s.environment_material;
+  out.env_tex = s.environment_material >= 0 ? s.materials[s.environment_material].emission_texture : 0u;  // texture + 1, 0 = none
+  if (out.env_tex) {
+    out.env_mapping = s.materials[s.environment_material].emission_mapping;
+    for (int c = 0; c < 3; ++c) out.env_e[c] = s.materials[s.environment_material].emission[c];
+  }
+  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (out.env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u) | (lights_by_area ? SC_LIGHTS_BY_AREA : 0u);
+  if (sc.any_tex & SC_TEX_ANY) {
+    out.textures.resize(s.num_textures);
+    out.texels.resize((size_t)total_texels);
+    uint32_t off = 0;
+    for (uint32_t t = 0; t < s.num_textures; ++t) {
+      const phx_texture& T = s.textures[t];
+      const uint32_t nt = T.width * T.height;
+      out.textures[t] = DevTexture{off, T.width, T.height, T.filter | (T.swrap << 8) | (T.twrap << 16)};
+      for (uint32_t k = 0; k < nt; ++k) out.texels[off + k] = make_float4(T.texels[3 * (size_t)k], T.texels[3 * (size_t)k + 1], T.texels[3 * (size_t)k + 2], 0.0f);
+      off += nt;
+    }
+  }
+
+  // which shade kernel the scene runs: textured lobes and environment maps are shaded by k_shade_g<.., TEX, ENV> only, and so is the pick by area
+  sc.diffuse_only = sc.any_tex ? 0 : 1;
+  for (auto& m : mats) {
+    if (m.per_hit) sc.diffuse_only = 0, sc.any_per_hit = 1;
+    for (uint32_t k = 0; k < m.num_lobes; ++k) if (m.lobes[k].type != L_DIFFUSE) sc.diffuse_only = 0;
+  }
+  bool single = sc.diffuse_only != 0;
+  for (auto& m : mats) single = single && m.num_lobes <= 1;
+  if (single) {  // at most one Lambert lobe everywhere (the soups, the Cornell box): a 32-byte material table for k_shade<2>
+    sc.diffuse_only = 2;
+    for (const DevMaterial& m : mats) {  // (a material without lobes has zero weights, whatever an emissive closure left in lobes[0])
+      const DevLobe l = m.num_lobes ? m.lobes[0] : DevLobe{};
+      out.mat_lite.push_back(DevMatLite{l.wx, l.wy, l.wz, m.num_lobes | (l.flags << 8), m.ex, m.ey, m.ez, 0u});
+    }
+  }
+
+  sc.num_lights = (uint32_t)out.lights.size();
+  sc.max_depth = opt.path_depth;
+  std::memcpy(sc.cam_m, s.camera.to_world, sizeof(sc.cam_m));
+  sc.zoom = 1.12f * std::tan(s.camera.fov * 0.5f);  // camera.hpp:113
+  sc.stepx = 1.0f / (float)s.camera.film_width; sc.stepy = 1.0f / (float)s.camera.film_height;
+  sc.ratio = (float)s.camera.film_width / (float)s.camera.film_height;
+  sc.width = s.camera.film_width; sc.height = s.camera.film_height;
+  sc.aperture_radius = s.camera.aperture_radius; sc.focal_distance = s.camera.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
+  return PHX_OK;
+}
+
+}  // namespace phx

@@ -1,0 +1,43 @@
+// scene_flatten.h — the host-only half of preprocess: everything the device derives from a caller's phx_scene before the first HIP call.
+//
+// flatten_scene validates the scene (every caller-supplied index is checked here, and nowhere else), lays its triangles out in
+// scene_t::triangles() order, bakes the materials and the light table with the fp32 operations bit parity with the oracle depends on, and
+// classifies the scene for the shade kernels.  It makes no HIP call and touches no device: <hip/hip_runtime.h> is here for float2 / float4
+// alone, so the translation unit also compiles with a plain host compiler (tests/native/host_flatten.cpp).  device.cpp commits the result.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/phx_xpu.h"
+#include "kernels.h"
+
+#include <string>
+#include <vector>
+
+namespace phx {
+
+struct FlatScene {
+  // triangles in scene_t::triangles() order: mesh order x face-set order (scene.cpp:58-62, mesh.cpp:118-128)
+  std::vector<float> abc;               // 9 floats per primitive
+  std::vector<uint32_t> prim_material;  // material | smooth << 31
+  std::vector<float> prim_normals;      // any_smooth: 9 floats per primitive (zero on flat faces)
+  std::vector<float2> prim_uv;          // SC_TEX_LOBES: 3 corner UVs per primitive
+  bool any_smooth = false;
+  std::vector<DevLight> lights;         // one per emissive face set; its triangles are light_tris[first_tri ...] in face order
+  std::vector<DevLightTri> light_tris;
+  std::vector<float> light_cdf;         // PHX_LIGHTS_BY_AREA: per light triangle, the light's running area up to and including it over the light's area
+  std::vector<DevMaterial> materials;
+  std::vector<uint32_t> lobe_tex;       // 8 per material: texture + 1 of baked lobe k
+  std::vector<DevMatLite> mat_lite;     // diffuse_only == 2: the 32-byte table
+  std::vector<uint8_t> mat_masked;      // per material: some lobe's factor is an image mask
+  std::vector<DevTexture> textures;     // the texture table and every texel as RGB + 0: packed only when scene.any_tex & SC_TEX_ANY
+  std::vector<float4> texels;
+  uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission
+  // every word of DevScene that needs no device: camera, film, environment, light count, any_tex, diffuse_only, any_per_hit, max_depth.
+  // The pointers and the tree's words stay zero for the commit stage.
+  DevScene scene{};
+};
+
+// PHX_OK, or PHX_ERR_ARG with the reason in `err`; `out` is meaningful only after PHX_OK
+int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err);
+
+}  // namespace phx

@@ -110,7 +110,7 @@ def fresnel_mix_factor(ior, n, view):  # fresnel_dielectric_node.osl:16-20 on I 
     return osl_fresnel_dielectric(c, np.where(c < 0, 1.0 / f, f))
 
 
-# ---- host parameter maps (device.cpp bake_material; params.hpp:36-43, 86-99) --------------------------------------------------------
+# ---- host parameter maps (scene_flatten.cpp bake_material; params.hpp:36-43, 86-99) --------------------------------------------------------
 def roughness_to_alpha(r):
     """the polynomial in log(max(r, 1e-5)), clamped to [1e-4, 1].  It is not monotonic: r = 0 gives 0.296, its minimum is ~0.0093
     near r = 1.5e-4, so the 1e-4 clamp is never reached."""

@@ -976,6 +976,58 @@ def test_auto_builder_falls_back_to_the_host_only_for_recoverable_failures(xpu, 
     assert ast_["bvh_built_on_device"] == 1 and bits_equal(again, want)
 
 
+def test_a_preprocess_that_fails_while_committing_leaves_the_device_without_a_scene(xpu):
+    """include/phx_xpu.h, phx_dev_preprocess: a call refused before anything is uploaded (the state checks, the scene's validation) keeps
+    the previous scene renderable; one that fails later — here the device builder's fatal error, forced in the fault-injection twin —
+    has already replaced buffers of the previous scene, so start and the stage hooks answer PHX_ERR_STATE (4) until a preprocess
+    succeeds.  Every failure here is a refused call; nothing faults."""
+    import os, subprocess, sys
+    from conftest import ROOT
+    hooks = os.path.join(ROOT, "phosphorus_mk2_amd", "libphx_hip_hooks.so")
+    assert os.path.exists(hooks), "build() makes the fault-injection twin"
+    code = ("import os, sys; sys.path.insert(0, %r)\n"
+            "import numpy as np\n"
+            "from phosphorus_mk2_amd import scenes, xpu\n"
+            "a, b = scenes.soup(500, width=32, height=32), scenes.soup(500, seed=77, width=32, height=32)\n"
+            "dark = scenes.cornell(32, 32); dark.meshes = dark.meshes[:5]\n"
+            "dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=4, paths_per_sample=1, path_depth=9, bvh_builder='device'))\n"
+            "def frame():\n"
+            "    film = xpu.Film(32, 32, 4)\n"
+            "    dev.start(a, xpu.FrameState(1, xpu.Tiles.make(32, 32, 32), film)); dev.join()\n"
+            "    return film.data.copy()\n"
+            "def refused(call):\n"
+            "    try:\n"
+            "        call()\n"
+            "    except xpu.DeviceError as e:\n"
+            "        return str(e)\n"
+            "    return 'NOT REFUSED'\n"
+            "ray = (np.zeros((1, 3), np.float32), np.array([[0, 0, -1]], np.float32), np.full(1, 1e30, np.float32))\n"
+            "dev.preprocess(a)\n"
+            "first = frame()\n"
+            "print('LIT', bool(first[..., :3].max() > 0.05))\n"
+            "os.environ['PHX_TEST_FAIL_DEVICE_BUILD'] = 'fatal'\n"
+            "print('BUILD', refused(lambda: dev.preprocess(b)))\n"
+            "print('START', refused(frame))\n"
+            "print('TRACE', refused(lambda: dev.trace(*ray)))\n"
+            "del os.environ['PHX_TEST_FAIL_DEVICE_BUILD']\n"
+            "dev.preprocess(a)\n"
+            "print('AGAIN', first.tobytes() == frame().tobytes())\n"
+            "print('DARK', refused(lambda: dev.preprocess(dark)))\n"
+            "print('KEPT', first.tobytes() == frame().tobytes(), len(dev.trace(*ray)['t']))\n"
+            "dev.close()\n") % ROOT
+    env = {k: v for k, v in os.environ.items() if k != "PHX_TEST_FAIL_DEVICE_BUILD"}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, env=dict(env, PHX_LIB=hooks))
+    assert r.returncode == 0, (r.stdout, r.stderr[-800:])
+    out = {l.split(" ", 1)[0]: l.split(" ", 1)[1] for l in r.stdout.splitlines() if " " in l}
+    assert out["LIT"] == "True"
+    assert "(2)" in out["BUILD"] and "device BVH build" in out["BUILD"]  # PHX_ERR_DEVICE
+    assert "phx_dev_start failed (4)" in out["START"] and "start before preprocess" in out["START"]
+    assert "(4)" in out["TRACE"] and "trace before preprocess" in out["TRACE"]
+    assert out["AGAIN"] == "True"
+    assert "(1)" in out["DARK"] and "no emissive face set" in out["DARK"]
+    assert out["KEPT"] == "True 1"
+
+
 def test_destroying_a_device_with_a_frame_in_flight_joins_it(xpu, orc):
     """phx_dev_destroy after phx_dev_start WITHOUT phx_dev_join (include/phx_xpu.h: destroy joins): the call returns when the frame has
     ended, every tile has been delivered through the add_tile callback by then, and the film is the one a joined frame gives."""
