@@ -138,7 +138,7 @@ typedef struct phx_material {
   uint32_t is_emitter;  /* material_t::is_emitter, src/material.cpp:487 */
   float    emission[3]; /* weight of the emission()/background() closure: hits.e */
   /* Environment map (environment_node.osl's Cout = environment(filename, I) into background_node.Cs): 0 = none, k = phx_scene.textures[k - 1].
-   * Allowed ONLY on phx_scene.environment_material (PHX_ERR_ARG elsewhere: textured surface emission is not supported).  Where a path
+   * Allowed ONLY on phx_scene.environment_material (PHX_ERR_ARG elsewhere: a surface emitter's image is emission_uv_texture).  Where a path
    * misses every surface (camera rays included) with direction d = (x, y, z), it adds beta * e with e = emission * texel(s, t), one fp32
    * multiply per channel; the environment is never sampled by next-event estimation.  (s, t) restates OpenImageIO's documented lat-long
    * convention (latlong_up "y" by default, or "z"), computed in binary64 from the fp32 components widened to double, operation by
@@ -150,7 +150,18 @@ typedef struct phx_material {
    * wrap modes (OpenImageIO's lat-long wrap is swrap periodic, twrap clamp); no MIP maps, no blur.  A zero or non-finite d reads black. */
   uint32_t emission_texture;
   uint32_t emission_mapping; /* PHX_ENV_LATLONG_*; any other value is PHX_ERR_ARG */
-  uint32_t pad;
+  /* Textured surface emission (texture_node.Cout into diffuse_emitter_node.Cs): 0 = none, k = phx_scene.textures[k - 1].  Allowed on
+   * is_emitter materials only, and not on phx_scene.environment_material; an index past the table is PHX_ERR_ARG too.  Wherever the
+   * material's emission e is used it is e * texel(s, t): one fp32 multiply per channel (no contraction), the phx_texture lookup with the
+   * image's own filter and wraps -- the expression emission_texture uses for the environment.
+   *   at a hit (depth == 0, or behind a specular bounce): (s, t) is the hit's interpolated mesh UV, as for a textured lobe;
+   *   at a light sample of next-event estimation: with (bu, bv) of triangle_t::sample, P = bu * a + bv * b + (1 - bu - bv) * c and
+   *       st = (bu * uv_a + bv * uv_b) + (1 - bu - bv) * uv_c        (fp32, in this order)
+   *     the UV of the sampled point itself.  A stated deviation (DESIGN: light_st_rotated): the reference reads the sample's (bu, bv) as
+   *     Moeller-Trumbore barycentrics (st = w * uv0 + u * uv1 + v * uv2, mesh.cpp:178-181,256) although barycentric_to_point puts them on
+   *     a and b (mesh.cpp:314-316), so it looks the image up at another point of the triangle than the one it lights from.
+   * A mesh without UVs has (s, t) = (0, 0).  The lobes of an emitter still take no image.  The scene is shaded by the TEX kernels. */
+  uint32_t emission_uv_texture;
   phx_lobe lobes[PHX_MAX_LOBES];
 } phx_material;
 enum { PHX_ENV_LATLONG_Y_UP = 0, PHX_ENV_LATLONG_Z_UP = 1 };
@@ -214,7 +225,7 @@ typedef struct phx_scene {
   const phx_material* materials;
   int32_t             environment_material; /* -1 = none (scene_t::environment, src/scene.cpp:126) */
   phx_camera          camera;
-  uint32_t            num_textures;  /* phx_lobe.texture, the mask of phx_lobe.fac_mode and phx_material.emission_texture index this table (1-based) */
+  uint32_t            num_textures;  /* phx_lobe.texture, the mask of phx_lobe.fac_mode, phx_material.emission_texture and emission_uv_texture index this table (1-based) */
   const phx_texture*  textures;
 } phx_scene;
 
@@ -406,6 +417,12 @@ int phx_dev_environment_lookup(phx_device* dev, uint32_t n, const float* dirs, f
  * order of the set), the barycentrics (bu, bv) of triangle_t::sample, the point P = bu * a + bv * b + (1 - bu - bv) * c and the light's lpdf.
  * A parity hook: it runs the device function k_shade_g runs.  PHX_ERR_STATE before preprocess. */
 int phx_dev_light_sample(phx_device* dev, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf);
+
+/* The emission next-event estimation uses at that light sample: for the same n triples u3 (pick, lu, lv per item) the (s, t) of the sampled
+ * point by the rule of phx_material.emission_uv_texture (st, 2 floats per item) and the light's emission e times the texel there (e, 3 floats
+ * per item).  A light whose material has no image returns its constant e and st = (0, 0).  A parity hook: it runs the device function
+ * k_shade_g runs.  PHX_ERR_STATE before preprocess. */
+int phx_dev_light_emission(phx_device* dev, uint32_t n, const float* u3, float* st, float* e);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -95,7 +95,7 @@ class Lobe(C.Structure):
 class Material(C.Structure):
     _fields_ = [
         ("num_lobes", C.c_uint32), ("is_emitter", C.c_uint32), ("emission", C.c_float * 3),
-        ("emission_texture", C.c_uint32), ("emission_mapping", C.c_uint32), ("pad", C.c_uint32), ("lobes", Lobe * MAX_LOBES),
+        ("emission_texture", C.c_uint32), ("emission_mapping", C.c_uint32), ("emission_uv_texture", C.c_uint32), ("lobes", Lobe * MAX_LOBES),
     ]
 
 
@@ -174,7 +174,7 @@ EXPORTS = [
     "phx_last_error", "phx_dev_get_stats", "phx_tiles_make", "phx_tiles_next", "phx_tiles_count", "phx_tiles_reset",
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
     "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
-    "phx_dev_light_sample",
+    "phx_dev_light_sample", "phx_dev_light_emission",
 ]
 
 
@@ -203,5 +203,6 @@ def declare(lib):
     lib.phx_dev_environment_lookup.argtypes = [vp, C.c_uint32, f32p, f32p]; lib.phx_dev_environment_lookup.restype = C.c_int
     lib.phx_dev_lobe_weights.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, u32p]; lib.phx_dev_lobe_weights.restype = C.c_int
     lib.phx_dev_light_sample.argtypes = [vp, C.c_uint32, f32p, u32p, u32p, f32p, f32p, f32p]; lib.phx_dev_light_sample.restype = C.c_int
+    lib.phx_dev_light_emission.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]; lib.phx_dev_light_emission.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

@@ -179,6 +179,8 @@ def transparent_bsdf_node(Cs=1.0, **_):
 
 
 def diffuse_emitter_node(power=1.0, Cs=1.0, **_):
+    if isinstance(Cs, Tex):  # (power / M_PI) * Cs * emission() with Cs the texel: power / M_PI joins the constant weight, the image multiplies at mesh UVs
+        return MulTex(Cs, mul(f32(f32(power) / M_PI), Comp(abi.LOBE_EMISSIVE)))
     return mul(f32(f32(power) / M_PI) * _color(Cs), Comp(abi.LOBE_EMISSIVE))
 
 
@@ -259,15 +261,16 @@ UNBAKEABLE = {"fresnel_node", "normal_map_node", "random_noise_2d_node", "random
 
 
 # ---- material.cpp:218-305 -------------------------------------------------------------------------------
-def flatten(tree, textures=None):
+def flatten(tree, textures=None, emitter_textures=False):
     """eval_closure: closure tree -> MaterialDesc (lobes in visiting order, e = last emission/background weight).  The tree is
     walked as material.cpp:218-305 walks it: MUL multiplies the weight down, ADD visits A then B.  A Fresnel-driven factor
     splits a closure's weight into the constant part above it (pre_weight), the factor itself (fac_mode, fac_ior) and the
     constant part below it (weight): at a hit the weight is (pre_weight * term) * weight, the same order of multiplications.
     A texture on a closure's colour: the lobe keeps the weight accumulated above it and `texture` = k + 1, k the texture's entry in
     `textures` (a list of {filename, swrap, twrap}, extended here by the ones not in it yet).  An image mask is a factor like the Fresnel
-    one with the image in place of the ior: fac_mode FAC_TEX_*, `fac_texture` = k + 1 in the same list."""
-    lobes, state = [], {"e": (0.0, 0.0, 0.0), "emitter": False, "env": 0}
+    one with the image in place of the ior: fac_mode FAC_TEX_*, `fac_texture` = k + 1 in the same list.  A texture on an emission closure's
+    colour is baked only with `emitter_textures`: emission = the constant weight accumulated above it and `emission_uv_texture` = k + 1."""
+    lobes, state = [], {"e": (0.0, 0.0, 0.0), "emitter": False, "env": 0, "emit_tex": 0}
     if textures is None:
         textures = []
 
@@ -309,10 +312,10 @@ def flatten(tree, textures=None):
             if c.cid in (abi.LOBE_EMISSIVE, abi.LOBE_BACKGROUND):
                 if fac is not None:
                     raise ValueError("emission under an image-masked mix is not supported" if fac[3] else "emission under a Fresnel-driven mix is not supported")
-                if tex:
-                    raise ValueError("textured emission is not supported")
+                if tex and (not emitter_textures or c.cid != abi.LOBE_EMISSIVE):
+                    raise ValueError("textured emission is baked only on request: bake_material(..., emitter_textures=True) / load_scene(..., emitter_textures=True)")
                 state["e"] = tuple(float(x) for x in w)  # assignment: a later emission overwrites an earlier one
-                state["env"] = env
+                state["env"], state["emit_tex"] = env, tex
                 state["emitter"] = state["emitter"] or c.cid == abi.LOBE_EMISSIVE  # material.cpp:205-211
                 return
             p = c.params
@@ -325,14 +328,18 @@ def flatten(tree, textures=None):
                                   xalpha=float(p.get("xalpha", 0.0)), yalpha=float(p.get("yalpha", 0.0)), refract=int(p.get("refract", 0)),
                                   r=float(p.get("r", 0.0)), texture=tex, **extra))
     visit(tree, np.ones(3, f32))
+    if state["emit_tex"] and any(l.texture or l.fac_texture for l in lobes):
+        raise ValueError("a textured emitter whose own closures carry a texture or a mask: images on the lobes of an emitter are not supported")
     if len(lobes) > abi.MAX_LOBES:
         raise ValueError(f"{len(lobes)} lobes: bsdf_t holds at most {abi.MAX_LOBES} (src/bsdf.hpp:9)")
-    return MaterialDesc(lobes=lobes, emission=state["e"], is_emitter=state["emitter"], emission_texture=state["env"])
+    return MaterialDesc(lobes=lobes, emission=state["e"], is_emitter=state["emitter"], emission_texture=state["env"], emission_uv_texture=state["emit_tex"])
 
 
-def bake_material(desc, textures=None):
+def bake_material(desc, textures=None, emitter_textures=False):
     """`desc`: one entry of the reference's YAML `materials:` map (already parsed, e.g. by yaml.safe_load).  `textures`: the scene's
-    list of texture specs {filename, swrap, twrap}, which the material's texture_nodes are added to (lobe.texture = index + 1)."""
+    list of texture specs {filename, swrap, twrap}, which the material's texture_nodes are added to (lobe.texture = index + 1).
+    `emitter_textures`: also bake texture_node.Cout -> diffuse_emitter_node.Cs (MaterialDesc.emission_uv_texture: the image multiplies the
+    emission at mesh UVs, with the light-sample UV rule of include/phx_xpu.h, a stated deviation from the reference); refused by default."""
     layers, order = {}, []
     for sh in desc["shaders"]:
         name, layer = sh["name"], sh["layer"]
@@ -370,17 +377,18 @@ def bake_material(desc, textures=None):
                 if layers[src_layer][0] is luminance_node and (src_slot != "out" or slot != "fac" or fn is not mix_closure_node):
                     raise ValueError(f"luminance {src_layer}.{src_slot} into {layer}.{slot}: luminance_node.out can drive only the fac of a mix_closure_node")
                 to_mask = fn is luminance_node and slot == "in"  # texture_node.Cout -> luminance_node.in: the one way an image reaches a mix's fac
-                if layers[src_layer][0] is texture_node and not to_mask and (slot != "Cs" or fn not in TEXTURABLE):
-                    raise ValueError(f"texture {src_layer}.Cout into {layer}.{slot}: a texture can drive only the Cs of a BSDF node or a luminance_node")
+                if layers[src_layer][0] is texture_node and not to_mask and (slot != "Cs" or (fn not in TEXTURABLE and not (emitter_textures and fn is diffuse_emitter_node))):
+                    raise ValueError(f"texture {src_layer}.Cout into {layer}.{slot}: a texture can drive only the Cs of a BSDF node or a luminance_node"
+                                     " (the Cs of a diffuse_emitter_node too with emitter_textures=True)")
                 if layers[src_layer][0] is environment_node and (slot != "Cs" or fn is not background_node):
                     raise ValueError(f"environment {src_layer}.Cout into {layer}.{slot}: an environment map can drive only the Cs of a background_node")
                 args[slot] = evaluate(src_layer)
             cache[layer] = fn(**args)
         return cache[layer]
-    return flatten(evaluate(order[-1]), textures)
+    return flatten(evaluate(order[-1]), textures, emitter_textures)
 
 
-def bake_materials(yaml_materials, textures=None):
+def bake_materials(yaml_materials, textures=None, emitter_textures=False):
     """name -> MaterialDesc for a whole `materials:` map; ids follow insertion order (scene_t::add, src/scene.cpp:84-90).  The
     texture specs the materials use are collected in `textures` (see bake_material)."""
-    return {name: bake_material(d, textures) for name, d in yaml_materials.items()}
+    return {name: bake_material(d, textures, emitter_textures) for name, d in yaml_materials.items()}

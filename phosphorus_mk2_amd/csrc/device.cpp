@@ -125,6 +125,7 @@ struct phx_device {
   DevBuf<DevMaterial> d_materials; DevBuf<DevMatLite> d_mat_lite; DevBuf<DevLight> d_lights; DevBuf<DevLightTri> d_light_tris;
   // image textures: held only while the preprocessed scene has a textured lobe
   DevBuf<float2> d_elem_uv; DevBuf<DevTexture> d_textures; DevBuf<float4> d_texels; DevBuf<uint32_t> d_lobe_tex; DevBuf<DevTexScene> d_tex_scene;
+  DevBuf<uint32_t> d_mat_emit_tex;  // per material: the image on its emission + 1 (scenes with emitter images only)
   DevScene scene{};
   uint32_t num_materials = 0, num_textures = 0;
   std::vector<uint8_t> mat_masked;  // per material: some lobe's factor is an image mask (the untextured KAT hooks refuse those)
@@ -194,7 +195,7 @@ struct phx_device {
   uint64_t device_bytes() const {
     return d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
            d_lights.bytes() + d_light_tris.bytes() + queues.bytes() + counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
-           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes();
+           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes() + d_mat_emit_tex.bytes();
   }
   // paths in flight this device may carry: up to 512 M (about 95 GB of queues + state: sized for 288 GB of HBM), but never more than 60 % of
   // what the device has free right now plus what this object already holds for queues (another device object, torch or RCCL may share the GPU)
@@ -333,14 +334,18 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   if (any_tex) {
     if ((rc = d_prim_uv.upload(fs.prim_uv)) || (rc = d->d_elem_uv.alloc(3 * (size_t)sc.num_elems)) || (rc = d->d_lobe_tex.upload(fs.lobe_tex))) return rc;
     launch_permute_uvs(d->stream, d_prim_uv.p, d_elem_of_prim.p, d->d_elem_uv.p, ntri);
+    // emitter images: every light triangle reaches its corner UVs by pool element (the smooth ones were remapped above)
+    if (fs.any_emit_tex) launch_remap_flat_light_tris(d->stream, d->d_light_tris.p, (uint32_t)fs.light_tris.size(), d_elem_of_prim.p);
   } else {
     d->d_elem_uv.release(); d->d_lobe_tex.release();
   }
   HIPCHK(hipGetLastError());
+  if (fs.any_emit_tex) { if ((rc = d->d_mat_emit_tex.upload(fs.mat_emit_tex))) return rc; } else d->d_mat_emit_tex.release();
   if (any_image) {  // the texture table and the texels, and the one record through which the shade kernels find them
     if ((rc = d->d_textures.upload(fs.textures)) || (rc = d->d_texels.upload(fs.texels))) return rc;
     const std::vector<DevTexScene> ts{DevTexScene{any_tex ? d->d_elem_uv.p : nullptr, d->d_textures.p, d->d_texels.p, any_tex ? d->d_lobe_tex.p : nullptr,
-                                                  fs.env_tex ? fs.env_tex - 1u : 0u, fs.env_mapping}};
+                                                  fs.env_tex ? fs.env_tex - 1u : 0u, fs.env_mapping, fs.any_emit_tex ? 1u : 0u, 0u,
+                                                  fs.any_emit_tex ? d->d_mat_emit_tex.p : nullptr}};
     if ((rc = d->d_tex_scene.upload(ts))) return rc;
   } else {
     d->d_textures.release(); d->d_texels.release(); d->d_tex_scene.release();
@@ -682,6 +687,16 @@ int phx_dev_light_sample(phx_device* d, uint32_t n, const float* u3, uint32_t* l
     const float* a = s.in(u3, 3 * (size_t)n);
     uint32_t *ol = s.out(light, n), *ot = s.out(tri, n); float *ob = s.out(bary, 2 * (size_t)n), *oP = s.out(P, 3 * (size_t)n), *op = s.out(pdf, n);
     return s.run([&] { launch_light_sample(d->stream, d->scene, n, a, ol, ot, ob, oP, op); });
+  });
+}
+
+int phx_dev_light_emission(phx_device* d, uint32_t n, const float* u3, float* st, float* e) {
+  return stage_hook(d, "light_emission", [&](Staging& s) -> int {
+    if (n == 0) return PHX_OK;
+    if (!u3 || !st || !e) return fail(PHX_ERR_ARG, "light_emission: null argument");
+    const float* a = s.in(u3, 3 * (size_t)n);
+    float *os = s.out(st, 2 * (size_t)n), *oe = s.out(e, 3 * (size_t)n);
+    return s.run([&] { launch_light_emission(d->stream, d->scene, n, a, os, oe); });
   });
 }
 

@@ -35,6 +35,10 @@ struct DevTexScene {
   const uint32_t* lobe_tex;       // 8 per material: texture + 1 of lobe k (DevMaterial::tex_lobes says which are textured)
   uint32_t env_tex;               // k_shade_g<.., ENV>: the environment's image (0-based index into `textures`)
   uint32_t env_mapping;           // and its lat-long mapping (ENV_LATLONG_*)
+  // textured surface emission (phx_material.emission_uv_texture; bsdf.h: hit_emission, kernels.hip: light_emission)
+  uint32_t any_emit_tex;          // some emitter's emission is multiplied by an image: the wave-uniform branch of the TEX kernels
+  uint32_t pad;
+  const uint32_t* mat_emit_tex;   // per material: its emission image + 1 (0 = none), indexed by the hit's material and by DevLight::material
 };
 // DevScene::any_tex bits: which image lookups the shade kernels compile in
 enum { SC_TEX_LOBES = 1u /* some lobe is textured or masked: TEX */, SC_TEX_ENV = 2u /* the environment has an image: ENV */,
@@ -150,11 +154,16 @@ void launch_build_shade_recs(hipStream_t stream, const TriRec* tris, const uint3
 void launch_permute_normals(hipStream_t stream, const float* prim_normals, const uint32_t* elem_of_prim, float* elem_normals, uint32_t num_prims);
 void launch_permute_uvs(hipStream_t stream, const float2* prim_uv, const uint32_t* elem_of_prim, float2* elem_uv, uint32_t num_prims);
 void launch_remap_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32_t num_light_tris, const uint32_t* elem_of_prim);
+// a scene with emitter images: the FLAT light triangles' `prim` becomes a pool element too (light_emission gathers the corner UVs by it; the
+// smooth ones are remapped by launch_remap_light_tris, whose kernel and whose readers are as they were)
+void launch_remap_flat_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32_t num_light_tris, const uint32_t* elem_of_prim);
 void launch_scatter_film(hipStream_t stream, const PassBuffers& pb, float* device_film, uint32_t film_width);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf
 void launch_light_sample(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf);
+// light_pick + triangle_t::sample + light_emission as k_shade_g's next-event block runs them: per item u3 -> st (2 floats), e (3 floats)
+void launch_light_emission(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, float* st, float* e);
 void launch_trace_rays(hipStream_t stream, const DevScene& sc, uint32_t n, const float4* ro, const float4* rd, float4* hit, int any);
 void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3);
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,

@@ -986,6 +986,36 @@ __device__ __forceinline__ void light_pick(const DevScene& sc, float pick, float
   lt = sc.lights[l].first_tri + ti;
 }
 
+// ---- textured surface emission (phx_material.emission_uv_texture; the rule is stated in include/phx_xpu.h) -----------------------------------
+// Both run only in a scene with DevTexScene::any_emit_tex, behind a wave-uniform branch on that word; `emit_tex` is DevTexScene::mat_emit_tex.
+// At a hit: e * texel at the hit's own (s, t), for a material that names an image.
+__device__ __forceinline__ v3 hit_emission(const DevTexture* textures, const float4* texels, const uint32_t* emit_tex, uint32_t mat, const v3& e, const float2& st) {
+  const uint32_t k = emit_tex[mat];
+  if (!k) return e;
+  const v3 c = tex_lookup(textures, texels, k - 1u, st.x, st.y);
+  return v3(e.x * c.x, e.y * c.y, e.z * c.z);
+}
+// At a light sample (bu, bv) of triangle_t::sample on light triangle LT of light L: the UV of the sampled point itself, st = (bu * uv_a +
+// bv * uv_b) + (1 - bu - bv) * uv_c with the weights P is built with -- NOT the reference's rotated reading of (bu, bv) as Moeller-Trumbore
+// barycentrics (DESIGN: light_st_rotated) -- and e * texel there.  LT.prim is a pool element in such a scene (launch_remap_flat_light_tris).
+// A light without an image: its constant e, st = (0, 0).  Used by k_shade_g<.., TEX> and by phx_dev_light_emission.
+__device__ __forceinline__ v3 light_emission(const float2* elem_uv, const DevTexture* textures, const float4* texels, const uint32_t* emit_tex, const DevLight& L,
+                                             const DevLightTri& LT, float bu, float bv, float2& st) {
+  const v3 e(L.ex, L.ey, L.ez);
+  st = make_float2(0.0f, 0.0f);
+  const uint32_t k = emit_tex[L.material];
+  if (!k) return e;
+  const CornerUVs C = request_corner_uvs(elem_uv, LT.prim);
+  const float w = 1 - bu - bv;
+  st = make_float2((bu * C.a.x + bv * C.b.x) + w * C.c.x, (bu * C.a.y + bv * C.b.y) + w * C.c.y);
+  const v3 c = tex_lookup(textures, texels, k - 1u, st.x, st.y);
+  return v3(e.x * c.x, e.y * c.y, e.z * c.z);
+}
+// DevTexScene::mat_emit_tex through the scalar cache, read where it is used (inside the any_emit_tex branch) so that no register holds it elsewhere
+__device__ __forceinline__ const uint32_t* emit_tex_table(const DevScene& sc) {
+  return ((const __attribute__((address_space(4))) DevTexScene*)sc.tex)->mat_emit_tex;
+}
+
 // ---- general closures: shade + NEE + integrate with the hits of a workgroup sorted by material ----------------------------------
 // k_shade_g replaces the round-2 k_shade<0/3> (128 VGPRs, 160-700 B of scratch per lane, 4 waves per SIMD: the weakest kernel of the
 // repo).  What changed, and why:
@@ -1151,7 +1181,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
   DevTexScene tx{};  // TEX / ENV: the scene's texture tables, pointers in SGPRs (constant address space: s_load)
   if constexpr (TEX || ENV) {
     const __attribute__((address_space(4))) DevTexScene* ctx = (const __attribute__((address_space(4))) DevTexScene*)sc.tex;
-    if constexpr (TEX) { tx.elem_uv = ctx->elem_uv; tx.textures = ctx->textures; tx.texels = ctx->texels; tx.lobe_tex = ctx->lobe_tex; }
+    if constexpr (TEX) { tx.elem_uv = ctx->elem_uv; tx.textures = ctx->textures; tx.texels = ctx->texels; tx.lobe_tex = ctx->lobe_tex; tx.any_emit_tex = ctx->any_emit_tex; }
     else { tx.textures = ctx->textures; tx.texels = ctx->texels; }
     if constexpr (ENV) { tx.env_tex = ctx->env_tex; tx.env_mapping = ctx->env_mapping; }
   }
@@ -1320,7 +1350,10 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           n = shading_normal(VN, (pm >> 31) != 0, v3(S.x, S.y, S.z), h.y, h.z);
           mat = pm & 0x7fffffffu;  // material_t::evaluate (material.cpp:419-458): the closure recipe at this hit
           if (pb.pn && (FIRST || depth == 0)) pb.pn[path] = make_float4(n.x, n.y, n.z, 1.0f);
-          if (depth == 0 || specular) { const DevMaterial& m = sc.materials[mat]; add_e = v3(m.ex, m.ey, m.ez); add_rad = true; }  // spt.hpp:177-179
+          if (depth == 0 || specular) {  // spt.hpp:177-179
+            const DevMaterial& m = sc.materials[mat]; add_e = v3(m.ex, m.ey, m.ez); add_rad = true;
+            if constexpr (TEX) if (tx.any_emit_tex) add_e = hit_emission(tx.textures, tx.texels, emit_tex_table(sc), mat, add_e, st);  // an emitter's image at the hit's (s, t)
+          }
         } else {
           // miss: environment lighting (deferred_shading_kernel.hpp:65-70, spt.hpp:199-202); the slot is MASKED|SHADOW in the
           // reference's shadow stream (spt.hpp:138-141): rays_masked = rays_closest - rays_shadow
@@ -1385,7 +1418,8 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             const DevLightTri& LT = sc.light_tris[lt];
             const v3 ln = LT.smooth ? shading_normal(sc, LT.prim, true, v3(LT.bx - LT.ax, LT.by - LT.ay, LT.bz - LT.az), v3(LT.cx - LT.ax, LT.cy - LT.ay, LT.cz - LT.az), bu, bv)
                                     : v3(LT.nx, LT.ny, LT.nz);
-            const v3 le(L.ex, L.ey, L.ez);
+            v3 le(L.ex, L.ey, L.ez);
+            if constexpr (TEX) if (tx.any_emit_tex) { float2 lst; le = light_emission(tx.elem_uv, tx.textures, tx.texels, emit_tex_table(sc), L, LT, bu, bv, lst); }  // material->evaluate(.., light_st, ..).e, spt.hpp:237-254
             const float pdf = L.lpdf * sh_t * sh_t / fabsf(dot(ln, -sh_d));
             const v3 li = ((le * 4.0f) * f) * (1.0f / pdf);
             contrib = beta * li;
@@ -1573,6 +1607,22 @@ __global__ void __launch_bounds__(64) k_light_sample(DevScene sc, uint32_t n, co
   light[i] = l; tri[i] = ti; bary[2 * i] = bu; bary[2 * i + 1] = bv;
   P3[3 * i] = P.x; P3[3 * i + 1] = P.y; P3[3 * i + 2] = P.z;
   pdf[i] = sc.lights[l].lpdf;
+}
+
+// phx_dev_light_emission: the same light sample, then light_emission as k_shade_g<.., TEX>'s next-event block runs it
+__global__ void __launch_bounds__(64) k_light_emission(DevScene sc, uint32_t n, const float* u3, float* st2, float* e3) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float pick = u3[3 * i], lu = u3[3 * i + 1], lv = u3[3 * i + 2];
+  uint32_t l, ti, lt; float remapped;
+  light_pick(sc, pick, lu, l, ti, lt, remapped);
+  const float x = sqrtf(remapped);
+  const float bu = 1 - x, bv = lv * x;     // triangle_t::sample, mesh.cpp:318-324
+  const DevLight& L = sc.lights[l];
+  v3 le(L.ex, L.ey, L.ez); float2 st = make_float2(0.0f, 0.0f);
+  if (sc.tex && sc.tex->any_emit_tex) le = light_emission(sc.tex->elem_uv, sc.tex->textures, sc.tex->texels, emit_tex_table(sc), L, sc.light_tris[lt], bu, bv, st);
+  st2[2 * i] = st.x; st2[2 * i + 1] = st.y;
+  e3[3 * i] = le.x; e3[3 * i + 1] = le.y; e3[3 * i + 2] = le.z;
 }
 
 // phx_dev_lobe_weights: lobe_weight_of as k_shade_g<.., TEX, ., MASK> (TEXTURED) or k_shade_g<PERHIT> (scenes without a texture table) resolves it
@@ -1822,6 +1872,12 @@ __global__ void k_remap_light_tris(DevLightTri* __restrict__ lt, uint32_t n, con
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < n && lt[i].smooth) lt[i].prim = elem_of_prim[lt[i].prim];
 }
+// (every primitive has a record: both builders make each of the n primitives, zero-area ones included, the one triangle of a leaf and write
+// elem_of_prim[p] with it -- bvh_build.cpp: the collapse's leaf children, bvh_gpu.hip: k_collapse -- which k_remap_light_tris relies on too)
+__global__ void k_remap_flat_light_tris(DevLightTri* __restrict__ lt, uint32_t n, const uint32_t* __restrict__ elem_of_prim) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n && !lt[i].smooth) lt[i].prim = elem_of_prim[lt[i].prim];
+}
 }  // namespace
 void launch_build_shade_recs(hipStream_t stream, const TriRec* tris, const uint32_t* elem_of_prim, float4* elem_shade, uint32_t num_prims) {
   if (num_prims) hipLaunchKernelGGL(k_build_shade_recs, dim3((num_prims + 255) / 256), dim3(256), 0, stream, tris, elem_of_prim, elem_shade, num_prims);
@@ -1834,6 +1890,9 @@ void launch_permute_uvs(hipStream_t stream, const float2* prim_uv, const uint32_
 }
 void launch_remap_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32_t num_light_tris, const uint32_t* elem_of_prim) {
   if (num_light_tris) hipLaunchKernelGGL(k_remap_light_tris, dim3((num_light_tris + 255) / 256), dim3(256), 0, stream, light_tris, num_light_tris, elem_of_prim);
+}
+void launch_remap_flat_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32_t num_light_tris, const uint32_t* elem_of_prim) {
+  if (num_light_tris) hipLaunchKernelGGL(k_remap_flat_light_tris, dim3((num_light_tris + 255) / 256), dim3(256), 0, stream, light_tris, num_light_tris, elem_of_prim);
 }
 void launch_film(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples, float inv) {
   hipLaunchKernelGGL(k_film, dim3((pb.num_pixels + PHX_FILM_PIX - 1) / PHX_FILM_PIX), dim3(256), 0, stream, pb, num_samples, inv);
@@ -1865,6 +1924,9 @@ void launch_lobe_weights(hipStream_t stream, const DevMaterial* mat, const DevTe
 }
 void launch_light_sample(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf) {
   hipLaunchKernelGGL(k_light_sample, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, light, tri, bary, P, pdf);
+}
+void launch_light_emission(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, float* st, float* e) {
+  hipLaunchKernelGGL(k_light_emission, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, st, e);
 }
 void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
   hipLaunchKernelGGL(k_texture_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, n, st, rgb);

@@ -80,7 +80,7 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
   const bool lights_by_area = opt.light_sampling == PHX_LIGHTS_BY_AREA;
 
   // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
-  // non-emitting materials may carry one (textured emission is not supported)
+  // non-emitting materials may carry one (an emitter's image is on its emission: emission_uv_texture)
   if (s.num_textures && !s.textures) return refuse("scene with textures but a null texture table");
   uint64_t total_texels = 0;
   for (uint32_t t = 0; t < s.num_textures; ++t) {
@@ -94,7 +94,8 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
     total_texels += (uint64_t)T.width * T.height;
   }
   if (total_texels > (1ull << 30)) return refuse("textures too large (at most 2^30 texels in all)");
-  bool any_tex = false, any_mask = false;  // any_tex: some lobe reads an image at the hit's UV (colour texture or mask)
+  bool any_tex = false, any_mask = false;  // any_tex: some lobe reads an image at the hit's UV (colour texture or mask), or some emitter's emission does
+  bool any_emit_tex = false;
   for (uint32_t i = 0; i < s.num_materials; ++i) {
     const phx_material& m = s.materials[i];
     for (uint32_t k = 0; k < m.num_lobes && k < PHX_MAX_LOBES; ++k) {
@@ -114,11 +115,18 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
       if (emits) return refuse(material(i) + ": textures on emitters / the environment are not supported");
       any_tex = true;
     }
-    // an environment map: only on the environment material (textured surface emission would need UVs at NEE's light samples)
+    // an environment map: only on the environment material (a surface emitter's image is emission_uv_texture, below)
     if (m.emission_mapping > PHX_ENV_LATLONG_Z_UP) return refuse(material(i) + ": unknown emission_mapping");
     if (m.emission_texture) {
       if ((int32_t)i != s.environment_material) return refuse(material(i) + ": emission_texture is allowed only on the environment material");
       if (m.emission_texture > s.num_textures) return refuse(material(i) + ": emission_texture index out of range");
+    }
+    // an image on a surface emitter's emission, read at mesh UVs (at hits and at next-event estimation's light samples)
+    if (m.emission_uv_texture) {
+      if ((int32_t)i == s.environment_material) return refuse(material(i) + ": emission_uv_texture is not allowed on the environment material (its image is emission_texture)");
+      if (!m.is_emitter) return refuse(material(i) + ": emission_uv_texture is allowed only on emitters");
+      if (m.emission_uv_texture > s.num_textures) return refuse(material(i) + ": emission_uv_texture index out of range");
+      any_tex = any_emit_tex = true;
     }
   }
 
@@ -197,6 +205,9 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
   for (uint32_t i = 0; i < s.num_materials; ++i)
     if (!bake_material(s.materials[i], L5, mats[i], out.lobe_tex.data() + 8 * (size_t)i)) return refuse("material with an unknown closure id");
   out.mat_masked.assign(s.num_materials, 0);
+  out.any_emit_tex = any_emit_tex;
+  out.mat_emit_tex.resize(s.num_materials);
+  for (uint32_t i = 0; i < s.num_materials; ++i) out.mat_emit_tex[i] = s.materials[i].emission_uv_texture;
   for (uint32_t i = 0; i < s.num_materials; ++i)
     for (uint32_t k = 0; k < mats[i].num_lobes; ++k) if (mats[i].lobes[k].fac_mode >= PHX_FAC_TEX_B) out.mat_masked[i] = 1;
 

@@ -20,7 +20,7 @@ struct FlatScene {
   std::vector<float> abc;               // 9 floats per primitive
   std::vector<uint32_t> prim_material;  // material | smooth << 31
   std::vector<float> prim_normals;      // any_smooth: 9 floats per primitive (zero on flat faces)
-  std::vector<float2> prim_uv;          // SC_TEX_LOBES: 3 corner UVs per primitive
+  std::vector<float2> prim_uv;          // SC_TEX_LOBES: 3 corner UVs per primitive (lobes' images, masks and emitters' images read them)
   bool any_smooth = false;
   std::vector<DevLight> lights;         // one per emissive face set; its triangles are light_tris[first_tri ...] in face order
   std::vector<DevLightTri> light_tris;
@@ -29,6 +29,8 @@ struct FlatScene {
   std::vector<uint32_t> lobe_tex;       // 8 per material: texture + 1 of baked lobe k
   std::vector<DevMatLite> mat_lite;     // diffuse_only == 2: the 32-byte table
   std::vector<uint8_t> mat_masked;      // per material: some lobe's factor is an image mask
+  std::vector<uint32_t> mat_emit_tex;   // per material: the image on its emission + 1 (phx_material.emission_uv_texture), 0 = none
+  bool any_emit_tex = false;            // some emitter has one: the scene has SC_TEX_LOBES whatever its lobes
   std::vector<DevTexture> textures;     // the texture table and every texel as RGB + 0: packed only when scene.any_tex & SC_TEX_ANY
   std::vector<float4> texels;
   uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission

@@ -17,6 +17,9 @@ Image textures (texture_node, baked by closures.py): `filename` is resolved rela
 binary PPM (P6, 8 bit, value / 255), PFM (rows flipped to top first), Radiance `.hdr` (RGBE, flat or new-style run-length scanlines,
 `-Y H +X W` only) or `.npy` ((H, W, 3) or (H, W) float) — as linear RGB.
 
+Textured emitters (texture_node into a diffuse_emitter_node's Cs) load only with `load_scene(..., emitter_textures=True)`: the image
+multiplies the emission at the mesh's UVs (phx_material.emission_uv_texture).
+
 Environment maps (environment_node into the world material's background_node.Cs): `world: {environment: <material>, environment-up: y|z}`
 selects OpenImageIO's lat-long layout with +y (the default) or +z up (phx_material.emission_mapping).
 """
@@ -261,11 +264,13 @@ def look_at(position, at, up):
     return m.astype(np.float32)
 
 
-def load_scene(path, width=1280, height=720):
+def load_scene(path, width=1280, height=720, emitter_textures=False):
+    """emitter_textures: bake texture_node.Cout -> diffuse_emitter_node.Cs into MaterialDesc.emission_uv_texture (closures.bake_material);
+    such a graph is refused by default."""
     cfg = yaml.safe_load(open(path))
     base = os.path.dirname(os.path.abspath(path))
     tex_specs = []
-    baked = closures.bake_materials(cfg["materials"], tex_specs)
+    baked = closures.bake_materials(cfg["materials"], tex_specs, emitter_textures)
     textures = [TextureDesc(load_image(os.path.join(base, t["filename"])), abi.TEX_LINEAR, t["swrap"], t["twrap"]) for t in tex_specs]
     names = list(baked)
     ids = {n: i for i, n in enumerate(names)}
@@ -292,6 +297,8 @@ def load_scene(path, width=1280, height=720):
     for i, m in enumerate(mats):
         if m.emission_texture and i != env:
             raise ValueError(f"{path}: material {names[i]!r} has an environment map but is not the world's environment")
+        if m.emission_uv_texture and i == env:
+            raise ValueError(f"{path}: material {names[i]!r} has a textured emitter but is the world's environment (use an environment_node)")
     if env >= 0:
         mats[env].emission_mapping = abi.ENV_LATLONG_Z_UP if up == "z" else abi.ENV_LATLONG_Y_UP
     return SceneDesc(meshes, mats, camera, environment_material=env, name=os.path.basename(path), textures=textures)

@@ -37,6 +37,7 @@ class MaterialDesc:
     is_emitter: bool = False
     emission_texture: int = 0   # environment map: k = textures[k - 1] (the environment material only), 0 = none
     emission_mapping: int = abi.ENV_LATLONG_Y_UP  # abi.ENV_LATLONG_*
+    emission_uv_texture: int = 0  # emitters only: the emission is multiplied by textures[k - 1] at mesh UVs (hits and light samples), 0 = none
 
 
 @dataclass
@@ -115,6 +116,7 @@ class SceneDesc:
             mats[i].is_emitter = 1 if m.is_emitter else 0
             mats[i].emission[:] = [np.float32(x) for x in m.emission]
             mats[i].emission_texture, mats[i].emission_mapping = m.emission_texture, m.emission_mapping
+            mats[i].emission_uv_texture = m.emission_uv_texture
             for j, l in enumerate(m.lobes):
                 d = mats[i].lobes[j]
                 d.type = l.type

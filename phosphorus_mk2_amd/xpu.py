@@ -333,6 +333,17 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_light_sample(self._h, k, fp(u3), up(light), up(tri), fp(bary), fp(P), fp(pdf)), "phx_dev_light_sample")
         return {"light": light, "tri": tri, "bary": bary, "P": P, "pdf": pdf}
 
+    def light_emission(self, u3):
+        """The emission next-event estimation uses at the light samples of light_sample(u3): u3 (n, 3) = (pick, lu, lv) per item -> dict of
+        st (n, 2) f32, the sampled point's texture coordinates by the rule of phx_material.emission_uv_texture, and e (n, 3) f32, the light's
+        emission times its image's texel there.  A light without an image: its constant emission and st = (0, 0).  phx_dev_light_emission."""
+        u3 = np.ascontiguousarray(u3, np.float32).reshape(-1, 3)
+        k = len(u3)
+        st = np.zeros((k, 2), np.float32); e = np.zeros((k, 3), np.float32)
+        fp = lambda a: a.ctypes.data_as(abi.f32p)
+        _check(self._lib, self._lib.phx_dev_light_emission(self._h, k, fp(u3), fp(st), fp(e)), "phx_dev_light_emission")
+        return {"st": st, "e": e}
+
     def texture_lookup(self, texture, st):
         """The shade kernel's image lookup on the device: texture `texture` (0-based index into SceneDesc.textures of the preprocessed
         scene, which must have a textured lobe) at st (n, 2) -> rgb (n, 3) f32."""

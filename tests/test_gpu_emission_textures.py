@@ -1,0 +1,363 @@
+"""Textured surface emission on the device (phx_material.emission_uv_texture: hit_emission / light_emission in kernels.hip, run by the 18
+k_shade_g<.., TEX> instantiations and by phx_dev_light_emission).  The oracle knows no image, so the feature is held to: the numpy
+restatement of tests/test_emission_textures.py, bit for bit, through the parity hook; the oracle's films of twin scenes that carry
+fp32(e * texel) as constant emissions, bit for bit, wherever every sample of a light reads one texel; and closed forms of direct lighting
+under a striped lamp, which tell the rule's (s, t) at a light sample from the reference's rotated one."""
+import copy
+
+import numpy as np
+import pytest
+
+from conftest import bits_equal
+from phosphorus_mk2_amd import abi, scenes
+from test_analytic_direct_light import LAMP, RHO, SPP, W
+from test_emission_textures import (ATLAS, LE_PANEL, ROOM_DEPTH, ROOM_SPP, SEED, STRIPES, atlas_room, lamp_image_box, light_emission, pixels_differing, striped_moments,
+                                    striped_quad, striped_sets, within_bounds)
+from test_gpu_light_sampling import three_lights_scene
+from test_gpu_shade_kernels import DEPTH as T_DEPTH, FAMILIES, SEED as T_SEED, SPP as T_SPP, build, expected_kernels
+from test_light_sampling import QUAD, LightTable, _camera, _floor, light_sample, rects_mesh
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+COUNTERS = ("camera_samples", "rays_closest", "rays_shadow", "rays_masked")
+TOP = F(1) - F(2.0 ** -24)
+
+
+@pytest.fixture(scope="module")
+def xpu():
+    from phosphorus_mk2_amd import xpu
+    xpu.load_library()
+    return xpu
+
+
+def _differing(got, want, n):
+    return (np.asarray(got).reshape(n, -1).view(np.uint32) != np.asarray(want).reshape(n, -1).view(np.uint32)).any(1).sum()
+
+
+# ---- 6. the hook is the restatement, bit for bit -------------------------------------------------------------------------------------------
+IMG53 = np.random.default_rng(41).uniform(0.05, 3.0, (3, 5, 3)).astype(F)
+
+
+def random_lamp(filter=abi.TEX_LINEAR, swrap=abi.WRAP_PERIODIC, twrap=abi.WRAP_PERIODIC, per_vertex=True, uvs=True, lo=0.0, hi=1.0, smooth=False):
+    """a lamp of 5 triangles of unequal size over the floor of test_light_sampling under IMG53, random UVs over [lo, hi]^2 per vertex or
+    per face corner (or none); smooth: its third triangle interpolates per-corner normals"""
+    rng = np.random.default_rng(42)
+    c = rng.uniform(-0.5, 0.5, (5, 1, 3)) + np.array([0.0, 1.2, 0.0])
+    v = (c + rng.uniform(-0.4, 0.4, (5, 3, 3))).astype(F).reshape(-1, 3)
+    f = np.arange(15, dtype=np.uint32).reshape(5, 3)
+    f[3] = (9, 3, 4)  # a face that shares vertices with another: per-vertex and per-corner UVs then differ in more than order
+    flags = abi.MESH_NORMALS_PER_VERTEX | (abi.MESH_UV_PER_VERTEX if per_vertex else 0)
+    uv = None
+    if uvs:
+        uv = rng.uniform(lo, hi, (15, 2)).astype(F)
+    lamp = scenes.MeshDesc(vertices=v, faces=f, sets=[(1, np.arange(5, dtype=np.uint32))], flags=flags, uvs=uv)
+    if smooth:
+        lamp.flags &= ~abi.MESH_NORMALS_PER_VERTEX
+        n = rng.normal(size=(15, 3)); n[:, 1] = -np.abs(n[:, 1]) - 1.0
+        lamp.normals = (n / np.linalg.norm(n, axis=1, keepdims=True)).astype(F)
+        lamp.smooth = np.array([0, 0, 1, 0, 0], np.uint8)
+    mats = [scenes.diffuse(RHO, RHO, RHO), scenes.MaterialDesc([], (3.0, 2.0, 1.0), True, emission_uv_texture=1)]
+    return scenes.SceneDesc(_floor() + [lamp], mats, _camera(), name="random_lamp", textures=[scenes.TextureDesc(IMG53, filter, swrap, twrap)])
+
+
+def three_lights_one_image():
+    """test_gpu_light_sampling's lights of 1, 2 and 37 triangles (first_tri 0, 1, 3), of which only the second has an image"""
+    sc = three_lights_scene()
+    sc.textures = [scenes.TextureDesc(np.full((1, 1, 3), 9.0, F)), scenes.TextureDesc(IMG53, abi.TEX_LINEAR)]
+    two = sc.meshes[-2]
+    assert [m for m, _ in two.sets] == [2] and len(two.vertices) == 4
+    two.uvs = np.array([[0.1, 0.9], [0.2, 0.1], [0.8, 0.3], [0.7, 0.8]], F)
+    sc.materials[2].emission_uv_texture = 2
+    return sc
+
+
+HOOK_SCENES = {
+    "striped_s": lambda: striped_quad("s"),                                                                          # (a)
+    "striped_t": lambda: striped_quad("t"),
+    "three_lights": three_lights_one_image,                                                                            # (b)
+    "per_vertex_linear": lambda: random_lamp(abi.TEX_LINEAR, per_vertex=True),                                         # (c), (e)
+    "per_corner_closest": lambda: random_lamp(abi.TEX_CLOSEST, per_vertex=False),                                      # (d), (e)
+    "periodic": lambda: random_lamp(abi.TEX_LINEAR, abi.WRAP_PERIODIC, abi.WRAP_PERIODIC, lo=-0.7, hi=1.8),           # (f)
+    "clamp": lambda: random_lamp(abi.TEX_CLOSEST, abi.WRAP_CLAMP, abi.WRAP_CLAMP, lo=-0.7, hi=1.8),
+    "black": lambda: random_lamp(abi.TEX_LINEAR, abi.WRAP_BLACK, abi.WRAP_BLACK, per_vertex=False, lo=-0.7, hi=1.8),
+    "mixed_wraps": lambda: random_lamp(abi.TEX_CLOSEST, abi.WRAP_BLACK, abi.WRAP_PERIODIC, lo=-0.7, hi=1.8),
+    "no_uvs": lambda: random_lamp(uvs=False),                                                                          # (g)
+    "smooth": lambda: random_lamp(per_vertex=False, smooth=True),                                                      # (h)
+}
+
+
+def hook_draws(sc):
+    """2^16 random triples; per light lu, lv in {0, 1 - 2^-24}; and on the striped lamp the draws whose st lies on a stripe's border (with
+    lv = 0 the sample's weight on the triangle's c corner is sqrt(remapped): k / 4 at remapped = k^2 / 16), with their neighbours"""
+    t = LightTable(sc)
+    rng = np.random.default_rng(43)
+    u3 = [rng.random((1 << 16, 3), dtype=F)]
+    for k in range(t.n):
+        pick = F((k + 0.5) / t.n)
+        u3.append(np.array([[pick, lu, lv] for lu in (F(0), TOP) for lv in (F(0), TOP)], F))
+        u3.append(np.stack([np.full(64, pick), rng.random(64, dtype=F), np.zeros(64, F)], -1))
+    if sc.name.startswith("striped_quad"):
+        for tri in (0, 1):
+            for k in (1, 2, 3):
+                lu = F(0.5 * tri + k * k / 32.0)
+                for x in (np.nextafter(lu, F(-1)), lu, np.nextafter(lu, F(2))):
+                    u3 += [np.array([[0.5, x, lv]], F) for lv in (F(0), TOP, F(0.5))]
+    return np.concatenate(u3).astype(F)
+
+
+# every scene under the reference pick; the lights of unequal triangles under the pick by area too (light_emission behind light_pick's other branch)
+HOOK_CASES = [(n, "reference") for n in HOOK_SCENES] + [(n, "area") for n in ("per_corner_closest", "black", "smooth")]
+
+
+@pytest.mark.parametrize("name,mode", HOOK_CASES, ids=[n if m == "reference" else f"{n}-by_area" for n, m in HOOK_CASES])
+def test_hook_is_the_restatement_bit_for_bit(xpu, name, mode):
+    sc = HOOK_SCENES[name]()
+    u3 = hook_draws(sc)
+    dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=1, paths_per_sample=1, path_depth=1, light_sampling=mode))
+    try:
+        with pytest.raises(xpu.DeviceError) as e:
+            dev.light_emission(u3[:4])
+        assert "(4)" in str(e.value)  # PHX_ERR_STATE before preprocess
+        dev.preprocess(sc)
+        got = dev.light_emission(u3)
+        sample = dev.light_sample(u3)
+    finally:
+        dev.close()
+    want = light_emission(sc, u3, by_area=mode == "area")
+    t = LightTable(sc)
+    want_sample = light_sample(t, u3, mode == "area")
+    if mode == "area":
+        assert not t.equal_pairs_only() and not bits_equal(want["st"], light_emission(sc, u3)["st"])  # the two picks differ on this scene
+    assert set(np.unique(want_sample["light"])) == set(range(t.n))
+    failed = [f"{key}: {_differing(got[key], want[key], len(u3))} of {len(u3)} differ" for key in ("st", "e") if not bits_equal(got[key], want[key])]
+    # phx_dev_light_sample returns what it returned before on the same scene
+    failed += [f"light_sample {key}: {_differing(sample[key], want_sample[key], len(u3))} of {len(u3)} differ"
+               for key in ("light", "tri", "bary", "P", "pdf") if not bits_equal(sample[key], want_sample[key])]
+    assert not failed, "\n".join(failed)
+    assert np.isfinite(got["e"]).all() and np.isfinite(got["st"]).all()
+    imaged = np.array([bool(sc.materials[m].emission_uv_texture) for m in [mat for ms in sc.meshes for mat, f in ms.sets if sc.materials[mat].is_emitter and len(f)]])[want_sample["light"]]
+    if name == "no_uvs":
+        assert not got["st"].any() and len(np.unique(got["e"], axis=0)) == 1  # st = (0, 0): one texel
+    else:
+        assert len(np.unique(got["e"][imaged], axis=0)) > 3  # the image is seen
+    assert not got["st"][~imaged].any()  # a light without an image: st = (0, 0) and its constant e
+    if name == "three_lights":
+        assert (~imaged).any() and all((got["e"][want_sample["light"] == k] == np.array(sc.materials[1 + k].emission, F)).all() for k in (0, 2))
+
+
+def test_a_scene_without_emitter_images_returns_the_constant_emission(xpu):
+    sc = scenes.cornell(16, 16)
+    u3 = np.random.default_rng(5).random((256, 3), dtype=F)
+    dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=1, paths_per_sample=1, path_depth=1))
+    try:
+        dev.preprocess(sc)  # k_shade<2>'s scene: no texture record at all
+        got = dev.light_emission(u3)
+    finally:
+        dev.close()
+    assert not got["st"].any() and (got["e"] == np.array(scenes.LE, F)).all()
+
+
+def test_a_smooth_light_triangle_keeps_its_normal(xpu, orc):
+    """(h) on the film: the remap of the flat light triangles to pool elements left the smooth one's vertex normals where they were.  The lamp's
+    UVs lie inside one texel, so the oracle's twin carries e * texel as its emission."""
+    st = random_lamp(abi.TEX_CLOSEST, per_vertex=False, smooth=True)
+    st.meshes[-1].uvs = np.tile(np.array([[0.5, 0.5]], F), (15, 1))  # the centre of texel (2, 1) of the 5 x 3 image
+    sb = copy.deepcopy(st)
+    sb.textures = []
+    sb.materials[1] = scenes.emitter(*(float(F(e) * c) for e, c in zip(st.materials[1].emission, IMG53[1, 2])))
+    film, s = xpu.render(st, spp=16, pps=1, depth=3, seed=SEED)
+    ref, ost = orc.Oracle(sb, spp=16, pps=1, depth=3).render(rng=orc.RNG_COUNTER, seed=SEED, threads=4)
+    assert all(s[k] == ost[k] for k in COUNTERS) and film[..., :3].max() > 0.05
+    assert bits_equal(film[..., :3], ref[..., :3])
+    flat = copy.deepcopy(sb); flat.meshes[-1].smooth[:] = 0
+    other, _ = orc.Oracle(flat, spp=16, pps=1, depth=3).render(rng=orc.RNG_COUNTER, seed=SEED, threads=4)
+    assert pixels_differing(ref, other) > 0.25  # the smooth normal reaches the film
+
+
+# ---- 7. atlas parity, bit for bit -----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def room_oracle(orc):
+    orc.set_tie_rule(1)
+    done = {}
+
+    def get(mode, lens):
+        if (mode, lens) not in done:
+            done[(mode, lens)] = orc.Oracle(atlas_room(mode, lens), spp=ROOM_SPP, pps=1, depth=ROOM_DEPTH).render(rng=orc.RNG_COUNTER, seed=SEED, threads=8)
+        return done[(mode, lens)]
+    yield get
+    orc.set_tie_rule(0)
+
+
+@pytest.mark.parametrize("builder", ["device", "host"])
+@pytest.mark.parametrize("flight", [0, 4])
+@pytest.mark.parametrize("lens", [False, True], ids=["pinhole", "lens"])
+def test_atlas_room_is_the_oracles_twin(xpu, room_oracle, lens, flight, builder):
+    film, st = xpu.render(atlas_room("atlas", lens), spp=ROOM_SPP, pps=1, depth=ROOM_DEPTH, seed=SEED, samples_in_flight=flight, bvh_builder=builder)
+    ref, ost = room_oracle("twin", lens)
+    failed = [f"{k}: {st[k]}, the oracle's {ost[k]}" for k in COUNTERS if st[k] != ost[k]]
+    family = abi.SHADE_FAMILY_GENERAL + (abi.SHADE_G_TEX | abi.SHADE_G_PERHIT)  # no lobe is textured: the emitter's image alone selects TEX
+    if st["shade_kernels"] != expected_kernels(family, lens):
+        failed.append(f"launched {abi.shade_kernel_names(st['shade_kernels'])}, expected {abi.shade_kernel_names(expected_kernels(family, lens))}")
+    if not (np.isfinite(film).all() and film[..., :3].max() > 0.05):
+        failed.append("the film is dark or not finite")
+    if not bits_equal(film[..., :3], ref[..., :3]):
+        failed.append(f"the film differs from the oracle's twin in {pixels_differing(film, ref):.1%} of the pixels")
+    # the image reaches the film: the atlas replaced by its mean texel changes at least a quarter of the pixels, on the device as on the oracle
+    mean, _ = xpu.render(atlas_room("mean", lens), spp=ROOM_SPP, pps=1, depth=ROOM_DEPTH, seed=SEED, samples_in_flight=flight, bvh_builder=builder)
+    changed, oracle_changed = pixels_differing(film, mean), pixels_differing(ref, room_oracle("mean_twin", lens)[0])
+    print(f"atlas against its mean texel: {changed:.1%} of the device's pixels differ, {oracle_changed:.1%} of the oracle's")
+    if not (changed >= 0.25 and oracle_changed >= 0.25):
+        failed.append(f"the atlas changes {changed:.1%} of the pixels ({oracle_changed:.1%} of the oracle's), not a quarter")
+    assert not failed, "\n".join(failed)
+
+
+# ---- 8. the branch through all 18 changed kernels ----------------------------------------------------------------------------------------------
+TEX_FAMILIES = ("tex", "tex_perhit", "env_tex", "env_tex_perhit", "mask", "mask_env")
+LAMP_ATLAS = np.array([[[7.0, 0.01, 0.3], [0.02, 9.0, 0.5], [0.75, 0.5, 1.25], [0.3, 0.04, 8.0]],
+                       [[5.0, 5.0, 0.01], [0.01, 0.6, 6.0], [9.0, 0.02, 0.02], [0.05, 7.0, 7.0]]], F)
+LAMP_TEXEL = (2, 0)  # column, row: (0.75, 0.5, 1.25), which no other image of the table's scenes holds
+
+
+def with_lamp_image(st, sb):
+    """every emitter of the table's scene `st` under LAMP_ATLAS (CLOSEST, appended behind the scene's images) read at LAMP_TEXEL, and the
+    oracle's scene `sb` with e * texel folded into each emitter's emission"""
+    st, sb = copy.deepcopy(st), copy.deepcopy(sb)
+    texel = LAMP_ATLAS[LAMP_TEXEL[1], LAMP_TEXEL[0]]
+    assert all((t.texels.reshape(-1, 3) != texel).any(-1).all() for t in st.textures)
+    st.textures = st.textures + [scenes.TextureDesc(LAMP_ATLAS, abi.TEX_CLOSEST)]
+    k = len(st.textures)
+    lamps = 0
+    for s, textured in ((st, True), (sb, False)):
+        for i, m in enumerate(s.materials):
+            if m.is_emitter:
+                assert i != s.environment_material
+                if textured:
+                    m.emission_uv_texture = k
+                else:
+                    m.emission = tuple(float(F(e) * c) for e, c in zip(m.emission, texel))
+    for m in st.meshes:
+        if any(st.materials[mat].is_emitter for mat, _ in m.sets):
+            assert all(st.materials[mat].is_emitter for mat, _ in m.sets) and not len(m.uvs), "a lamp is a mesh of its own, without UVs so far"
+            m.uvs = np.tile(np.array([[(LAMP_TEXEL[0] + 0.5) / 4, (LAMP_TEXEL[1] + 0.5) / 2]], F), (len(m.vertices), 1))
+            m.flags |= abi.MESH_UV_PER_VERTEX
+            lamps += 1
+    assert lamps >= 1
+    return st, sb
+
+
+@pytest.mark.parametrize("lens", [False, True], ids=["pinhole", "lens"])
+@pytest.mark.parametrize("name", TEX_FAMILIES)
+def test_every_tex_family_shades_an_emitter_image(xpu, orc, name, lens):
+    base_t, base_b = build(name, lens)
+    st_scene, sb_scene = with_lamp_image(base_t, base_b)
+    film, st = xpu.render(st_scene, spp=T_SPP, pps=1, depth=T_DEPTH, seed=T_SEED)
+    orc.set_tie_rule(1)
+    try:
+        ref, ost = orc.Oracle(sb_scene, spp=T_SPP, pps=1, depth=T_DEPTH).render(rng=orc.RNG_COUNTER, seed=T_SEED, threads=8)
+        plain, _ = orc.Oracle(base_b, spp=T_SPP, pps=1, depth=T_DEPTH).render(rng=orc.RNG_COUNTER, seed=T_SEED, threads=8)
+    finally:
+        orc.set_tie_rule(0)
+    family = FAMILIES[name][0]
+    failed = [f"{k}: {st[k]}, the oracle's {ost[k]}" for k in COUNTERS if st[k] != ost[k]]
+    if st["shade_kernels"] != expected_kernels(family, lens):
+        failed.append(f"launched {abi.shade_kernel_names(st['shade_kernels'])}, expected {abi.shade_kernel_names(expected_kernels(family, lens))}")
+    if not (np.isfinite(film).all() and film[..., :3].max() > 0.05):
+        failed.append("the film is dark or not finite")
+    if not bits_equal(film[..., :3], ref[..., :3]):
+        failed.append(f"the film differs from the oracle's in {pixels_differing(film, ref):.1%} of the pixels")
+    if not pixels_differing(ref, plain) > 0.25:
+        failed.append("the lamp's texel does not reach the oracle's film")
+    assert not failed, f"{name}, {'lens' if lens else 'pinhole'}:\n" + "\n".join(failed)
+
+
+# ---- 9. the striped lamp on the device ------------------------------------------------------------------------------------------------------
+def test_striped_lamp_of_four_sets_is_the_oracles_twin_and_meets_the_closed_form(xpu, orc):
+    film, st = xpu.render(striped_sets(True), spp=SPP, pps=1, depth=1, seed=SEED)
+    ref, ost = orc.Oracle(striped_sets(False), spp=SPP, pps=1, depth=1).render(rng=orc.RNG_COUNTER, seed=SEED, threads=4)
+    assert st["rays_shadow"] == st["rays_closest"] == W * W * SPP == ost["rays_closest"]
+    assert st["shade_kernels"] == 1 << abi.shade_kernel_bit(abi.SHADE_FAMILY_GENERAL + abi.SHADE_G_TEX, abi.SHADE_PASS_CAMERA)  # depth 1: the camera rays' pass alone
+    assert bits_equal(film[..., :3], ref[..., :3]), f"{pixels_differing(film, ref):.1%} of the pixels differ from the oracle's four-lamp twin"
+    mean, m2 = striped_moments("sets")
+    assert within_bounds(film, mean, m2, "four sets")
+
+
+@pytest.mark.parametrize("axis", ["s", "t"])
+def test_striped_lamp_of_one_light_meets_the_closed_form(xpu, axis):
+    """THE test of the light sample's (s, t): one light of two triangles with UVs over [0, 1]^2 under four stripes, along x ("s") or along z
+    ("t": every stripe crosses the triangles' shared diagonal).  No oracle twin exists for it (one light cannot carry four emissions): it is
+    held to the closed form sum_k c_k G(strip k) alone, within 4 standard errors of the film mean and 5 of a pixel.  Without the feature the
+    lamp is constant; under the reference's rotated (s, t) each triangle's stripes land on other points of it.  Both miss the pixel bound by
+    far (DESIGN section 13 records the figures)."""
+    film, st = xpu.render(striped_quad(axis), spp=SPP, pps=1, depth=1, seed=SEED)
+    assert st["rays_shadow"] == st["rays_closest"] == W * W * SPP
+    mean, m2 = striped_moments(axis)
+    assert within_bounds(film, mean, m2, f"one light, stripes along {axis}")
+    assert not within_bounds(film, *striped_moments("t" if axis == "s" else "s"), "against the other axis' model")  # ... and it is not the other axis' film
+
+
+# ---- 10. refusals through the C ABI; scenes without emitter images are untouched -------------------------------------------------------------
+def test_bad_emitter_images_are_refused_and_the_device_keeps_its_scene(xpu):
+    good = lamp_image_box()
+
+    def not_an_emitter(s):
+        s.materials[0].emission_uv_texture = 1
+
+    def on_the_environment(s):
+        s.materials.append(scenes.MaterialDesc([], (0.5, 0.5, 0.5), is_emitter=True, emission_uv_texture=1))
+        s.environment_material = len(s.materials) - 1
+
+    def past_the_table(s):
+        s.materials[3].emission_uv_texture = 2
+
+    dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=4, paths_per_sample=1, path_depth=9))
+    try:
+        def frame():
+            film = xpu.Film(32, 32, 4)
+            dev.start(good, xpu.FrameState(1, xpu.Tiles.make(32, 32, 32), film)); dev.join()
+            return film.data.copy(), dev.stats()
+        dev.preprocess(good)
+        ref, st = frame()
+        assert ref[..., :3].max() > 0.05 and st["shade_kernels"] == expected_kernels(abi.SHADE_FAMILY_GENERAL + abi.SHADE_G_TEX, False)
+        u3 = np.random.default_rng(2).random((64, 3), dtype=F)
+        hook = dev.light_emission(u3)
+        for bad in (not_an_emitter, on_the_environment, past_the_table):
+            s = copy.deepcopy(good)
+            bad(s)
+            with pytest.raises(xpu.DeviceError) as e:
+                dev.preprocess(s)
+            assert "(1)" in str(e.value) and "emission_uv_texture" in str(e.value), bad.__name__  # PHX_ERR_ARG with a message
+            again, st2 = frame()  # the previous scene is still there: no second preprocess
+            assert bits_equal(again, ref) and all(st[k] == st2[k] for k in COUNTERS), bad.__name__
+            assert bits_equal(dev.light_emission(u3)["e"], hook["e"])
+    finally:
+        dev.close()
+    # the image reaches the film, and its bytes are counted: texture table, texels, corner UVs, lobe_tex, the record and the per-material words
+    plain = scenes.cornell(32, 32)
+    film0, st0 = xpu.render(plain, spp=4, pps=1, depth=9, seed=1)
+    assert pixels_differing(film0, ref) > 0.25
+    assert st["device_bytes"] > st0["device_bytes"]
+
+
+def test_scenes_without_emitter_images_render_what_they_rendered(xpu, orc):
+    """the Cornell box (k_shade<2>) bit for bit against the oracle, and a textured scene whose emitters have no image (the TEX kernels with
+    the branch not taken) against its baked oracle scene"""
+    sc = scenes.cornell(64, 48)
+    film, st = xpu.render(sc, spp=8, pps=1, depth=9, seed=3)
+    ref, ost = orc.Oracle(sc, spp=8, pps=1, depth=9).render(rng=orc.RNG_COUNTER, seed=3, threads=4)
+    assert bits_equal(film[..., :3], ref[..., :3]) and all(st[k] == ost[k] for k in COUNTERS)
+    assert st["shade_kernels"] == expected_kernels(abi.SHADE_FAMILY_LAMBERT1, False)
+    # a zero field on every material is the parent's scene: device_bytes holds no per-material emission words
+    tex_t, tex_b = build("tex", False)
+    assert not any(m.emission_uv_texture for m in tex_t.materials)
+    film, st = xpu.render(tex_t, spp=8, pps=1, depth=9, seed=3)
+    orc.set_tie_rule(1)
+    try:
+        ref, ost = orc.Oracle(tex_b, spp=8, pps=1, depth=9).render(rng=orc.RNG_COUNTER, seed=3, threads=8)
+    finally:
+        orc.set_tie_rule(0)
+    assert bits_equal(film[..., :3], ref[..., :3]) and all(st[k] == ost[k] for k in COUNTERS)
+    with_image, _ = with_lamp_image(tex_t, tex_b)
+    _, st_img = xpu.render(with_image, spp=8, pps=1, depth=9, seed=3)
+    # what the emitter image adds to a scene that is textured already: its texels (16 B each) and table entry, and one word per material
+    assert st_img["device_bytes"] - st["device_bytes"] == 16 * 8 + 16 + 4 * len(tex_t.materials)
