@@ -3,9 +3,11 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
+ * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
+ * light, so the film is the same again.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -67,6 +69,10 @@ int main(int argc, char** argv) {
   for (int i = 2; i < argc; ++i)
     if (strcmp(argv[i], "area-lights") == 0) {  /* taken out of the list: the other arguments keep their places */
       opt.light_sampling = PHX_LIGHTS_BY_AREA;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    } else if (strcmp(argv[i], "power-lights") == 0) {
+      opt.light_sampling = PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     }

@@ -62,7 +62,7 @@ typedef struct phx_options {
   uint32_t samples_in_flight; /* samples of one pixel carried per wavefront pass */
   uint32_t tiles_per_batch;   /* tiles pulled from the queue per pass */
   uint32_t bvh_builder;       /* PHX_BVH_AUTO (default), PHX_BVH_DEVICE_LBVH or PHX_BVH_HOST_SAH: where preprocess builds the tree */
-  uint32_t light_sampling;    /* PHX_LIGHTS_REFERENCE (default) or PHX_LIGHTS_BY_AREA: how next-event estimation picks a triangle of the chosen light */
+  uint32_t light_sampling;    /* PHX_LIGHTS_REFERENCE (default) or PHX_LIGHTS_BY_AREA: how next-event estimation picks a triangle of the chosen light; | PHX_LIGHT_SELECT_BY_POWER */
   uint32_t reserved[4];
 } phx_options;
 /* AUTO = the device builder (LBVH over extended Morton codes + the optimal 8-wide collapse) for every scene with at least 64
@@ -84,8 +84,34 @@ enum { PHX_BVH_AUTO = 0, PHX_BVH_DEVICE_LBVH = 1, PHX_BVH_HOST_SAH = 2 };
  *     and everything behind the pick is unchanged: triangle_t::sample(remapped, lv), P, lpdf, which is now the true density.  A triangle
  *     of zero area has cdf[i] == lo and is never chosen.  A light of one triangle, or of two whose fp32 areas are bit-equal (cdf = {0.5, 1}),
  *     is sampled bit for bit as under PHX_LIGHTS_REFERENCE; three or more equal triangles are not (3 * a rounds).  The scene is shaded by
- *     k_shade_g (phx_stats.shade_general = 1) whatever its closures.  Lights are still chosen uniformly, not by power. */
+ *     k_shade_g (phx_stats.shade_general = 1) whatever its closures.  Lights are chosen uniformly unless PHX_LIGHT_SELECT_BY_POWER (below,
+ *     DESIGN 14) is set in the same word. */
 enum { PHX_LIGHTS_REFERENCE = 0, PHX_LIGHTS_BY_AREA = 1 };
+/* The word is packed like phx_lobe.fac_mode: the low byte is the triangle pick above, bit 8 chooses how a LIGHT is selected.  The valid
+ * words are 0, 1 and 0x101 (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); every other word, 0x100 among them (selection by power needs the
+ * unbiased triangle pick), is PHX_ERR_ARG at phx_dev_preprocess.
+ *   PHX_LIGHT_SELECT_BY_POWER: a light by its power instead of uniformly.  Lights stay in the light table's order (mesh x face-set order);
+ *   all host arithmetic below is binary64, without contraction, in the order written.
+ *     weight   m_l = the per-channel mean of |texel| over ALL texels of the image named by the material's emission_uv_texture, summed
+ *              sequentially in row-major texel order and divided by W * H; (1, 1, 1) without an image.  With area_l and e the fp32 values of the
+ *              light's record widened to double,
+ *                w_l = area_l * ((0.2126 |e_r| m_r + 0.7152 |e_g| m_g) + 0.0722 |e_b| m_b)
+ *              The image mean stands for the light's true power: it ignores which part of the image the UVs show, and only ever affects variance.
+ *     totals   n+ = the number of lights with w_l > 0;  Wsum = sum of w_l, sequentially in light order.
+ *     fallback if any w_l is not finite, or n+ = 0: q_l = 1 / nlights (uniform selection through the same table; the scene is black or broken).
+ *     floor    q_l = w_l > 0 ? (1 - phi) w_l / Wsum + phi / n+ : 0, phi = PHX_LIGHT_POWER_FLOOR = 1/8.  Every lamp that emits anything keeps
+ *              q_l >= 1 / (8 n+), so the estimator's second moment is at most 8 x uniform selection's and 8/7 x pure power selection's, and a
+ *              24-bit draw realises such a probability to a relative 2^-24 * 8 n+.  A black lamp is never sampled.
+ *     table    acc_l = acc_{l-1} + q_l;  pcdf[l] = fp32(acc_l / acc_last): monotone, the last entry 1.0f exactly.
+ *     pick     l = the smallest index with pick < pcdf[l], or nlights - 1 when there is none (binary search);  lo = l ? pcdf[l - 1] : 0;
+ *              p_l = pcdf[l] - lo in fp32, and the light's density lpdf = (1.0f / area_l) * p_l in fp32, evaluated at preprocess.  `pick` is used
+ *              for nothing else; a light with p_l = 0 cannot be chosen.
+ *   Everything behind the pick is PHX_LIGHTS_BY_AREA's: the triangle by the area CDF, triangle_t::sample, P, the emission.  A scene with ONE
+ *   light has pcdf = {1}, l = 0 and lpdf = 1.0f / area: bit for bit what PHX_LIGHTS_BY_AREA alone renders. */
+enum { PHX_LIGHT_SELECT_BY_POWER = 0x100 };
+#define PHX_LIGHT_SAMPLING_MODE(x) ((x) & 0xffu)    /* PHX_LIGHTS_* */
+#define PHX_LIGHT_SELECTION(x) ((x) & ~0xffu)       /* 0 or PHX_LIGHT_SELECT_BY_POWER */
+#define PHX_LIGHT_POWER_FLOOR 0.125
 
 /* ---- scene: what the device reads through scene_t (src/scene.hpp:14-50) --------------- */
 

@@ -31,6 +31,7 @@ def fac_texture(word):
 
 BVH_AUTO, BVH_DEVICE_LBVH, BVH_HOST_SAH = 0, 1, 2
 LIGHTS_REFERENCE, LIGHTS_BY_AREA = 0, 1  # Options.light_sampling: a light's triangle by index (the reference) or by area
+LIGHT_SELECT_BY_POWER = 0x100  # bit 8 of the same word: the light by power, not uniformly (needs LIGHTS_BY_AREA in the low byte)
 MESH_UV_PER_VERTEX, MESH_NORMALS_PER_VERTEX = 1, 2
 TEX_LINEAR, TEX_CLOSEST = 0, 1
 WRAP_PERIODIC, WRAP_CLAMP, WRAP_BLACK = 0, 1, 2

@@ -310,6 +310,11 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   if (sc.stack_levels > PHX_MAX_BVH_DEPTH)
     return fail(PHX_ERR_ARG, "tree too deep: " + std::to_string(sc.stack_levels) + " levels, the traversal stack in LDS holds " + std::to_string(PHX_MAX_BVH_DEPTH));
   if ((rc = d->d_materials.upload(fs.materials))) return rc;
+  if (sc.any_tex & SC_LIGHTS_BY_POWER) {  // the selection table rides directly behind the light records (kernels.hip: light_pcdf), padded to whole records
+    const size_t nl = fs.lights.size();
+    fs.lights.resize(nl + (fs.light_pcdf.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
+    std::memcpy(static_cast<void*>(fs.lights.data() + nl), fs.light_pcdf.data(), fs.light_pcdf.size() * sizeof(float));
+  }
   if (sc.any_tex & SC_LIGHTS_BY_AREA) {  // the CDF rides behind the light table (kernels.hip: light_cdf): one float per light triangle, in records of the table's size
     const size_t nl = fs.lights.size();
     fs.lights.resize(nl + (fs.light_cdf.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});

@@ -21,7 +21,7 @@ namespace phx {
 
 // Light table (light_t::make_area, src/light.cpp:10-45).  What k_shade would otherwise fetch through three more dependent loads per
 // shaded hit is resolved once at preprocess, with the same fp32 operations the kernel would use: the pick pdf (1/area)/nlights
-// (spt.hpp:95-149), the light material's emission (material_t::evaluate's e) and, per triangle, the geometric normal of a flat face.
+// (spt.hpp:95-149; under PHX_LIGHT_SELECT_BY_POWER (1/area) * p_l, p_l the light's interval of the selection table), the light material's emission (material_t::evaluate's e) and, per triangle, the geometric normal of a flat face.
 struct DevLight { uint32_t first_tri, num_tris; float area; uint32_t material; float lpdf, ex, ey, ez; };                 // 32 B
 struct DevLightTri { float ax, ay, az, bx, by, bz, cx, cy, cz, nx, ny, nz; uint32_t prim, smooth, mesh_mat, face; };   // 64 B
 // A material of a scene in which every material is at most ONE Lambert lobe (the soups, the Cornell box): 32 B instead of 544
@@ -46,7 +46,10 @@ enum { SC_TEX_LOBES = 1u /* some lobe is textured or masked: TEX */, SC_TEX_ENV 
        SC_TEX_ANY = 7u,
        // not an image bit: PHX_LIGHTS_BY_AREA.  k_shade_g picks a light's triangle by the area CDF (light_pick); the scene then runs k_shade_g
        // (diffuse_only = 0) and `lights` has the CDF behind it
-       SC_LIGHTS_BY_AREA = 8u };
+       SC_LIGHTS_BY_AREA = 8u,
+       // PHX_LIGHT_SELECT_BY_POWER, always with SC_LIGHTS_BY_AREA: light_pick searches the selection table pcdf, which sits between the light
+       // records and the area CDF: num_lights floats, padded to whole records of the light table
+       SC_LIGHTS_BY_POWER = 16u };
 
 struct DevScene {
   const uint32_t* pool;           // the BVH8 pool: 16 words per element, element 0 = root nodelet (bvh8.h)
@@ -61,7 +64,7 @@ struct DevScene {
   const DevMaterial* materials;
   const DevMatLite* mat_lite;     // diffuse_only == 2: the same table, 32 B per material
   const DevLight* lights;         // num_lights records; under SC_LIGHTS_BY_AREA the area CDF follows them in the same allocation: one float per light
-                                  // triangle, indexed like light_tris (light_cdf)
+                                  // triangle, indexed like light_tris (light_cdf); under SC_LIGHTS_BY_POWER the selection table comes first (light_pcdf)
   const DevLightTri* light_tris;
   uint32_t num_lights;
   int32_t env_material;

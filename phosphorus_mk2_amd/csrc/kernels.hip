@@ -961,11 +961,27 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_D) __attribute__((amdgpu_waves
 // equal triangles.  PHX_LIGHTS_BY_AREA (SC_LIGHTS_BY_AREA, a wave-uniform branch on a kernel argument): by the area CDF that follows the light
 // table, the rule of include/phx_xpu.h.  Used by k_shade_g and by phx_dev_light_sample; k_shade<1/2> keep their own copy of the reference
 // pick (a BY_AREA scene never runs them).
-__device__ __forceinline__ const float* light_cdf(const DevScene& sc) { return reinterpret_cast<const float*>(sc.lights + sc.num_lights); }
+// PHX_LIGHT_SELECT_BY_POWER (SC_LIGHTS_BY_POWER, wave-uniform likewise): the light itself by the selection table pcdf, which sits between the
+// light records and the area CDF (num_lights floats, padded to whole records); DevLight::lpdf then holds (1 / area) * p_l.
+__device__ __forceinline__ const float* light_pcdf(const DevScene& sc) { return reinterpret_cast<const float*>(sc.lights + sc.num_lights); }
+__device__ __forceinline__ const float* light_cdf(const DevScene& sc) {
+  const uint32_t pcdf_records = (sc.any_tex & SC_LIGHTS_BY_POWER) ? (sc.num_lights + 7u) >> 3 : 0u;  // 8 floats per 32-byte record
+  return reinterpret_cast<const float*>(sc.lights + sc.num_lights + pcdf_records);
+}
 __device__ __forceinline__ void light_pick(const DevScene& sc, float pick, float lu, uint32_t& l, uint32_t& ti, uint32_t& lt, float& remapped) {
-  const float nlf = (float)sc.num_lights;
-  l = (uint32_t)floorf(pick * nlf);
-  if (l > sc.num_lights - 1) l = sc.num_lights - 1;
+  if (sc.any_tex & SC_LIGHTS_BY_POWER) {
+    const float* pcdf = light_pcdf(sc);          // monotone, pcdf[num_lights - 1] == 1
+    uint32_t lo = 0, hi = sc.num_lights - 1;     // the smallest l with pick < pcdf[l], or num_lights - 1: reads pcdf[0 .. num_lights - 2] only
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (pick < pcdf[mid]) hi = mid; else lo = mid + 1;
+    }
+    l = lo;
+  } else {
+    const float nlf = (float)sc.num_lights;
+    l = (uint32_t)floorf(pick * nlf);
+    if (l > sc.num_lights - 1) l = sc.num_lights - 1;
+  }
   const uint32_t ltris = sc.lights[l].num_tris;
   if (sc.any_tex & SC_LIGHTS_BY_AREA) {
     const float* cdf = light_cdf(sc) + sc.lights[l].first_tri;  // cdf[i] = (area_0 + ... + area_i) / area, monotone, cdf[ltris - 1] == 1

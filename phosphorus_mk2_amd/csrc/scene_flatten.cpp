@@ -64,6 +64,48 @@ bool bake_material(const phx_material& m, float sheen_L5, DevMaterial& out, uint
   return true;
 }
 
+// PHX_LIGHT_SELECT_BY_POWER, the rule of include/phx_xpu.h: the selection table pcdf and every light's lpdf = (1 / area) * p_l.  The weights,
+// their sums and the running table are binary64 in the order written (the file is compiled without contraction); pcdf, p_l and lpdf are fp32.
+void light_power_table(const phx_scene& s, FlatScene& out) {
+  const size_t nl = out.lights.size();
+  std::vector<double> w(nl), img(3 * (size_t)s.num_textures, -1.0);  // img: an image's channel means, computed at its first use
+  bool finite = true; size_t npos = 0; double wsum = 0.0;
+  for (size_t l = 0; l < nl; ++l) {
+    const DevLight& L = out.lights[l];
+    double m[3] = {1.0, 1.0, 1.0};
+    if (const uint32_t t = s.materials[L.material].emission_uv_texture) {
+      double* mt = &img[3 * (size_t)(t - 1u)];
+      if (mt[0] < 0.0 || mt[0] != mt[0]) {  // (a NaN mean is recomputed: it stays NaN)
+        const phx_texture& T = s.textures[t - 1u];
+        const size_t nt = (size_t)T.width * T.height;
+        double sum[3] = {0.0, 0.0, 0.0};
+        for (size_t k = 0; k < nt; ++k) for (int c = 0; c < 3; ++c) sum[c] += std::fabs((double)T.texels[3 * k + c]);
+        for (int c = 0; c < 3; ++c) mt[c] = sum[c] / (double)nt;
+      }
+      for (int c = 0; c < 3; ++c) m[c] = mt[c];
+    }
+    const double er = std::fabs((double)L.ex), eg = std::fabs((double)L.ey), eb = std::fabs((double)L.ez);
+    w[l] = (double)L.area * ((0.2126 * er * m[0] + 0.7152 * eg * m[1]) + 0.0722 * eb * m[2]);
+    if (!std::isfinite(w[l])) finite = false;
+    if (w[l] > 0.0) ++npos;
+    wsum += w[l];
+  }
+  const bool uniform = !finite || npos == 0;  // a black or broken scene: uniform selection through the same table
+  const double phi = PHX_LIGHT_POWER_FLOOR;
+  std::vector<double> acc(nl);
+  double run = 0.0;
+  for (size_t l = 0; l < nl; ++l) {
+    const double q = uniform ? 1.0 / (double)nl : (w[l] > 0.0 ? (1.0 - phi) * w[l] / wsum + phi / (double)npos : 0.0);
+    run += q; acc[l] = run;
+  }
+  out.light_pcdf.resize(nl);
+  for (size_t l = 0; l < nl; ++l) out.light_pcdf[l] = (float)(acc[l] / acc[nl - 1]);
+  for (size_t l = 0; l < nl; ++l) {
+    const float p = out.light_pcdf[l] - (l ? out.light_pcdf[l - 1] : 0.0f);
+    out.lights[l].lpdf = (1.0f / out.lights[l].area) * p;
+  }
+}
+
 }  // namespace
 
 int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err) {
@@ -76,8 +118,12 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
   if (s.camera.film_width == 0 || s.camera.film_height == 0 || s.camera.film_width > 65535 || s.camera.film_height > 65535)
     return refuse("film size out of range");
   if (s.environment_material >= (int32_t)s.num_materials) return refuse("environment material out of range");
-  if (opt.light_sampling > PHX_LIGHTS_BY_AREA) return refuse("unknown light_sampling");
-  const bool lights_by_area = opt.light_sampling == PHX_LIGHTS_BY_AREA;
+  // the packed word: the triangle pick in the low byte, the light's selection above it.  Valid: 0, 1 and BY_AREA | SELECT_BY_POWER
+  if (PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) > PHX_LIGHTS_BY_AREA) return refuse("unknown light_sampling");
+  if (PHX_LIGHT_SELECTION(opt.light_sampling) & ~(uint32_t)PHX_LIGHT_SELECT_BY_POWER) return refuse("unknown light_sampling: bits above PHX_LIGHT_SELECT_BY_POWER");
+  const bool lights_by_area = PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) == PHX_LIGHTS_BY_AREA;
+  const bool lights_by_power = PHX_LIGHT_SELECTION(opt.light_sampling) == PHX_LIGHT_SELECT_BY_POWER;
+  if (lights_by_power && !lights_by_area) return refuse("light_sampling: PHX_LIGHT_SELECT_BY_POWER needs PHX_LIGHTS_BY_AREA");
 
   // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
   // non-emitting materials may carry one (an emitter's image is on its emission: emission_uv_texture)
@@ -218,6 +264,7 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
       L.ex = mats[L.material].ex; L.ey = mats[L.material].ey; L.ez = mats[L.material].ez;
     }
   }
+  if (lights_by_power) light_power_table(s, out);
 
   // the environment's image, and every texture's texels as float4 (one 16-byte load per texel) behind a small table
   DevScene& sc = out.scene;
@@ -227,7 +274,8 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
     out.env_mapping = s.materials[s.environment_material].emission_mapping;
     for (int c = 0; c < 3; ++c) out.env_e[c] = s.materials[s.environment_material].emission[c];
   }
-  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (out.env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u) | (lights_by_area ? SC_LIGHTS_BY_AREA : 0u);
+  sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (out.env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u) | (lights_by_area ? SC_LIGHTS_BY_AREA : 0u) |
+               (lights_by_power ? SC_LIGHTS_BY_POWER : 0u);
   if (sc.any_tex & SC_TEX_ANY) {
     out.textures.resize(s.num_textures);
     out.texels.resize((size_t)total_texels);

@@ -25,6 +25,7 @@ struct FlatScene {
   std::vector<DevLight> lights;         // one per emissive face set; its triangles are light_tris[first_tri ...] in face order
   std::vector<DevLightTri> light_tris;
   std::vector<float> light_cdf;         // PHX_LIGHTS_BY_AREA: per light triangle, the light's running area up to and including it over the light's area
+  std::vector<float> light_pcdf;        // PHX_LIGHT_SELECT_BY_POWER: per light, the running selection probability up to and including it (the last is 1)
   std::vector<DevMaterial> materials;
   std::vector<uint32_t> lobe_tex;       // 8 per material: texture + 1 of baked lobe k
   std::vector<DevMatLite> mat_lite;     // diffuse_only == 2: the 32-byte table

@@ -636,3 +636,20 @@ def bmw_showroom(n=500_000, width=1920, height=1080, per_hit_glass=True):
     s = showroom(n, width=width, height=height, materials=showroom_materials(per_hit_glass), closed=True)
     s.name = f"bmw_showroom{n}" + ("" if per_hit_glass else "_constant_glass")
     return s
+
+
+def lamp_showroom(n=500_000, lamps=64, width=1920, height=1080, side=0.05, emission=(1.0, 0.1, 0.1)):
+    """bmw_showroom plus `lamps` small dim emissive quads (indicator LEDs of side `side`) in a grid on the back wall, each a mesh and a light of
+    its own: one lamp delivers nearly all of the light, and uniform light selection sends lamps / (lamps + 1) of its shadow rays to the
+    rest (light_selection="power")."""
+    s = bmw_showroom(n, width, height)
+    s.materials.append(emitter(*emission))
+    cols = int(math.ceil(math.sqrt(lamps)))
+    rows = (lamps + cols - 1) // cols
+    z = -4.6 + 0.001  # a millimetre in front of the back wall, facing the room (+z)
+    for k in range(lamps):
+        x = -1.75 + 3.5 * ((k % cols) + 0.5) / cols; y = -0.7 + 2.0 * ((k // cols) + 0.5) / rows
+        h = 0.5 * side
+        s.meshes.append(_quad((x - h, y - h, z), (x + h, y - h, z), (x + h, y + h, z), (x - h, y + h, z), len(s.materials) - 1))
+    s.name = f"lamp_showroom{n}_{lamps}"
+    return s

@@ -55,7 +55,7 @@ class Options:
 
     def __init__(self, samples_per_pixel=16, paths_per_sample=16, path_depth=9, single_threaded=False, host_only=False,
                  render_normals=False, verbose=False, device_ordinal=-1, samples_in_flight=0, tiles_per_batch=0, bvh_builder="auto",
-                 light_sampling="reference"):
+                 light_sampling="reference", light_selection="uniform"):
         self.samples_per_pixel = samples_per_pixel
         self.paths_per_sample = paths_per_sample
         self.path_depth = path_depth
@@ -70,6 +70,9 @@ class Options:
         # "reference": next-event estimation picks a light's triangle by index, as the reference does (biased for lights of unequal triangles);
         # "area": by the light's area CDF (unbiased; the scene is shaded by k_shade_g).  An int is passed through as it is.
         self.light_sampling = light_sampling
+        # "uniform": next-event estimation chooses among the lights uniformly; "power": by area x luminance of the emission (bit 8 of the packed
+        # word, abi.LIGHT_SELECT_BY_POWER), which needs light_sampling "area"
+        self.light_selection = light_selection
 
     def pack(self):
         o = abi.Options()
@@ -80,6 +83,10 @@ class Options:
         o.bvh_builder = {"auto": abi.BVH_AUTO, "host": abi.BVH_HOST_SAH, "device": abi.BVH_DEVICE_LBVH}[self.bvh_builder]
         ls = self.light_sampling
         o.light_sampling = ls if isinstance(ls, int) else {"reference": abi.LIGHTS_REFERENCE, "area": abi.LIGHTS_BY_AREA}[ls]
+        if {"uniform": False, "power": True}[self.light_selection]:
+            if o.light_sampling != abi.LIGHTS_BY_AREA:
+                raise ValueError('light_selection="power" needs light_sampling="area"')
+            o.light_sampling |= abi.LIGHT_SELECT_BY_POWER
         return o
 
 
@@ -399,11 +406,12 @@ def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_s
 
 
 def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=32, rank=0, world=1, callback_tiles=False,
-           samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference"):
+           samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference",
+           light_selection="uniform"):
     """Convenience: the call sequence of session_t::render (plugins/blender/session.cpp:73-94):
     make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats)."""
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
-                   tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling)
+                   tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling, light_selection=light_selection)
     # ONE device, on the caller's current GPU (device_ordinal -1): discover() is for hosts that drive every GPU (render_on) and
     # would build a context, a stream and the kernel attributes on each of them only to use the first
     dev = HipDevice.make(opts)

@@ -1,0 +1,56 @@
+#!/usr/bin/env python3
+"""Per-symbol comparison of two kernels.s files (`make -C phosphorus_mk2_amd/csrc asm` on two trees): which kernels' instruction streams
+differ, with basic-block labels renumbered by first appearance and comments, debug and CFI directives dropped.
+
+    python scripts/asm_compare.py PARENT/phosphorus_mk2_amd/csrc/kernels.s phosphorus_mk2_amd/csrc/kernels.s
+"""
+import re
+import subprocess
+import sys
+
+
+def bodies(path):
+    """symbol -> its lines up to .Lfunc_end, comments stripped"""
+    out, cur = {}, None
+    for line in open(path):
+        m = re.match(r"^(_Z\w+|[A-Za-z_]\w*):\s*(;.*)?$", line)
+        if m:
+            cur = None if m.group(1).startswith("__hip_cuid") else m.group(1)  # (the build's id symbol: data, and the file's metadata behind it)
+            if cur:
+                out[cur] = []
+            continue
+        if cur is None:
+            continue
+        if line.lstrip().startswith(".Lfunc_end"):
+            cur = None
+            continue
+        s = line.split(";")[0].strip()
+        if s and not s.startswith((".loc", ".cfi", ".file")):
+            out[cur].append(s)
+    return out
+
+
+def renumbered(lines):
+    seen = {}
+    return [re.sub(r"\.LBB\d+_\d+", lambda x: seen.setdefault(x.group(0), f".L{len(seen)}"), l) for l in lines]
+
+
+def main():
+    a, b = bodies(sys.argv[1]), bodies(sys.argv[2])
+    names = sorted(set(a) | set(b))
+    plain = dict(zip(names, subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.splitlines()))
+    both = [n for n in names if n in a and n in b]
+    changed = [n for n in both if renumbered(a[n]) != renumbered(b[n])]
+    new, gone = [n for n in names if n not in a], [n for n in names if n not in b]
+    print(f"symbols: {len(names)}; identical instruction for instruction (basic-block labels renumbered): {len(both) - len(changed)}; "
+          f"changed: {len(changed)}; new: {len(new)}; gone: {len(gone)}")
+    for n in changed:
+        print(f"changed  {re.sub(r'[(]phx::DevScene.*', '', plain[n]):70s} {len(a[n]):6d} -> {len(b[n]):6d} lines")
+    for n in new:
+        print("new     ", plain[n])
+    for n in gone:
+        print("gone    ", plain[n])
+
+
+if __name__ == "__main__":
+    main()
