@@ -3,11 +3,13 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
  * light, so the film is the same again.
+ * sample-environment: the room gets a sky -- an environment material with a small lat-long image, dim but for one bright texel -- and next-event
+ * estimation samples it beside the panel (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT).
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -35,7 +37,7 @@ int main(int argc, char** argv) {
   static const uint32_t faces[] = {0, 1, 2, 0, 2, 3, 4, 5, 6, 4, 6, 7, 8, 9, 10, 8, 10, 11, 12, 13, 14, 15, 16, 17};
   static const uint32_t grey_faces[] = {0, 1, 2, 3}, light_faces[] = {4, 5}, red_faces[] = {6, 7};
 
-  phx_material materials[3];
+  phx_material materials[4]; /* [3]: the sky of sample-environment, outside the scene otherwise */
   memset(materials, 0, sizeof(materials));
   materials[0].num_lobes = 1; /* diffuse_bsdf_node, Cs = 0.73 */
   materials[0].lobes[0].type = PHX_LOBE_DIFFUSE;
@@ -73,6 +75,20 @@ int main(int argc, char** argv) {
       --argc; --i;
     } else if (strcmp(argv[i], "power-lights") == 0) {
       opt.light_sampling = PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    } else if (strcmp(argv[i], "sample-environment") == 0) {
+      static float sky[8 * 4 * 3];
+      static phx_texture sky_image;
+      for (int k = 0; k < 8 * 4 * 3; ++k) sky[k] = 0.2f;
+      sky[(1 * 8 + 5) * 3] = sky[(1 * 8 + 5) * 3 + 1] = 60.0f; sky[(1 * 8 + 5) * 3 + 2] = 40.0f; /* the sun: row 1, column 5 */
+      sky_image.width = 8; sky_image.height = 4; sky_image.texels = sky;
+      sky_image.filter = PHX_TEX_CLOSEST; sky_image.swrap = PHX_WRAP_PERIODIC; sky_image.twrap = PHX_WRAP_CLAMP;
+      materials[3].emission[0] = materials[3].emission[1] = materials[3].emission[2] = 1.0f;
+      materials[3].emission_texture = 1; materials[3].emission_mapping = PHX_ENV_LATLONG_Y_UP;
+      scene.num_materials = 4; scene.environment_material = 3;
+      scene.num_textures = 1; scene.textures = &sky_image;
+      opt.light_sampling = PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     }

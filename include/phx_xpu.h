@@ -62,7 +62,7 @@ typedef struct phx_options {
   uint32_t samples_in_flight; /* samples of one pixel carried per wavefront pass */
   uint32_t tiles_per_batch;   /* tiles pulled from the queue per pass */
   uint32_t bvh_builder;       /* PHX_BVH_AUTO (default), PHX_BVH_DEVICE_LBVH or PHX_BVH_HOST_SAH: where preprocess builds the tree */
-  uint32_t light_sampling;    /* PHX_LIGHTS_REFERENCE (default) or PHX_LIGHTS_BY_AREA: how next-event estimation picks a triangle of the chosen light; | PHX_LIGHT_SELECT_BY_POWER */
+  uint32_t light_sampling;    /* PHX_LIGHTS_REFERENCE (default) or PHX_LIGHTS_BY_AREA: how next-event estimation picks a triangle of the chosen light; | PHX_LIGHT_SELECT_BY_POWER [| PHX_LIGHT_INCLUDE_ENVIRONMENT] */
   uint32_t reserved[4];
 } phx_options;
 /* AUTO = the device builder (LBVH over extended Morton codes + the optimal 8-wide collapse) for every scene with at least 64
@@ -88,7 +88,7 @@ enum { PHX_BVH_AUTO = 0, PHX_BVH_DEVICE_LBVH = 1, PHX_BVH_HOST_SAH = 2 };
  *     DESIGN 14) is set in the same word. */
 enum { PHX_LIGHTS_REFERENCE = 0, PHX_LIGHTS_BY_AREA = 1 };
 /* The word is packed like phx_lobe.fac_mode: the low byte is the triangle pick above, bit 8 chooses how a LIGHT is selected.  The valid
- * words are 0, 1 and 0x101 (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); every other word, 0x100 among them (selection by power needs the
+ * words are 0, 1, 0x101 (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER) and 0x301 (below); every other word, 0x100 among them (selection by power needs the
  * unbiased triangle pick), is PHX_ERR_ARG at phx_dev_preprocess.
  *   PHX_LIGHT_SELECT_BY_POWER: a light by its power instead of uniformly.  Lights stay in the light table's order (mesh x face-set order);
  *   all host arithmetic below is binary64, without contraction, in the order written.
@@ -109,8 +109,57 @@ enum { PHX_LIGHTS_REFERENCE = 0, PHX_LIGHTS_BY_AREA = 1 };
  *   Everything behind the pick is PHX_LIGHTS_BY_AREA's: the triangle by the area CDF, triangle_t::sample, P, the emission.  A scene with ONE
  *   light has pcdf = {1}, l = 0 and lpdf = 1.0f / area: bit for bit what PHX_LIGHTS_BY_AREA alone renders. */
 enum { PHX_LIGHT_SELECT_BY_POWER = 0x100 };
+/* Bit 9 of the same word: next-event estimation samples the ENVIRONMENT IMAGE too.  The only new valid word is 0x301
+ * (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT): the valid words are 0, 1, 0x101 and 0x301, and every other one
+ * (0x200, 0x201, 0x300 among them) is PHX_ERR_ARG at phx_dev_preprocess, as is 0x301 on a scene whose environment material has no
+ * emission_texture (a constant sky is served by cosine-weighted BSDF sampling already).  The scene still needs an emissive face set.
+ * With the bit clear nothing changes.  All host arithmetic below is binary64, without contraction, in the order written; device tables are fp32.
+ *   importance T = the environment image (W x H), e = the environment material's emission, Y(c) = (0.2126 c_r + 0.7152 c_g) + 0.0722 c_b.
+ *              Per texel (column i, row j) y_ij = Y(|e| * |texel_ij|) (per channel), and
+ *                g_ij = yhat_ij * sin((pi * (j + 0.5)) / H)
+ *              with yhat_ij = y_ij under PHX_TEX_CLOSEST.  Under PHX_TEX_LINEAR yhat_ij starts as y_ij and is replaced by every y of the 3 x 3
+ *              neighbourhood of (i, j) that compares greater (rows j - 1 .. j + 1, in each columns i - 1 .. i + 1), the neighbours taken through
+ *              the image's own wrap modes; one outside the image under PHX_WRAP_BLACK counts 0.  So g > 0 wherever the bilinear lookup can be
+ *              non-zero inside the texel: the sampled density is positive wherever the integrand is.
+ *              G = the sum of g_ij, sequentially in row-major order;  rowsum_j = the sum of g_ij over i, sequentially.
+ *   weight     the environment is ONE MORE ENTRY of PHX_LIGHT_SELECT_BY_POWER's table, behind the nlights mesh lights, with
+ *                w_env = (((4 pi) * R) * R) * (G / (W * H)) * (pi / 2)
+ *              R = 0.5 * sqrt(dx*dx + dy*dy + dz*dz) of the scene's bounding box (fp32 min / max of every triangle corner, the extents
+ *              subtracted after widening to double).  sum g / (W H) approximates (1 / pi) * integral of yhat sin(theta) dtheta dphi / (2 pi),
+ *              so w_env is 4 pi R^2 x the solid-angle-weighted mean luminance: an area light's A * Y against pi R^2 * integral of L d omega
+ *              with the common pi divided out.  Like m_l it only ever affects variance.  n+, Wsum, the fallback, the floor, pcdf and p_l are
+ *              the rule above applied to nlights + 1 entries; pcdf has nlights + 1 entries, the last 1.0f.  The mesh lights keep
+ *              lpdf = (1.0f / area_l) * p_l, and p_env = pcdf[nlights] - pcdf[nlights - 1] in fp32.  A black image has w_env = 0 and is never chosen.
+ *   directions mcdf[j] = fp32((rowsum_0 + ... + rowsum_j) / G), the last entry set to 1.0f;  ccdf[j][i] = fp32((g_0j + ... + g_ij) / rowsum_j), a
+ *              row of zero sum all 1.0f (it has mcdf[j] == mcdf[j - 1] and is never chosen).  Both are monotone.  If G is zero or not finite
+ *              (a black or broken image: w_env is then 0, or not finite and the whole table uniform) the two tables are built from
+ *              g_ij = sin((pi * (j + 0.5)) / H) instead: uniform over the sphere.
+ *   sample     when the pick returns l == nlights: j = the smallest index with lu < mcdf[j], else H - 1;  lo = j ? mcdf[j - 1] : 0;
+ *              P_row = mcdf[j] - lo;  ru = min((lu - lo) / P_row, 1 - FLT_EPSILON);  i, P_col and rv likewise from lv in ccdf[j].  Binary searches
+ *              of at most 17 steps with clamped indices: a NaN draw ends at the last index, no draw reads outside a table.  All fp32:
+ *                s = (i + rv) / W    t = (j + ru) / H    phi = (s - 0.5f) * 2 pi    lambda = (0.5f - t) * pi      (2 pi, pi: the nearest floats)
+ *                PHX_ENV_LATLONG_Y_UP: d = (-cos(lambda) sin(phi), sin(lambda), cos(lambda) cos(phi))
+ *                PHX_ENV_LATLONG_Z_UP: d = ( cos(lambda) cos(phi), cos(lambda) sin(phi), sin(lambda))
+ *              the inverses of phx_material.emission_texture's mapping, and
+ *                pdf_omega = ((P_row * P_col) * (W * H)) / (2 pi^2 * sin(pi * t))          pdf = p_env * pdf_omega
+ *              (W * H and 2 pi^2 rounded to fp32 once; sin(pi t) = cos(y), y = pi * (0.5 - t) in binary64, by the Taylor polynomial
+ *              1 - y^2 (1/2! - y^2 (1/4! - ... - y^2 / 20!)) evaluated in binary64 from the inside out and rounded to fp32 once: no library
+ *              function enters the density).  The estimator divides by the tables' own intervals, so it is unbiased to the draw's 24
+ *              bits whatever rounding went into g.  If sin(pi t) <= 0, or pdf is not finite and positive, there is no shadow ray.
+ *   estimate   le = the environment's e in direction d exactly as a miss computes it, f = bsdf_t::f(d, wo) with the sign of the cosine n.d it
+ *              carries dropped (f * -1 where n.d < 0: |n.d|, as in the weight of a BSDF sample),
+ *                contrib = beta * ((le * f) * (1.0f / pdf))
+ *              with NO factor 4 (that is a quirk of the reference's area lights; it has no environment sampling) and without the mesh
+ *              lights' n.d >= 0 gate: bsdf_t::f decides, so transmissive lobes keep their environment light.  The shadow ray starts at
+ *              p + n * (n.d < 0 ? -1e-4f : 1e-4f), runs along d, tmax = FLT_MAX, and counts in rays_shadow; a sample whose f is zero in every
+ *              channel (a direction below an opaque surface) issues none.
+ *   miss       a path that misses adds the environment only at depth 0 or behind a specular bounce (the gate of surface emission):
+ *              everywhere else next-event estimation has accounted for it.  The film's expectation is the one of 0x101; its variance is not.
+ *   limits     no MIS; where a lobe's sampling pdf is one of DESIGN 4.11's quirks the two films' expectations differ by that documented bias. */
+enum { PHX_LIGHT_INCLUDE_ENVIRONMENT = 0x200 };
 #define PHX_LIGHT_SAMPLING_MODE(x) ((x) & 0xffu)    /* PHX_LIGHTS_* */
 #define PHX_LIGHT_SELECTION(x) ((x) & ~0xffu)       /* 0 or PHX_LIGHT_SELECT_BY_POWER */
+#define PHX_LIGHT_ENVIRONMENT(x) ((x) & 0x200u)     /* 0 or PHX_LIGHT_INCLUDE_ENVIRONMENT */
 #define PHX_LIGHT_POWER_FLOOR 0.125
 
 /* ---- scene: what the device reads through scene_t (src/scene.hpp:14-50) --------------- */
@@ -166,7 +215,7 @@ typedef struct phx_material {
   /* Environment map (environment_node.osl's Cout = environment(filename, I) into background_node.Cs): 0 = none, k = phx_scene.textures[k - 1].
    * Allowed ONLY on phx_scene.environment_material (PHX_ERR_ARG elsewhere: a surface emitter's image is emission_uv_texture).  Where a path
    * misses every surface (camera rays included) with direction d = (x, y, z), it adds beta * e with e = emission * texel(s, t), one fp32
-   * multiply per channel; the environment is never sampled by next-event estimation.  (s, t) restates OpenImageIO's documented lat-long
+   * multiply per channel; the environment is sampled by next-event estimation only under PHX_LIGHT_INCLUDE_ENVIRONMENT.  (s, t) restates OpenImageIO's documented lat-long
    * convention (latlong_up "y" by default, or "z"), computed in binary64 from the fp32 components widened to double, operation by
    * operation in the order written (no contraction), each result rounded to fp32 once; INV_2PI and INV_PI are the doubles nearest
    * 1/(2 pi) and 1/pi:
@@ -449,6 +498,14 @@ int phx_dev_light_sample(phx_device* dev, uint32_t n, const float* u3, uint32_t*
  * per item).  A light whose material has no image returns its constant e and st = (0, 0).  A parity hook: it runs the device function
  * k_shade_g runs.  PHX_ERR_STATE before preprocess. */
 int phx_dev_light_emission(phx_device* dev, uint32_t n, const float* u3, float* st, float* e);
+
+/* The environment sample of next-event estimation under PHX_LIGHT_INCLUDE_ENVIRONMENT as the shade kernel draws it: for n triples u3 (pick, lu,
+ * lv per item) the pick (light[k] == nlights marks an environment pick; for a mesh light every other output is zero), the texel (i, j: 2 words
+ * per item), (s, t) (2 floats), the direction d (3 floats), pdf = p_env * pdf_omega (0 where the rule issues no shadow ray) and the environment's e
+ * in direction d (3 floats; zero where pdf is 0).  A parity hook: it runs the device functions k_shade_g runs.  PHX_ERR_STATE before preprocess;
+ * PHX_ERR_ARG when the preprocessed scene does not sample its environment.  Under that option phx_dev_light_sample answers an environment pick
+ * with light = nlights, tri = 0xffffffff and zeros elsewhere, and phx_dev_light_emission with zeros. */
+int phx_dev_environment_sample(phx_device* dev, uint32_t n, const float* u3, uint32_t* light, uint32_t* texel, float* st, float* dir, float* pdf, float* e);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -32,6 +32,7 @@ def fac_texture(word):
 BVH_AUTO, BVH_DEVICE_LBVH, BVH_HOST_SAH = 0, 1, 2
 LIGHTS_REFERENCE, LIGHTS_BY_AREA = 0, 1  # Options.light_sampling: a light's triangle by index (the reference) or by area
 LIGHT_SELECT_BY_POWER = 0x100  # bit 8 of the same word: the light by power, not uniformly (needs LIGHTS_BY_AREA in the low byte)
+LIGHT_INCLUDE_ENVIRONMENT = 0x200  # bit 9: next-event estimation samples the environment image too (needs LIGHT_SELECT_BY_POWER: the word 0x301)
 MESH_UV_PER_VERTEX, MESH_NORMALS_PER_VERTEX = 1, 2
 TEX_LINEAR, TEX_CLOSEST = 0, 1
 WRAP_PERIODIC, WRAP_CLAMP, WRAP_BLACK = 0, 1, 2
@@ -175,7 +176,7 @@ EXPORTS = [
     "phx_last_error", "phx_dev_get_stats", "phx_tiles_make", "phx_tiles_next", "phx_tiles_count", "phx_tiles_reset",
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
     "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
-    "phx_dev_light_sample", "phx_dev_light_emission",
+    "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample",
 ]
 
 
@@ -205,5 +206,6 @@ def declare(lib):
     lib.phx_dev_lobe_weights.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, u32p]; lib.phx_dev_lobe_weights.restype = C.c_int
     lib.phx_dev_light_sample.argtypes = [vp, C.c_uint32, f32p, u32p, u32p, f32p, f32p, f32p]; lib.phx_dev_light_sample.restype = C.c_int
     lib.phx_dev_light_emission.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]; lib.phx_dev_light_emission.restype = C.c_int
+    lib.phx_dev_environment_sample.argtypes = [vp, C.c_uint32, f32p, u32p, u32p, f32p, f32p, f32p, f32p]; lib.phx_dev_environment_sample.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

@@ -126,6 +126,7 @@ struct phx_device {
   // image textures: held only while the preprocessed scene has a textured lobe
   DevBuf<float2> d_elem_uv; DevBuf<DevTexture> d_textures; DevBuf<float4> d_texels; DevBuf<uint32_t> d_lobe_tex; DevBuf<DevTexScene> d_tex_scene;
   DevBuf<uint32_t> d_mat_emit_tex;  // per material: the image on its emission + 1 (scenes with emitter images only)
+  DevBuf<float> d_env_cdf;          // PHX_LIGHT_INCLUDE_ENVIRONMENT: the environment's direction tables (FlatScene::env_cdf)
   DevScene scene{};
   uint32_t num_materials = 0, num_textures = 0;
   std::vector<uint8_t> mat_masked;  // per material: some lobe's factor is an image mask (the untextured KAT hooks refuse those)
@@ -195,7 +196,7 @@ struct phx_device {
   uint64_t device_bytes() const {
     return d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
            d_lights.bytes() + d_light_tris.bytes() + queues.bytes() + counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
-           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes() + d_mat_emit_tex.bytes();
+           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes() + d_mat_emit_tex.bytes() + d_env_cdf.bytes();
   }
   // paths in flight this device may carry: up to 512 M (about 95 GB of queues + state: sized for 288 GB of HBM), but never more than 60 % of
   // what the device has free right now plus what this object already holds for queues (another device object, torch or RCCL may share the GPU)
@@ -346,11 +347,12 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   }
   HIPCHK(hipGetLastError());
   if (fs.any_emit_tex) { if ((rc = d->d_mat_emit_tex.upload(fs.mat_emit_tex))) return rc; } else d->d_mat_emit_tex.release();
+  if (sc.any_tex & SC_LIGHTS_ENV) { if ((rc = d->d_env_cdf.upload(fs.env_cdf))) return rc; } else d->d_env_cdf.release();
   if (any_image) {  // the texture table and the texels, and the one record through which the shade kernels find them
     if ((rc = d->d_textures.upload(fs.textures)) || (rc = d->d_texels.upload(fs.texels))) return rc;
     const std::vector<DevTexScene> ts{DevTexScene{any_tex ? d->d_elem_uv.p : nullptr, d->d_textures.p, d->d_texels.p, any_tex ? d->d_lobe_tex.p : nullptr,
-                                                  fs.env_tex ? fs.env_tex - 1u : 0u, fs.env_mapping, fs.any_emit_tex ? 1u : 0u, 0u,
-                                                  fs.any_emit_tex ? d->d_mat_emit_tex.p : nullptr}};
+                                                  fs.env_tex ? fs.env_tex - 1u : 0u, fs.env_mapping, fs.any_emit_tex ? 1u : 0u, fs.env_p,
+                                                  fs.any_emit_tex ? d->d_mat_emit_tex.p : nullptr, (sc.any_tex & SC_LIGHTS_ENV) ? d->d_env_cdf.p : nullptr}};
     if ((rc = d->d_tex_scene.upload(ts))) return rc;
   } else {
     d->d_textures.release(); d->d_texels.release(); d->d_tex_scene.release();
@@ -702,6 +704,18 @@ int phx_dev_light_emission(phx_device* d, uint32_t n, const float* u3, float* st
     const float* a = s.in(u3, 3 * (size_t)n);
     float *os = s.out(st, 2 * (size_t)n), *oe = s.out(e, 3 * (size_t)n);
     return s.run([&] { launch_light_emission(d->stream, d->scene, n, a, os, oe); });
+  });
+}
+
+int phx_dev_environment_sample(phx_device* d, uint32_t n, const float* u3, uint32_t* light, uint32_t* texel, float* st, float* dir, float* pdf, float* e) {
+  return stage_hook(d, "environment_sample", [&](Staging& s) -> int {
+    if (!(d->scene.any_tex & SC_LIGHTS_ENV)) return fail(PHX_ERR_ARG, "environment_sample: the scene does not sample its environment (light_sampling without PHX_LIGHT_INCLUDE_ENVIRONMENT)");
+    if (n == 0) return PHX_OK;
+    if (!u3 || !light || !texel || !st || !dir || !pdf || !e) return fail(PHX_ERR_ARG, "environment_sample: null argument");
+    const float* a = s.in(u3, 3 * (size_t)n);
+    uint32_t *ol = s.out(light, n), *ot = s.out(texel, 2 * (size_t)n);
+    float *os = s.out(st, 2 * (size_t)n), *od = s.out(dir, 3 * (size_t)n), *op = s.out(pdf, n), *oe = s.out(e, 3 * (size_t)n);
+    return s.run([&] { launch_environment_sample(d->stream, d->scene, d->env_e[0], d->env_e[1], d->env_e[2], n, a, ol, ot, os, od, op, oe); });
   });
 }
 

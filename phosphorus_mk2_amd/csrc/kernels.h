@@ -37,8 +37,9 @@ struct DevTexScene {
   uint32_t env_mapping;           // and its lat-long mapping (ENV_LATLONG_*)
   // textured surface emission (phx_material.emission_uv_texture; bsdf.h: hit_emission, kernels.hip: light_emission)
   uint32_t any_emit_tex;          // some emitter's emission is multiplied by an image: the wave-uniform branch of the TEX kernels
-  uint32_t pad;
+  float env_p;                    // SC_LIGHTS_ENV: the environment's interval of the selection table, p_env (this word was padding)
   const uint32_t* mat_emit_tex;   // per material: its emission image + 1 (0 = none), indexed by the hit's material and by DevLight::material
+  const float* env_cdf;           // SC_LIGHTS_ENV: the environment's direction tables, mcdf (H floats) then ccdf (H rows of W floats); nullptr otherwise
 };
 // DevScene::any_tex bits: which image lookups the shade kernels compile in
 enum { SC_TEX_LOBES = 1u /* some lobe is textured or masked: TEX */, SC_TEX_ENV = 2u /* the environment has an image: ENV */,
@@ -49,7 +50,10 @@ enum { SC_TEX_LOBES = 1u /* some lobe is textured or masked: TEX */, SC_TEX_ENV 
        SC_LIGHTS_BY_AREA = 8u,
        // PHX_LIGHT_SELECT_BY_POWER, always with SC_LIGHTS_BY_AREA: light_pick searches the selection table pcdf, which sits between the light
        // records and the area CDF: num_lights floats, padded to whole records of the light table
-       SC_LIGHTS_BY_POWER = 16u };
+       SC_LIGHTS_BY_POWER = 16u,
+       // PHX_LIGHT_INCLUDE_ENVIRONMENT, always with SC_LIGHTS_BY_POWER and SC_TEX_ENV: pcdf has num_lights + 1 entries, the last one the environment's,
+       // and k_shade_g<.., ENV> samples the image by DevTexScene::env_cdf when the pick lands there (kernels.hip: env_sample)
+       SC_LIGHTS_ENV = 32u };
 
 struct DevScene {
   const uint32_t* pool;           // the BVH8 pool: 16 words per element, element 0 = root nodelet (bvh8.h)
@@ -167,6 +171,10 @@ void launch_scatter_film(hipStream_t stream, const PassBuffers& pb, float* devic
 void launch_light_sample(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf);
 // light_pick + triangle_t::sample + light_emission as k_shade_g's next-event block runs them: per item u3 -> st (2 floats), e (3 floats)
 void launch_light_emission(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, float* st, float* e);
+// SC_LIGHTS_ENV: light_pick + env_sample + env_emission as k_shade_g<.., ENV>'s next-event block runs them: per item u3 -> the pick, and for an
+// environment pick the texel (i, j), (s, t), the direction, pdf = p_env * pdf_omega (0: no shadow ray) and the environment's e there (emission ex, ey, ez)
+void launch_environment_sample(hipStream_t stream, const DevScene& sc, float ex, float ey, float ez, uint32_t n, const float* u3, uint32_t* light, uint32_t* texel,
+                               float* st, float* dir, float* pdf, float* e);
 void launch_trace_rays(hipStream_t stream, const DevScene& sc, uint32_t n, const float4* ro, const float4* rd, float4* hit, int any);
 void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3);
 void launch_bsdf_sample(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* u2,

@@ -1002,6 +1002,85 @@ __device__ __forceinline__ void light_pick(const DevScene& sc, float pick, float
   lt = sc.lights[l].first_tri + ti;
 }
 
+// light_pick where the scene may have PHX_LIGHT_INCLUDE_ENVIRONMENT (SC_LIGHTS_ENV, a wave-uniform branch; always with SC_LIGHTS_BY_POWER and
+// SC_LIGHTS_BY_AREA): pcdf has one more entry, the environment's, so the area CDF starts one entry's padding later, and a pick that lands there
+// returns l == num_lights with ti = lt = 0 and remapped = 0 and reads no light record (there is none: the caller samples the image, env_sample).
+// Used by the ENV instantiations of k_shade_g and by the hooks' kernels for such scenes; light_pick and its callers are as they were.
+__device__ __forceinline__ void light_pick_env(const DevScene& sc, float pick, float lu, uint32_t& l, uint32_t& ti, uint32_t& lt, float& remapped) {
+  if (!(sc.any_tex & SC_LIGHTS_ENV)) { light_pick(sc, pick, lu, l, ti, lt, remapped); return; }
+  const float* pcdf = light_pcdf(sc);            // monotone, pcdf[num_lights] == 1
+  uint32_t lo = 0, hi = sc.num_lights;           // the smallest l with pick < pcdf[l], or num_lights: reads pcdf[0 .. num_lights - 1] only
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (pick < pcdf[mid]) hi = mid; else lo = mid + 1;
+  }
+  l = lo;
+  if (l == sc.num_lights) { ti = 0u; lt = 0u; remapped = 0.0f; return; }
+  const float* cdf = reinterpret_cast<const float*>(sc.lights + sc.num_lights + ((sc.num_lights + 8u) >> 3)) + sc.lights[l].first_tri;
+  lo = 0; hi = sc.lights[l].num_tris - 1;        // the smallest i with lu < cdf[i], or num_tris - 1, as light_pick searches it
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (lu < cdf[mid]) hi = mid; else lo = mid + 1;
+  }
+  ti = lo;
+  const float below = ti ? cdf[ti - 1] : 0.0f;
+  remapped = fminf((lu - below) / (cdf[ti] - below), 1.0f - FLT_EPSILON);
+  lt = sc.lights[l].first_tri + ti;
+}
+
+// ---- the environment's sample (PHX_LIGHT_INCLUDE_ENVIRONMENT; the rule is stated in include/phx_xpu.h) ---------------------------------------
+// The smallest i with u < cdf[i], or n - 1: a binary search of at most 17 steps (n <= 65536 needs 16) that reads cdf[0 .. n - 2] only; a NaN
+// draw compares false everywhere and ends at n - 1.
+__device__ __forceinline__ uint32_t env_cdf_search(const float* cdf, uint32_t n, float u) {
+  uint32_t lo = 0u, hi = n - 1u;
+  for (int step = 0; step < 17 && lo < hi; ++step) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (u < cdf[mid]) hi = mid; else lo = mid + 1u;
+  }
+  return min(lo, n - 1u);
+}
+// The texel (i, j) of the W x H image by the tables env_cdf = mcdf[H], ccdf[H][W], the point (s, t) inside it, its direction d and
+// pdf = p_env * pdf_omega.  -> false: no shadow ray (sin(pi t) <= 0, or pdf not finite and positive; pdf is then 0).  Used by k_shade_g<.., ENV>
+// and by phx_dev_environment_sample.  sin(pi t) = cos(pi (0.5 - t)) is the Taylor polynomial of the header, Horner in binary64, rounded once: no
+// library function enters the density, so the tests restate it bit for bit; d goes through sinf / cosf and is held to a tolerance.
+__device__ __forceinline__ float env_sin_pi_t(float t) {
+  const double y = kPiD * (0.5 - (double)t), y2 = y * y;
+  double c = 1.0 / 2432902008176640000.0;  // 1 / 20!
+  c = 1.0 / 6402373705728000.0 - y2 * c;   // 1 / 18! ...
+  c = 1.0 / 20922789888000.0 - y2 * c;
+  c = 1.0 / 87178291200.0 - y2 * c;
+  c = 1.0 / 479001600.0 - y2 * c;
+  c = 1.0 / 3628800.0 - y2 * c;
+  c = 1.0 / 40320.0 - y2 * c;
+  c = 1.0 / 720.0 - y2 * c;
+  c = 1.0 / 24.0 - y2 * c;
+  c = 1.0 / 2.0 - y2 * c;
+  c = 1.0 - y2 * c;
+  return (float)c;
+}
+__device__ __forceinline__ bool env_sample(const float* env_cdf, uint32_t W, uint32_t H, uint32_t mapping, float p_env, float lu, float lv, uint32_t& i, uint32_t& j,
+                                           float& s, float& t, v3& d, float& pdf) {
+  j = env_cdf_search(env_cdf, H, lu);
+  const float rlo = j ? env_cdf[j - 1u] : 0.0f;
+  const float prow = env_cdf[j] - rlo;
+  const float ru = fminf((lu - rlo) / prow, 1.0f - FLT_EPSILON);
+  const float* row = env_cdf + H + (size_t)j * W;
+  i = env_cdf_search(row, W, lv);
+  const float clo = i ? row[i - 1u] : 0.0f;
+  const float pcol = row[i] - clo;
+  const float rv = fminf((lv - clo) / pcol, 1.0f - FLT_EPSILON);
+  s = ((float)i + rv) / (float)W;
+  t = ((float)j + ru) / (float)H;
+  const float phi = (s - 0.5f) * (float)(2.0 * kPiD), lam = (0.5f - t) * (float)kPiD;
+  const float cl = cosf(lam), sl = sinf(lam), cp = cosf(phi), sp = sinf(phi);
+  d = mapping == ENV_LATLONG_Z_UP ? v3(cl * cp, cl * sp, sl) : v3(-(cl * sp), sl, cl * cp);
+  const float sin_t = env_sin_pi_t(t);
+  pdf = p_env * (((prow * pcol) * (float)(W * H)) / ((float)(2.0 * kPiD * kPiD) * sin_t));
+  const bool ok = sin_t > 0.0f && pdf > 0.0f && pdf <= FLT_MAX;
+  if (!ok) pdf = 0.0f;
+  return ok;
+}
+
 // ---- textured surface emission (phx_material.emission_uv_texture; the rule is stated in include/phx_xpu.h) -----------------------------------
 // Both run only in a scene with DevTexScene::any_emit_tex, behind a wave-uniform branch on that word; `emit_tex` is DevTexScene::mat_emit_tex.
 // At a hit: e * texel at the hit's own (s, t), for a material that names an image.
@@ -1377,7 +1456,12 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             const DevMaterial& m = sc.materials[sc.env_material]; add_e = v3(m.ex, m.ey, m.ez);
             // ENV: e = emission * texel at the ray's direction (environment_node.osl: environment(filename, I)); the binary64 mapping runs
             // on this branch only
-            if constexpr (ENV) add_e = env_emission(tx.textures, tx.texels, tx.env_tex, tx.env_mapping, d, add_e);
+            // ... and, under SC_LIGHTS_ENV (wave-uniform), only at depth 0 or behind a specular bounce, the gate of surface emission above:
+            // everywhere else next-event estimation has sampled the image already
+            if constexpr (ENV) {
+              if ((sc.any_tex & SC_LIGHTS_ENV) && !(depth == 0 || specular)) add_e = v3(0.0f);
+              else add_e = env_emission(tx.textures, tx.texels, tx.env_tex, tx.env_mapping, d, add_e);
+            }
           }
           add_rad = true;
           if (FIRST && pb.pn) pb.pn[path] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1403,9 +1487,25 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           const uint32_t b0 = depth * DIMS_PER_STEP;
           const float pick = draw_f32(key, b0 + DIM_LIGHT_PICK), lu = draw_f32(key, b0 + DIM_LIGHT_U), lv = draw_f32(key, b0 + DIM_LIGHT_V);
           uint32_t l, ti, lt; float remapped;
-          light_pick(sc, pick, lu, l, ti, lt, remapped);  // the triangle by index (the reference) or by area (PHX_LIGHTS_BY_AREA)
+          if constexpr (ENV) light_pick_env(sc, pick, lu, l, ti, lt, remapped); else light_pick(sc, pick, lu, l, ti, lt, remapped);  // the triangle by index (the reference) or by area (PHX_LIGHTS_BY_AREA)
           const float x = sqrtf(remapped);
           const float bu = 1 - x, bv = lv * x;     // triangle_t::sample, mesh.cpp:318-324
+          // PHX_LIGHT_INCLUDE_ENVIRONMENT: the pick landed on the environment's entry (l == num_lights happens under SC_LIGHTS_ENV only)
+          // (`ENV ? .. : constant` conditions: an instantiation without ENV compiles the block it always had)
+          bool env_pick = false, env_ok = false;
+          if constexpr (ENV) {
+            env_pick = l == sc.num_lights;
+            if (env_pick) {  // a direction of the image by its tables; the ray runs to infinity, from the side of the surface d leaves on
+              const __attribute__((address_space(4))) DevTexScene* ctx = (const __attribute__((address_space(4))) DevTexScene*)sc.tex;
+              const DevTexture ET = tx.textures[tx.env_tex];
+              uint32_t ei, ej; float es, et, epdf;
+              env_ok = env_sample(ctx->env_cdf, ET.width, ET.height, tx.env_mapping, ctx->env_p, lu, lv, ei, ej, es, et, sh_d, epdf);
+              const float side = sdot(n, sh_d) < 0.0f ? -0.0001f : 0.0001f;
+              sh_o = v3(p.x + n.x * side, p.y + n.y * side, p.z + n.z * side);
+              sh_t = 1.0f / epdf;  // 1 / (p_env * pdf_omega) crosses bsdf_f in the register that holds a mesh sample's distance; tmax is set behind it
+            }
+          }
+          if (ENV ? !env_pick : true) {
           {
             const DevLightTri& LT = sc.light_tris[lt];
             const v3 la(LT.ax, LT.ay, LT.az), lb(LT.bx, LT.by, LT.bz), lc(LT.cx, LT.cy, LT.cz);
@@ -1417,7 +1517,8 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           sh_t = sqrtf(l2) - 0.0001f;
           const float oolen = 1.0f / sqrtf(l2);
           sh_d = v3(sh_d.x * oolen, sh_d.y * oolen, sh_d.z * oolen);
-          if (sdot(n, sh_d) >= 0.0f) {
+          }
+          if (ENV ? (env_pick ? env_ok : sdot(n, sh_d) >= 0.0f) : sdot(n, sh_d) >= 0.0f) {
             // li(), spt.hpp:212-255 — evaluated before the occlusion test; k_trace adds it if the ray is unoccluded.  bsdf_f's lobe loop reads the
             // recipe through the scalar cache: -0.6 % shade time, 128 -> 121 VGPRs; in the per-hit (glass) instantiations too, which have the registers
             // since the ring append: closed showroom -4.4 %, glass showroom -2.9 % shade time (profiles/r06_i_perhit_knobs_ab.log)
@@ -1430,6 +1531,19 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             }
             // the light's record again (L1-resident), behind an empty asm so that the first read is not kept alive across bsdf_f
             asm volatile("" : "+v"(l), "+v"(lt));
+            if constexpr (ENV) {
+              if (env_pick) {  // le: the radiance a BSDF ray in this direction would add at its miss; no factor 4, no n.d gate (bsdf_f decided)
+                const DevMaterial& em = sc.materials[sc.env_material];
+                const v3 le = env_emission(tx.textures, tx.texels, tx.env_tex, tx.env_mapping, sh_d, v3(em.ex, em.ey, em.ez));
+                // bsdf_f carries the SIGNED cosine n.d, which the mesh lights' gate keeps positive; here it may be negative (a transmissive
+                // lobe lit from below), and the estimate takes |n.d| as the BSDF sample's weight does
+                const float sign = sdot(n, sh_d) < 0.0f ? -1.0f : 1.0f;
+                contrib = beta * ((le * (f * sign)) * sh_t);
+                sh_t = FLT_MAX;
+                want_shadow = !(f.x == 0.0f && f.y == 0.0f && f.z == 0.0f);  // (a direction the closures do not see costs no ray)
+              }
+            }
+            if (ENV ? !env_pick : true) {
             const DevLight& L = sc.lights[l];
             const DevLightTri& LT = sc.light_tris[lt];
             const v3 ln = LT.smooth ? shading_normal(sc, LT.prim, true, v3(LT.bx - LT.ax, LT.by - LT.ay, LT.bz - LT.az), v3(LT.cx - LT.ax, LT.cy - LT.ay, LT.cz - LT.az), bu, bv)
@@ -1440,6 +1554,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
             const v3 li = ((le * 4.0f) * f) * (1.0f / pdf);
             contrib = beta * li;
             want_shadow = true;
+            }
           }
         }
       }
@@ -1639,6 +1754,64 @@ __global__ void __launch_bounds__(64) k_light_emission(DevScene sc, uint32_t n, 
   if (sc.tex && sc.tex->any_emit_tex) le = light_emission(sc.tex->elem_uv, sc.tex->textures, sc.tex->texels, emit_tex_table(sc), L, sc.light_tris[lt], bu, bv, st);
   st2[2 * i] = st.x; st2[2 * i + 1] = st.y;
   e3[3 * i] = le.x; e3[3 * i + 1] = le.y; e3[3 * i + 2] = le.z;
+}
+
+// The two hooks above on a scene with SC_LIGHTS_ENV (launch_light_sample / launch_light_emission choose): the pick over num_lights + 1 entries; an
+// environment pick answers light = num_lights, tri = 0xffffffff and zeros, and reads no light record.  The kernels above stay as they were.
+__global__ void __launch_bounds__(64) k_light_sample_env(DevScene sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P3, float* pdf) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float pick = u3[3 * i], lu = u3[3 * i + 1], lv = u3[3 * i + 2];
+  uint32_t l, ti, lt; float remapped;
+  light_pick_env(sc, pick, lu, l, ti, lt, remapped);
+  const bool env = l == sc.num_lights;
+  float bu = 0.0f, bv = 0.0f; v3 P(0.0f);
+  if (!env) {
+    const float x = sqrtf(remapped);
+    bu = 1 - x; bv = lv * x;
+    const DevLightTri& LT = sc.light_tris[lt];
+    const v3 la(LT.ax, LT.ay, LT.az), lb(LT.bx, LT.by, LT.bz), lc(LT.cx, LT.cy, LT.cz);
+    P = bu * la + bv * lb + (1 - bu - bv) * lc;
+  }
+  light[i] = l; tri[i] = env ? 0xffffffffu : ti; bary[2 * i] = bu; bary[2 * i + 1] = bv;
+  P3[3 * i] = P.x; P3[3 * i + 1] = P.y; P3[3 * i + 2] = P.z;
+  pdf[i] = env ? 0.0f : sc.lights[l].lpdf;
+}
+__global__ void __launch_bounds__(64) k_light_emission_env(DevScene sc, uint32_t n, const float* u3, float* st2, float* e3) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float pick = u3[3 * i], lu = u3[3 * i + 1], lv = u3[3 * i + 2];
+  uint32_t l, ti, lt; float remapped;
+  light_pick_env(sc, pick, lu, l, ti, lt, remapped);
+  v3 le(0.0f); float2 st = make_float2(0.0f, 0.0f);
+  if (l != sc.num_lights) {
+    const float x = sqrtf(remapped);
+    const float bu = 1 - x, bv = lv * x;
+    const DevLight& L = sc.lights[l];
+    le = v3(L.ex, L.ey, L.ez);
+    if (sc.tex->any_emit_tex) le = light_emission(sc.tex->elem_uv, sc.tex->textures, sc.tex->texels, emit_tex_table(sc), L, sc.light_tris[lt], bu, bv, st);
+  }
+  st2[2 * i] = st.x; st2[2 * i + 1] = st.y;
+  e3[3 * i] = le.x; e3[3 * i + 1] = le.y; e3[3 * i + 2] = le.z;
+}
+// phx_dev_environment_sample: light_pick, env_sample and env_emission as k_shade_g<.., ENV>'s next-event block runs them
+__global__ void __launch_bounds__(64) k_environment_sample(DevScene sc, float ex, float ey, float ez, uint32_t n, const float* u3, uint32_t* light, uint32_t* texel,
+                                                           float* st2, float* dir3, float* pdf, float* e3) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const float pick = u3[3 * k], lu = u3[3 * k + 1], lv = u3[3 * k + 2];
+  uint32_t l, ti, lt; float remapped;
+  light_pick_env(sc, pick, lu, l, ti, lt, remapped);
+  uint32_t i = 0u, j = 0u; float s = 0.0f, t = 0.0f, p = 0.0f; v3 d(0.0f), le(0.0f);
+  if (l == sc.num_lights) {
+    const DevTexScene& tx = *sc.tex;
+    const DevTexture ET = tx.textures[tx.env_tex];
+    if (env_sample(tx.env_cdf, ET.width, ET.height, tx.env_mapping, tx.env_p, lu, lv, i, j, s, t, d, p))
+      le = env_emission(tx.textures, tx.texels, tx.env_tex, tx.env_mapping, d, v3(ex, ey, ez));
+  }
+  light[k] = l; texel[2 * k] = i; texel[2 * k + 1] = j; st2[2 * k] = s; st2[2 * k + 1] = t;
+  dir3[3 * k] = d.x; dir3[3 * k + 1] = d.y; dir3[3 * k + 2] = d.z; pdf[k] = p;
+  e3[3 * k] = le.x; e3[3 * k + 1] = le.y; e3[3 * k + 2] = le.z;
 }
 
 // phx_dev_lobe_weights: lobe_weight_of as k_shade_g<.., TEX, ., MASK> (TEXTURED) or k_shade_g<PERHIT> (scenes without a texture table) resolves it
@@ -1939,10 +2112,16 @@ void launch_lobe_weights(hipStream_t stream, const DevMaterial* mat, const DevTe
   else hipLaunchKernelGGL(k_lobe_weights<false>, dim3((n + 63) / 64), dim3(64), 0, stream, mat, textures, texels, lobe_tex, n, n3, wi3, st, w, kept);
 }
 void launch_light_sample(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, uint32_t* light, uint32_t* tri, float* bary, float* P, float* pdf) {
-  hipLaunchKernelGGL(k_light_sample, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, light, tri, bary, P, pdf);
+  if (sc.any_tex & SC_LIGHTS_ENV) hipLaunchKernelGGL(k_light_sample_env, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, light, tri, bary, P, pdf);
+  else hipLaunchKernelGGL(k_light_sample, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, light, tri, bary, P, pdf);
 }
 void launch_light_emission(hipStream_t stream, const DevScene& sc, uint32_t n, const float* u3, float* st, float* e) {
-  hipLaunchKernelGGL(k_light_emission, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, st, e);
+  if (sc.any_tex & SC_LIGHTS_ENV) hipLaunchKernelGGL(k_light_emission_env, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, st, e);
+  else hipLaunchKernelGGL(k_light_emission, dim3((n + 63) / 64), dim3(64), 0, stream, sc, n, u3, st, e);
+}
+void launch_environment_sample(hipStream_t stream, const DevScene& sc, float ex, float ey, float ez, uint32_t n, const float* u3, uint32_t* light, uint32_t* texel,
+                               float* st, float* dir, float* pdf, float* e) {
+  hipLaunchKernelGGL(k_environment_sample, dim3((n + 63) / 64), dim3(64), 0, stream, sc, ex, ey, ez, n, u3, light, texel, st, dir, pdf, e);
 }
 void launch_texture_lookup(hipStream_t stream, const DevTexture* textures, const float4* texels, uint32_t tex, uint32_t n, const float* st, float* rgb) {
   hipLaunchKernelGGL(k_texture_lookup, dim3((n + 63) / 64), dim3(64), 0, stream, textures, texels, tex, n, st, rgb);

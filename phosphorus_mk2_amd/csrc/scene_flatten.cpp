@@ -66,11 +66,20 @@ bool bake_material(const phx_material& m, float sheen_L5, DevMaterial& out, uint
 
 // PHX_LIGHT_SELECT_BY_POWER, the rule of include/phx_xpu.h: the selection table pcdf and every light's lpdf = (1 / area) * p_l.  The weights,
 // their sums and the running table are binary64 in the order written (the file is compiled without contraction); pcdf, p_l and lpdf are fp32.
-void light_power_table(const phx_scene& s, FlatScene& out) {
-  const size_t nl = out.lights.size();
+// PHX_LIGHT_INCLUDE_ENVIRONMENT (w_env != nullptr): the environment is one more entry behind the mesh lights, with that weight; its interval
+// of the table goes to out.env_p.
+void light_power_table(const phx_scene& s, FlatScene& out, const double* w_env = nullptr) {
+  const size_t nm = out.lights.size(), nl = nm + (w_env ? 1u : 0u);  // mesh lights, table entries
   std::vector<double> w(nl), img(3 * (size_t)s.num_textures, -1.0);  // img: an image's channel means, computed at its first use
   bool finite = true; size_t npos = 0; double wsum = 0.0;
   for (size_t l = 0; l < nl; ++l) {
+    if (l == nm) {
+      w[l] = *w_env;
+      if (!std::isfinite(w[l])) finite = false;
+      if (w[l] > 0.0) ++npos;
+      wsum += w[l];
+      break;
+    }
     const DevLight& L = out.lights[l];
     double m[3] = {1.0, 1.0, 1.0};
     if (const uint32_t t = s.materials[L.material].emission_uv_texture) {
@@ -100,10 +109,65 @@ void light_power_table(const phx_scene& s, FlatScene& out) {
   }
   out.light_pcdf.resize(nl);
   for (size_t l = 0; l < nl; ++l) out.light_pcdf[l] = (float)(acc[l] / acc[nl - 1]);
-  for (size_t l = 0; l < nl; ++l) {
+  for (size_t l = 0; l < nm; ++l) {
     const float p = out.light_pcdf[l] - (l ? out.light_pcdf[l - 1] : 0.0f);
     out.lights[l].lpdf = (1.0f / out.lights[l].area) * p;
   }
+  if (w_env) out.env_p = out.light_pcdf[nm] - out.light_pcdf[nm - 1];  // (a scene has at least one mesh light)
+}
+
+// PHX_LIGHT_INCLUDE_ENVIRONMENT, the rule of include/phx_xpu.h: the importance g of every texel of the environment image T, the direction
+// tables out.env_cdf (mcdf, then ccdf row by row) and the environment's weight in the selection table, out.env_w.  One pass over the image,
+// one row of g at a time; a black or broken image (G zero or not finite) gets the tables of the uniform sphere in a second pass.
+void environment_tables(const phx_scene& s, FlatScene& out) {
+  const phx_material& m = s.materials[s.environment_material];
+  const phx_texture& T = s.textures[m.emission_texture - 1u];
+  const int W = (int)T.width, H = (int)T.height;
+  const double e[3] = {std::fabs((double)m.emission[0]), std::fabs((double)m.emission[1]), std::fabs((double)m.emission[2])};
+  auto y_at = [&](int i, int j) {
+    const float* c = T.texels + 3 * ((size_t)j * (size_t)W + (size_t)i);
+    return (0.2126 * (e[0] * std::fabs((double)c[0])) + 0.7152 * (e[1] * std::fabs((double)c[1]))) + 0.0722 * (e[2] * std::fabs((double)c[2]));
+  };
+  auto yhat = [&](int i, int j) {
+    double v = y_at(i, j);
+    if (T.filter == PHX_TEX_CLOSEST) return v;
+    for (int dj = -1; dj <= 1; ++dj)
+      for (int di = -1; di <= 1; ++di) {
+        bool outside = false;
+        const int x = tex_wrap(i + di, W, T.swrap, outside), y = tex_wrap(j + dj, H, T.twrap, outside);
+        const double n = outside ? 0.0 : y_at(x, y);
+        if (n > v) v = n;
+      }
+    return v;
+  };
+  out.env_cdf.assign((size_t)H + (size_t)H * (size_t)W, 1.0f);
+  std::vector<double> g((size_t)W), rowsum((size_t)H);
+  auto build = [&](bool sphere) {  // -> G
+    double G = 0.0;
+    for (int j = 0; j < H; ++j) {
+      const double sj = std::sin((kPiD * ((double)j + 0.5)) / (double)H);
+      double rs = 0.0;
+      for (int i = 0; i < W; ++i) {
+        g[(size_t)i] = sphere ? sj : yhat(i, j) * sj;
+        G += g[(size_t)i]; rs += g[(size_t)i];
+      }
+      rowsum[(size_t)j] = rs;
+      float* row = out.env_cdf.data() + (size_t)H + (size_t)j * (size_t)W;
+      double run = 0.0;
+      for (int i = 0; i < W; ++i) { run += g[(size_t)i]; row[i] = rs > 0.0 && std::isfinite(rs) ? (float)(run / rs) : 1.0f; }
+    }
+    double run = 0.0;
+    for (int j = 0; j < H; ++j) { run += rowsum[(size_t)j]; out.env_cdf[(size_t)j] = (float)(run / G); }
+    out.env_cdf[(size_t)H - 1] = 1.0f;
+    return G;
+  };
+  const double G = build(false);
+  if (!(G > 0.0) || !std::isfinite(G)) build(true);
+  float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  for (size_t k = 0; k < out.abc.size(); ++k) { lo[k % 3] = std::min(lo[k % 3], out.abc[k]); hi[k % 3] = std::max(hi[k % 3], out.abc[k]); }
+  const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1], dz = (double)hi[2] - (double)lo[2];
+  const double R = 0.5 * std::sqrt((dx * dx + dy * dy) + dz * dz);
+  out.env_w = ((((4.0 * kPiD) * R) * R) * (G / ((double)W * (double)H))) * (kPiD / 2.0);
 }
 
 }  // namespace
@@ -118,12 +182,15 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
   if (s.camera.film_width == 0 || s.camera.film_height == 0 || s.camera.film_width > 65535 || s.camera.film_height > 65535)
     return refuse("film size out of range");
   if (s.environment_material >= (int32_t)s.num_materials) return refuse("environment material out of range");
-  // the packed word: the triangle pick in the low byte, the light's selection above it.  Valid: 0, 1 and BY_AREA | SELECT_BY_POWER
+  // the packed word: the triangle pick in the low byte, the light's selection above it, the environment's bit above that.  Valid: 0, 1, 0x101 and 0x301
   if (PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) > PHX_LIGHTS_BY_AREA) return refuse("unknown light_sampling");
-  if (PHX_LIGHT_SELECTION(opt.light_sampling) & ~(uint32_t)PHX_LIGHT_SELECT_BY_POWER) return refuse("unknown light_sampling: bits above PHX_LIGHT_SELECT_BY_POWER");
+  if (PHX_LIGHT_SELECTION(opt.light_sampling) & ~(uint32_t)(PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT))
+    return refuse("unknown light_sampling: bits above PHX_LIGHT_INCLUDE_ENVIRONMENT");
   const bool lights_by_area = PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) == PHX_LIGHTS_BY_AREA;
-  const bool lights_by_power = PHX_LIGHT_SELECTION(opt.light_sampling) == PHX_LIGHT_SELECT_BY_POWER;
+  const bool lights_by_power = (opt.light_sampling & PHX_LIGHT_SELECT_BY_POWER) != 0;
+  const bool lights_env = PHX_LIGHT_ENVIRONMENT(opt.light_sampling) != 0;
   if (lights_by_power && !lights_by_area) return refuse("light_sampling: PHX_LIGHT_SELECT_BY_POWER needs PHX_LIGHTS_BY_AREA");
+  if (lights_env && !lights_by_power) return refuse("light_sampling: PHX_LIGHT_INCLUDE_ENVIRONMENT needs PHX_LIGHT_SELECT_BY_POWER");
 
   // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
   // non-emitting materials may carry one (an emitter's image is on its emission: emission_uv_texture)
@@ -175,6 +242,9 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
       any_tex = any_emit_tex = true;
     }
   }
+  // a constant sky is served by cosine-weighted BSDF sampling; the refusal also keeps the option out of every kernel without the image lookup
+  if (lights_env && (s.environment_material < 0 || !s.materials[s.environment_material].emission_texture))
+    return refuse("light_sampling: PHX_LIGHT_INCLUDE_ENVIRONMENT needs an environment material with an emission_texture");
 
   out = FlatScene{};
   for (uint32_t mi = 0; mi < s.num_meshes; ++mi) {
@@ -264,7 +334,8 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
       L.ex = mats[L.material].ex; L.ey = mats[L.material].ey; L.ez = mats[L.material].ez;
     }
   }
-  if (lights_by_power) light_power_table(s, out);
+  if (lights_env) { environment_tables(s, out); light_power_table(s, out, &out.env_w); }
+  else if (lights_by_power) light_power_table(s, out);
 
   // the environment's image, and every texture's texels as float4 (one 16-byte load per texel) behind a small table
   DevScene& sc = out.scene;
@@ -275,7 +346,7 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
     for (int c = 0; c < 3; ++c) out.env_e[c] = s.materials[s.environment_material].emission[c];
   }
   sc.any_tex = (any_tex ? SC_TEX_LOBES : 0u) | (out.env_tex ? SC_TEX_ENV : 0u) | (any_mask ? SC_TEX_MASK : 0u) | (lights_by_area ? SC_LIGHTS_BY_AREA : 0u) |
-               (lights_by_power ? SC_LIGHTS_BY_POWER : 0u);
+               (lights_by_power ? SC_LIGHTS_BY_POWER : 0u) | (lights_env ? SC_LIGHTS_ENV : 0u);
   if (sc.any_tex & SC_TEX_ANY) {
     out.textures.resize(s.num_textures);
     out.texels.resize((size_t)total_texels);

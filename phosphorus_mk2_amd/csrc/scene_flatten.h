@@ -35,6 +35,10 @@ struct FlatScene {
   std::vector<DevTexture> textures;     // the texture table and every texel as RGB + 0: packed only when scene.any_tex & SC_TEX_ANY
   std::vector<float4> texels;
   uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission
+  // PHX_LIGHT_INCLUDE_ENVIRONMENT: the environment's direction tables, mcdf (H floats) then ccdf (H rows of W), and its interval p_env of the
+  // selection table (light_pcdf then has lights.size() + 1 entries); w_env is the weight it entered the table with
+  std::vector<float> env_cdf;
+  float env_p = 0.0f; double env_w = 0.0;
   // every word of DevScene that needs no device: camera, film, environment, light count, any_tex, diffuse_only, any_per_hit, max_depth.
   // The pointers and the tree's words stay zero for the commit stage.
   DevScene scene{};

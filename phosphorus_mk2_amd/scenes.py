@@ -653,3 +653,34 @@ def lamp_showroom(n=500_000, lamps=64, width=1920, height=1080, side=0.05, emiss
         s.meshes.append(_quad((x - h, y - h, z), (x + h, y - h, z), (x + h, y + h, z), (x - h, y + h, z), len(s.materials) - 1))
     s.name = f"lamp_showroom{n}_{lamps}"
     return s
+
+
+def sun_and_sky(width=64, height=32, sky=0.1, sun=2000.0, sun_texel=(40, 8)):
+    """A small lat-long sky (height, width, 3) f32: `sky` everywhere and ONE texel (column, row) of radiance `sun` -- row 8 of 32 is about
+    42 degrees of elevation.  The image environment sampling is tested on: nearly all of its light comes from 1 texel of 2048."""
+    img = np.full((height, width, 3), sky, np.float32)
+    img[sun_texel[1], sun_texel[0]] = sun
+    return img
+
+
+SUN_FLOOR_RHO = (0.8, 0.5, 0.2)
+
+
+def sun_floor(width=32, height=32, image=None, mapping=abi.ENV_LATLONG_Y_UP, look="down"):
+    """A Lambert floor (y = 0, rho = SUN_FLOOR_RHO) that fills the view of a camera looking straight down from y = 1, under sun_and_sky() as a
+    CLOSEST lat-long environment.  A black emitter triangle hides below the floor: a scene needs one emissive face set, and selection by power
+    never samples it (w = 0).  Every floor point sees the whole upper hemisphere, so every pixel has the same closed-form expectation.
+    look "horizon": the same eye looking along -z with a wide lens instead: sky above the horizon, floor below it."""
+    floor = _quad((-4.0, 0.0, 4.0), (4.0, 0.0, 4.0), (4.0, 0.0, -4.0), (-4.0, 0.0, -4.0), 0)
+    hidden = MeshDesc(vertices=np.array([(-0.5, -1.0, 0.5), (0.5, -1.0, 0.5), (0.0, -1.0, -0.5)], np.float32), faces=np.array([[0, 1, 2]], np.uint32),
+                      sets=[(1, np.array([0], np.uint32))])
+    mats = [diffuse(*SUN_FLOOR_RHO), emitter(0.0, 0.0, 0.0),
+            MaterialDesc(lobes=[], emission=(1.0, 1.0, 1.0), emission_texture=1, emission_mapping=mapping)]
+    to_world = np.array([[1, 0, 0, 0], [0, 0, -1, 0], [0, 1, 0, 0], [0, 1, 0, 1]], np.float32)  # -z of the camera is -y of the world; eye at (0, 1, 0)
+    if look == "horizon":
+        to_world = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 1, 0, 1]], np.float32)
+    elif look != "down":
+        raise ValueError(f"look {look!r}: down or horizon")
+    img = sun_and_sky() if image is None else image
+    return SceneDesc([floor, hidden], mats, CameraDesc(width, height, 0.6 if look == "down" else 1.9, to_world), environment_material=2, name="sun_floor",
+                     textures=[TextureDesc(img, abi.TEX_CLOSEST, abi.WRAP_PERIODIC, abi.WRAP_CLAMP)])

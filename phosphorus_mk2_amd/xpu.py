@@ -55,7 +55,7 @@ class Options:
 
     def __init__(self, samples_per_pixel=16, paths_per_sample=16, path_depth=9, single_threaded=False, host_only=False,
                  render_normals=False, verbose=False, device_ordinal=-1, samples_in_flight=0, tiles_per_batch=0, bvh_builder="auto",
-                 light_sampling="reference", light_selection="uniform"):
+                 light_sampling="reference", light_selection="uniform", environment_sampling=False):
         self.samples_per_pixel = samples_per_pixel
         self.paths_per_sample = paths_per_sample
         self.path_depth = path_depth
@@ -73,6 +73,9 @@ class Options:
         # "uniform": next-event estimation chooses among the lights uniformly; "power": by area x luminance of the emission (bit 8 of the packed
         # word, abi.LIGHT_SELECT_BY_POWER), which needs light_sampling "area"
         self.light_selection = light_selection
+        # True: next-event estimation samples the environment image too (bit 9, abi.LIGHT_INCLUDE_ENVIRONMENT), which needs light_selection
+        # "power" and an environment material with an image
+        self.environment_sampling = environment_sampling
 
     def pack(self):
         o = abi.Options()
@@ -87,6 +90,10 @@ class Options:
             if o.light_sampling != abi.LIGHTS_BY_AREA:
                 raise ValueError('light_selection="power" needs light_sampling="area"')
             o.light_sampling |= abi.LIGHT_SELECT_BY_POWER
+        if self.environment_sampling:
+            if not o.light_sampling & abi.LIGHT_SELECT_BY_POWER:
+                raise ValueError('environment_sampling=True needs light_selection="power"')
+            o.light_sampling |= abi.LIGHT_INCLUDE_ENVIRONMENT
         return o
 
 
@@ -351,6 +358,21 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_light_emission(self._h, k, fp(u3), fp(st), fp(e)), "phx_dev_light_emission")
         return {"st": st, "e": e}
 
+    def environment_sample(self, u3):
+        """Next-event estimation's environment sample under environment_sampling, as the shade kernel draws it: u3 (n, 3) = (pick, lu, lv) per
+        item -> dict of light (n,) u32 (== the number of mesh lights for an environment pick; every other output is zero for a mesh pick),
+        texel (n, 2) u32 (i, j), st (n, 2) f32, dir (n, 3) f32, pdf (n,) f32 = p_env * pdf_omega (0: no shadow ray) and e (n, 3) f32, the
+        environment's emission in that direction.  phx_dev_environment_sample."""
+        u3 = np.ascontiguousarray(u3, np.float32).reshape(-1, 3)
+        k = len(u3)
+        light = np.zeros(k, np.uint32); texel = np.zeros((k, 2), np.uint32)
+        st = np.zeros((k, 2), np.float32); d = np.zeros((k, 3), np.float32); pdf = np.zeros(k, np.float32); e = np.zeros((k, 3), np.float32)
+        fp = lambda a: a.ctypes.data_as(abi.f32p)
+        up = lambda a: a.ctypes.data_as(abi.u32p)
+        _check(self._lib, self._lib.phx_dev_environment_sample(self._h, k, fp(u3), up(light), up(texel), fp(st), fp(d), fp(pdf), fp(e)),
+               "phx_dev_environment_sample")
+        return {"light": light, "texel": texel, "st": st, "dir": d, "pdf": pdf, "e": e}
+
     def texture_lookup(self, texture, st):
         """The shade kernel's image lookup on the device: texture `texture` (0-based index into SceneDesc.textures of the preprocessed
         scene, which must have a textured lobe) at st (n, 2) -> rgb (n, 3) f32."""
@@ -407,11 +429,12 @@ def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_s
 
 def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=32, rank=0, world=1, callback_tiles=False,
            samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference",
-           light_selection="uniform"):
+           light_selection="uniform", environment_sampling=False):
     """Convenience: the call sequence of session_t::render (plugins/blender/session.cpp:73-94):
     make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats)."""
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
-                   tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling, light_selection=light_selection)
+                   tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling, light_selection=light_selection,
+                   environment_sampling=environment_sampling)
     # ONE device, on the caller's current GPU (device_ordinal -1): discover() is for hosts that drive every GPU (render_on) and
     # would build a context, a stream and the kernel attributes on each of them only to use the first
     dev = HipDevice.make(opts)
