@@ -81,21 +81,27 @@ struct DevBuf {
 };
 
 // Queues + state of the paths in flight, 16 bytes per path each (kernels.h: PassBuffers): ray queues 2 x 32, path state travelling with them
-// 2 x 16, hit 16, shadow queue 48, radiance 16, and the primary normal 16 when the frame has a normals channel.
+// 2 x 16, shadow queue 48, radiance 16, and the primary normal 16 when the frame has a normals channel; the hit record is two streams of 8:
+// (t, triangle) always, the barycentrics only for a scene that reads them (`uv`: phx_device::hit_uv).
 struct PathQueues {
-  enum { RO, RD, QS, RO1, RD1, QS1, HIT, SO, SD, SC, PR, PN, COUNT };  // PN last: allocated only for a frame with a normals channel
+  enum { RO, RD, QS, RO1, RD1, QS1, SO, SD, SC, PR, PN, COUNT };  // PN last: allocated only for a frame with a normals channel
   DevBuf<float4> q[COUNT];
-  static constexpr size_t bytes_per_path(bool normals) { return (COUNT - (normals ? 0 : 1)) * sizeof(float4); }
-  int alloc(size_t npaths, bool normals) {
+  DevBuf<uint2> hit_tt; DevBuf<float2> hit_uv;
+  // (with both hit streams: what a scene without barycentrics saves is not handed to more paths in flight, so a batch is cut the same way either way)
+  static constexpr size_t bytes_per_path(bool normals) { return (COUNT - (normals ? 0 : 1)) * sizeof(float4) + sizeof(uint2) + sizeof(float2); }
+  int alloc(size_t npaths, bool normals, bool uv) {
     for (int i = 0; i < COUNT - (normals ? 0 : 1); ++i) if (const int rc = q[i].alloc(npaths)) return rc;
-    return PHX_OK;
+    if (const int rc = hit_tt.alloc(npaths)) return rc;
+    if (!uv) { hit_uv.release(); return PHX_OK; }  // a scene switch: the stream goes with the scene that read it
+    return hit_uv.alloc(npaths);
   }
-  void release() { for (auto& b : q) b.release(); }
-  size_t bytes() const { size_t n = 0; for (auto& b : q) n += b.bytes(); return n; }
-  size_t capacity() const { return q[HIT].n; }  // paths the queues hold
-  void fill(PassBuffers& B, bool normals) const {
+  void release() { for (auto& b : q) b.release(); hit_tt.release(); hit_uv.release(); }
+  size_t bytes() const { size_t n = hit_tt.bytes() + hit_uv.bytes(); for (auto& b : q) n += b.bytes(); return n; }
+  size_t capacity() const { return hit_tt.n; }  // paths the queues hold
+  void fill(PassBuffers& B, bool normals, bool uv) const {
     for (int k = 0; k < 2; ++k) { B.ro[k] = q[RO + 3 * k].p; B.rd[k] = q[RD + 3 * k].p; B.qs[k] = q[QS + 3 * k].p; }
-    B.hit = q[HIT].p; B.so = q[SO].p; B.sd = q[SD].p; B.sc = q[SC].p; B.pr = q[PR].p; B.pn = normals ? q[PN].p : nullptr;
+    B.hit_tt = hit_tt.p; B.hit_uv = uv ? hit_uv.p : nullptr;
+    B.so = q[SO].p; B.sd = q[SD].p; B.sc = q[SC].p; B.pr = q[PR].p; B.pn = normals ? q[PN].p : nullptr;
   }
 };
 static_assert(PathQueues::bytes_per_path(false) == 176 && PathQueues::bytes_per_path(true) == 192, "what path_budget divides the device's memory by");
@@ -155,6 +161,8 @@ struct phx_device {
   phx_stats stats{};
   TracePlan plan{};
   uint64_t paths_in_flight = 0;
+  // the committed scene reads the barycentrics of a hit (commit_scene): the passes carry PassBuffers::hit_uv and the trace kernels run as UV = true
+  bool hit_uv = false;
   double bvh_cost_model = 0; uint32_t bvh_built_on_device = 0;
   enum class Launch { Trace, Primary, Shade, Pass /* begin-pass, film */ };
   struct Timed { size_t begin, end; Launch kind; };  // (event before, event behind, what ran between them)
@@ -381,6 +389,12 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   d->env_tex = fs.env_tex; d->env_mapping = fs.env_mapping;
   for (int c = 0; c < 3; ++c) d->env_e[c] = fs.env_e[c];
   d->num_triangles = ntri;
+  // Who reads (u, v) of a hit: a smooth face's normal, the corner UVs' interpolation (lobe images, masks, emitter images: SC_TEX_LOBES) and a
+  // per-hit material — the classes flatten_scene made for launch_shade.  PHX_HIT_UV=1 (tests only) carries the stream on a scene that does not.
+  {
+    const char* force = std::getenv("PHX_HIT_UV");
+    d->hit_uv = fs.any_smooth || any_tex || sc.any_per_hit != 0 || (force && std::atoi(force) != 0);
+  }
   d->budget_bytes = 0;  // the next frame asks the device again how much memory is free
   d->preprocessed = true;
   return PHX_OK;
@@ -903,7 +917,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   size_t npaths = 0;
   for (;;) {
     npaths = (size_t)P * S;
-    if (!(rc = queues.alloc(npaths, normals))) break;
+    if (!(rc = queues.alloc(npaths, normals, hit_uv))) break;
     if (rc != PHX_ERR_OOM || S == 1) return rc;
     (void)hipGetLastError();
     queues.release();
@@ -914,7 +928,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   tb_alloc = Clock::now();
 
   PassBuffers B{};
-  queues.fill(B, normals);
+  queues.fill(B, normals, hit_uv);
   B.counters = counters.p; B.stats = dstats.p; B.pix_xy = pix_xy.p; B.jitter = jitter.p; B.acc = acc.p;
   B.num_pixels = P; B.xstride = xs; B.normals_offset = frame.normals_channel ? frame.primary_components : 0;
   B.seed = frame.sampler_seed;

@@ -2,9 +2,11 @@
 // implemented in kernels.hip.  One "pass" carries P pixels x S samples = npaths paths through
 // generate -> [trace closest -> shade/NEE/integrate -> trace shadow] x depth -> film.
 //
-// HBM layout (all records 16 B so that a wave reads/writes 1 KiB per instruction):
+// HBM layout (records of 16 B, so that a wave reads/writes 1 KiB per instruction, except the hit records, which are two streams of 8 B):
 //   ray queue (x2, ping-pong)  ro[i] = (o.xyz, path | SPECULAR<<31)   rd[i] = (d.xyz, tmax)
-//   hit records                hit[i] = (t, u, v, triangle-record index)
+//   hit records                hit_tt[i] = (t, triangle-record index)   always
+//                              hit_uv[i] = (u, v)                       only when the committed scene reads barycentrics: a smooth face, a UV
+//                                                                       consumer (TEX / MASK / emitter images) or a per-hit material
 //   shadow queue               so[i] = (o.xyz, path)  sd[i] = (d.xyz, tmax)  sc[i] = (beta*Li rgb, 0)
 //   path state (by path id)    pb[path] = (beta.rgb, depth)   pr[path] = (radiance.rgb, 0)
 //   path id = sample_in_pass * P + pixel_in_batch  (neighbouring lanes = neighbouring pixels)
@@ -117,7 +119,8 @@ struct DevStats {
 
 struct PassBuffers {
   float4* ro[2]; float4* rd[2];
-  float4* hit;
+  uint2* hit_tt;              // (t as bits, pool index of the hit triangle | 0xffffffff = miss): written by every closest-hit trace, read by every shade
+  float2* hit_uv;             // the hit's barycentrics, or nullptr: the trace kernels are instantiated without them (UV = false) and no shade kernel asks
   float4* so; float4* sd; float4* sc;
   float4* qs[2];              // path state (beta, depth) of the queue entry: it travels WITH the ray (round 6; before: an array by path id, a dependent gather)
   float4* pr;

@@ -187,7 +187,8 @@ struct DynQueue {            // the launch is persistent and every WAVE pulls ch
   uint32_t num_waves;
   uint32_t* cursor;          // pb.counters + CNT_CURSOR: two global cursors, zeroed by the kernel that filled the queues
 };
-template <int BLOCK, bool SPILL /* the stack's deep levels live in HBM */, bool PACKED /* 5-byte stack entries in LDS */>
+template <int BLOCK, bool SPILL /* the stack's deep levels live in HBM */, bool PACKED /* 5-byte stack entries in LDS */,
+          bool UV /* the scene reads barycentrics: keep (u, v) of the closest hit and store pb.hit_uv beside pb.hit_tt */>
 __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffers& pb, int q,
                                              uint32_t* cursor /* LDS: the workgroup's ranges */, uint2* stack_base, uint8_t* stack_valid /* PHX_STACK_PACKED: this thread's dword of the valid-mask rows */, uint32_t lds_levels,
                                              uint2* spill_base /* this thread's column of sc.stack_spill */, uint32_t refill_min,
@@ -390,7 +391,8 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
       ++cnt_tri[any ? 1 : 0];
 #endif
       if (mt_intersect(T, r.o, r.d, tbest, hprim, us, vs, ds)) {
-        tbest = ds; hu = us; hv = vs; htri = ti; hprim = T.prim;
+        tbest = ds; htri = ti; hprim = T.prim;
+        if constexpr (UV) { hu = us; hv = vs; }  // UV = false: us, vs feed the accept test only, and two VGPRs leave the loop
         if (any) active = false;  // occluded: nothing to add
       }
       if (!(tg & TG_PENDING) && tq != 0u) { tg_base = tq_base; tg = tq; tq = 0u; }  // this group is done and another one waits
@@ -405,7 +407,8 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
             rr.x += cc.x; rr.y += cc.y; rr.z += cc.z;
             pb.pr[path] = rr;
           } else {
-            pb.hit[idx] = make_float4(tbest, hu, hv, u2f(htri));
+            pb.hit_tt[idx] = make_uint2(f2u(tbest), htri);
+            if constexpr (UV) pb.hit_uv[idx] = make_float2(hu, hv);
           }
           active = false;
         }
@@ -454,7 +457,7 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
 //   with per-wave global chunks 512 rays were the optimum, 64-ray chunks were atomic-bound).  A wave
 //   drains once per launch, not once per slice, and a slow image region is shared by everyone.
 // Dynamic LDS layout: [ntop pool elements x 80 B][levels x BLOCK stack entries x 8 B][12 cursor words][2 KB octant table].
-template <int BLOCK, bool SPILL = false, bool PACKED = false>
+template <int BLOCK, bool SPILL = false, bool PACKED = false, bool UV = false>
 __global__ void __launch_bounds__(BLOCK, 8) k_trace(DevScene sc, PassBuffers pb, int q, int sq, int do_closest, int do_shadow, uint32_t refill_min,
                                                  uint32_t ntop, uint32_t levels, uint32_t min_chunks, uint32_t target_chunks) {
   extern __shared__ uint4 smem[];
@@ -506,10 +509,10 @@ __global__ void __launch_bounds__(BLOCK, 8) k_trace(DevScene sc, PassBuffers pb,
   for (uint32_t i = threadIdx.x; i < PHX_PERM_LUT_BYTES; i += BLOCK) perm_lut[i] = (uint8_t)perm_xor8(i & 0xffu, i >> 8);
   __syncthreads();
   if constexpr (PACKED)
-    trace_stream<BLOCK, SPILL, true>(sc, pb, q, cursor, reinterpret_cast<uint2*>(stack_words + threadIdx.x), reinterpret_cast<uint8_t*>(valid_rows + threadIdx.x), levels,
+    trace_stream<BLOCK, SPILL, true, UV>(sc, pb, q, cursor, reinterpret_cast<uint2*>(stack_words + threadIdx.x), reinterpret_cast<uint8_t*>(valid_rows + threadIdx.x), levels,
                                      sc.stack_spill + (size_t)blockIdx.x * BLOCK + threadIdx.x, refill_min, top, ntop, dq, perm_lut);
   else
-    trace_stream<BLOCK, SPILL, false>(sc, pb, q, cursor, stack + threadIdx.x, nullptr, levels, sc.stack_spill + (size_t)blockIdx.x * BLOCK + threadIdx.x,
+    trace_stream<BLOCK, SPILL, false, UV>(sc, pb, q, cursor, stack + threadIdx.x, nullptr, levels, sc.stack_spill + (size_t)blockIdx.x * BLOCK + threadIdx.x,
                                       refill_min, top, ntop, dq, perm_lut);
 }
 
@@ -602,7 +605,7 @@ __device__ __forceinline__ uint32_t packet_node_hit8(const uint32_t* w, const Sc
 #endif
 // RPL rays per lane: a packet is 64 x RPL consecutive paths (ray k of lane l is path base + 64 k + l).  The node tests are per packet,
 // so they are shared by more rays; the host picks RPL so that a packet stays inside one pixel's samples (launch_trace_primary).
-template <int RPL, bool LENS = false /* thin-lens camera: camera_ray<true> */>
+template <int RPL, bool LENS = false /* thin-lens camera: camera_ray<true> */, bool UV = false /* store pb.hit_uv too (k_trace) */>
 __global__ void __launch_bounds__(PHX_PRIMARY_BLOCK) __attribute__((amdgpu_waves_per_eu(PHX_PRIMARY_WAVES, 8))) k_trace_primary(DevScene sc, PassBuffers pb, uint32_t npaths, uint32_t sample0, int q, int sq) {
   extern __shared__ uint2 primary_lds[];  // [4 waves x PHX_MAX_BVH_DEPTH] one shared stack per wave, then [levels x 256] per-lane stacks of the fallback walk
   uint2* lane_stacks = primary_lds + (PHX_PRIMARY_BLOCK / 64) * PHX_MAX_BVH_DEPTH;
@@ -639,7 +642,8 @@ __global__ void __launch_bounds__(PHX_PRIMARY_BLOCK) __attribute__((amdgpu_waves
       // a NaN ray (LENS: a lens sample with a zero coordinate) hits nothing, but the conservative box test ignores NaNs: no walk of the whole tree
       if constexpr (LENS) { const float chk = (r[k].o.x + r[k].o.y + r[k].o.z) + (r[k].d.x + r[k].d.y + r[k].d.z); if (!(fabsf(chk) <= FLT_MAX)) continue; }
       traverse8<false>(sc.pool, sc.grid, r[k].o, r[k].d, FLT_MAX, h, st);
-      tbest[k] = h.t; hu[k] = h.u; hv[k] = h.v; htri[k] = h.tri;
+      tbest[k] = h.t; htri[k] = h.tri;
+      if constexpr (UV) { hu[k] = h.u; hv[k] = h.v; }
     }
 #if PHX_COUNT
     if (lane == 0) { atomicAdd(&pb.stats->primary_packets, 1ull); atomicAdd(&pb.stats->primary_fallbacks, 1ull); }
@@ -701,7 +705,7 @@ __global__ void __launch_bounds__(PHX_PRIMARY_BLOCK) __attribute__((amdgpu_waves
         for (int m = 0; m < RPL; ++m) {
           float us, vs, ds;
           const bool better = mt_intersect(T, r[m].o, r[m].d, tbest[m], hprim[m], us, vs, ds);
-          if (better) { tbest[m] = ds; hu[m] = us; hv[m] = vs; htri[m] = ti; hprim[m] = T.prim; }
+          if (better) { tbest[m] = ds; htri[m] = ti; hprim[m] = T.prim; if constexpr (UV) { hu[m] = us; hv[m] = vs; } }
           any_better = any_better || better;
           tworst = fmaxf(tworst, tbest[m]);
         }
@@ -728,7 +732,10 @@ __global__ void __launch_bounds__(PHX_PRIMARY_BLOCK) __attribute__((amdgpu_waves
   }
 #pragma unroll
   for (int k = 0; k < RPL; ++k)
-    if (idx[k] < npaths) pb.hit[idx[k]] = make_float4(tbest[k], hu[k], hv[k], u2f(htri[k]));
+    if (idx[k] < npaths) {
+      pb.hit_tt[idx[k]] = make_uint2(f2u(tbest[k]), htri[k]);
+      if constexpr (UV) pb.hit_uv[idx[k]] = make_float2(hu[k], hv[k]);
+    }
 }
 
 // ---- shade + next-event estimation + integrate ------------------------------------------------------
@@ -803,7 +810,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_D) __attribute__((amdgpu_waves
   float sh_t = 0.0f;
   if (live) {
     float4 a, b, bd;
-    const float4 h = pb.hit[i];
+    const uint2 h = pb.hit_tt[i];  // (t, pool index): 8 bytes; the barycentrics are a stream of their own, read for smooth faces only (below)
     if (FIRST) {
       v3 co, cd;
       camera_ray<LENS>(sc, pb, i, sample0, co, cd);
@@ -830,14 +837,18 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_D) __attribute__((amdgpu_waves
     } else {
       key = f2u(b.w);
     }
-    const uint32_t tri = f2u(h.w);
+    const uint32_t tri = h.y;
     const v3 o(a.x, a.y, a.z), d(b.x, b.y, b.z);
     if (tri != 0xffffffffu) {
       const float4 S = sc.elem_shade[tri];  // (geometric normal, material | smooth << 31): 16 bytes of the hit triangle instead of its 64-byte record
       const uint32_t pm = f2u(S.w);
-      const v3 p = o + d * h.x;            // hits.p = p + wi*d
+      const v3 p = o + d * u2f(h.x);       // hits.p = p + wi*d
       const v3 wo = -d;                    // hits.wi = -wi
-      const v3 n = (pm >> 31) != 0 ? shading_normal(sc, tri, true, v3(0.0f), v3(0.0f), h.y, h.z) : v3(S.x, S.y, S.z);
+      v3 n(S.x, S.y, S.z);
+      if ((pm >> 31) != 0) {  // a smooth face: the scene has one, so the trace kernels wrote pb.hit_uv (device.cpp: the scene's hit_uv flag)
+        const float2 uv = pb.hit_uv[i];
+        n = shading_normal(sc, tri, true, v3(0.0f), v3(0.0f), uv.x, uv.y);
+      }
       // material_t::evaluate (material.cpp:419-458): the closure list at this hit.  A constant recipe is read from the table; a
       // material with a hit-dependent weight (glass: Fresnel-driven mix) gets its weights resolved for (n, hits.wi) first.
       const DevMaterial* mp = &sc.materials[pm & 0x7fffffffu];
@@ -1291,7 +1302,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
       const uint32_t i = b + k * BLOCK + threadIdx.x;
-      tri[k] = i < count ? f2u(pb.hit[i].w) : 0xfffffffeu;
+      tri[k] = i < count ? pb.hit_tt[i].y : 0xfffffffeu;  // 4 B at an 8-B stride (a 16-B stride until the hit record was split: every sector came in for a quarter of its bytes)
     }
   };
   auto request_keys = [&](const uint32_t (&tri)[ITEMS], uint32_t (&key)[ITEMS]) {
@@ -1350,7 +1361,10 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
     // (Round 3 requested them at the START of a round and held them across the closure code: 5-12 VGPRs where the kernel has none to spare,
     // 1.2 of 42.7 ms: profiles/r03_q_prefetch_ab.log.)
     uint32_t next_i = 0, next_tri = 0xffffffffu; bool next_live = false;
-    float4 next_h = make_float4(0.f, 0.f, 0.f, 0.f), next_a = next_h, next_b = next_h, next_S = next_h;
+    // the hit's barycentrics are read where something consumes them: the corner UVs' interpolation (TEX) and a smooth face's normal
+    const bool want_uv = TEX || sc.elem_normals != nullptr;  // wave-uniform; either one makes the scene's hit_uv stream exist (device.cpp)
+    float next_t = 0.f; float2 next_uv = make_float2(0.f, 0.f);
+    float4 next_a = make_float4(0.f, 0.f, 0.f, 0.f), next_b = next_a, next_S = next_a;
     const uint32_t nslices = (min((uint32_t)WINDOW, count - base) + 63u) >> 6;
     auto take_slice = [&]() -> uint32_t {
       uint32_t s_ = 0;
@@ -1364,7 +1378,8 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
         next_i = base + perm[sorted_slot(k)];
         next_live = next_i < count;
         if (next_live) {
-          next_h = pb.hit[next_i];
+          next_t = u2f(pb.hit_tt[next_i].x);  // the pool index of this record is in LDS already (tri_sorted)
+          if (want_uv) next_uv = pb.hit_uv[next_i];
           if (!FIRST) { next_a = pb.ro[q][next_i]; next_b = pb.rd[q][next_i]; }
           next_tri = tri_sorted[sorted_slot(k)];  // the shade record does not wait for the hit record: its index is in LDS (four registers across the append)
           if (next_tri != 0xffffffffu) next_S = sc.elem_shade[next_tri];
@@ -1394,8 +1409,9 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
       uint32_t mat = 0;  // the hit's material: an INDEX — bsdf_f / bsdf_sample read the recipe through the scalar cache, one distinct material of the wave at a time
       if (live) {
         float4 a, b, bd;
-        float4 h;
-        if constexpr (PREFETCH) h = next_h; else h = pb.hit[i];
+        float ht; float2 huv = make_float2(0.f, 0.f);  // the hit's distance and barycentrics
+        if constexpr (PREFETCH) { ht = next_t; huv = next_uv; }
+        else { ht = u2f(pb.hit_tt[i].x); if (want_uv) huv = pb.hit_uv[i]; }
         // the hit's pool index comes from the sort phase (LDS), so its shade record, vertex normals and corner UVs are requested HERE, beside the
         // hit record and the ray (one memory round trip less on the critical path of a round; the texel gathers then wait on u, v only)
         uint32_t tri = 0xffffffffu; float4 S = make_float4(0.f, 0.f, 0.f, 0.f);  // S: (geometric normal, material | smooth << 31), DevScene::elem_shade
@@ -1438,11 +1454,11 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
           VertexNormals VN;  // (these two copies compute nothing, but the register allocation depends on them: EXPERIMENTS.md, "Retired A/B knobs")
           CornerUVs UV{};
           VN = VN_early; if constexpr (TEX) UV = UV_early;
-          if constexpr (TEX) st = hit_st(UV, h.y, h.z);
+          if constexpr (TEX) st = hit_st(UV, huv.x, huv.y);
           const uint32_t pm = f2u(S.w);
-          p = o + d * h.x;            // hits.p = p + wi*d
+          p = o + d * ht;             // hits.p = p + wi*d
           wo = -d;                    // hits.wi = -wi
-          n = shading_normal(VN, (pm >> 31) != 0, v3(S.x, S.y, S.z), h.y, h.z);
+          n = shading_normal(VN, (pm >> 31) != 0, v3(S.x, S.y, S.z), huv.x, huv.y);
           mat = pm & 0x7fffffffu;  // material_t::evaluate (material.cpp:419-458): the closure recipe at this hit
           if (pb.pn && (FIRST || depth == 0)) pb.pn[path] = make_float4(n.x, n.y, n.z, 1.0f);
           if (depth == 0 || specular) {  // spt.hpp:177-179
@@ -1839,6 +1855,8 @@ static inline uint32_t blocks_for(uint32_t n) { return (n + PHX_BLOCK - 1) / PHX
 void launch_begin_pass(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples) {
   hipLaunchKernelGGL(k_begin_pass, dim3(1), dim3(1), 0, stream, pb, num_samples);
 }
+// A run-time flag becomes a template argument in ONE place: f is called with std::true_type or std::false_type.
+template <typename F> static auto with_flag(bool v, F&& f) { if (v) return f(std::true_type{}); else return f(std::false_type{}); }
 namespace {
 struct TraceEnv {
   int grid_mul, wg_cap;
@@ -1869,11 +1887,15 @@ const TraceEnv& trace_env() {
 }
 template <typename F>
 void for_each_trace_kernel(F&& f) {
-  f(reinterpret_cast<const void*>(&k_trace<256>)); f(reinterpret_cast<const void*>(&k_trace<512>)); f(reinterpret_cast<const void*>(&k_trace<1024>));
-  f(reinterpret_cast<const void*>(&k_trace<1024, true>)); f(reinterpret_cast<const void*>(&k_trace<1024, true, true>));
+  auto both = [&](auto UV) {  // every instantiation launch_trace / launch_trace_primary can pick, with and without the barycentrics
+    constexpr bool uv = decltype(UV)::value;
+    f(reinterpret_cast<const void*>(&k_trace<256, false, false, uv>)); f(reinterpret_cast<const void*>(&k_trace<512, false, false, uv>)); f(reinterpret_cast<const void*>(&k_trace<1024, false, false, uv>));
+    f(reinterpret_cast<const void*>(&k_trace<1024, true, false, uv>)); f(reinterpret_cast<const void*>(&k_trace<1024, true, true, uv>));
+    f(reinterpret_cast<const void*>(&k_trace_primary<1, false, uv>)); f(reinterpret_cast<const void*>(&k_trace_primary<2, false, uv>)); f(reinterpret_cast<const void*>(&k_trace_primary<4, false, uv>));
+    f(reinterpret_cast<const void*>(&k_trace_primary<1, true, uv>)); f(reinterpret_cast<const void*>(&k_trace_primary<2, true, uv>)); f(reinterpret_cast<const void*>(&k_trace_primary<4, true, uv>));
+  };
+  both(std::false_type{}); both(std::true_type{});
   f(reinterpret_cast<const void*>(&k_trace_rays<true>)); f(reinterpret_cast<const void*>(&k_trace_rays<false>));
-  f(reinterpret_cast<const void*>(&k_trace_primary<1>)); f(reinterpret_cast<const void*>(&k_trace_primary<2>)); f(reinterpret_cast<const void*>(&k_trace_primary<4>));
-  f(reinterpret_cast<const void*>(&k_trace_primary<1, true>)); f(reinterpret_cast<const void*>(&k_trace_primary<2, true>)); f(reinterpret_cast<const void*>(&k_trace_primary<4, true>));
 }
 }  // namespace
 
@@ -1950,10 +1972,14 @@ void launch_trace(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, g, b, lds, stream, sc, pb, q, sq, do_closest, do_shadow, E.refill, ntop, levels, E.min_chunks, E.target_chunks);
   };
-  if (P.lds_levels < P.levels) { if (P.packed) go(&k_trace<1024, true, true>); else go(&k_trace<1024, true>); }  // deep tree: 1024-thread workgroups, the stack's deep levels in HBM
-  else if (block == 256) go(&k_trace<256>);
-  else if (block == 512) go(&k_trace<512>);
-  else go(&k_trace<1024>);
+  // UV: the pass has a barycentrics stream exactly when the committed scene reads them (device.cpp), so its presence picks the instantiation
+  with_flag(pb.hit_uv != nullptr, [&](auto UV) {
+    constexpr bool uv = decltype(UV)::value;
+    if (P.lds_levels < P.levels) { if (P.packed) go(&k_trace<1024, true, true, uv>); else go(&k_trace<1024, true, false, uv>); }  // deep tree: 1024-thread workgroups, the stack's deep levels in HBM
+    else if (block == 256) go(&k_trace<256, false, false, uv>);
+    else if (block == 512) go(&k_trace<512, false, false, uv>);
+    else go(&k_trace<1024, false, false, uv>);
+  });
 }
 // k_shade / k_shade_g walk the queue with a fixed grid: PHX_SHADE_GRID workgroups per resident slot (never more than the queue's
 // capacity needs)
@@ -1986,8 +2012,6 @@ static uint64_t shade_g(dim3 g, dim3 b, hipStream_t stream, const DevScene& sc, 
   hipLaunchKernelGGL((k_shade_g<PERHIT, FIRST, LENS, TEX, ENV, MASK>), g, b, 0, stream, sc, pb, q, sq, sample0);
   return 1ull << bit;
 }
-// A run-time flag becomes a template argument in ONE place: f is called with std::true_type or std::false_type.
-template <typename F> static auto with_flag(bool v, F&& f) { if (v) return f(std::true_type{}); else return f(std::false_type{}); }
 // (camera_rays, lens) -> the three legal (FIRST, LENS) pairs: the lens bends camera rays only
 template <typename F> static auto with_pass(bool camera_rays, bool lens, F&& f) {
   if (camera_rays) return with_flag(lens, [&](auto LENS) { return f(std::true_type{}, LENS); });
@@ -2027,8 +2051,10 @@ void launch_trace_primary(hipStream_t stream, const DevScene& sc, const PassBuff
   const dim3 g((npaths + PHX_PRIMARY_BLOCK * rpl - 1) / (PHX_PRIMARY_BLOCK * rpl)), b(PHX_PRIMARY_BLOCK);
   // thin lens: the rays of a packet leave from a disc, not a point (the packet's bounds know origins apart)
   with_flag(sc.aperture_radius != 0.0f, [&](auto LENS) {
-    auto go = [&](auto RPL) { hipLaunchKernelGGL((k_trace_primary<decltype(RPL)::value, decltype(LENS)::value>), g, b, lds, stream, sc, pb, npaths, sample0, q, sq); };
-    if (rpl == 4) go(std::integral_constant<int, 4>{}); else if (rpl == 2) go(std::integral_constant<int, 2>{}); else go(std::integral_constant<int, 1>{});
+    with_flag(pb.hit_uv != nullptr, [&](auto UV) {  // (launch_trace: the barycentrics stream exists when the scene reads them)
+      auto go = [&](auto RPL) { hipLaunchKernelGGL((k_trace_primary<decltype(RPL)::value, decltype(LENS)::value, decltype(UV)::value>), g, b, lds, stream, sc, pb, npaths, sample0, q, sq); };
+      if (rpl == 4) go(std::integral_constant<int, 4>{}); else if (rpl == 2) go(std::integral_constant<int, 2>{}); else go(std::integral_constant<int, 1>{});
+    });
   });
 }
 namespace {
