@@ -337,7 +337,7 @@ typedef struct phx_frame {
 } phx_frame;
 
 /* ---- statistics ------------------------------------------------------------------------ */
-/* The shade kernels (kernels.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
+/* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
  * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
 enum {
   PHX_SHADE_PASS_LATER   = 0, /* a later bounce */
@@ -374,7 +374,7 @@ typedef struct phx_stats {
   uint64_t triangles;
   double   preprocess_ms;    /* wall time of the last phx_dev_preprocess */
   double   bvh_build_ms;     /* of which: tree construction (host SAH, or device LBVH incl. its upload of the triangles) */
-  /* the k_trace launch plan of the preprocessed scene (kernels.hip: trace_plan) */
+  /* the k_trace launch plan of the preprocessed scene (trace.hip: trace_plan) */
   uint64_t trace_block;      /* threads per k_trace workgroup: 256, 512 or 1024 */
   uint64_t trace_ntop;       /* top-of-tree elements staged in LDS by every workgroup */
   uint64_t trace_levels;     /* per-lane stack entries (= tree depth - 1, at least 2) */

@@ -52,7 +52,7 @@ def shade_kernel_bit(family, pass_):
 
 
 def shade_kernel_name(bit):
-    """the instantiation behind bit `bit` of Stats.shade_kernels, as launch_shade (kernels.hip) spells it"""
+    """the instantiation behind bit `bit` of Stats.shade_kernels, as launch_shade (shade_general.hip) spells it"""
     if not 0 <= bit < SHADE_KERNELS:
         raise ValueError(f"no shade kernel has bit {bit}")
     family, p = divmod(bit, SHADE_PASSES)

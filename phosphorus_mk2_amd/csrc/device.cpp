@@ -3,7 +3,7 @@
 // Mirrors cpu_t (reference src/xpu/cpu.cpp:208-248): preprocess() flattens the scene and builds the
 // accelerator (cpu.cpp:35-44), start() spawns a driver thread that drains the shared tile queue
 // (cpu.cpp:223-238) — in batches of many tiles, each carried through the wavefront kernels of
-// kernels.hip — and hands finished tiles to the film sink (cpu.cpp:201), join() waits for it.
+// trace.hip, shade_lambert.hip, shade_general.hip, film_hooks.hip — and hands finished tiles to the film sink (cpu.cpp:201), join() waits for it.
 // There is no CPU rendering path in this library: without a gfx950 device every entry point fails.
 #include "../../include/phx_xpu.h"
 #include "bvh_build.h"
@@ -319,12 +319,12 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   if (sc.stack_levels > PHX_MAX_BVH_DEPTH)
     return fail(PHX_ERR_ARG, "tree too deep: " + std::to_string(sc.stack_levels) + " levels, the traversal stack in LDS holds " + std::to_string(PHX_MAX_BVH_DEPTH));
   if ((rc = d->d_materials.upload(fs.materials))) return rc;
-  if (sc.any_tex & SC_LIGHTS_BY_POWER) {  // the selection table rides directly behind the light records (kernels.hip: light_pcdf), padded to whole records
+  if (sc.any_tex & SC_LIGHTS_BY_POWER) {  // the selection table rides directly behind the light records (shade_common.h: light_pcdf), padded to whole records
     const size_t nl = fs.lights.size();
     fs.lights.resize(nl + (fs.light_pcdf.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
     std::memcpy(static_cast<void*>(fs.lights.data() + nl), fs.light_pcdf.data(), fs.light_pcdf.size() * sizeof(float));
   }
-  if (sc.any_tex & SC_LIGHTS_BY_AREA) {  // the CDF rides behind the light table (kernels.hip: light_cdf): one float per light triangle, in records of the table's size
+  if (sc.any_tex & SC_LIGHTS_BY_AREA) {  // the CDF rides behind the light table (shade_common.h: light_cdf): one float per light triangle, in records of the table's size
     const size_t nl = fs.lights.size();
     fs.lights.resize(nl + (fs.light_cdf.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
     std::memcpy(static_cast<void*>(fs.lights.data() + nl), fs.light_cdf.data(), fs.light_cdf.size() * sizeof(float));
@@ -379,7 +379,7 @@ int commit_scene(phx_device* d, FlatScene& fs) {
     sc.num_cus = (uint32_t)prop.multiProcessorCount;
   }
   d->plan = trace_plan(sc);
-  if (d->plan.spill_threads) {  // stack levels below the ones k_trace keeps in LDS (kernels.hip: trace_plan)
+  if (d->plan.spill_threads) {  // stack levels below the ones k_trace keeps in LDS (trace.hip: trace_plan)
     if ((rc = d->d_spill.alloc((size_t)d->plan.spill_threads * (d->plan.levels - d->plan.lds_levels)))) return rc;
     sc.stack_spill = d->d_spill.p; sc.spill_stride = d->plan.spill_threads;
   }

@@ -1,6 +1,14 @@
 // kernels.h — device-side data layout of the wavefront path tracer and the launch entry points
-// implemented in kernels.hip.  One "pass" carries P pixels x S samples = npaths paths through
+// implemented by the kernel families below.  One "pass" carries P pixels x S samples = npaths paths through
 // generate -> [trace closest -> shade/NEE/integrate -> trace shadow] x depth -> film.
+//
+// One translation unit per kernel family (the head of each file maps its kernels to the reference's sources):
+//   trace.hip          k_trace, k_trace_primary, k_trace_rays; trace_plan, init_kernels_on_current_device, launch_trace*
+//   shade_lambert.hip  k_shade<MATS, FIRST, LENS> (Lambert-only scenes), block_append2
+//   shade_general.hip  k_shade_g and its append ring; launch_shade (which reaches k_shade through shade_launch.h)
+//   film_hooks.hip     k_begin_pass, k_film, k_scatter_film; the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
+//   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
+// A family's code can change another's only through a shared header.
 //
 // HBM layout (records of 16 B, so that a wave reads/writes 1 KiB per instruction, except the hit records, which are two streams of 8 B):
 //   ray queue (x2, ping-pong)  ro[i] = (o.xyz, path | SPECULAR<<31)   rd[i] = (d.xyz, tmax)
@@ -37,7 +45,7 @@ struct DevTexScene {
   const uint32_t* lobe_tex;       // 8 per material: texture + 1 of lobe k (DevMaterial::tex_lobes says which are textured)
   uint32_t env_tex;               // k_shade_g<.., ENV>: the environment's image (0-based index into `textures`)
   uint32_t env_mapping;           // and its lat-long mapping (ENV_LATLONG_*)
-  // textured surface emission (phx_material.emission_uv_texture; bsdf.h: hit_emission, kernels.hip: light_emission)
+  // textured surface emission (phx_material.emission_uv_texture; bsdf.h: hit_emission, shade_common.h: light_emission)
   uint32_t any_emit_tex;          // some emitter's emission is multiplied by an image: the wave-uniform branch of the TEX kernels
   float env_p;                    // SC_LIGHTS_ENV: the environment's interval of the selection table, p_env (this word was padding)
   const uint32_t* mat_emit_tex;   // per material: its emission image + 1 (0 = none), indexed by the hit's material and by DevLight::material
@@ -54,7 +62,7 @@ enum { SC_TEX_LOBES = 1u /* some lobe is textured or masked: TEX */, SC_TEX_ENV 
        // records and the area CDF: num_lights floats, padded to whole records of the light table
        SC_LIGHTS_BY_POWER = 16u,
        // PHX_LIGHT_INCLUDE_ENVIRONMENT, always with SC_LIGHTS_BY_POWER and SC_TEX_ENV: pcdf has num_lights + 1 entries, the last one the environment's,
-       // and k_shade_g<.., ENV> samples the image by DevTexScene::env_cdf when the pick lands there (kernels.hip: env_sample)
+       // and k_shade_g<.., ENV> samples the image by DevTexScene::env_cdf when the pick lands there (shade_common.h: env_sample)
        SC_LIGHTS_ENV = 32u };
 
 struct DevScene {

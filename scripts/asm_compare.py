@@ -1,16 +1,36 @@
 #!/usr/bin/env python3
-"""Per-symbol comparison of two kernels.s files (`make -C phosphorus_mk2_amd/csrc asm` on two trees): which kernels' instruction streams
-differ, with basic-block labels renumbered by first appearance and comments, debug and CFI directives dropped.
+"""Per-symbol comparison of the kernels' assembly of two trees (`make -C phosphorus_mk2_amd/csrc asm` on both): which kernels' instruction
+streams differ, with basic-block labels renumbered by first appearance and comments, debug and CFI directives dropped.  Each side is one .s
+file, several joined by commas, or a directory of them (one .s per kernel family: trace.s, shade_lambert.s, shade_general.s, film_hooks.s):
 
-    python scripts/asm_compare.py PARENT/phosphorus_mk2_amd/csrc/kernels.s phosphorus_mk2_amd/csrc/kernels.s
+    python scripts/asm_compare.py PARENT/phosphorus_mk2_amd/csrc phosphorus_mk2_amd/csrc
 """
+import os
 import re
 import subprocess
 import sys
 
 
-def bodies(path):
-    """symbol -> its lines up to .Lfunc_end, comments stripped"""
+def files_of(side):
+    """a side of the comparison: one .s file, several joined by commas, or a directory (every .s file in it)"""
+    paths = []
+    for p in side.split(","):
+        paths += sorted(os.path.join(p, f) for f in os.listdir(p) if f.endswith(".s")) if os.path.isdir(p) else [p]
+    return paths
+
+
+def bodies(side):
+    """symbol -> its lines up to .Lfunc_end, comments stripped, over all files of the side"""
+    out = {}
+    for path in files_of(side):
+        for name, lines in bodies_of_file(path).items():
+            if name in out and renumbered(out[name]) != renumbered(lines):
+                sys.exit(f"{name} is defined with different bodies in two files of {side}")
+            out[name] = lines
+    return out
+
+
+def bodies_of_file(path):
     out, cur = {}, None
     for line in open(path):
         m = re.match(r"^(_Z\w+|[A-Za-z_]\w*):\s*(;.*)?$", line)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Resource table of every kernel of the device library (VGPRs, SGPRs, scratch, LDS, occupancy, code bytes) from the compiler's
 kernel-resource-usage remarks: `python scripts/kernel_resources.py [-DNAME=VALUE ...] > profiles/rNN_kernel_resources.txt`.
-Runs `hipcc -S --cuda-device-only` on kernels.hip and bvh_gpu.hip with the flags of csrc/Makefile; needs no GPU."""
+Runs `hipcc -S --cuda-device-only` on every kernel source (csrc/Makefile: KSRCS, and bvh_gpu.hip) with the flags of csrc/Makefile; needs no GPU."""
 import os
 import re
 import subprocess
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
 FLAGS = "-std=c++17 -O3 -fno-slp-vectorize -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math".split()
 rows = []
-for src in ("kernels.hip", "bvh_gpu.hip"):
+for src in ("trace.hip", "shade_lambert.hip", "shade_general.hip", "film_hooks.hip", "bvh_gpu.hip"):
     out = "/tmp/_phx_%s.s" % src.split(".")[0]
     r = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *sys.argv[1:], "-S", "--cuda-device-only", "-o", out, src,
                         "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True)

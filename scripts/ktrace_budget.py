@@ -3,7 +3,7 @@
 
     make -C phosphorus_mk2_amd/csrc asm && python scripts/ktrace_budget.py [--kernel k_traceILi1024ELb0] > profiles/r04_ktrace_budget.md
 
-The loop of trace_stream (kernels.hip) compiles to a handful of basic-block regions that are recognised here by their
+The loop of trace_stream (trace.hip) compiles to a handful of basic-block regions that are recognised here by their
 instructions, not by label numbers (those change from build to build):
   head      loop counter, ballot of idle lanes, refill decision                 (every iteration)
   refill    chunk bookkeeping, ranks of the idle lanes, ray fetch, reciprocals  (when >= refill_min lanes are idle)
@@ -79,7 +79,7 @@ def instructions(lines):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--asm", default=os.path.join(ROOT, "phosphorus_mk2_amd", "csrc", "kernels.s"))
+    ap.add_argument("--asm", default=os.path.join(ROOT, "phosphorus_mk2_amd", "csrc", "trace.s"))
     ap.add_argument("--kernel", default="k_traceILi1024ELb0")
     a = ap.parse_args()
     ins = instructions(kernel_text(a.asm, a.kernel))
@@ -124,7 +124,7 @@ def main():
         ("tri: Moeller-Trumbore incl. IEEE division, tie rule, accept", tri_fetch_end + 1, tri_end - 8, "per tri-block execution"),
         ("pop / finish: group done?, stack pop, hit record store, radiance read-modify-write", tri_end - 8, pop_end + 1, "per iteration (divergent)"),
     ]
-    print("# k_trace instruction budget (`" + a.kernel + "`, from `kernels.s`)\n")
+    print("# k_trace instruction budget (`" + a.kernel + "`, from `trace.s`)\n")
     print("Generated by `scripts/ktrace_budget.py` from the assembly of the committed sources (`make -C phosphorus_mk2_amd/csrc asm`).")
     print("Clocks = issue time of ONE wave on its SIMD with the measured per-instruction costs of `profiles/r02_valu_ops.json`.\n")
     print("| region | when | VALU | of which 4-clock | VALU clocks | SALU | branches | LDS | VMEM | waitcnt |")

@@ -1,6 +1,6 @@
 // Micro-benchmark (round 5): the shade kernels' shape — a 1 024-thread workgroup reads 1 024 records, decides per record whether it
 // survives (85 %) and whether it sends a shadow ray (55 %), reserves slots in two output queues with ONE returning atomic per queue
-// between two barriers (kernels.hip: block_append2) and writes 2 + 3 records per slot plus one by path — with the queue counters
+// between two barriers (shade_lambert.hip: block_append2) and writes 2 + 3 records per slot plus one by path — with the queue counters
 //   mode 0: one counter per queue (the product)
 //   mode 1: K counters per queue, counter (workgroup id % K) owns every K-th slab of 1 024 slots of the same queue ("striped")
 //   mode 2: no atomics at all (slot = own index: what the streams alone cost)

@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(256, 8) k(SceneGrid grid, int iters, uint32_t*
   // hoisting 8 of the 48 conversions and ~26 of the 192 node-test instructions out of a loop that changed two words per iteration):
   // every one of the sixteen node words, the ray's origin and reciprocal direction and tbest change in every iteration — in MODE 2
   // (the skeleton that is subtracted) exactly as in MODE 0.  scripts/valu_mix_asm.py checks the compiled loop: 48 v_cvt_f32_ubyteN
-  // and a VALU count (loop of MODE 0 minus loop of MODE 2) within 5 % of the node test's in kernels.s.
+  // and a VALU count (loop of MODE 0 minus loop of MODE 2) within 5 % of the node test's in trace.s.
   const float fx = (float)(s & 1023u) * (1.0f / 1024.0f) - 0.5f, fy = (float)((s >> 10) & 1023u) * (1.0f / 1024.0f) - 0.5f;
   RayCtx r = make_ray_ctx(v3(0.1f * fx, 0.1f * fy, 0.0f), v3(fx, fy, -0.8f));
   uint32_t w[16];

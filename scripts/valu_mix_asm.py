@@ -7,7 +7,7 @@ Compiles the micro-benchmark to gfx950 assembly, reads the inner loops of its no
     VALU instructions of the priced test = loop(MODE 0) - loop(MODE 2)
     v_cvt_f32_ubyteN in loop(MODE 0)
 
-with the node test inside k_trace<1024, false> in csrc/kernels.s (`make -C phosphorus_mk2_amd/csrc asm`): the instructions from
+with the node test inside k_trace<1024, false> in csrc/trace.s (`make -C phosphorus_mk2_amd/csrc asm`): the instructions from
 the last of the node's four global loads to the octant-table lookup that ends node_hitmask — origin decode, scale exponents,
 near / far selects, the slab arithmetic of the eight children, the valid / inner masks — and likewise for the triangle test (MODE 1
 minus MODE 3 against k_trace's Moeller-Trumbore, loads to the |det| compare).  Asserts 48 conversions in both and a VALU count
@@ -104,7 +104,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--no-assert", action="store_true")
     ap.add_argument("--tolerance", type=float, default=0.05)
-    ap.add_argument("--kernels-asm", default=os.path.join(CSRC, "kernels.s"))
+    ap.add_argument("--kernels-asm", default=os.path.join(CSRC, "trace.s"))
     a = ap.parse_args()
     if not os.path.exists(a.kernels_asm):
         subprocess.run(["make", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)

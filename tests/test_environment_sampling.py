@@ -129,7 +129,7 @@ class EnvTable(PowerTable):
 
 
 def sin_pi_t(t):
-    """kernels.hip: env_sin_pi_t -- cos(pi (0.5 - t)) by its Taylor polynomial to y^20, Horner in binary64, rounded to fp32 once"""
+    """shade_common.h: env_sin_pi_t -- cos(pi (0.5 - t)) by its Taylor polynomial to y^20, Horner in binary64, rounded to fp32 once"""
     y = D(math.pi) * (D(0.5) - np.asarray(t, F).astype(D))
     y2 = y * y
     c = D(1.0) / D(2432902008176640000.0)

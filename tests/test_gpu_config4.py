@@ -59,7 +59,7 @@ def test_config4_trace_and_tiles_match_oracle(c4, orc, builder):
     print(f"\n[config 4/{builder}] preprocess {time.time() - t0:.1f} s (tree {st['bvh_build_ms']:.0f} ms), {st['bvh_nodes']} nodes, "
           f"{st['bvh_bytes'] / 1e6:.0f} MB, depth {st['bvh_depth']}; k_trace plan: block {st['trace_block']}, "
           f"{st['trace_ntop']} elements in LDS, {st['trace_levels']} stack levels ({st['trace_lds_levels']} in LDS), {st['trace_waves_per_cu']} waves/CU")
-    # (c) the launch plan this tree runs with (kernels.hip: trace_plan): consistent with the depth and with the CU's 160 KB of LDS
+    # (c) the launch plan this tree runs with (trace.hip: trace_plan): consistent with the depth and with the CU's 160 KB of LDS
     assert st["triangles"] == N_TRI + 2 and st["bvh_bytes"] > 600e6
     assert 8 <= st["bvh_depth"] <= 64 and st["trace_levels"] == max(2, st["bvh_depth"] - 1)
     assert st["trace_block"] in (256, 512, 1024) and st["trace_ntop"] >= 9 and st["trace_waves_per_cu"] >= 16

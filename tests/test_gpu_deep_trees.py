@@ -1,4 +1,4 @@
-"""k_trace's stack layouts on trees deep enough to use them (kernels.hip: trace_plan / launch_trace).  A lane's stack of pending sibling
+"""k_trace's stack layouts on trees deep enough to use them (trace.hip: trace_plan / launch_trace).  A lane's stack of pending sibling
 groups lives in one of three layouts:
 
 - every level in LDS, 8-byte entries (k_trace<256 / 512 / 1024>): trees of < 10 stack levels;
@@ -24,8 +24,8 @@ from conftest import ROOT, bits_equal
 
 pytestmark = pytest.mark.gpu
 
-SPILL_LDS_LEVELS = 7  # kernels.hip: PHX_SPILL_LDS_LEVELS
-SPILL_FROM_LEVELS = 10  # kernels.hip: PHX_SPILL_FROM_LEVELS
+SPILL_LDS_LEVELS = 7  # trace.hip: PHX_SPILL_LDS_LEVELS
+SPILL_FROM_LEVELS = 10  # trace.hip: PHX_SPILL_FROM_LEVELS
 COMB_SPP, DEPTH, SEED = 16, 9, 3
 LIBDIR = os.path.join(ROOT, "phosphorus_mk2_amd")
 COUNT_LIB, NOPACK_LIB = os.path.join(LIBDIR, "libphx_hip_count.so"), os.path.join(LIBDIR, "libphx_hip_nopack.so")

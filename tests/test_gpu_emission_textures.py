@@ -1,4 +1,4 @@
-"""Textured surface emission on the device (phx_material.emission_uv_texture: hit_emission / light_emission in kernels.hip, run by the 18
+"""Textured surface emission on the device (phx_material.emission_uv_texture: hit_emission / light_emission in shade_common.h, run by the 18
 k_shade_g<.., TEX> instantiations and by phx_dev_light_emission).  The oracle knows no image, so the feature is held to: the numpy
 restatement of tests/test_emission_textures.py, bit for bit, through the parity hook; the oracle's films of twin scenes that carry
 fp32(e * texel) as constant emissions, bit for bit, wherever every sample of a light reads one texel; and closed forms of direct lighting

@@ -3,7 +3,7 @@ bit-equal to the CPU oracle's (under the device's tie rule), and both are within
 (tests/integrator64.py) -- the recorded standard errors, never a spread of the device's own film -- so that this file stands on its own.
 
 The cavity's answer depends neither on the camera nor on the kernel that shades it, so one scene reaches every shade path (launch_shade,
-kernels.hip); each case's docstring entry names the DevScene state that selects it."""
+shade_general.hip); each case's docstring entry names the DevScene state that selects it."""
 import copy
 from dataclasses import replace
 
@@ -138,7 +138,7 @@ SE_VARIANT = {
 @pytest.mark.parametrize("name", list(CAVITIES))
 def test_cavity_on_every_shade_path(xpu, oracle, name):
     """The coloured cavity at depth 5 through each shade kernel.  The comment above each entry of CAVITIES names the instantiation and the
-    DevScene state that selects it in launch_shade (kernels.hip): sc.diffuse_only == 2 -> k_shade<2>; 0 -> k_shade_g, <PERHIT> with
+    DevScene state that selects it in launch_shade (shade_general.hip): sc.diffuse_only == 2 -> k_shade<2>; 0 -> k_shade_g, <PERHIT> with
     sc.any_per_hit, <TEX> / <ENV> with sc.any_tex & SC_TEX_LOBES / SC_TEX_ENV, the LENS twins with sc.aperture_radius != 0 on the camera
     rays' pass.  Stats' shade_kernels names the instantiations the frame launched: exactly the entry's two."""
     make, make_ref, opts, kernels, se_key, ref_key = CAVITIES[name]

@@ -1,5 +1,5 @@
 """Choosing next-event estimation's light by power on the device (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER: the search over the selection
-table in light_pick, kernels.hip, run by k_shade_g and by the two light hooks).  The oracle selects uniformly, so the mode is held to: the
+table in light_pick, shade_common.h, run by k_shade_g and by the two light hooks).  The oracle selects uniformly, so the mode is held to: the
 numpy restatement of tests/test_light_power.py, bit for bit, through the hooks; the closed form of direct lighting under seven lamps with the
 variance of the power table's estimator (which the uniform selection's film does not have); a black lamp that changes nothing; the oracle's
 own films, bit for bit, wherever the scene has ONE light (the table is {1}: all 30 k_shade_g instantiations); dispatch, bytes and refusals."""

@@ -1,4 +1,4 @@
-"""Picking a mesh light's triangle by area on the device (phx_options.light_sampling = PHX_LIGHTS_BY_AREA: light_pick in kernels.hip, run by
+"""Picking a mesh light's triangle by area on the device (phx_options.light_sampling = PHX_LIGHTS_BY_AREA: light_pick in shade_common.h, run by
 k_shade_g and by phx_dev_light_sample).  The oracle knows the reference's pick only, so the new mode is held to three things: the numpy
 restatement of tests/test_light_sampling.py, bit for bit, through the parity hook; closed forms of direct lighting under lamps of unequal
 triangles, which the reference's pick misses and this one must meet; and the oracle's own films, bit for bit, on every scene whose lights

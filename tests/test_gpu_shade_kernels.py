@@ -1,4 +1,4 @@
-"""Every shade kernel on a scene that selects it.  launch_shade (kernels.hip) picks one of 36 instantiations -- 12 families (k_shade<2>,
+"""Every shade kernel on a scene that selects it.  launch_shade (shade_general.hip) picks one of 36 instantiations -- 12 families (k_shade<2>,
 k_shade<1> and k_shade_g with PERHIT / TEX / ENV / MASK) times the pass (a later bounce, camera rays through a pinhole, camera rays
 through a lens) -- and phx_stats::shade_kernels names the ones a frame launched.  One table: each family on a pinhole and on a lens
 camera, each case against the CPU oracle's film of the same scene with its images baked in (the oracle knows neither textures nor

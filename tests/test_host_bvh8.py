@@ -173,7 +173,7 @@ def test_any_hit_answers_do_not_depend_on_the_visiting_order(host_bvh8):
     assert np.array_equal(full["prim"], narrow["prim"]) and bits_equal(full["t"], narrow["t"]) and narrow["node_visits"] > full["node_visits"]
 
 
-SPILL_LDS_LEVELS = 7  # kernels.hip: PHX_SPILL_LDS_LEVELS, the stack levels k_trace's SPILL plan keeps in LDS (the rest live in HBM)
+SPILL_LDS_LEVELS = 7  # trace.hip: PHX_SPILL_LDS_LEVELS, the stack levels k_trace's SPILL plan keeps in LDS (the rest live in HBM)
 
 
 @pytest.mark.parametrize("n,ratio,lamp", [(400, 1.08, True), (200, 1.2, True), (400, 1.08, False)])
