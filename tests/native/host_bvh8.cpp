@@ -2,6 +2,7 @@
 // template on the CPU so that topology-independent closest-hit parity can be checked without a GPU.
 #include "../../phosphorus_mk2_amd/csrc/bvh_build.h"
 #include <cstdio>
+#include <cstring>
 using namespace phx;
 struct HostStack {
   uint32_t b[64], h[64]; int sp = 0; int max_sp = 0;
@@ -14,6 +15,15 @@ void* hb8_build(const float* tri_abc, uint32_t n, int threads) { Bvh8* b = new B
 double hb8_cost(void* h, float cn, float ct) { return bvh8_sah_cost(*(Bvh8*)h, cn, ct); }
 void hb8_free(void* h) { delete (Bvh8*)h; }
 void hb8_info(void* h, uint64_t* out) { Bvh8* b = (Bvh8*)h; out[0] = b->num_nodes; out[1] = b->num_tris; out[2] = b->depth; }
+// the finished tree as the kernels would read it (tests/test_bvh_model.py): returns the number of pool elements; fills grid6 (grid.lo, grid.cell),
+// *cost (Bvh8::cost) and, when `capacity` elements suffice, the pool's 16 words per element
+uint64_t hb8_copy_pool(void* h, uint32_t* out, uint64_t capacity, float* grid6, float* cost) {
+  Bvh8* b = (Bvh8*)h;
+  if (grid6) for (int a = 0; a < 3; ++a) { grid6[a] = b->grid.lo[a]; grid6[3 + a] = b->grid.cell[a]; }
+  if (cost) *cost = b->cost;
+  if (out && capacity >= b->pool.size()) std::memcpy(out, b->pool.data(), b->pool.size() * sizeof(PoolElem));
+  return b->pool.size();
+}
 // returns max stack depth used
 int hb8_trace(void* h, uint32_t n, const float* o, const float* d, const float* tmax, int any, float* t, float* u, float* v, uint32_t* prim, uint64_t* counters) {
   Bvh8* b = (Bvh8*)h; int max_sp = 0; uint64_t nv = 0, tt = 0;
