@@ -191,9 +191,11 @@ class BottomUpFilm(Film):
 class FrameState:
     """frame_state_t (src/state.hpp:18-31).  `sampler_seed` replaces the shared sampler_t."""
 
-    def __init__(self, sampler_seed, tiles, film, device_film_ptr=None, native_sink=False):
+    def __init__(self, sampler_seed, tiles, film, device_film_ptr=None, native_sink=False, primary_components=4, normals=False):
         self.sampler_seed, self.tiles, self.film, self.device_film_ptr = sampler_seed, tiles, film, device_film_ptr
         self.native_sink = native_sink  # fill film.data from C (phx_frame.host_film) instead of one Python add_tile call per tile
+        # the pixel layout of device_film_ptr when there is no `film` to take it from (a film's own layout wins)
+        self.primary_components, self.normals = primary_components, normals
 
 
 class HipDevice:
@@ -269,7 +271,8 @@ class HipDevice:
             f.primary_components = film.primary_components
             f.normals_channel = 1 if film.normals else 0
         else:
-            f.primary_components = 4
+            f.primary_components = frame.primary_components
+            f.normals_channel = 1 if frame.normals else 0
         if frame.device_film_ptr:
             f.device_film = frame.device_film_ptr
         f.sampler_seed = frame.sampler_seed

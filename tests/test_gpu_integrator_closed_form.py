@@ -155,9 +155,10 @@ def test_cavity_on_every_shade_path(xpu, oracle, name):
 
 
 def test_cavity_on_an_odd_film(xpu):
-    """17 x 13: a partial tile whose width is no multiple of 8, which the oracle (like the reference, SURVEY A-2) does not render -- the
-    device against the model alone.  The standard error is the 16 x 16 film's scaled by sqrt(256 / 221): the same cavity, the same
-    samples per pixel, pixels independent of each other."""
+    """17 x 13: a partial tile whose width is no multiple of 8, here against the model alone.  (The oracle, like the reference, SURVEY A-2,
+    restricts the width of a TILE to multiples of 8, not the film's: it renders such a film as overlapping 8-wide strips, and
+    test_gpu_frame_shapes.py compares films of this shape with it bit for bit.)  The standard error is the 16 x 16 film's scaled by
+    sqrt(256 / 221): the same cavity, the same samples per pixel, pixels independent of each other."""
     for hidden, general in ((None, 0), (GGX, 1)):
         film, st = device(xpu, I.cavity(width=17, height=13, hidden=hidden), DEPTH)
         assert st["shade_general"] == general and st["camera_samples"] == 17 * 13 * T.SPP and np.isfinite(film).all()
