@@ -3,17 +3,20 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
  * light, so the film is the same again.
  * sample-environment: the room gets a sky -- an environment material with a small lat-long image, dim but for one bright texel -- and next-event
  * estimation samples it beside the panel (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT).
+ * error-estimate: the frame asks for the per-pixel error estimate (phx_frame.moments_channel: 3 more floats per pixel, the centred second
+ * moment of the pixel's samples) and the host prints the film's mean relative standard error; the file written stays H x W x 4, the same floats.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -68,8 +71,13 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
+  int error_estimate = 0;
   for (int i = 2; i < argc; ++i)
-    if (strcmp(argv[i], "area-lights") == 0) {  /* taken out of the list: the other arguments keep their places */
+    if (strcmp(argv[i], "error-estimate") == 0) {
+      error_estimate = 1;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    } else if (strcmp(argv[i], "area-lights") == 0) {  /* taken out of the list: the other arguments keep their places */
       opt.light_sampling = PHX_LIGHTS_BY_AREA;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
@@ -107,13 +115,15 @@ int main(int argc, char** argv) {
     if (phx_dev_preprocess(devs[i], &scene) != PHX_OK) return fail("phx_dev_preprocess"); /* every device holds its own copy + BVH */
   }
 
-  float* film = (float*)calloc((size_t)W * H * 4, sizeof(float));
+  const size_t xstride = 4 + (error_estimate ? 3 : 0); /* primary rgba [, m2 rgb] */
+  float* film = (float*)calloc((size_t)W * H * xstride, sizeof(float));
   phx_tiles* tiles = phx_tiles_make(W, H, 32, 0, 1); /* ONE job::tiles_t for all devices */
   phx_frame frame;
   memset(&frame, 0, sizeof(frame));
   frame.tiles_user = tiles; frame.next_tile = phx_tiles_next;
   frame.sampler_seed = 7; frame.primary_components = 4;
   frame.host_film = film;                             /* ONE film: tiles are disjoint, so no lock and no reduce */
+  frame.moments_channel = (uint32_t)error_estimate;
   for (int i = 0; i < num_devices; ++i)
     if (phx_dev_start(devs[i], &frame) != PHX_OK) return fail("phx_dev_start");
   for (int i = 0; i < num_devices; ++i)
@@ -130,9 +140,22 @@ int main(int argc, char** argv) {
   st = sum;
   printf("tiles %llu camera_samples %llu rays %llu+%llu bvh_nodes %llu\n", (unsigned long long)st.tiles, (unsigned long long)st.camera_samples,
          (unsigned long long)st.rays_closest, (unsigned long long)st.rays_shadow, (unsigned long long)st.bvh_nodes);
+  if (error_estimate) {
+    /* a pixel's value is a sum of S samples whose centred sum of squares is m2: its variance is estimated by m2 * S / (S - 1) */
+    const double S = (double)opt.samples_per_pixel;
+    double sum_rse = 0.0; size_t lit = 0;
+    for (size_t p = 0; p < (size_t)W * H; ++p)
+      for (int c = 0; c < 3; ++c) {
+        const double v = film[p * xstride + c], m2 = film[p * xstride + 4 + c];
+        if (v > 0.0 && S > 1.0) { sum_rse += sqrt(m2 * S / (S - 1.0)) / v; ++lit; }
+      }
+    printf("error estimate: mean relative standard error %.4f over %llu lit values\n", lit ? sum_rse / (double)lit : 0.0, (unsigned long long)lit);
+  }
   if (argc > 1) {
     FILE* f = fopen(argv[1], "wb");
-    if (!f || fwrite(film, sizeof(float), (size_t)W * H * 4, f) != (size_t)W * H * 4) { fprintf(stderr, "cannot write %s\n", argv[1]); return 1; }
+    int ok = f != NULL;
+    for (size_t p = 0; ok && p < (size_t)W * H; ++p) ok = fwrite(film + p * xstride, sizeof(float), 4, f) == 4; /* H x W x 4 whatever the film holds */
+    if (!ok) { fprintf(stderr, "cannot write %s\n", argv[1]); return 1; }
     fclose(f);
   }
   phx_tiles_free(tiles);

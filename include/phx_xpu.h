@@ -333,7 +333,26 @@ typedef struct phx_frame {
    * effect as an add_tile callback that copies into a frame buffer (film::file_t, src/film/file.cpp:27-41)
    * without a foreign-function call per tile. */
   float*           host_film;
-  uint32_t         reserved[2];
+  /* Per-pixel error estimate.  0: off, and nothing changes by a byte.  1: a channel "m2" of 3 floats (r, g, b) is appended to
+   * every pixel behind "primary" and, when present, "normals": its offset is primary_components + (normals_channel ? 3 : 0), and xstride
+   * grows by 3.  Any other value is PHX_ERR_ARG at phx_dev_start.  "primary" and "normals" are bit for bit what the frame without the
+   * channel holds.  The channel is the centred second moment of the pixel's samples.  Per pixel and colour channel, for a pass that
+   * carries samples s0 .. s0 + ns - 1 of the pixel (x_s the radiance of sample s, f_prev the pixel's fp32 "primary" value and m2_prev the
+   * channel's value before the pass; the batch buffer is zeroed at the start of a batch), in binary64 without contraction:
+   *     y_s  = fp32(x_s * inv)                    the very value the film adds; inv = 1.0f / (spp * pps)
+   *     n    = s0;   mean = s0 ? (double)f_prev / (double)s0 : 0.0;   M2 = (double)m2_prev
+   *     for each sample, in sample order:
+   *         n   += 1;  r_n = 1.0 / (double)n      IEEE binary64 division
+   *         d    = (double)y_s - mean
+   *         mean = mean + d * r_n
+   *         M2   = M2 + d * ((double)y_s - mean)
+   *     m2_out = fp32(M2)
+   * A frame of one pass holds the centred sum of squares to one fp32 rounding; a pixel whose samples are all equal holds +0.0 exactly, and
+   * so does every pixel at spp == 1.  The film value is a sum of S = spp samples y_s, so the unbiased estimate of ITS variance is
+   * m2 * S / (S - 1): no subtraction of squares ever happens.  A non-finite sample makes that pixel's m2 non-finite, and no other pixel's.
+   * The channel is a statistic of ONE frame: nothing accumulates across frames. */
+  uint32_t         moments_channel;
+  uint32_t         reserved[1];
 } phx_frame;
 
 /* ---- statistics ------------------------------------------------------------------------ */
@@ -506,6 +525,14 @@ int phx_dev_light_emission(phx_device* dev, uint32_t n, const float* u3, float* 
  * PHX_ERR_ARG when the preprocessed scene does not sample its environment.  Under that option phx_dev_light_sample answers an environment pick
  * with light = nlights, tri = 0xffffffff and zeros elsewhere, and phx_dev_light_emission with zeros. */
 int phx_dev_environment_sample(phx_device* dev, uint32_t n, const float* u3, uint32_t* light, uint32_t* texel, float* st, float* dir, float* pdf, float* e);
+
+/* One pass of the film stage with phx_frame.moments_channel on, run on the caller's data: radiance holds num_pixels x num_samples records
+ * of 4 floats (r, g, b, unused), pixel-major, the samples samples_done .. samples_done + num_samples - 1 of every pixel; acc holds 6 floats
+ * per pixel, primary rgb and m2 rgb, as the previous passes left them (zeros before the first), and receives both after this pass by the
+ * rule of phx_frame.moments_channel with s0 = samples_done.  A parity hook: it runs the film kernel of such a frame itself.  It needs a
+ * device but no scene.  PHX_ERR_ARG for a null array or num_pixels x num_samples of 2^31 or more. */
+int phx_dev_film_moments(phx_device* dev, uint32_t num_pixels, uint32_t num_samples, uint32_t samples_done, float inv,
+                         const float* radiance, float* acc);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -147,7 +147,7 @@ class Frame(C.Structure):
     _fields_ = [
         ("tiles_user", C.c_void_p), ("next_tile", C.c_void_p), ("film_user", C.c_void_p), ("add_tile", C.c_void_p),
         ("sampler_seed", C.c_uint64), ("primary_components", C.c_uint32), ("normals_channel", C.c_uint32),
-        ("device_film", C.c_void_p), ("host_film", C.c_void_p), ("reserved", C.c_uint32 * 2),
+        ("device_film", C.c_void_p), ("host_film", C.c_void_p), ("moments_channel", C.c_uint32), ("reserved", C.c_uint32 * 1),
     ]
 
 
@@ -176,7 +176,7 @@ EXPORTS = [
     "phx_last_error", "phx_dev_get_stats", "phx_tiles_make", "phx_tiles_next", "phx_tiles_count", "phx_tiles_reset",
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
     "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
-    "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample",
+    "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample", "phx_dev_film_moments",
 ]
 
 
@@ -199,6 +199,7 @@ def declare(lib):
     lib.phx_dev_trace.argtypes = [vp, C.c_uint32, f32p, f32p, f32p, C.c_int, f32p, f32p, f32p, u32p, u8p]
     lib.phx_dev_trace.restype = C.c_int
     lib.phx_dev_bsdf_f.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p]; lib.phx_dev_bsdf_f.restype = C.c_int
+    lib.phx_dev_film_moments.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, f32p, f32p]; lib.phx_dev_film_moments.restype = C.c_int
     lib.phx_dev_bsdf_sample.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, u32p]
     lib.phx_dev_bsdf_sample.restype = C.c_int
     lib.phx_dev_texture_lookup.argtypes = [vp, C.c_uint32, C.c_uint32, f32p, f32p]; lib.phx_dev_texture_lookup.restype = C.c_int

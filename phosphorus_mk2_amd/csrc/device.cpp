@@ -104,6 +104,9 @@ struct PathQueues {
     B.so = q[SO].p; B.sd = q[SD].p; B.sc = q[SC].p; B.pr = q[PR].p; B.pn = normals ? q[PN].p : nullptr;
   }
 };
+// phx_frame.moments_channel: the channel's 3 floats of the batch buffer, counted once per path as if every pixel carried one sample (the
+// buffer's other floats never were counted: 16 bytes a pixel against 176 a path)
+size_t moments_bytes(const phx_frame& f) { return f.moments_channel ? 3 * sizeof(float) : 0; }
 static_assert(PathQueues::bytes_per_path(false) == 176 && PathQueues::bytes_per_path(true) == 192, "what path_budget divides the device's memory by");
 
 bool host_timing() {  // PHX_HOST_TIMING, read at the first frame: where a frame's and a batch's host time goes, on stderr (probe)
@@ -479,6 +482,7 @@ int phx_dev_start(phx_device* d, const phx_frame* f) {
   if (!f->next_tile) return fail(PHX_ERR_ARG, "frame without a tile queue");
   if (!f->add_tile && !f->device_film && !f->host_film) return fail(PHX_ERR_ARG, "frame without a film sink");
   if (f->primary_components != 3 && f->primary_components != 4) return fail(PHX_ERR_ARG, "primary channel must have 3 or 4 components");
+  if (f->moments_channel > 1) return fail(PHX_ERR_ARG, "moments_channel must be 0 or 1");
   d->frame = *f;
   {
     static const int timing_env = [] { const char* v = std::getenv("PHX_KERNEL_TIMING"); return v ? std::atoi(v) : -1; }();
@@ -653,6 +657,26 @@ int phx_dev_bsdf_f(phx_device* d, uint32_t material, uint32_t n, const float* n3
   });
 }
 
+// (no stage_hook: the film stage reads no scene, so a device that has preprocessed nothing serves)
+int phx_dev_film_moments(phx_device* d, uint32_t num_pixels, uint32_t num_samples, uint32_t samples_done, float inv, const float* radiance, float* acc) {
+  return guarded([&]() -> int {
+    if (!d) return fail(PHX_ERR_ARG, "film_moments: null device");
+    if (d->running) return fail(PHX_ERR_STATE, "film_moments while a frame is running");
+    if (num_pixels == 0 || num_samples == 0) return PHX_OK;
+    if (!radiance || !acc) return fail(PHX_ERR_ARG, "film_moments: null argument");
+    const size_t npaths = (size_t)num_pixels * num_samples;
+    if (npaths >= 0x7fffffffull) return fail(PHX_ERR_ARG, "film_moments: too many samples");
+    Staging s{d};
+    const float4* pr = reinterpret_cast<const float4*>(s.in(radiance, 4 * npaths));
+    float* a = s.out(acc, 6 * (size_t)num_pixels);
+    if (s.rc) return s.rc;
+    HIPCHK(hipMemcpy(a, acc, 6 * (size_t)num_pixels * sizeof(float), hipMemcpyHostToDevice));
+    PassBuffers B{};
+    B.pr = const_cast<float4*>(pr); B.acc = a; B.num_pixels = num_pixels; B.num_samples = num_samples; B.xstride = 6;
+    return s.run([&] { launch_film_moments(d->stream, B, num_samples, inv, samples_done, 3); });
+  });
+}
+
 int phx_dev_bsdf_sample(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags) {
   return stage_hook(d, "bsdf_sample", [&](Staging& s) -> int {
@@ -823,7 +847,7 @@ int phx_device::run_frame() {
   // pixel keeps the 64 lanes of a wave — and the 256 rays of a camera-ray packet — on ONE pixel.  (Round 3 took 8 M pixels whatever the spp:
   // the 3840x2160, 256-spp frame of BASELINE config 4 went through as 8 passes of 32 samples; as 8 batches of 256 samples it is 6.8 %
   // faster — camera rays 67.9 -> 36.0 ms, k_trace -4 %: profiles/r04_v_batch_probe.log.)
-  const size_t path_bytes = PathQueues::bytes_per_path(frame.normals_channel != 0);
+  const size_t path_bytes = PathQueues::bytes_per_path(frame.normals_channel != 0) + moments_bytes(frame);
   // (divided by the samples a pass will really carry: with an explicit samples_in_flight only P x S paths are ever in flight)
   const uint32_t pass_samples = std::max(1u, std::min(opt.samples_per_pixel, opt.samples_in_flight ? opt.samples_in_flight : opt.samples_per_pixel));
   const uint64_t pixel_cap = std::min<uint64_t>(8u << 20, std::max<uint64_t>(path_budget(path_bytes) / pass_samples, 64u << 10));
@@ -879,9 +903,9 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   uint32_t P = 0;
   for (auto& t : tiles) P += t.w * t.h;
   const uint32_t spp = opt.samples_per_pixel;
-  const uint32_t xs = frame.primary_components + (frame.normals_channel ? 3u : 0u);
+  const uint32_t xs = frame.primary_components + (frame.normals_channel ? 3u : 0u) + (frame.moments_channel ? 3u : 0u);
   const bool normals = frame.normals_channel != 0;
-  const size_t path_bytes = PathQueues::bytes_per_path(normals);
+  const size_t path_bytes = PathQueues::bytes_per_path(normals) + moments_bytes(frame);
   // paths in flight: the device's budget (path_budget: up to 512 M paths).  Deep bounces keep only a few percent of the paths alive, so
   // many paths per pass are what keeps late launches full; a batch that cannot carry all its samples at once splits the spp range
   // into equal passes.
@@ -1067,7 +1091,12 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
       q ^= 1;
     }
     if ((rc = timed_launch(Launch::Trace, [&]() { launch_trace(stream, scene, B, q, (int)((opt.path_depth - 1) & 1), 0, 1, cap); }))) return rc;
-    if ((rc = timed_launch(Launch::Pass, [&]() { launch_film(stream, B, ns, inv); }))) return rc;
+    // the frame's error estimate (phx_frame.moments_channel) is made in the film's walk: k_film_moments INSTEAD of k_film, the channel behind the others
+    if ((rc = timed_launch(Launch::Pass, [&]() {
+           if (frame.moments_channel) launch_film_moments(stream, B, ns, inv, s0, xs - 3u);
+           else launch_film(stream, B, ns, inv);
+         })))
+      return rc;
     HIPCHK(hipGetLastError());
   }
   // film_t<>::add_tile (film.hpp:12-15)

@@ -3,6 +3,7 @@
 // exactly as the shade kernels call it), and the preprocess kernels that lay the scene's tables out in pool order.
 //
 //   k_film      the per-sample film add of tile_renderer_t::render_tile (reference src/xpu/cpu.cpp:175-198), in sample order
+//   k_film_moments  the same add, and beside it the centred second moment of a pixel's samples (phx_frame.moments_channel; no counterpart in the reference)
 #include "shade_common.h"
 
 namespace phx {
@@ -56,6 +57,57 @@ __global__ void __launch_bounds__(256) k_film(PassBuffers pb, uint32_t num_sampl
   }
   if (owner) {
     out[0] = r; out[1] = g; out[2] = b;
+    if (have_n) { out[pb.normals_offset] = nx; out[pb.normals_offset + 1] = ny; out[pb.normals_offset + 2] = nz; }
+  }
+}
+
+// ---- film with the moments channel ---------------------------------------------------------------------
+// phx_frame.moments_channel (phx_xpu.h states the rule): k_film's walk — the same staging, the same fp32 chain of `primary`, the same
+// normals — and beside it, per colour, the centred second moment of the pixel's samples y_s = x_s * inv by Welford's update in binary64.  The
+// three colours' chains are independent, so a pixel has three owner threads, one per colour (thread = colour * 64 + pixel: waves 0-2 of the
+// block; colour 0's also keeps the normals), and the block's fourth wave makes what is uniform over pixels: r_n = 1 / n, one IEEE division
+// per sample index of the tile, handed over through LDS.  `samples_done` = the samples earlier passes have added to the batch buffer (s0).
+__global__ void __launch_bounds__(256) k_film_moments(PassBuffers pb, uint32_t num_samples, float inv, uint32_t samples_done, uint32_t m2_offset) {
+  __shared__ float4 tile[PHX_FILM_PIX * (PHX_FILM_SMP + 1)];
+  __shared__ double rn[PHX_FILM_SMP];
+  const uint32_t pix0 = blockIdx.x * PHX_FILM_PIX;
+  const uint32_t lp = threadIdx.x % PHX_FILM_PIX, col = threadIdx.x / PHX_FILM_PIX;  // col 3: the wave of r_n
+  const uint32_t my_pix = pix0 + lp;
+  const bool owner = col < 3u && my_pix < pb.num_pixels;
+  float f = 0.0f, m2 = 0.0f;
+  float* out = pb.acc + (size_t)my_pix * pb.xstride;
+  if (owner) { f = out[col]; m2 = out[m2_offset + col]; }
+  double mean = samples_done ? (double)f / (double)samples_done : 0.0, M2 = (double)m2;
+  float nx = 0.0f, ny = 0.0f, nz = 0.0f; bool have_n = false;
+  const int nsrc = pb.pn ? 2 : 1;
+  for (uint32_t s0 = 0; s0 < num_samples; s0 += PHX_FILM_SMP) {
+    for (int src = 0; src < nsrc; ++src) {
+      const float4* __restrict__ in = src ? pb.pn : pb.pr;
+      __syncthreads();  // the previous tile has been consumed
+#pragma unroll
+      for (int k = 0; k < PHX_FILM_PIX * PHX_FILM_SMP / 256; ++k) {
+        const uint32_t e = k * 256 + threadIdx.x, p = e / PHX_FILM_SMP, sm = e % PHX_FILM_SMP;
+        if (pix0 + p < pb.num_pixels && s0 + sm < num_samples) tile[p * (PHX_FILM_SMP + 1) + sm] = in[(size_t)(pix0 + p) * num_samples + s0 + sm];
+      }
+      if (src == 0 && col == 3u && lp < PHX_FILM_SMP) rn[lp] = 1.0 / (double)(samples_done + s0 + lp + 1u);
+      __syncthreads();
+      if (owner) {
+        const uint32_t cnt = min((uint32_t)PHX_FILM_SMP, num_samples - s0);
+        for (uint32_t sm = 0; sm < cnt; ++sm) {
+          const float4 c = tile[lp * (PHX_FILM_SMP + 1) + sm];
+          if (src == 0) {
+            const float y = (col == 0u ? c.x : col == 1u ? c.y : c.z) * inv;
+            f += y;  // k_film's chain
+            const double d = (double)y - mean;
+            mean = mean + d * rn[sm];
+            M2 = M2 + d * ((double)y - mean);
+          } else if (col == 0u && c.w != 0.0f) { nx = c.x; ny = c.y; nz = c.z; have_n = true; }  // the last sample with a primary hit wins
+        }
+      }
+    }
+  }
+  if (owner) {
+    out[col] = f; out[m2_offset + col] = (float)M2;
     if (have_n) { out[pb.normals_offset] = nx; out[pb.normals_offset + 1] = ny; out[pb.normals_offset + 2] = nz; }
   }
 }
@@ -244,6 +296,9 @@ void launch_remap_flat_light_tris(hipStream_t stream, DevLightTri* light_tris, u
 }
 void launch_film(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples, float inv) {
   hipLaunchKernelGGL(k_film, dim3((pb.num_pixels + PHX_FILM_PIX - 1) / PHX_FILM_PIX), dim3(256), 0, stream, pb, num_samples, inv);
+}
+void launch_film_moments(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples, float inv, uint32_t samples_done, uint32_t m2_offset) {
+  hipLaunchKernelGGL(k_film_moments, dim3((pb.num_pixels + PHX_FILM_PIX - 1) / PHX_FILM_PIX), dim3(256), 0, stream, pb, num_samples, inv, samples_done, m2_offset);
 }
 void launch_scatter_film(hipStream_t stream, const PassBuffers& pb, float* device_film, uint32_t film_width) {
   hipLaunchKernelGGL(k_scatter_film, dim3(blocks_for(pb.num_pixels)), dim3(PHX_BLOCK), 0, stream, pb, device_film, film_width);

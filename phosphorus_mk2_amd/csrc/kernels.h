@@ -6,7 +6,7 @@
 //   trace.hip          k_trace, k_trace_primary, k_trace_rays; trace_plan, init_kernels_on_current_device, launch_trace*
 //   shade_lambert.hip  k_shade<MATS, FIRST, LENS> (Lambert-only scenes), block_append2
 //   shade_general.hip  k_shade_g and its append ring; launch_shade (which reaches k_shade through shade_launch.h)
-//   film_hooks.hip     k_begin_pass, k_film, k_scatter_film; the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
+//   film_hooks.hip     k_begin_pass, k_film, k_film_moments, k_scatter_film; the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
 //
@@ -166,6 +166,10 @@ void launch_trace_primary(hipStream_t stream, const DevScene& sc, const PassBuff
 // -> the launched kernel's bit of phx_stats::shade_kernels
 uint64_t launch_shade(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, int q, int sq, uint32_t capacity, uint32_t sample0, int camera_rays);
 void launch_film(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples, float inv_spp_pps);
+// launch_film for a frame with phx_frame.moments_channel: the same film add, and the channel m2 (3 floats at m2_offset of a pixel) by the rule of
+// phx_xpu.h; samples_done = the samples of every pixel that earlier passes of the batch have added.  They are arguments of this launch and not
+// fields of PassBuffers, which every kernel takes by value: a new field would move the kernel-argument offsets of all of them
+void launch_film_moments(hipStream_t stream, const PassBuffers& pb, uint32_t num_samples, float inv_spp_pps, uint32_t samples_done, uint32_t m2_offset);
 // preprocess: vertex normals from scene_t::triangles() order to pool-element order (elem_of_prim: the builders' map), and the smooth light
 // triangles' `prim` from primitive to pool element (they look their normals up in the same table)
 void launch_build_shade_recs(hipStream_t stream, const TriRec* tris, const uint32_t* elem_of_prim, float4* elem_shade, uint32_t num_prims);

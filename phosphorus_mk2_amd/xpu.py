@@ -154,10 +154,12 @@ class Film:
     """An in-memory film sink: film_t<>::add_tile copies a tile's render buffer into a full frame
     (what film::file_t / the Blender sink do, src/film/file.cpp:27-41)."""
 
-    def __init__(self, width, height, primary_components=4, normals=False):
+    def __init__(self, width, height, primary_components=4, normals=False, moments=False):
         self.width, self.height = width, height
-        self.primary_components, self.normals = primary_components, normals
-        self.xstride = primary_components + (3 if normals else 0)
+        self.primary_components, self.normals, self.moments = primary_components, normals, moments
+        # channel "m2" (phx_frame.moments_channel), when asked for, sits behind "primary" and "normals"
+        self.m2_offset = primary_components + (3 if normals else 0)
+        self.xstride = self.m2_offset + (3 if moments else 0)
         self.data = np.zeros((height, width, self.xstride), np.float32)
         self.tiles = 0
         self._lock = threading.Lock()
@@ -171,6 +173,13 @@ class Film:
     @property
     def primary(self):
         return self.data[..., :3]
+
+    @property
+    def m2(self):
+        """channel "m2": per pixel and colour the centred second moment of the samples the film summed (see film_variance)"""
+        if not self.moments:
+            raise AttributeError("this film was made without moments=True")
+        return self.data[..., self.m2_offset:self.m2_offset + 3]
 
 
 class BottomUpFilm(Film):
@@ -191,11 +200,11 @@ class BottomUpFilm(Film):
 class FrameState:
     """frame_state_t (src/state.hpp:18-31).  `sampler_seed` replaces the shared sampler_t."""
 
-    def __init__(self, sampler_seed, tiles, film, device_film_ptr=None, native_sink=False, primary_components=4, normals=False):
+    def __init__(self, sampler_seed, tiles, film, device_film_ptr=None, native_sink=False, primary_components=4, normals=False, moments=False):
         self.sampler_seed, self.tiles, self.film, self.device_film_ptr = sampler_seed, tiles, film, device_film_ptr
         self.native_sink = native_sink  # fill film.data from C (phx_frame.host_film) instead of one Python add_tile call per tile
         # the pixel layout of device_film_ptr when there is no `film` to take it from (a film's own layout wins)
-        self.primary_components, self.normals = primary_components, normals
+        self.primary_components, self.normals, self.moments = primary_components, normals, moments
 
 
 class HipDevice:
@@ -270,9 +279,12 @@ class HipDevice:
                 f.add_tile = C.cast(cb_add, C.c_void_p)
             f.primary_components = film.primary_components
             f.normals_channel = 1 if film.normals else 0
+            moments = getattr(film, "moments", False)
         else:
             f.primary_components = frame.primary_components
             f.normals_channel = 1 if frame.normals else 0
+            moments = frame.moments
+        f.moments_channel = int(moments)  # False / True; another int is passed through as it is (and refused by phx_dev_start)
         if frame.device_film_ptr:
             f.device_film = frame.device_film_ptr
         f.sampler_seed = frame.sampler_seed
@@ -311,6 +323,21 @@ class HipDevice:
         out = np.zeros_like(wi)
         fp = lambda a: a.ctypes.data_as(abi.f32p)
         _check(self._lib, self._lib.phx_dev_bsdf_f(self._h, material, len(wi), fp(n), fp(wi), fp(wo), fp(out)), "phx_dev_bsdf_f")
+        return out
+
+    def film_moments(self, radiance, acc, samples_done, inv):
+        """One pass of the film stage of a frame with moments=True on the caller's data (phx_dev_film_moments): radiance (pixels, samples, 4)
+        f32, the samples samples_done .. samples_done + samples - 1 of every pixel; acc (pixels, 6) f32 = primary rgb and m2 rgb as the passes
+        before left them (zeros before the first) -> the new (pixels, 6).  Needs no scene."""
+        radiance = np.ascontiguousarray(radiance, np.float32)
+        if radiance.ndim != 3 or radiance.shape[2] != 4:
+            raise ValueError("film_moments: radiance must be (pixels, samples, 4)")
+        out = np.array(acc, np.float32, order="C").reshape(-1, 6)
+        if len(out) != radiance.shape[0]:
+            raise ValueError("film_moments: acc must have one row of 6 per pixel")
+        fp = lambda a: a.ctypes.data_as(abi.f32p)
+        _check(self._lib, self._lib.phx_dev_film_moments(self._h, radiance.shape[0], radiance.shape[1], int(samples_done), float(inv), fp(radiance), fp(out)),
+               "phx_dev_film_moments")
         return out
 
     def bsdf_sample(self, material, n, wi, u2):
@@ -416,13 +443,27 @@ class HipDevice:
             pass
 
 
-def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_sink=True, rank=0, world=1):
+def film_variance(data, spp, primary_components=4, normals=False):
+    """The unbiased estimate of the variance of every pixel's film value from a film rendered with moments=True: data (..., xstride) as
+    render() returns it -> m2 * S / (S - 1) in float64, shape (..., 3); S = spp.  The film value is a SUM of S samples y_s (each carries the
+    film's 1 / (spp * pps)), and m2 is their centred sum of squares, so S / (S - 1) * m2 estimates S * var(y).  spp == 1 says nothing: inf."""
+    data = np.asarray(data)
+    off = primary_components + (3 if normals else 0)
+    if data.shape[-1] != off + 3:
+        raise ValueError(f"film_variance: a film with the m2 channel has {off + 3} floats per pixel, this one {data.shape[-1]}")
+    m2 = data[..., off:off + 3].astype(np.float64)
+    if spp <= 1:
+        return np.full(m2.shape, np.inf)
+    return m2 * (spp / (spp - 1.0))
+
+
+def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_sink=True, rank=0, world=1, moments=False):
     """The reference's frame on SEVERAL devices in one process (src/core.cpp:103-115): every device is started on the SAME tile
     queue and the SAME film and joined in turn; no collective.  `devices` must have been preprocessed with `scene_desc`.
     Returns (film array, [stats per device])."""
     W, H = scene_desc.camera.width, scene_desc.camera.height
     tiles = Tiles.make(W, H, tile_size, rank, world)
-    film = Film(W, H, 4, normals)
+    film = Film(W, H, 4, normals, moments)
     for d in devices:
         d.start(scene_desc, FrameState(seed, tiles, film, native_sink=native_sink))
     for d in devices:
@@ -432,7 +473,7 @@ def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_s
 
 def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=32, rank=0, world=1, callback_tiles=False,
            samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference",
-           light_selection="uniform", environment_sampling=False):
+           light_selection="uniform", environment_sampling=False, moments=False):
     """Convenience: the call sequence of session_t::render (plugins/blender/session.cpp:73-94):
     make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats)."""
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
@@ -453,7 +494,7 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
                     break
                 lst.append(t)
             tiles = CallbackTiles(lst)
-        film = Film(W, H, 4, normals)
+        film = Film(W, H, 4, normals, moments)
         dev.start(scene_desc, FrameState(seed, tiles, film, native_sink=native_sink))
         dev.join()
         return film.data, dev.stats()
