@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -12,6 +12,9 @@
  * estimation samples it beside the panel (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT).
  * error-estimate: the frame asks for the per-pixel error estimate (phx_frame.moments_channel: 3 more floats per pixel, the centred second
  * moment of the pixel's samples) and the host prints the film's mean relative standard error; the file written stays H x W x 4, the same floats.
+ * adaptive TAU: adaptive sampling (phx_dev_set_adaptive) with threshold TAU, a first decision after 4 of the 8 samples and one every 2 from there
+ * on: a pixel stops once the standard error of its extrapolated value is at most TAU times the value.  The frame carries the error estimate
+ * and one more float per pixel, the samples the pixel took; the host prints their mean.  The file written stays H x W x 4.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -71,9 +74,16 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0;
+  int error_estimate = 0, adaptive = 0;
+  phx_adaptive ad;
+  memset(&ad, 0, sizeof(ad));
   for (int i = 2; i < argc; ++i)
-    if (strcmp(argv[i], "error-estimate") == 0) {
+    if (strcmp(argv[i], "adaptive") == 0 && i + 1 < argc) {  /* the keyword and its number */
+      adaptive = 1;
+      ad.threshold = (float)atof(argv[i + 1]); ad.floor = 0.0f; ad.min_samples = 4; ad.step = 2;
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else if (strcmp(argv[i], "error-estimate") == 0) {
       error_estimate = 1;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
@@ -113,9 +123,11 @@ int main(int argc, char** argv) {
     devs[i] = phx_dev_make(&opt);
     if (!devs[i]) return fail("phx_dev_make");
     if (phx_dev_preprocess(devs[i], &scene) != PHX_OK) return fail("phx_dev_preprocess"); /* every device holds its own copy + BVH */
+    if (adaptive && phx_dev_set_adaptive(devs[i], &ad) != PHX_OK) return fail("phx_dev_set_adaptive"); /* the setting is the device's, not the frame's */
   }
 
-  const size_t xstride = 4 + (error_estimate ? 3 : 0); /* primary rgba [, m2 rgb] */
+  if (adaptive) error_estimate = 1; /* the stopping rule reads the estimate: such a frame must carry it */
+  const size_t xstride = 4 + (error_estimate ? 3 : 0) + (adaptive ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */
   float* film = (float*)calloc((size_t)W * H * xstride, sizeof(float));
   phx_tiles* tiles = phx_tiles_make(W, H, 32, 0, 1); /* ONE job::tiles_t for all devices */
   phx_frame frame;
@@ -142,14 +154,21 @@ int main(int argc, char** argv) {
          (unsigned long long)st.rays_closest, (unsigned long long)st.rays_shadow, (unsigned long long)st.bvh_nodes);
   if (error_estimate) {
     /* a pixel's value is a sum of S samples whose centred sum of squares is m2: its variance is estimated by m2 * S / (S - 1) */
-    const double S = (double)opt.samples_per_pixel;
     double sum_rse = 0.0; size_t lit = 0;
-    for (size_t p = 0; p < (size_t)W * H; ++p)
+    for (size_t p = 0; p < (size_t)W * H; ++p) {
+      const double S = adaptive ? (double)film[p * xstride + 7] : (double)opt.samples_per_pixel; /* under adaptive sampling: the pixel's own count */
       for (int c = 0; c < 3; ++c) {
         const double v = film[p * xstride + c], m2 = film[p * xstride + 4 + c];
         if (v > 0.0 && S > 1.0) { sum_rse += sqrt(m2 * S / (S - 1.0)) / v; ++lit; }
       }
+    }
     printf("error estimate: mean relative standard error %.4f over %llu lit values\n", lit ? sum_rse / (double)lit : 0.0, (unsigned long long)lit);
+  }
+  if (adaptive) {
+    double taken = 0.0;
+    for (size_t p = 0; p < (size_t)W * H; ++p) taken += film[p * xstride + 7];
+    printf("adaptive: mean samples per pixel %.4f of %u (camera_samples %llu)\n", taken / (double)((size_t)W * H), opt.samples_per_pixel,
+           (unsigned long long)st.camera_samples);
   }
   if (argc > 1) {
     FILE* f = fopen(argv[1], "wb");

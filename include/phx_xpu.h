@@ -355,6 +355,44 @@ typedef struct phx_frame {
   uint32_t         reserved[1];
 } phx_frame;
 
+/* ---- adaptive sampling: a pixel stops taking samples once its own error estimate is small enough ---------- */
+/* Off by default, and then nothing changes by a byte.  The setting belongs to the device object (phx_dev_set_adaptive) and applies to every
+ * frame started afterwards.  A frame started while it is on must have moments_channel == 1 (PHX_ERR_ARG at phx_dev_start otherwise) and
+ * carries one more channel, "samples": 1 float per pixel behind "m2", at offset primary_components + (normals_channel ? 3 : 0) + 3; xstride
+ * grows by 1.  It holds (float)n, the samples the pixel took.  With spp = samples_per_pixel, tau = threshold, a = floor; all arithmetic
+ * is binary64, without contraction, in the order written:
+ *   rounds    the rounds end at e_0 = min(min_samples, spp) and e_{j+1} = min(e_j + step, spp).  A round is carried as one pass; only when
+ *             samples_in_flight is set, or the path budget forces it, is it split into passes of at most that many samples, by the rule
+ *             that splits a frame's spp without the setting, applied to the round.  Decisions happen at round ends only.
+ *   decision  after a round that ends at n < spp, for every pixel still active, with f_c its fp32 "primary" and m2_c its fp32 "m2" per colour:
+ *                 q = (double)n / (double)(n - 1)
+ *                 g = ((double)a * (double)n) / (double)spp
+ *                 per colour:  L = (double)m2_c * q;   b = (double)tau * (fabs((double)f_c) + g);   ok_c = L <= b * b
+ *                 stop = ok_r && ok_g && ok_b          (a NaN compares false: such a pixel never stops)
+ *             which is se(V_c) <= tau * (|V_c| + a) for the pixel's extrapolated final value V_c = f_c * spp / n, the standard error
+ *             taken from the centred second moment.
+ *   rescale   a pixel that stops is rescaled once:
+ *                 k       = (double)spp / (double)n
+ *                 primary = fp32((double)f_c * k)
+ *                 m2      = fp32(((double)m2_c * k) * k)
+ *                 samples = (float)n
+ *             "normals" (and the fourth component of "primary") are never rescaled.
+ *   the rest  a pixel that reaches spp is not touched: its "primary", "normals" and "m2" are what the same pass schedule writes without
+ *             the setting, and its samples = (float)spp.
+ *   variance  after the rescale the unbiased variance of ANY pixel's value is m2 * n / (n - 1), n its own "samples".
+ * A pixel's path keys are (seed, film pixel, absolute sample index), so a pixel that stops after n samples holds exactly the first n samples
+ * of the frame without the setting; its result depends on its own samples and this schedule alone, not on the batch, the tile order, the
+ * tiling or the number of devices.  phx_stats.camera_samples is the sum of the channel.
+ * Limits: the estimator is biased, as every variance-driven stopping rule is; a pixel whose first min_samples samples are all equal stops
+ * (m2 = +0.0), even if a rare bright path would have reached it; the film jitter stays stratified for spp, not for n. */
+typedef struct phx_adaptive {
+  float    threshold;    /* tau: relative standard error at which a pixel stops; finite, >= 0 */
+  float    floor;        /* a: absolute floor added to |value| in film units; finite, >= 0 */
+  uint32_t min_samples;  /* samples every pixel takes before the first decision; >= 2 */
+  uint32_t step;         /* samples per later round; >= 1 */
+  uint32_t reserved[4];  /* must be 0 */
+} phx_adaptive;
+
 /* ---- statistics ------------------------------------------------------------------------ */
 /* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
  * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
@@ -458,6 +496,10 @@ void        phx_dev_destroy(phx_device* dev);
 /* last error message of the calling thread (a frame's error is handed to the thread that calls phx_dev_join) */
 const char* phx_last_error(void);
 int         phx_dev_get_stats(const phx_device* dev, phx_stats* out);
+/* Adaptive sampling (phx_adaptive above) for every frame this device starts from now on; NULL turns it off, which is the default.  Needs no
+ * scene.  PHX_ERR_STATE while a frame is started and not yet joined; PHX_ERR_ARG, with the field's name in the message, for a value outside
+ * the ranges stated at the struct or a non-zero reserved word: the previous setting then stays in force. */
+int         phx_dev_set_adaptive(phx_device* dev, const phx_adaptive* a /* NULL: off */);
 
 /* ---- native tile queue: job::tiles_t (src/jobs/tiles.hpp:10-90) ----------------------- */
 /* make(): row-major tile_size x tile_size tiles with edge remainders (tiles.hpp:49-89);
@@ -533,6 +575,17 @@ int phx_dev_environment_sample(phx_device* dev, uint32_t n, const float* u3, uin
  * device but no scene.  PHX_ERR_ARG for a null array or num_pixels x num_samples of 2^31 or more. */
 int phx_dev_film_moments(phx_device* dev, uint32_t num_pixels, uint32_t num_samples, uint32_t samples_done, float inv,
                          const float* radiance, float* acc);
+
+/* The selection of adaptive sampling after a round that ended at samples_done, run on the caller's data: the decision of phx_adaptive for
+ * every row named by `active`, the rescale of the rows that stop (samples = (float)samples_done), and the rows that go on, in the order of
+ * `active` (a STABLE compaction), in survivors[0 .. *num_survivors - 1].  acc holds 7 floats per row: primary rgb, m2 rgb, samples; rows that
+ * go on and rows outside `active` come back unchanged.  A parity hook: it runs the selection kernels of such a frame themselves.  It needs a
+ * device but no scene.  PHX_ERR_ARG for a null array, samples_done < 2, samples_done >= spp, an index >= num_rows, indices that do not
+ * ascend strictly, num_active > num_rows, or a phx_adaptive that phx_dev_set_adaptive would refuse. */
+int phx_dev_adaptive_select(phx_device* dev, uint32_t num_active, const uint32_t* active /* indices into acc rows, ascending; NULL = 0..num_active-1 */,
+                            uint32_t num_rows, float* acc /* num_rows x 7: primary rgb, m2 rgb, samples; in and out */,
+                            uint32_t samples_done, uint32_t spp, const phx_adaptive* a,
+                            uint32_t* survivors /* num_active words */, uint32_t* num_survivors);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -151,6 +151,11 @@ class Frame(C.Structure):
     ]
 
 
+class Adaptive(C.Structure):
+    """phx_adaptive: the setting of adaptive sampling (phx_dev_set_adaptive)"""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32), ("step", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("camera_samples", C.c_uint64), ("rays_closest", C.c_uint64), ("rays_shadow", C.c_uint64),
@@ -177,6 +182,7 @@ EXPORTS = [
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
     "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
     "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample", "phx_dev_film_moments",
+    "phx_dev_set_adaptive", "phx_dev_adaptive_select",
 ]
 
 
@@ -208,5 +214,8 @@ def declare(lib):
     lib.phx_dev_light_sample.argtypes = [vp, C.c_uint32, f32p, u32p, u32p, f32p, f32p, f32p]; lib.phx_dev_light_sample.restype = C.c_int
     lib.phx_dev_light_emission.argtypes = [vp, C.c_uint32, f32p, f32p, f32p]; lib.phx_dev_light_emission.restype = C.c_int
     lib.phx_dev_environment_sample.argtypes = [vp, C.c_uint32, f32p, u32p, u32p, f32p, f32p, f32p, f32p]; lib.phx_dev_environment_sample.restype = C.c_int
+    lib.phx_dev_set_adaptive.argtypes = [vp, C.POINTER(Adaptive)]; lib.phx_dev_set_adaptive.restype = C.c_int
+    lib.phx_dev_adaptive_select.argtypes = [vp, C.c_uint32, u32p, C.c_uint32, f32p, C.c_uint32, C.c_uint32, C.POINTER(Adaptive), u32p, u32p]
+    lib.phx_dev_adaptive_select.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

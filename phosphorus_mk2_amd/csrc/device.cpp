@@ -107,6 +107,29 @@ struct PathQueues {
 // phx_frame.moments_channel: the channel's 3 floats of the batch buffer, counted once per path as if every pixel carried one sample (the
 // buffer's other floats never were counted: 16 bytes a pixel against 176 a path)
 size_t moments_bytes(const phx_frame& f) { return f.moments_channel ? 3 * sizeof(float) : 0; }
+// adaptive sampling, counted the same way: the "samples" float, the working copy of a pixel's row of the batch buffer, its word of the
+// working pixel table and its words of the two index lists
+size_t adaptive_bytes(const phx_frame& f, bool on) {
+  const size_t xs = f.primary_components + (f.normals_channel ? 3u : 0u) + 4u;
+  return on ? sizeof(float) + xs * sizeof(float) + 3 * sizeof(uint32_t) : 0;
+}
+// phx_adaptive: the name of the first field outside its range, or nullptr
+const char* adaptive_invalid(const phx_adaptive& a) {
+  if (!std::isfinite(a.threshold) || a.threshold < 0.0f) return "threshold";
+  if (!std::isfinite(a.floor) || a.floor < 0.0f) return "floor";
+  if (a.min_samples < 2u) return "min_samples";
+  if (a.step < 1u) return "step";
+  for (uint32_t w : a.reserved) if (w) return "reserved";
+  return nullptr;
+}
+// what the selection behind a round that ended at n of spp samples takes from the setting (phx_adaptive: q, g, k), in binary64
+void adaptive_args(const phx_adaptive& a, uint32_t n, uint32_t spp, AdaptiveArgs& A) {
+  A.q = (double)n / (double)(n - 1u);
+  A.g = ((double)a.floor * (double)n) / (double)spp;
+  A.tau = (double)a.threshold;
+  A.k = (double)spp / (double)n;
+  A.n = (float)n;
+}
 static_assert(PathQueues::bytes_per_path(false) == 176 && PathQueues::bytes_per_path(true) == 192, "what path_budget divides the device's memory by");
 
 bool host_timing() {  // PHX_HOST_TIMING, read at the first frame: where a frame's and a batch's host time goes, on stderr (probe)
@@ -150,6 +173,12 @@ struct phx_device {
   float* h_acc = nullptr; size_t h_acc_n = 0;  // pinned staging for add_tile
   uint32_t* h_qlen = nullptr; size_t h_qlen_n = 0;  // pinned, device-visible: queue lengths published by k_trace, one word per (pass, step) of a batch (enqueue_batch)
   std::vector<phx_tile> pix_xy_tiles;          // the tiles pix_xy currently describes
+  // adaptive sampling (phx_dev_set_adaptive), held only by a device that rendered a frame with it: the working copies of acc and pix_xy that a
+  // pass over the pixels still active reads (working row w = row sel_idx[.][w] of the batch), the two lists a selection reads and writes
+  // by turns, a word per workgroup of the selection, and the pinned word through which the host reads how many pixels go on
+  DevBuf<float> w_acc; DevBuf<uint32_t> w_xy, sel_idx[2], sel_blocks;
+  uint32_t* h_sel = nullptr;
+  phx_adaptive adaptive{}; bool adaptive_on = false;
 
   // frame
   phx_frame frame{};
@@ -192,6 +221,7 @@ struct phx_device {
     for (auto e : direct.events) (void)hipEventDestroy(e);
     if (h_acc) (void)hipHostFree(h_acc);
     if (h_qlen) (void)hipHostFree(h_qlen);
+    if (h_sel) (void)hipHostFree(h_sel);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -207,7 +237,8 @@ struct phx_device {
   uint64_t device_bytes() const {
     return d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
            d_lights.bytes() + d_light_tris.bytes() + queues.bytes() + counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
-           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes() + d_mat_emit_tex.bytes() + d_env_cdf.bytes();
+           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes() + d_mat_emit_tex.bytes() + d_env_cdf.bytes() +
+           w_acc.bytes() + w_xy.bytes() + sel_idx[0].bytes() + sel_idx[1].bytes() + sel_blocks.bytes();
   }
   // paths in flight this device may carry: up to 512 M (about 95 GB of queues + state: sized for 288 GB of HBM), but never more than 60 % of
   // what the device has free right now plus what this object already holds for queues (another device object, torch or RCCL may share the GPU)
@@ -223,7 +254,8 @@ struct phx_device {
   }
   void driver_loop();
   int run_frame();
-  int enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, uint32_t S, uint32_t xs);
+  struct Pass { uint32_t s0, ns; bool round_end; };  // samples s0 .. s0 + ns - 1 of every pixel it carries; round_end: a decision of adaptive sampling follows
+  int enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, const std::vector<Pass>& passes, uint32_t xs);
   int render_batch(const std::vector<phx_tile>& tiles);
 };
 
@@ -483,6 +515,7 @@ int phx_dev_start(phx_device* d, const phx_frame* f) {
   if (!f->add_tile && !f->device_film && !f->host_film) return fail(PHX_ERR_ARG, "frame without a film sink");
   if (f->primary_components != 3 && f->primary_components != 4) return fail(PHX_ERR_ARG, "primary channel must have 3 or 4 components");
   if (f->moments_channel > 1) return fail(PHX_ERR_ARG, "moments_channel must be 0 or 1");
+  if (d->adaptive_on && f->moments_channel != 1) return fail(PHX_ERR_ARG, "adaptive sampling is on (phx_dev_set_adaptive): the frame must have moments_channel == 1");
   d->frame = *f;
   {
     static const int timing_env = [] { const char* v = std::getenv("PHX_KERNEL_TIMING"); return v ? std::atoi(v) : -1; }();
@@ -533,9 +566,18 @@ uint32_t phx_abi_sizeof(int which) {
     case 0: return sizeof(phx_options); case 1: return sizeof(phx_lobe); case 2: return sizeof(phx_material);
     case 3: return sizeof(phx_face_set); case 4: return sizeof(phx_mesh); case 5: return sizeof(phx_camera);
     case 6: return sizeof(phx_scene); case 7: return sizeof(phx_tile); case 8: return sizeof(phx_frame);
-    case 9: return sizeof(phx_stats); case 10: return sizeof(phx_texture);
+    case 9: return sizeof(phx_stats); case 10: return sizeof(phx_texture); case 11: return sizeof(phx_adaptive);
     default: return 0;
   }
+}
+
+int phx_dev_set_adaptive(phx_device* d, const phx_adaptive* a) {
+  if (!d) return fail(PHX_ERR_ARG, "set_adaptive: null device");
+  if (d->running) return fail(PHX_ERR_STATE, "set_adaptive while a frame is running");
+  if (!a) { d->adaptive_on = false; return PHX_OK; }
+  if (const char* field = adaptive_invalid(*a)) return fail(PHX_ERR_ARG, std::string("set_adaptive: ") + field + " is outside its range (phx_adaptive)");
+  d->adaptive = *a; d->adaptive_on = true;
+  return PHX_OK;
 }
 
 // ---- tile queue: job::tiles_t (src/jobs/tiles.hpp:10-90) ------------------------------------------------
@@ -674,6 +716,37 @@ int phx_dev_film_moments(phx_device* d, uint32_t num_pixels, uint32_t num_sample
     PassBuffers B{};
     B.pr = const_cast<float4*>(pr); B.acc = a; B.num_pixels = num_pixels; B.num_samples = num_samples; B.xstride = 6;
     return s.run([&] { launch_film_moments(d->stream, B, num_samples, inv, samples_done, 3); });
+  });
+}
+
+// (no stage_hook either: the selection reads no scene)
+int phx_dev_adaptive_select(phx_device* d, uint32_t num_active, const uint32_t* active, uint32_t num_rows, float* acc, uint32_t samples_done, uint32_t spp,
+                            const phx_adaptive* a, uint32_t* survivors, uint32_t* num_survivors) {
+  return guarded([&]() -> int {
+    if (!d) return fail(PHX_ERR_ARG, "adaptive_select: null device");
+    if (d->running) return fail(PHX_ERR_STATE, "adaptive_select while a frame is running");
+    if (!acc || !a || !survivors || !num_survivors) return fail(PHX_ERR_ARG, "adaptive_select: null argument");
+    if (samples_done < 2u || samples_done >= spp) return fail(PHX_ERR_ARG, "adaptive_select: samples_done must be at least 2 and below spp");
+    if (const char* field = adaptive_invalid(*a)) return fail(PHX_ERR_ARG, std::string("adaptive_select: ") + field + " is outside its range (phx_adaptive)");
+    if (num_active > num_rows) return fail(PHX_ERR_ARG, "adaptive_select: more active rows than rows");
+    for (uint32_t i = 0; active && i < num_active; ++i) {
+      if (active[i] >= num_rows) return fail(PHX_ERR_ARG, "adaptive_select: an index past num_rows");
+      if (i && active[i] <= active[i - 1]) return fail(PHX_ERR_ARG, "adaptive_select: the indices must ascend strictly");
+    }
+    *num_survivors = 0;
+    if (num_active == 0) return PHX_OK;
+    Staging s{d};
+    const size_t nfl = 7 * (size_t)num_rows;
+    AdaptiveArgs A{};
+    A.acc = s.out(acc, nfl); A.xstride = 7; A.m2_offset = 3; A.samples_offset = 6;
+    A.active = active ? s.in(active, num_active) : nullptr; A.num_active = num_active;
+    adaptive_args(*a, samples_done, spp, A);
+    uint32_t* scratch = s.out<uint32_t>(nullptr, (num_active + PHX_ADAPTIVE_BLOCK - 1) / PHX_ADAPTIVE_BLOCK);
+    uint32_t *surv = s.out(survivors, num_active), *total = s.out(num_survivors, 1);
+    if (s.rc) return s.rc;
+    HIPCHK(hipMemcpy(A.acc, acc, nfl * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(surv, 0, (size_t)num_active * sizeof(uint32_t), d->stream));  // the words past the survivors: zeros, not what the allocation held
+    return s.run([&] { launch_adaptive_select(d->stream, A, scratch, surv, total); });
   });
 }
 
@@ -847,9 +920,11 @@ int phx_device::run_frame() {
   // pixel keeps the 64 lanes of a wave — and the 256 rays of a camera-ray packet — on ONE pixel.  (Round 3 took 8 M pixels whatever the spp:
   // the 3840x2160, 256-spp frame of BASELINE config 4 went through as 8 passes of 32 samples; as 8 batches of 256 samples it is 6.8 %
   // faster — camera rays 67.9 -> 36.0 ms, k_trace -4 %: profiles/r04_v_batch_probe.log.)
-  const size_t path_bytes = PathQueues::bytes_per_path(frame.normals_channel != 0) + moments_bytes(frame);
-  // (divided by the samples a pass will really carry: with an explicit samples_in_flight only P x S paths are ever in flight)
-  const uint32_t pass_samples = std::max(1u, std::min(opt.samples_per_pixel, opt.samples_in_flight ? opt.samples_in_flight : opt.samples_per_pixel));
+  const size_t path_bytes = PathQueues::bytes_per_path(frame.normals_channel != 0) + moments_bytes(frame) + adaptive_bytes(frame, adaptive_on);
+  // (divided by the samples a pass will really carry: with an explicit samples_in_flight only P x S paths are ever in flight; under adaptive
+  // sampling a pass carries at most a round, and the longest round has max(min_samples, step) samples)
+  const uint32_t frame_samples = adaptive_on ? std::min(opt.samples_per_pixel, std::max(adaptive.min_samples, adaptive.step)) : opt.samples_per_pixel;
+  const uint32_t pass_samples = std::max(1u, std::min(opt.samples_per_pixel, opt.samples_in_flight ? opt.samples_in_flight : frame_samples));
   const uint64_t pixel_cap = std::min<uint64_t>(8u << 20, std::max<uint64_t>(path_budget(path_bytes) / pass_samples, 64u << 10));
   // A batch never EXCEEDS the cap (the tile that would is kept for the next batch): its paths then fit the queues the first full batch
   // allocated, whatever mix of whole and edge tiles it holds.  (Until round 5 a batch overshot by up to one tile; a 4 096-spp batch that grew
@@ -903,26 +978,42 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   uint32_t P = 0;
   for (auto& t : tiles) P += t.w * t.h;
   const uint32_t spp = opt.samples_per_pixel;
-  const uint32_t xs = frame.primary_components + (frame.normals_channel ? 3u : 0u) + (frame.moments_channel ? 3u : 0u);
+  const uint32_t xs = frame.primary_components + (frame.normals_channel ? 3u : 0u) + (frame.moments_channel ? 3u : 0u) + (adaptive_on ? 1u : 0u);
   const bool normals = frame.normals_channel != 0;
-  const size_t path_bytes = PathQueues::bytes_per_path(normals) + moments_bytes(frame);
+  const size_t path_bytes = PathQueues::bytes_per_path(normals) + moments_bytes(frame) + adaptive_bytes(frame, adaptive_on);
   // paths in flight: the device's budget (path_budget: up to 512 M paths).  Deep bounces keep only a few percent of the paths alive, so
   // many paths per pass are what keeps late launches full; a batch that cannot carry all its samples at once splits the spp range
-  // into equal passes.
-  auto pick_samples = [&]() -> uint32_t {
+  // into equal passes.  (r: the samples to split — the frame's spp, or one round of adaptive sampling)
+  auto pick_samples = [&](uint32_t r) -> uint32_t {
     if (opt.samples_in_flight) return opt.samples_in_flight;
     const uint64_t budget = std::max<uint64_t>(path_budget(path_bytes), P);
     // (no slack: run_frame never hands over a batch above its pixel cap = budget / samples of a pass, so P x spp <= budget holds for every
     // batch it sized; a caller's own tile list — or the cap's floor of 64 k pixels — may exceed it, and then the spp range is split)
     const uint32_t smax = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / P, 0x7ffffff0ull / P));
-    const uint32_t npasses = (spp + smax - 1) / smax;
-    return (spp + npasses - 1) / npasses;
+    const uint32_t npasses = (r + smax - 1) / smax;
+    return (r + npasses - 1) / npasses;
   };
-  uint32_t S = std::min(pick_samples(), spp);
+  // The passes of the batch.  Without adaptive sampling the frame's spp is one "round"; with it the rounds end at e_0 = min(min_samples, spp),
+  // e_{j+1} = min(e_j + step, spp) (phx_adaptive), each split by the same rule, and a decision follows every round.  `limit`: the back-off
+  // below.  -> S, the most samples of a pixel any pass carries: what the queues are sized for.
+  std::vector<Pass> passes;
+  auto plan = [&](uint32_t limit) -> uint32_t {
+    passes.clear();
+    uint32_t S = 0;
+    for (uint32_t begin = 0; begin < spp;) {
+      const uint32_t end = !adaptive_on ? spp : (uint32_t)std::min<uint64_t>(spp, begin ? (uint64_t)begin + adaptive.step : adaptive.min_samples);
+      const uint32_t Sr = std::min({pick_samples(end - begin), end - begin, limit});
+      for (uint32_t s0 = begin; s0 < end; s0 += Sr) passes.push_back(Pass{s0, std::min(Sr, end - s0), adaptive_on && s0 + Sr >= end});
+      S = std::max(S, Sr);
+      begin = end;
+    }
+    return S;
+  };
+  uint32_t S = plan(~0u);
   // The budget is a cached reading of the device's free memory (hipMemGetInfo costs ~0.1 ms).  It is only trusted while the queues this
   // object already holds are large enough: a batch that has to GROW them asks the device again — another device object, torch films or
   // RCCL buffers may have taken memory since the reading was made.
-  if ((size_t)P * S > queues.capacity() && !opt.samples_in_flight) { budget_bytes = 0; S = std::min(pick_samples(), spp); }
+  if ((size_t)P * S > queues.capacity() && !opt.samples_in_flight) { budget_bytes = 0; S = plan(~0u); }
   if ((size_t)P * S >= 0x7fffffffull) return fail(PHX_ERR_ARG, "too many paths in flight");
 
   // pixel table of the batch; a frame loop presents the same tiles again and again, so the upload is skipped when nothing changed
@@ -937,6 +1028,12 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
     pix_xy_tiles = tiles;
   }
   if ((rc = acc.alloc((size_t)P * xs))) return rc;
+  if (adaptive_on) {
+    if ((rc = w_acc.alloc((size_t)P * xs)) || (rc = w_xy.alloc(P)) || (rc = sel_idx[0].alloc(P)) || (rc = sel_idx[1].alloc(P)) ||
+        (rc = sel_blocks.alloc((P + PHX_ADAPTIVE_BLOCK - 1) / PHX_ADAPTIVE_BLOCK)))
+      return rc;
+    if (!h_sel) HIPCHK(hipHostMalloc((void**)&h_sel, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+  }
   // queues + state; when the device cannot hold S samples per pixel in flight, back off to half as many (more, shorter passes)
   size_t npaths = 0;
   for (;;) {
@@ -946,7 +1043,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
     (void)hipGetLastError();
     queues.release();
     budget_bytes = 0;  // the reading was stale: the next path_budget() — of this batch, of the next one, of the next frame — asks the device again
-    S = std::min((S + 1) / 2, std::min(pick_samples(), spp));
+    S = plan((S + 1) / 2);
   }
   paths_in_flight = npaths;
   tb_alloc = Clock::now();
@@ -958,7 +1055,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   B.seed = frame.sampler_seed;
 
   direct.events_used = 0; direct.timed.clear();
-  if ((rc = enqueue_batch(direct, B, P, S, xs))) return rc;
+  if ((rc = enqueue_batch(direct, B, P, passes, xs))) return rc;
   tb_enq = Clock::now();
   if (frame.add_tile || frame.host_film) {
     const size_t nfl = (size_t)P * xs;
@@ -1015,7 +1112,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
 }
 
 // The launches of one batch, in stream order.
-int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, uint32_t S, uint32_t xs) {
+int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, const std::vector<Pass>& passes, uint32_t xs) {
   int rc;
   PassBuffers B = B0;
   const uint32_t spp = opt.samples_per_pixel;
@@ -1045,9 +1142,9 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
   // (measured: k_shade 8.6 -> 7.5 ms on the bench frame, profiles/r06_v_grid_by_queue_ab.log).
   // (PHX_SHADE_GRID_BY_QUEUE=0: grids for the capacity, everything enqueued at once, as before.)
   static const bool grid_by_queue = [] { const char* v = std::getenv("PHX_SHADE_GRID_BY_QUEUE"); return !(v && v[0] == '0'); }();
-  const uint32_t depth = opt.path_depth, npasses = (spp + S - 1) / S;
+  const uint32_t depth = opt.path_depth;
   if (grid_by_queue) {
-    const size_t need = (size_t)npasses * depth;
+    const size_t need = passes.size() * depth;  // (under adaptive sampling: of the passes a batch in which no pixel stops would take)
     if (need > h_qlen_n) {
       if (h_qlen) (void)hipHostFree(h_qlen);
       h_qlen = nullptr; h_qlen_n = 0;
@@ -1066,10 +1163,16 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
       if ((spins & 1023u) == 1023u && Clock::now() - t0 > std::chrono::seconds(2)) return cap;
     }
   };
-  uint32_t pass = 0;
-  for (uint32_t s0 = 0; s0 < spp; s0 += S, ++pass) {
-    const uint32_t ns = std::min(S, spp - s0);
-    const uint32_t cap = P * ns;
+  // Adaptive sampling (phx_adaptive).  The first round runs on the batch's own tables.  Behind every round the selection decides
+  // the pixels still active, in the batch buffer (their "home" rows); the rows that go on are gathered, in their order, into the working
+  // tables, and the next round is the same kernels with B.pix_xy, B.acc and B.num_pixels naming those; behind it the rows go home again.
+  const uint32_t m2_offset = frame.primary_components + (frame.normals_channel ? 3u : 0u);
+  uint32_t active = P;                 // pixels the next pass carries
+  const uint32_t* home_of = nullptr;   // their home rows (nullptr: the pass runs on the batch's own tables)
+  int next_list = 0;
+  for (uint32_t pass = 0; pass < (uint32_t)passes.size(); ++pass) {
+    const uint32_t s0 = passes[pass].s0, ns = passes[pass].ns;
+    const uint32_t cap = active * ns;
     B.num_samples = ns;
     B.qlen_out = nullptr;
     if ((rc = timed_launch(Launch::Pass, [&]() { launch_begin_pass(stream, B, ns); }))) return rc;
@@ -1093,14 +1196,49 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
     if ((rc = timed_launch(Launch::Trace, [&]() { launch_trace(stream, scene, B, q, (int)((opt.path_depth - 1) & 1), 0, 1, cap); }))) return rc;
     // the frame's error estimate (phx_frame.moments_channel) is made in the film's walk: k_film_moments INSTEAD of k_film, the channel behind the others
     if ((rc = timed_launch(Launch::Pass, [&]() {
-           if (frame.moments_channel) launch_film_moments(stream, B, ns, inv, s0, xs - 3u);
+           if (frame.moments_channel) launch_film_moments(stream, B, ns, inv, s0, m2_offset);
            else launch_film(stream, B, ns, inv);
          })))
       return rc;
     HIPCHK(hipGetLastError());
+    if (!passes[pass].round_end) continue;
+    const uint32_t n = s0 + ns;  // samples every active pixel has taken
+    uint32_t* const survivors = sel_idx[next_list].p;
+    __atomic_store_n(h_sel, 0xffffffffu, __ATOMIC_RELEASE);  // (the previous round's count has been read, and nothing in the stream writes the word)
+    if ((rc = timed_launch(Launch::Pass, [&]() {
+           if (home_of) launch_adaptive_move(stream, acc.p, w_acc.p, pix_xy.p, w_xy.p, home_of, active, xs, 1);
+           if (n == spp) { launch_adaptive_mark(stream, acc.p, xs, xs - 1u, home_of, active, (float)spp); return; }  // these took every sample: untouched
+           AdaptiveArgs A{};
+           A.acc = acc.p; A.xstride = xs; A.m2_offset = m2_offset; A.samples_offset = xs - 1u; A.active = home_of; A.num_active = active;
+           adaptive_args(adaptive, n, spp, A);
+           launch_adaptive_select(stream, A, sel_blocks.p, survivors, h_sel);
+         })))
+      return rc;
+    HIPCHK(hipGetLastError());
+    if (n == spp) break;
+    // How many go on: the host's one wait of a round (it sizes the next round's launches by the count).  k_adaptive_scan publishes the count in
+    // pinned memory, as k_trace publishes its queue lengths, and the host reads it there without draining the stream; never for ever: after
+    // two seconds the stream is synchronised, which reports a device that has stopped.
+    uint32_t going_on = 0xffffffffu;
+    {
+      const auto t0 = Clock::now();
+      for (uint32_t spins = 0; (going_on = __atomic_load_n(h_sel, __ATOMIC_ACQUIRE)) == 0xffffffffu; ++spins)
+        if ((spins & 1023u) == 1023u && Clock::now() - t0 > std::chrono::seconds(2)) {
+          HIPCHK(hipStreamSynchronize(stream));
+          going_on = __atomic_load_n(h_sel, __ATOMIC_ACQUIRE);
+          break;
+        }
+    }
+    if (going_on > active) return fail(PHX_ERR_DEVICE, "adaptive sampling: the selection reports more pixels than it was given");
+    if (going_on == 0) break;  // every pixel of the batch has stopped: its remaining passes are not run
+    launch_adaptive_move(stream, acc.p, w_acc.p, pix_xy.p, w_xy.p, survivors, going_on, xs, 0);
+    HIPCHK(hipGetLastError());
+    B.acc = w_acc.p; B.pix_xy = w_xy.p; B.num_pixels = active = going_on;
+    home_of = survivors; next_list ^= 1;
   }
   // film_t<>::add_tile (film.hpp:12-15)
   if (frame.device_film) {
+    B.acc = acc.p; B.pix_xy = pix_xy.p; B.num_pixels = P;  // the batch's own tables (they never were anything else without adaptive sampling)
     launch_scatter_film(stream, B, frame.device_film, scene.width);
     HIPCHK(hipGetLastError());
   }

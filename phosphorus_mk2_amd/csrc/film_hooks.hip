@@ -3,6 +3,7 @@
 // exactly as the shade kernels call it), and the preprocess kernels that lay the scene's tables out in pool order.
 //
 //   k_film      the per-sample film add of tile_renderer_t::render_tile (reference src/xpu/cpu.cpp:175-198), in sample order
+//   k_adaptive_*    adaptive sampling: the decision behind a round, the stable compaction of the pixels that go on, the rows' moves (no counterpart in the reference)
 //   k_film_moments  the same add, and beside it the centred second moment of a pixel's samples (phx_frame.moments_channel; no counterpart in the reference)
 #include "shade_common.h"
 
@@ -120,6 +121,106 @@ __global__ void __launch_bounds__(PHX_BLOCK) k_scatter_film(PassBuffers pb, floa
   const float* src = pb.acc + (size_t)pix * pb.xstride;
   float* dst = film + ((size_t)(xy >> 16) * film_width + (xy & 0xffffu)) * pb.xstride;
   for (uint32_t c = 0; c < pb.xstride; ++c) dst[c] = src[c];
+}
+
+// ---- adaptive sampling: the selection behind a round (phx_adaptive in phx_xpu.h states the rule) -----------------------------------
+// A STABLE compaction of the rows that go on, as three launches with no waiting between workgroups: k_adaptive_count decides per row and
+// counts each block's survivors, k_adaptive_scan (one workgroup) turns the counts into offsets and publishes the total, k_adaptive_write
+// decides again — the same expression on the same floats — writes every survivor's row index at its place and rescales the rows that stop.
+// A row belongs to ONE thread, and a row that goes on is not written: the second decision reads what the first one read.
+// q, g and k are uniform over the rows and come from the host (adaptive_args in device.cpp: IEEE binary64 divisions).
+#define PHX_SEL_BLOCK 256
+static_assert(PHX_SEL_BLOCK == PHX_ADAPTIVE_BLOCK, "the host sizes the block-count scratch by it");
+// the decision for row `row`: true = it stops.  A NaN compares false: such a pixel never stops.
+__device__ __forceinline__ bool adaptive_stops(const AdaptiveArgs& A, const float* row) {
+  bool stop = true;
+#pragma unroll
+  for (uint32_t c = 0; c < 3u; ++c) {
+    const double L = (double)row[A.m2_offset + c] * A.q;
+    const double b = A.tau * (fabs((double)row[c]) + A.g);
+    stop = stop && (L <= b * b);
+  }
+  return stop;
+}
+// -> this thread's row goes on (false for threads past num_active); `row` = its index
+__device__ __forceinline__ bool adaptive_survives(const AdaptiveArgs& A, uint32_t i, uint32_t& row) {
+  if (i >= A.num_active) { row = 0u; return false; }
+  row = A.active ? A.active[i] : i;
+  return !adaptive_stops(A, A.acc + (size_t)row * A.xstride);
+}
+// survivors among the block's threads before this one (exclusive) and in the whole block: a ballot per wave, a 4-entry scan in LDS
+__device__ __forceinline__ uint32_t block_rank(bool alive, uint32_t& block_total) {
+  __shared__ uint32_t wave_count[PHX_SEL_BLOCK / 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(alive);
+  if (lane == 0u) wave_count[wave] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t before = 0u, total = 0u;
+#pragma unroll
+  for (uint32_t w = 0; w < PHX_SEL_BLOCK / 64; ++w) { const uint32_t c = wave_count[w]; before += w < wave ? c : 0u; total += c; }
+  block_total = total;
+  return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+__global__ void __launch_bounds__(PHX_SEL_BLOCK) k_adaptive_count(AdaptiveArgs A, uint32_t* __restrict__ block_counts) {
+  uint32_t row, total;
+  const bool alive = adaptive_survives(A, blockIdx.x * PHX_SEL_BLOCK + threadIdx.x, row);
+  (void)block_rank(alive, total);
+  if (threadIdx.x == 0u) block_counts[blockIdx.x] = total;
+}
+// one workgroup: counts[0 .. n) -> their exclusive prefix sums in place, the total to *total_out.  Thread t owns a run of ceil(n / 256) counts.
+__global__ void __launch_bounds__(PHX_SEL_BLOCK) k_adaptive_scan(uint32_t* __restrict__ counts, uint32_t n, uint32_t* __restrict__ total_out) {
+  __shared__ uint32_t run_sum[PHX_SEL_BLOCK];
+  const uint32_t per = (n + PHX_SEL_BLOCK - 1) / PHX_SEL_BLOCK;
+  const uint32_t i0 = min(threadIdx.x * per, n), i1 = min(i0 + per, n);
+  uint32_t s = 0u;
+  for (uint32_t i = i0; i < i1; ++i) s += counts[i];
+  run_sum[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    uint32_t t = 0u;
+    for (uint32_t w = 0; w < PHX_SEL_BLOCK; ++w) { const uint32_t c = run_sum[w]; run_sum[w] = t; t += c; }
+    *total_out = t;
+  }
+  __syncthreads();
+  uint32_t t = run_sum[threadIdx.x];
+  for (uint32_t i = i0; i < i1; ++i) { const uint32_t c = counts[i]; counts[i] = t; t += c; }
+}
+__global__ void __launch_bounds__(PHX_SEL_BLOCK) k_adaptive_write(AdaptiveArgs A, const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ survivors) {
+  const uint32_t i = blockIdx.x * PHX_SEL_BLOCK + threadIdx.x;
+  uint32_t row, total;
+  const bool alive = adaptive_survives(A, i, row);
+  const uint32_t rank = block_rank(alive, total);
+  if (alive) survivors[block_offsets[blockIdx.x] + rank] = row;  // < the total of the scan <= num_active
+  else if (i < A.num_active) {  // the row stops: rescaled once, and it says how many samples it took
+    float* r = A.acc + (size_t)row * A.xstride;
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; ++c) {
+      r[c] = (float)((double)r[c] * A.k);
+      r[A.m2_offset + c] = (float)(((double)r[A.m2_offset + c] * A.k) * A.k);
+    }
+    r[A.samples_offset] = A.n;
+  }
+}
+// Rows between home order and working order, a thread per float so that the working side coalesces: working row w is home row idx[w].
+// to_home == 0: home -> working, the pixel words (pix_xy) with them; 1: working -> home (the pixel words never change).
+__global__ void __launch_bounds__(PHX_SEL_BLOCK) k_adaptive_move(float* __restrict__ home, float* __restrict__ work, const uint32_t* __restrict__ home_xy,
+                                                                 uint32_t* __restrict__ work_xy, const uint32_t* __restrict__ idx, uint32_t n, uint32_t xstride, int to_home) {
+  const size_t t = (size_t)blockIdx.x * PHX_SEL_BLOCK + threadIdx.x;
+  const size_t w = t / xstride; const uint32_t c = (uint32_t)(t % xstride);
+  if (w >= n) return;
+  const size_t h = idx[w];
+  if (to_home) home[h * xstride + c] = work[w * xstride + c];
+  else {
+    work[w * xstride + c] = home[h * xstride + c];
+    if (c == 0u) work_xy[w] = home_xy[h];
+  }
+}
+// channel "samples" of the rows idx[0 .. n) (nullptr: rows 0 .. n - 1): the pixels that took every sample of the frame
+__global__ void __launch_bounds__(PHX_SEL_BLOCK) k_adaptive_mark(float* __restrict__ acc, uint32_t xstride, uint32_t samples_offset, const uint32_t* __restrict__ idx,
+                                                                 uint32_t n, float value) {
+  const uint32_t i = blockIdx.x * PHX_SEL_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  acc[(size_t)(idx ? idx[i] : i) * xstride + samples_offset] = value;
 }
 
 // ---- KAT kernels ------------------------------------------------------------------------------------
@@ -302,6 +403,20 @@ void launch_film_moments(hipStream_t stream, const PassBuffers& pb, uint32_t num
 }
 void launch_scatter_film(hipStream_t stream, const PassBuffers& pb, float* device_film, uint32_t film_width) {
   hipLaunchKernelGGL(k_scatter_film, dim3(blocks_for(pb.num_pixels)), dim3(PHX_BLOCK), 0, stream, pb, device_film, film_width);
+}
+void launch_adaptive_select(hipStream_t stream, const AdaptiveArgs& A, uint32_t* block_scratch, uint32_t* survivors, uint32_t* total_out) {
+  const uint32_t nblocks = (A.num_active + PHX_SEL_BLOCK - 1) / PHX_SEL_BLOCK;
+  hipLaunchKernelGGL(k_adaptive_count, dim3(nblocks), dim3(PHX_SEL_BLOCK), 0, stream, A, block_scratch);
+  hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(PHX_SEL_BLOCK), 0, stream, block_scratch, nblocks, total_out);
+  hipLaunchKernelGGL(k_adaptive_write, dim3(nblocks), dim3(PHX_SEL_BLOCK), 0, stream, A, block_scratch, survivors);
+}
+void launch_adaptive_move(hipStream_t stream, float* home, float* work, const uint32_t* home_xy, uint32_t* work_xy, const uint32_t* idx, uint32_t n,
+                          uint32_t xstride, int to_home) {
+  const size_t nfl = (size_t)n * xstride;
+  if (nfl) hipLaunchKernelGGL(k_adaptive_move, dim3((uint32_t)((nfl + PHX_SEL_BLOCK - 1) / PHX_SEL_BLOCK)), dim3(PHX_SEL_BLOCK), 0, stream, home, work, home_xy, work_xy, idx, n, xstride, to_home);
+}
+void launch_adaptive_mark(hipStream_t stream, float* acc, uint32_t xstride, uint32_t samples_offset, const uint32_t* idx, uint32_t n, float value) {
+  if (n) hipLaunchKernelGGL(k_adaptive_mark, dim3((n + PHX_SEL_BLOCK - 1) / PHX_SEL_BLOCK), dim3(PHX_SEL_BLOCK), 0, stream, acc, xstride, samples_offset, idx, n, value);
 }
 void launch_bsdf_f(hipStream_t stream, const DevMaterial* mat, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3) {
   hipLaunchKernelGGL(k_bsdf_f, dim3((n + 63) / 64), dim3(64), 0, stream, mat, n, n3, wi3, wo3, f3);

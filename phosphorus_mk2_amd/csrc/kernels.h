@@ -6,7 +6,7 @@
 //   trace.hip          k_trace, k_trace_primary, k_trace_rays; trace_plan, init_kernels_on_current_device, launch_trace*
 //   shade_lambert.hip  k_shade<MATS, FIRST, LENS> (Lambert-only scenes), block_append2
 //   shade_general.hip  k_shade_g and its append ring; launch_shade (which reaches k_shade through shade_launch.h)
-//   film_hooks.hip     k_begin_pass, k_film, k_film_moments, k_scatter_film; the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
+//   film_hooks.hip     k_begin_pass, k_film, k_film_moments, k_scatter_film; k_adaptive_* (the selection of adaptive sampling); the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
 //
@@ -180,6 +180,24 @@ void launch_remap_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32
 // smooth ones are remapped by launch_remap_light_tris, whose kernel and whose readers are as they were)
 void launch_remap_flat_light_tris(hipStream_t stream, DevLightTri* light_tris, uint32_t num_light_tris, const uint32_t* elem_of_prim);
 void launch_scatter_film(hipStream_t stream, const PassBuffers& pb, float* device_film, uint32_t film_width);
+
+// Adaptive sampling (phx_adaptive in phx_xpu.h): the selection behind a round that ended at n samples of spp.  PassBuffers has no
+// field for it; a pass over the rows that go on is the same kernels with other values in pix_xy, acc and num_pixels.
+struct AdaptiveArgs {
+  float* acc; uint32_t xstride, m2_offset, samples_offset;  // rows of the batch buffer: primary at 0, m2 and samples at their offsets
+  const uint32_t* active; uint32_t num_active;              // the rows to decide, ascending; nullptr: 0 .. num_active - 1
+  double q, g, tau, k; float n;                             // n / (n - 1), (a * n) / spp, the threshold, spp / n, (float)n
+};
+enum { PHX_ADAPTIVE_BLOCK = 256 };  // rows per workgroup of the selection
+// Decides every active row, rescales those that stop and writes the indices of those that go on to `survivors` in the order of `active`
+// (k_adaptive_count, k_adaptive_scan, k_adaptive_write).  block_scratch: ceil(num_active / PHX_ADAPTIVE_BLOCK) words; *total_out receives
+// the number of survivors (a device word, or a host word the device can write).  num_active >= 1.
+void launch_adaptive_select(hipStream_t stream, const AdaptiveArgs& A, uint32_t* block_scratch, uint32_t* survivors, uint32_t* total_out);
+// n rows of xstride floats between home order and working order (working row w = home row idx[w]); to_home == 0 also carries pix_xy along
+void launch_adaptive_move(hipStream_t stream, float* home, float* work, const uint32_t* home_xy, uint32_t* work_xy, const uint32_t* idx, uint32_t n,
+                          uint32_t xstride, int to_home);
+// channel "samples" = value in rows idx[0 .. n) of acc (idx == nullptr: rows 0 .. n - 1)
+void launch_adaptive_mark(hipStream_t stream, float* acc, uint32_t xstride, uint32_t samples_offset, const uint32_t* idx, uint32_t n, float value);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf

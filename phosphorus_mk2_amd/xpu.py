@@ -154,12 +154,16 @@ class Film:
     """An in-memory film sink: film_t<>::add_tile copies a tile's render buffer into a full frame
     (what film::file_t / the Blender sink do, src/film/file.cpp:27-41)."""
 
-    def __init__(self, width, height, primary_components=4, normals=False, moments=False):
+    def __init__(self, width, height, primary_components=4, normals=False, moments=False, adaptive=False):
+        if adaptive and not moments:
+            raise ValueError("a film of adaptive sampling needs moments=True (phx_dev_start refuses the frame otherwise)")
         self.width, self.height = width, height
-        self.primary_components, self.normals, self.moments = primary_components, normals, moments
+        self.primary_components, self.normals, self.moments, self.adaptive = primary_components, normals, moments, adaptive
         # channel "m2" (phx_frame.moments_channel), when asked for, sits behind "primary" and "normals"
         self.m2_offset = primary_components + (3 if normals else 0)
-        self.xstride = self.m2_offset + (3 if moments else 0)
+        # channel "samples" (adaptive sampling: the device adds it to every frame started while HipDevice.set_adaptive is on) sits behind "m2"
+        self.samples_offset = self.m2_offset + 3
+        self.xstride = self.m2_offset + (3 if moments else 0) + (1 if adaptive else 0)
         self.data = np.zeros((height, width, self.xstride), np.float32)
         self.tiles = 0
         self._lock = threading.Lock()
@@ -181,6 +185,13 @@ class Film:
             raise AttributeError("this film was made without moments=True")
         return self.data[..., self.m2_offset:self.m2_offset + 3]
 
+    @property
+    def samples(self):
+        """channel "samples": (float)n per pixel, the samples the pixel took under adaptive sampling"""
+        if not self.adaptive:
+            raise AttributeError("this film was made without adaptive=True")
+        return self.data[..., self.samples_offset]
+
 
 class BottomUpFilm(Film):
     """The Blender-style sink (plugins/blender/sink.cpp:34-69): the host's (0,0) is the BOTTOM-left pixel, so a tile lands at
@@ -200,11 +211,15 @@ class BottomUpFilm(Film):
 class FrameState:
     """frame_state_t (src/state.hpp:18-31).  `sampler_seed` replaces the shared sampler_t."""
 
-    def __init__(self, sampler_seed, tiles, film, device_film_ptr=None, native_sink=False, primary_components=4, normals=False, moments=False):
+    def __init__(self, sampler_seed, tiles, film, device_film_ptr=None, native_sink=False, primary_components=4, normals=False, moments=False,
+                 adaptive=False):
         self.sampler_seed, self.tiles, self.film, self.device_film_ptr = sampler_seed, tiles, film, device_film_ptr
         self.native_sink = native_sink  # fill film.data from C (phx_frame.host_film) instead of one Python add_tile call per tile
         # the pixel layout of device_film_ptr when there is no `film` to take it from (a film's own layout wins)
         self.primary_components, self.normals, self.moments = primary_components, normals, moments
+        # the frame's pixels carry the channel "samples": what the device writes while HipDevice.set_adaptive is on.  It says how the CALLER
+        # sized device_film_ptr; the device itself goes by its own setting (phx_frame has no word for it)
+        self.adaptive = adaptive
 
 
 class HipDevice:
@@ -214,6 +229,7 @@ class HipDevice:
         self._h, self._lib, self.options = handle, lib, options
         self._keep = None
         self._scene = None
+        self._adaptive = False  # set_adaptive is on: this device's frames carry the channel "samples"
 
     @staticmethod
     def discover(options):
@@ -284,6 +300,11 @@ class HipDevice:
             f.primary_components = frame.primary_components
             f.normals_channel = 1 if frame.normals else 0
             moments = frame.moments
+        # the device writes xstride floats per pixel by ITS setting: a sink sized otherwise would be overrun (or left with holes)
+        sized_for = bool(getattr(frame.film, "adaptive", False)) if frame.film is not None else bool(frame.adaptive)
+        if sized_for != self._adaptive and moments == 1:
+            raise ValueError(f"the film is sized {'with' if sized_for else 'without'} the channel \"samples\", but adaptive sampling is "
+                             f"{'on' if self._adaptive else 'off'} for this device (HipDevice.set_adaptive; Film(..., adaptive=True))")
         f.moments_channel = int(moments)  # False / True; another int is passed through as it is (and refused by phx_dev_start)
         if frame.device_film_ptr:
             f.device_film = frame.device_film_ptr
@@ -307,7 +328,36 @@ class HipDevice:
             out[k] = list(v) if hasattr(v, "__len__") else v
         return out
 
+    def set_adaptive(self, threshold, floor=0.0, min_samples=16, step=16):
+        """Adaptive sampling for every frame this device starts from now on (phx_dev_set_adaptive; include/phx_xpu.h states the rule): a
+        pixel stops once the standard error of its extrapolated value is at most threshold * (|value| + floor), tested after min_samples
+        samples and then every `step`.  Such a frame needs a film with moments=True, adaptive=True.  set_adaptive(None) turns it off."""
+        if threshold is None:
+            _check(self._lib, self._lib.phx_dev_set_adaptive(self._h, None), "phx_dev_set_adaptive")
+            self._adaptive = False
+            return
+        a = abi.Adaptive(threshold=threshold, floor=floor, min_samples=min_samples, step=step)
+        _check(self._lib, self._lib.phx_dev_set_adaptive(self._h, C.byref(a)), "phx_dev_set_adaptive")
+        self._adaptive = True
+
     # ---- stage-level hooks (parity tests) -------------------------------------------------------
+    def adaptive_select(self, acc, samples_done, spp, threshold, floor=0.0, min_samples=16, step=16, active=None, num_active=None):
+        """The selection of adaptive sampling behind a round that ended at samples_done of spp samples, on the caller's data
+        (phx_dev_adaptive_select): acc (rows, 7) f32 = primary rgb, m2 rgb, samples; active: ascending row indices, or None for rows
+        0 .. num_active - 1 (default: every row) -> (the new acc, survivors (k,) u32: the rows that go on, in the order of active).  Needs no scene."""
+        out = np.array(acc, np.float32, order="C").reshape(-1, 7)
+        if active is not None:
+            active = np.ascontiguousarray(active, np.uint32)
+            num_active = len(active)
+        elif num_active is None:
+            num_active = len(out)
+        a = abi.Adaptive(threshold=threshold, floor=floor, min_samples=min_samples, step=step)
+        surv = np.zeros(max(num_active, 1), np.uint32); n = C.c_uint32(0)
+        up = lambda x: x.ctypes.data_as(abi.u32p)
+        _check(self._lib, self._lib.phx_dev_adaptive_select(self._h, num_active, None if active is None else up(active), len(out), out.ctypes.data_as(abi.f32p),
+                                                            int(samples_done), int(spp), C.byref(a), up(surv), C.byref(n)), "phx_dev_adaptive_select")
+        return out, surv[:n.value].copy()
+
     def trace(self, o, d, tmax, shadow=False):
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32); tmax = np.ascontiguousarray(tmax, np.float32)
         n = len(tmax)
@@ -443,27 +493,34 @@ class HipDevice:
             pass
 
 
-def film_variance(data, spp, primary_components=4, normals=False):
+def film_variance(data, spp, primary_components=4, normals=False, adaptive=False):
     """The unbiased estimate of the variance of every pixel's film value from a film rendered with moments=True: data (..., xstride) as
     render() returns it -> m2 * S / (S - 1) in float64, shape (..., 3); S = spp.  The film value is a SUM of S samples y_s (each carries the
-    film's 1 / (spp * pps)), and m2 is their centred sum of squares, so S / (S - 1) * m2 estimates S * var(y).  spp == 1 says nothing: inf."""
+    film's 1 / (spp * pps)), and m2 is their centred sum of squares, so S / (S - 1) * m2 estimates S * var(y).  spp == 1 says nothing: inf.
+    adaptive=True: a film of adaptive sampling (one more float per pixel, "samples"): m2 * n / (n - 1) from the pixel's OWN n, which holds
+    after the rescale of a pixel that stopped as well; inf where n <= 1.  spp is not used then."""
     data = np.asarray(data)
     off = primary_components + (3 if normals else 0)
-    if data.shape[-1] != off + 3:
-        raise ValueError(f"film_variance: a film with the m2 channel has {off + 3} floats per pixel, this one {data.shape[-1]}")
+    if data.shape[-1] != off + 3 + (1 if adaptive else 0):
+        raise ValueError(f"film_variance: a film with the m2 channel has {off + 3 + (1 if adaptive else 0)} floats per pixel, this one {data.shape[-1]}")
     m2 = data[..., off:off + 3].astype(np.float64)
+    if adaptive:
+        n = data[..., off + 3].astype(np.float64)[..., None]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 1, m2 * (n / (n - 1.0)), np.inf)
     if spp <= 1:
         return np.full(m2.shape, np.inf)
     return m2 * (spp / (spp - 1.0))
 
 
-def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_sink=True, rank=0, world=1, moments=False):
+def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_sink=True, rank=0, world=1, moments=False, adaptive=False):
     """The reference's frame on SEVERAL devices in one process (src/core.cpp:103-115): every device is started on the SAME tile
     queue and the SAME film and joined in turn; no collective.  `devices` must have been preprocessed with `scene_desc`.
+    adaptive=True only sizes the film for the channel "samples": the caller has set every device (HipDevice.set_adaptive).
     Returns (film array, [stats per device])."""
     W, H = scene_desc.camera.width, scene_desc.camera.height
     tiles = Tiles.make(W, H, tile_size, rank, world)
-    film = Film(W, H, 4, normals, moments)
+    film = Film(W, H, 4, normals, moments, bool(adaptive))
     for d in devices:
         d.start(scene_desc, FrameState(seed, tiles, film, native_sink=native_sink))
     for d in devices:
@@ -473,9 +530,11 @@ def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_s
 
 def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=32, rank=0, world=1, callback_tiles=False,
            samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference",
-           light_selection="uniform", environment_sampling=False, moments=False):
+           light_selection="uniform", environment_sampling=False, moments=False, adaptive=None):
     """Convenience: the call sequence of session_t::render (plugins/blender/session.cpp:73-94):
-    make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats)."""
+    make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats).
+    adaptive: a dict of HipDevice.set_adaptive's arguments (threshold=..., floor=, min_samples=, step=) turns adaptive sampling on; the film then
+    needs moments=True and carries the channel "samples"."""
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
                    tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling, light_selection=light_selection,
                    environment_sampling=environment_sampling)
@@ -483,6 +542,8 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
     # would build a context, a stream and the kernel attributes on each of them only to use the first
     dev = HipDevice.make(opts)
     try:
+        if adaptive is not None:
+            dev.set_adaptive(**adaptive)
         dev.preprocess(scene_desc)
         W, H = scene_desc.camera.width, scene_desc.camera.height
         tiles = Tiles.make(W, H, tile_size, rank, world)
@@ -494,7 +555,7 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
                     break
                 lst.append(t)
             tiles = CallbackTiles(lst)
-        film = Film(W, H, 4, normals, moments)
+        film = Film(W, H, 4, normals, moments, adaptive is not None)
         dev.start(scene_desc, FrameState(seed, tiles, film, native_sink=native_sink))
         dev.join()
         return film.data, dev.stats()
