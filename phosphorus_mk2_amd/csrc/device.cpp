@@ -4,10 +4,13 @@
 // accelerator (cpu.cpp:35-44), start() spawns a driver thread that drains the shared tile queue
 // (cpu.cpp:223-238) — in batches of many tiles, each carried through the wavefront kernels of
 // trace.hip, shade_lambert.hip, shade_general.hip, film_hooks.hip — and hands finished tiles to the film sink (cpu.cpp:201), join() waits for it.
+// What needs no device lives beside this file: scene_flatten.cpp is the host-only half of preprocess, frame_plan.cpp that of the frame driver
+// (the film's pixel layout, the pixel cap, the batch cutter, the pass schedule); here are the allocations, the launches and the waits.
 // There is no CPU rendering path in this library: without a gfx950 device every entry point fails.
 #include "../../include/phx_xpu.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
+#include "frame_plan.h"
 #include "kernels.h"
 #include "scene_flatten.h"
 
@@ -79,6 +82,21 @@ struct DevBuf {
   size_t bytes() const { return p ? std::max<size_t>(n, 1) * sizeof(T) : 0; }
   ~DevBuf() { release(); }
 };
+// Pinned host memory (flags: hipHostMalloc's).  Grow-only, as DevBuf: a larger request frees and allocates anew, a smaller one is served in place.
+template <typename T>
+struct PinnedBuf {
+  T* p = nullptr; size_t n = 0;
+  int alloc(size_t count, unsigned flags) {
+    if (count <= n && p) return PHX_OK;
+    release();
+    hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T), flags);
+    if (e != hipSuccess) { p = nullptr; return fail(PHX_ERR_DEVICE, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
+    n = count;
+    return PHX_OK;
+  }
+  void release() { if (p) { (void)hipHostFree(p); p = nullptr; n = 0; } }
+  ~PinnedBuf() { release(); }
+};
 
 // Queues + state of the paths in flight, 16 bytes per path each (kernels.h: PassBuffers): ray queues 2 x 32, path state travelling with them
 // 2 x 16, shadow queue 48, radiance 16, and the primary normal 16 when the frame has a normals channel; the hit record is two streams of 8:
@@ -104,15 +122,6 @@ struct PathQueues {
     B.so = q[SO].p; B.sd = q[SD].p; B.sc = q[SC].p; B.pr = q[PR].p; B.pn = normals ? q[PN].p : nullptr;
   }
 };
-// phx_frame.moments_channel: the channel's 3 floats of the batch buffer, counted once per path as if every pixel carried one sample (the
-// buffer's other floats never were counted: 16 bytes a pixel against 176 a path)
-size_t moments_bytes(const phx_frame& f) { return f.moments_channel ? 3 * sizeof(float) : 0; }
-// adaptive sampling, counted the same way: the "samples" float, the working copy of a pixel's row of the batch buffer, its word of the
-// working pixel table and its words of the two index lists
-size_t adaptive_bytes(const phx_frame& f, bool on) {
-  const size_t xs = f.primary_components + (f.normals_channel ? 3u : 0u) + 4u;
-  return on ? sizeof(float) + xs * sizeof(float) + 3 * sizeof(uint32_t) : 0;
-}
 // phx_adaptive: the name of the first field outside its range, or nullptr
 const char* adaptive_invalid(const phx_adaptive& a) {
   if (!std::isfinite(a.threshold) || a.threshold < 0.0f) return "threshold";
@@ -130,7 +139,8 @@ void adaptive_args(const phx_adaptive& a, uint32_t n, uint32_t spp, AdaptiveArgs
   A.k = (double)spp / (double)n;
   A.n = (float)n;
 }
-static_assert(PathQueues::bytes_per_path(false) == 176 && PathQueues::bytes_per_path(true) == 192, "what path_budget divides the device's memory by");
+static_assert(PathQueues::bytes_per_path(false) == queue_bytes_per_path(false) && PathQueues::bytes_per_path(true) == queue_bytes_per_path(true),
+              "what path_budget divides the device's memory by (frame_plan.h: FilmLayout::path_bytes)");
 
 bool host_timing() {  // PHX_HOST_TIMING, read at the first frame: where a frame's and a batch's host time goes, on stderr (probe)
   static const bool on = std::getenv("PHX_HOST_TIMING") != nullptr;
@@ -138,6 +148,17 @@ bool host_timing() {  // PHX_HOST_TIMING, read at the first frame: where a frame
 }
 using Clock = std::chrono::steady_clock;
 double ms_between(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// A word in pinned memory that the host set to 0xffffffff and a kernel overwrites: its value once the kernel has written it.  Never for ever:
+// the clock is looked at every 1 024 spins, and after two seconds the answer is 0xffffffff — a device that has stopped (fault, watchdog) is
+// reported by the caller's next synchronisation, not here.
+uint32_t device_word(const uint32_t* w) {
+  const auto t0 = Clock::now();
+  for (uint32_t spins = 0;; ++spins) {
+    const uint32_t v = __atomic_load_n(w, __ATOMIC_ACQUIRE);
+    if (v != 0xffffffffu || ((spins & 1023u) == 1023u && Clock::now() - t0 > std::chrono::seconds(2))) return v;
+  }
+}
 
 }  // namespace
 
@@ -170,18 +191,19 @@ struct phx_device {
   PathQueues queues;
   DevBuf<uint32_t> counters; DevBuf<DevStats> dstats; DevBuf<uint32_t> pix_xy; DevBuf<float2> jitter; DevBuf<float> acc;
   uint64_t jitter_seed = 0; uint32_t jitter_spp = 0;  // what the jitter table on the device was made for
-  float* h_acc = nullptr; size_t h_acc_n = 0;  // pinned staging for add_tile
-  uint32_t* h_qlen = nullptr; size_t h_qlen_n = 0;  // pinned, device-visible: queue lengths published by k_trace, one word per (pass, step) of a batch (enqueue_batch)
+  PinnedBuf<float> h_acc;      // pinned staging for add_tile
+  PinnedBuf<uint32_t> h_qlen;  // pinned, device-visible: queue lengths published by k_trace, one word per (pass, step) of a batch (enqueue_batch)
   std::vector<phx_tile> pix_xy_tiles;          // the tiles pix_xy currently describes
   // adaptive sampling (phx_dev_set_adaptive), held only by a device that rendered a frame with it: the working copies of acc and pix_xy that a
   // pass over the pixels still active reads (working row w = row sel_idx[.][w] of the batch), the two lists a selection reads and writes
   // by turns, a word per workgroup of the selection, and the pinned word through which the host reads how many pixels go on
   DevBuf<float> w_acc; DevBuf<uint32_t> w_xy, sel_idx[2], sel_blocks;
-  uint32_t* h_sel = nullptr;
+  PinnedBuf<uint32_t> h_sel;
   phx_adaptive adaptive{}; bool adaptive_on = false;
 
   // frame
   phx_frame frame{};
+  FilmLayout layout;  // of `frame` (run_frame)
   // ONE driver thread per device, kept across frames (cpu_t spawns its workers per frame, src/xpu/cpu.cpp:223-238; here a frame of a rank
   // of eight lasts 9 ms and a thread start costs 50-70 us of it): phx_dev_start hands it the frame, phx_dev_join waits for `frame_done`
   std::thread driver;
@@ -219,9 +241,6 @@ struct phx_device {
     cv.notify_all();
     if (driver.joinable()) driver.join();
     for (auto e : direct.events) (void)hipEventDestroy(e);
-    if (h_acc) (void)hipHostFree(h_acc);
-    if (h_qlen) (void)hipHostFree(h_qlen);
-    if (h_sel) (void)hipHostFree(h_sel);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
@@ -254,8 +273,12 @@ struct phx_device {
   }
   void driver_loop();
   int run_frame();
-  struct Pass { uint32_t s0, ns; bool round_end; };  // samples s0 .. s0 + ns - 1 of every pixel it carries; round_end: a decision of adaptive sampling follows
-  int enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, const std::vector<Pass>& passes, uint32_t xs);
+  const phx_adaptive* adaptive_setting() const { return adaptive_on ? &adaptive : nullptr; }
+  // the passes of a batch of P pixels under today's budget (frame_plan.h: plan_passes; with samples_in_flight set the device is not asked)
+  uint32_t plan_batch(uint32_t P, uint32_t limit, std::vector<Pass>& passes) const {
+    return plan_passes(P, opt.samples_per_pixel, opt.samples_in_flight, opt.samples_in_flight ? 0 : path_budget(layout.path_bytes), adaptive_setting(), limit, passes);
+  }
+  int enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, const std::vector<Pass>& passes);
   int render_batch(const std::vector<phx_tile>& tiles);
 };
 
@@ -915,41 +938,15 @@ int phx_device::run_frame() {
     jitter_seed = frame.sampler_seed; jitter_spp = spp;
   }
 
-  // drain the shared tile queue in batches (cpu.cpp:233-234 pulls one tile at a time).  A batch holds as many pixels as can carry ALL
-  // their samples in one pass (P x spp <= the path budget, at most 8 M pixels): path ids are pixel-major, so a pass with every sample of a
-  // pixel keeps the 64 lanes of a wave — and the 256 rays of a camera-ray packet — on ONE pixel.  (Round 3 took 8 M pixels whatever the spp:
-  // the 3840x2160, 256-spp frame of BASELINE config 4 went through as 8 passes of 32 samples; as 8 batches of 256 samples it is 6.8 %
-  // faster — camera rays 67.9 -> 36.0 ms, k_trace -4 %: profiles/r04_v_batch_probe.log.)
-  const size_t path_bytes = PathQueues::bytes_per_path(frame.normals_channel != 0) + moments_bytes(frame) + adaptive_bytes(frame, adaptive_on);
-  // (divided by the samples a pass will really carry: with an explicit samples_in_flight only P x S paths are ever in flight; under adaptive
-  // sampling a pass carries at most a round, and the longest round has max(min_samples, step) samples)
-  const uint32_t frame_samples = adaptive_on ? std::min(opt.samples_per_pixel, std::max(adaptive.min_samples, adaptive.step)) : opt.samples_per_pixel;
-  const uint32_t pass_samples = std::max(1u, std::min(opt.samples_per_pixel, opt.samples_in_flight ? opt.samples_in_flight : frame_samples));
-  const uint64_t pixel_cap = std::min<uint64_t>(8u << 20, std::max<uint64_t>(path_budget(path_bytes) / pass_samples, 64u << 10));
-  // A batch never EXCEEDS the cap (the tile that would is kept for the next batch): its paths then fit the queues the first full batch
-  // allocated, whatever mix of whole and edge tiles it holds.  (Until round 5 a batch overshot by up to one tile; a 4 096-spp batch that grew
-  // from 131 072 to 131 584 pixels re-allocated 86 GB of queues — 2.6 s of hipFree — in the middle of a frame: profiles/r05_f_c5_batch_probe.log.)
-  phx_tile held{}; bool have_held = false;
+  // drain the shared tile queue in batches (cpu.cpp:233-234 pulls one tile at a time) of at most the frame's pixel cap, each in Morton order
+  // (frame_plan.h: pixel_cap, BatchCutter)
+  layout = FilmLayout(frame, adaptive_on);
+  BatchCutter cutter{frame.next_tile, frame.tiles_user, pixel_cap(path_budget(layout.path_bytes), opt, adaptive_setting()), opt.tiles_per_batch, scene.width, scene.height};
+  std::vector<phx_tile> tiles;
+  std::string why;
   for (;;) {
-    std::vector<phx_tile> tiles;
-    uint64_t px = 0;
-    while ((opt.tiles_per_batch == 0 || tiles.size() < opt.tiles_per_batch) && px < pixel_cap) {
-      phx_tile t;
-      if (have_held) { t = held; have_held = false; }
-      else if (!frame.next_tile(frame.tiles_user, &t)) break;
-      if (t.w == 0 || t.h == 0 || (uint64_t)t.x + t.w > scene.width || (uint64_t)t.y + t.h > scene.height) return fail(PHX_ERR_ARG, "tile outside the film");
-      if (!tiles.empty() && px + (uint64_t)t.w * t.h > pixel_cap) { held = t; have_held = true; break; }
-      tiles.push_back(t); px += (uint64_t)t.w * t.h;
-    }
+    if ((rc = cutter.next(tiles, why))) return fail(rc, why);
     if (tiles.empty()) break;
-    {
-      // the batch's tiles in Morton order of their film position: path ids are pixel-major, so the batch's queue — and with it each
-      // XCD's eighth of it (k_trace's segments) — covers a compact block of the film instead of a row of tiles 3840 pixels wide
-      // (1 M soup + 2.3 % against queue order, 100 k soup and config 4 unchanged, films bit-identical: profiles/r04_y_morton.log)
-      auto spread = [](uint32_t v) { v &= 0xffffu; v = (v | (v << 8)) & 0x00ff00ffu; v = (v | (v << 4)) & 0x0f0f0f0fu; v = (v | (v << 2)) & 0x33333333u; v = (v | (v << 1)) & 0x55555555u; return v; };
-      auto key = [&](const phx_tile& t) { return spread(t.x >> 5) | (spread(t.y >> 5) << 1); };
-      std::stable_sort(tiles.begin(), tiles.end(), [&](const phx_tile& a, const phx_tile& b) { return key(a) < key(b); });
-    }
     if ((rc = render_batch(tiles))) return rc;
     stats.tiles += tiles.size();
   }
@@ -977,43 +974,15 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   auto tb_alloc = tb0, tb_enq = tb0;
   uint32_t P = 0;
   for (auto& t : tiles) P += t.w * t.h;
-  const uint32_t spp = opt.samples_per_pixel;
-  const uint32_t xs = frame.primary_components + (frame.normals_channel ? 3u : 0u) + (frame.moments_channel ? 3u : 0u) + (adaptive_on ? 1u : 0u);
+  const uint32_t xs = layout.xstride;
   const bool normals = frame.normals_channel != 0;
-  const size_t path_bytes = PathQueues::bytes_per_path(normals) + moments_bytes(frame) + adaptive_bytes(frame, adaptive_on);
-  // paths in flight: the device's budget (path_budget: up to 512 M paths).  Deep bounces keep only a few percent of the paths alive, so
-  // many paths per pass are what keeps late launches full; a batch that cannot carry all its samples at once splits the spp range
-  // into equal passes.  (r: the samples to split — the frame's spp, or one round of adaptive sampling)
-  auto pick_samples = [&](uint32_t r) -> uint32_t {
-    if (opt.samples_in_flight) return opt.samples_in_flight;
-    const uint64_t budget = std::max<uint64_t>(path_budget(path_bytes), P);
-    // (no slack: run_frame never hands over a batch above its pixel cap = budget / samples of a pass, so P x spp <= budget holds for every
-    // batch it sized; a caller's own tile list — or the cap's floor of 64 k pixels — may exceed it, and then the spp range is split)
-    const uint32_t smax = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / P, 0x7ffffff0ull / P));
-    const uint32_t npasses = (r + smax - 1) / smax;
-    return (r + npasses - 1) / npasses;
-  };
-  // The passes of the batch.  Without adaptive sampling the frame's spp is one "round"; with it the rounds end at e_0 = min(min_samples, spp),
-  // e_{j+1} = min(e_j + step, spp) (phx_adaptive), each split by the same rule, and a decision follows every round.  `limit`: the back-off
-  // below.  -> S, the most samples of a pixel any pass carries: what the queues are sized for.
+  // the passes of the batch, and S, the most samples of a pixel any of them carries: what the queues are sized for
   std::vector<Pass> passes;
-  auto plan = [&](uint32_t limit) -> uint32_t {
-    passes.clear();
-    uint32_t S = 0;
-    for (uint32_t begin = 0; begin < spp;) {
-      const uint32_t end = !adaptive_on ? spp : (uint32_t)std::min<uint64_t>(spp, begin ? (uint64_t)begin + adaptive.step : adaptive.min_samples);
-      const uint32_t Sr = std::min({pick_samples(end - begin), end - begin, limit});
-      for (uint32_t s0 = begin; s0 < end; s0 += Sr) passes.push_back(Pass{s0, std::min(Sr, end - s0), adaptive_on && s0 + Sr >= end});
-      S = std::max(S, Sr);
-      begin = end;
-    }
-    return S;
-  };
-  uint32_t S = plan(~0u);
+  uint32_t S = plan_batch(P, ~0u, passes);
   // The budget is a cached reading of the device's free memory (hipMemGetInfo costs ~0.1 ms).  It is only trusted while the queues this
   // object already holds are large enough: a batch that has to GROW them asks the device again — another device object, torch films or
   // RCCL buffers may have taken memory since the reading was made.
-  if ((size_t)P * S > queues.capacity() && !opt.samples_in_flight) { budget_bytes = 0; S = plan(~0u); }
+  if ((size_t)P * S > queues.capacity() && !opt.samples_in_flight) { budget_bytes = 0; S = plan_batch(P, ~0u, passes); }
   if ((size_t)P * S >= 0x7fffffffull) return fail(PHX_ERR_ARG, "too many paths in flight");
 
   // pixel table of the batch; a frame loop presents the same tiles again and again, so the upload is skipped when nothing changed
@@ -1032,7 +1001,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
     if ((rc = w_acc.alloc((size_t)P * xs)) || (rc = w_xy.alloc(P)) || (rc = sel_idx[0].alloc(P)) || (rc = sel_idx[1].alloc(P)) ||
         (rc = sel_blocks.alloc((P + PHX_ADAPTIVE_BLOCK - 1) / PHX_ADAPTIVE_BLOCK)))
       return rc;
-    if (!h_sel) HIPCHK(hipHostMalloc((void**)&h_sel, sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
+    if ((rc = h_sel.alloc(1, hipHostMallocMapped | hipHostMallocCoherent))) return rc;
   }
   // queues + state; when the device cannot hold S samples per pixel in flight, back off to half as many (more, shorter passes)
   size_t npaths = 0;
@@ -1043,7 +1012,7 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
     (void)hipGetLastError();
     queues.release();
     budget_bytes = 0;  // the reading was stale: the next path_budget() — of this batch, of the next one, of the next frame — asks the device again
-    S = plan((S + 1) / 2);
+    S = plan_batch(P, (S + 1) / 2, passes);
   }
   paths_in_flight = npaths;
   tb_alloc = Clock::now();
@@ -1051,34 +1020,30 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
   PassBuffers B{};
   queues.fill(B, normals, hit_uv);
   B.counters = counters.p; B.stats = dstats.p; B.pix_xy = pix_xy.p; B.jitter = jitter.p; B.acc = acc.p;
-  B.num_pixels = P; B.xstride = xs; B.normals_offset = frame.normals_channel ? frame.primary_components : 0;
+  B.num_pixels = P; B.xstride = xs; B.normals_offset = layout.normals_offset;
   B.seed = frame.sampler_seed;
 
   direct.events_used = 0; direct.timed.clear();
-  if ((rc = enqueue_batch(direct, B, P, passes, xs))) return rc;
+  if ((rc = enqueue_batch(direct, B, P, passes))) return rc;
   tb_enq = Clock::now();
   if (frame.add_tile || frame.host_film) {
     const size_t nfl = (size_t)P * xs;
-    if (nfl > h_acc_n) {
-      if (h_acc) (void)hipHostFree(h_acc);
-      HIPCHK(hipHostMalloc((void**)&h_acc, nfl * sizeof(float), hipHostMallocDefault));
-      h_acc_n = nfl;
-    }
-    HIPCHK(hipMemcpyAsync(h_acc, acc.p, nfl * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if ((rc = h_acc.alloc(nfl, hipHostMallocDefault))) return rc;
+    HIPCHK(hipMemcpyAsync(h_acc.p, acc.p, nfl * sizeof(float), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     std::vector<size_t> offs(tiles.size() + 1, 0);
     for (size_t i = 0; i < tiles.size(); ++i) offs[i + 1] = offs[i] + (size_t)tiles[i].w * tiles[i].h * xs;
     if (frame.add_tile)
       for (size_t i = 0; i < tiles.size(); ++i) {
         const phx_tile& t = tiles[i];
-        frame.add_tile(frame.film_user, (int32_t)t.x, (int32_t)t.y, (int32_t)t.w, (int32_t)t.h, h_acc + offs[i], xs, xs * t.w);
+        frame.add_tile(frame.film_user, (int32_t)t.x, (int32_t)t.y, (int32_t)t.w, (int32_t)t.h, h_acc.p + offs[i], xs, xs * t.w);
       }
     if (frame.host_film) {  // what an add_tile that copies into a frame buffer does, spread over a few host threads
       auto copy_range = [&](size_t i0, size_t i1) {
         for (size_t i = i0; i < i1; ++i) {
           const phx_tile& t = tiles[i];
           for (uint32_t y = 0; y < t.h; ++y)
-            std::memcpy(frame.host_film + ((size_t)(t.y + y) * scene.width + t.x) * xs, h_acc + offs[i] + (size_t)y * t.w * xs, (size_t)t.w * xs * sizeof(float));
+            std::memcpy(frame.host_film + ((size_t)(t.y + y) * scene.width + t.x) * xs, h_acc.p + offs[i] + (size_t)y * t.w * xs, (size_t)t.w * xs * sizeof(float));
         }
       };
       const size_t nthreads = std::min<size_t>({8, std::max(1u, std::thread::hardware_concurrency() / 2), (nfl * sizeof(float)) >> 20});
@@ -1112,10 +1077,10 @@ int phx_device::render_batch(const std::vector<phx_tile>& tiles) {
 }
 
 // The launches of one batch, in stream order.
-int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, const std::vector<Pass>& passes, uint32_t xs) {
+int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t P, const std::vector<Pass>& passes) {
   int rc;
   PassBuffers B = B0;
-  const uint32_t spp = opt.samples_per_pixel;
+  const uint32_t spp = opt.samples_per_pixel, xs = layout.xstride;
   HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)P * xs * sizeof(float), stream));
   const float inv = 1.0f / (float)(spp * opt.paths_per_sample);  // cpu.cpp:191
   // One event BETWEEN two launches serves as the end of the first and the start of the second (an event record is a packet of its own in
@@ -1145,29 +1110,15 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
   const uint32_t depth = opt.path_depth;
   if (grid_by_queue) {
     const size_t need = passes.size() * depth;  // (under adaptive sampling: of the passes a batch in which no pixel stops would take)
-    if (need > h_qlen_n) {
-      if (h_qlen) (void)hipHostFree(h_qlen);
-      h_qlen = nullptr; h_qlen_n = 0;
-      HIPCHK(hipHostMalloc((void**)&h_qlen, need * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-      h_qlen_n = need;
-    }
-    for (size_t k = 0; k < need; ++k) __atomic_store_n(&h_qlen[k], 0xffffffffu, __ATOMIC_RELAXED);  // the previous batch has been joined (render_batch)
+    if ((rc = h_qlen.alloc(need, hipHostMallocMapped | hipHostMallocCoherent))) return rc;
+    for (size_t k = 0; k < need; ++k) __atomic_store_n(&h_qlen.p[k], 0xffffffffu, __ATOMIC_RELAXED);  // the previous batch has been joined (render_batch)
   }
-  auto queue_bound = [&](uint32_t pass, uint32_t step, uint32_t cap) -> uint32_t {  // length of the ray queue k_trace(step) of this pass traced, once it has started
-    const volatile uint32_t* w = &h_qlen[(size_t)pass * depth + step];
-    const auto t0 = Clock::now();
-    for (uint32_t spins = 0;; ++spins) {
-      const uint32_t v = __atomic_load_n(const_cast<const uint32_t*>(w), __ATOMIC_ACQUIRE);
-      if (v != 0xffffffffu) return std::min(v, cap);
-      // never for ever: a device that has stopped (fault, watchdog) is found by the synchronisation behind the batch — size for the capacity and go on
-      if ((spins & 1023u) == 1023u && Clock::now() - t0 > std::chrono::seconds(2)) return cap;
-    }
-  };
+  // length of the ray queue k_trace(step) of this pass traced, once it has started; a device that never says (device_word's 0xffffffff): the capacity
+  auto queue_bound = [&](uint32_t pass, uint32_t step, uint32_t cap) -> uint32_t { return std::min(device_word(&h_qlen.p[(size_t)pass * depth + step]), cap); };
   // Adaptive sampling (phx_adaptive).  The first round runs on the batch's own tables.  Behind every round the selection decides
   // the pixels still active, in the batch buffer (their "home" rows); the rows that go on are gathered, in their order, into the working
   // tables, and the next round is the same kernels with B.pix_xy, B.acc and B.num_pixels naming those; behind it the rows go home again.
-  const uint32_t m2_offset = frame.primary_components + (frame.normals_channel ? 3u : 0u);
-  uint32_t active = P;                 // pixels the next pass carries
+  uint32_t active = P;                // pixels the next pass carries
   const uint32_t* home_of = nullptr;   // their home rows (nullptr: the pass runs on the batch's own tables)
   int next_list = 0;
   for (uint32_t pass = 0; pass < (uint32_t)passes.size(); ++pass) {
@@ -1183,7 +1134,7 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
       if (bounce == 0) {  // the camera rays: one packet walk per 64 x n of them
         if ((rc = timed_launch(Launch::Primary, [&]() { launch_trace_primary(stream, scene, B, cap, s0, q, sq_read); }))) return rc;
       } else {
-        B.qlen_out = grid_by_queue ? h_qlen + (size_t)pass * depth + bounce : nullptr;
+        B.qlen_out = grid_by_queue ? h_qlen.p + (size_t)pass * depth + bounce : nullptr;
         if ((rc = timed_launch(Launch::Trace, [&]() { launch_trace(stream, scene, B, q, sq_read, 1, 1, cap); }))) return rc;
         B.qlen_out = nullptr;
       }
@@ -1196,7 +1147,7 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
     if ((rc = timed_launch(Launch::Trace, [&]() { launch_trace(stream, scene, B, q, (int)((opt.path_depth - 1) & 1), 0, 1, cap); }))) return rc;
     // the frame's error estimate (phx_frame.moments_channel) is made in the film's walk: k_film_moments INSTEAD of k_film, the channel behind the others
     if ((rc = timed_launch(Launch::Pass, [&]() {
-           if (frame.moments_channel) launch_film_moments(stream, B, ns, inv, s0, m2_offset);
+           if (frame.moments_channel) launch_film_moments(stream, B, ns, inv, s0, layout.m2_offset);
            else launch_film(stream, B, ns, inv);
          })))
       return rc;
@@ -1204,14 +1155,14 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
     if (!passes[pass].round_end) continue;
     const uint32_t n = s0 + ns;  // samples every active pixel has taken
     uint32_t* const survivors = sel_idx[next_list].p;
-    __atomic_store_n(h_sel, 0xffffffffu, __ATOMIC_RELEASE);  // (the previous round's count has been read, and nothing in the stream writes the word)
+    __atomic_store_n(h_sel.p, 0xffffffffu, __ATOMIC_RELEASE);  // (the previous round's count has been read, and nothing in the stream writes the word)
     if ((rc = timed_launch(Launch::Pass, [&]() {
            if (home_of) launch_adaptive_move(stream, acc.p, w_acc.p, pix_xy.p, w_xy.p, home_of, active, xs, 1);
-           if (n == spp) { launch_adaptive_mark(stream, acc.p, xs, xs - 1u, home_of, active, (float)spp); return; }  // these took every sample: untouched
+           if (n == spp) { launch_adaptive_mark(stream, acc.p, xs, layout.samples_offset, home_of, active, (float)spp); return; }  // these took every sample: untouched
            AdaptiveArgs A{};
-           A.acc = acc.p; A.xstride = xs; A.m2_offset = m2_offset; A.samples_offset = xs - 1u; A.active = home_of; A.num_active = active;
+           A.acc = acc.p; A.xstride = xs; A.m2_offset = layout.m2_offset; A.samples_offset = layout.samples_offset; A.active = home_of; A.num_active = active;
            adaptive_args(adaptive, n, spp, A);
-           launch_adaptive_select(stream, A, sel_blocks.p, survivors, h_sel);
+           launch_adaptive_select(stream, A, sel_blocks.p, survivors, h_sel.p);
          })))
       return rc;
     HIPCHK(hipGetLastError());
@@ -1219,15 +1170,10 @@ int phx_device::enqueue_batch(BatchLaunches& g, const PassBuffers& B0, uint32_t 
     // How many go on: the host's one wait of a round (it sizes the next round's launches by the count).  k_adaptive_scan publishes the count in
     // pinned memory, as k_trace publishes its queue lengths, and the host reads it there without draining the stream; never for ever: after
     // two seconds the stream is synchronised, which reports a device that has stopped.
-    uint32_t going_on = 0xffffffffu;
-    {
-      const auto t0 = Clock::now();
-      for (uint32_t spins = 0; (going_on = __atomic_load_n(h_sel, __ATOMIC_ACQUIRE)) == 0xffffffffu; ++spins)
-        if ((spins & 1023u) == 1023u && Clock::now() - t0 > std::chrono::seconds(2)) {
-          HIPCHK(hipStreamSynchronize(stream));
-          going_on = __atomic_load_n(h_sel, __ATOMIC_ACQUIRE);
-          break;
-        }
+    uint32_t going_on = device_word(h_sel.p);
+    if (going_on == 0xffffffffu) {
+      HIPCHK(hipStreamSynchronize(stream));
+      going_on = __atomic_load_n(h_sel.p, __ATOMIC_ACQUIRE);
     }
     if (going_on > active) return fail(PHX_ERR_DEVICE, "adaptive sampling: the selection reports more pixels than it was given");
     if (going_on == 0) break;  // every pixel of the batch has stopped: its remaining passes are not run
