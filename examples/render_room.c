@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -15,6 +15,9 @@
  * adaptive TAU: adaptive sampling (phx_dev_set_adaptive) with threshold TAU, a first decision after 4 of the 8 samples and one every 2 from there
  * on: a pixel stops once the standard error of its extrapolated value is at most TAU times the value.  The frame carries the error estimate
  * and one more float per pixel, the samples the pixel took; the host prints their mean.  The file written stays H x W x 4.
+ * denoise: the joined film goes through the film denoiser (phx_dev_denoise, 5 iterations, sigma_l 4; the film has no normals channel, so the
+ * filter is guided by luminance alone) in place before it is written; the frame carries the error estimate, which is the filter's yardstick,
+ * and the host prints the mean of the m2 channel before and after.  Without the keyword nothing of this runs.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -74,7 +77,7 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0, adaptive = 0;
+  int error_estimate = 0, adaptive = 0, denoise = 0;
   phx_adaptive ad;
   memset(&ad, 0, sizeof(ad));
   for (int i = 2; i < argc; ++i)
@@ -83,6 +86,10 @@ int main(int argc, char** argv) {
       ad.threshold = (float)atof(argv[i + 1]); ad.floor = 0.0f; ad.min_samples = 4; ad.step = 2;
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
+    } else if (strcmp(argv[i], "denoise") == 0) {
+      denoise = 1;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
     } else if (strcmp(argv[i], "error-estimate") == 0) {
       error_estimate = 1;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
@@ -126,7 +133,7 @@ int main(int argc, char** argv) {
     if (adaptive && phx_dev_set_adaptive(devs[i], &ad) != PHX_OK) return fail("phx_dev_set_adaptive"); /* the setting is the device's, not the frame's */
   }
 
-  if (adaptive) error_estimate = 1; /* the stopping rule reads the estimate: such a frame must carry it */
+  if (adaptive || denoise) error_estimate = 1; /* the stopping rule and the denoiser read the estimate: such a frame must carry it */
   const size_t xstride = 4 + (error_estimate ? 3 : 0) + (adaptive ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */
   float* film = (float*)calloc((size_t)W * H * xstride, sizeof(float));
   phx_tiles* tiles = phx_tiles_make(W, H, 32, 0, 1); /* ONE job::tiles_t for all devices */
@@ -169,6 +176,17 @@ int main(int argc, char** argv) {
     for (size_t p = 0; p < (size_t)W * H; ++p) taken += film[p * xstride + 7];
     printf("adaptive: mean samples per pixel %.4f of %u (camera_samples %llu)\n", taken / (double)((size_t)W * H), opt.samples_per_pixel,
            (unsigned long long)st.camera_samples);
+  }
+  if (denoise) { /* after the join; with several ranks: after the film reduce.  Any device serves: the call reads the film, not the scene */
+    phx_denoise dn;
+    memset(&dn, 0, sizeof(dn));
+    dn.width = W; dn.height = H; dn.xstride = (uint32_t)xstride; dn.m2_offset = 4; dn.samples_offset = adaptive ? 7 : 0;
+    dn.spp = opt.samples_per_pixel; dn.iterations = 5; dn.sigma_l = 4.0f; dn.normal_power_log2 = 7;
+    double before = 0.0, after = 0.0;
+    for (size_t p = 0; p < (size_t)W * H; ++p) for (int c = 0; c < 3; ++c) before += film[p * xstride + 4 + c];
+    if (phx_dev_denoise(devs[0], &dn, film, film) != PHX_OK) return fail("phx_dev_denoise");
+    for (size_t p = 0; p < (size_t)W * H; ++p) for (int c = 0; c < 3; ++c) after += film[p * xstride + 4 + c];
+    printf("denoise: mean m2 %.6g -> %.6g\n", before / (3.0 * W * H), after / (3.0 * W * H));
   }
   if (argc > 1) {
     FILE* f = fopen(argv[1], "wb");

@@ -393,6 +393,56 @@ typedef struct phx_adaptive {
   uint32_t reserved[4];  /* must be 0 */
 } phx_adaptive;
 
+/* ---- film denoiser: an edge-avoiding a-trous filter whose yardstick is the film's own error estimate ------ */
+/* A post-process of a finished film that has the channel "m2" (phx_frame.moments_channel): a pixel is averaged with neighbours that are the
+ * same surface (the "normals" channel) and statistically the same value (their luminance differs by less than sigma_l standard deviations,
+ * the deviation taken from m2).  Nothing calls it unless the host does; it reads no scene and changes no frame.
+ * State, per pixel: the colour C[3] and the variance of the pixel's value V[3] as fp32; the normal N[3] as the film holds it (fp32, constant,
+ * all zero where the camera ray missed); a flag `valid` (constant).  All arithmetic is binary64, without contraction, in the order written;
+ * fp32 values are widened first, and a result is rounded to fp32 once, where fp32(...) says so.
+ *   init      n     = (double) of the pixel's "samples" float, or (double)spp when samples_offset == 0
+ *             valid = the 3 "primary" floats, the 3 "m2" floats and N are finite, every m2 >= 0, and n is finite and >= 2
+ *             V_c   = fp32(m2_c * (n / (n - 1)))
+ *             An invalid pixel is never a tap below and never part of the 3 x 3; its output floats are its input floats.
+ *   iteration i = 0 .. iterations - 1, step s = 2^i: every valid pixel p reads the state the iteration started from and writes a second one.
+ *             l_x   = (0.2126 * C_r + 0.7152 * C_g) + 0.0722 * C_b                          luminance of pixel x
+ *             e_x   = (0.2126 * sqrt(V_r) + 0.7152 * sqrt(V_g)) + 0.0722 * sqrt(V_b)        its deviation, were the colours' noise fully correlated
+ *             S_p   = (sum of (g * e_q) * e_q) / (sum of g)   over q = p + (dx, dy), dy = -1 .. 1 outer, dx = -1 .. 1 inner (ONE pixel apart,
+ *                     whatever s), only q inside the film and valid;  g = k3[dy] * k3[dx], k3 = (1/4, 1/2, 1/4);  both sums start at 0.0
+ *             sig   = sigma_l * sqrt(S_p)
+ *             taps  q = p + s * (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner; a tap outside the film or invalid is skipped.
+ *                     h   = k5[dy] * k5[dx],  k5 = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *                     centre tap (dx == dy == 0):  w = h   (9/64)
+ *                     otherwise
+ *                       w_n = 1                                        if N_p and N_q are both all-zero, or normals_offset == 0
+ *                             else d = (Nx * Nx' + Ny * Ny') + Nz * Nz';  d = d > 0 ? d : 0;  d = d * d, normal_power_log2 times;  w_n = d
+ *                       w_l = (l_q == l_p ? 1 : 0)                     if sig == 0
+ *                             else u = fabs(l_q - l_p) / sig;  t = 1 - u * u;  w_l = u < 1 ? t * t : 0       (Tukey's biweight)
+ *                       w   = (h * w_n) * w_l
+ *                     W += w;   A_c += w * (C_q,c - C_p,c);   B_c += (w * w) * V_q,c          (W, A_c, B_c start at 0.0)
+ *             result  C'_c = fp32(C_p,c + A_c / W);   V'_c = fp32(B_c / (W * W))              (W >= 9/64: the centre tap)
+ *   output    every float of the pixel is film_in's, except, for a valid pixel when iterations >= 1:
+ *             primary rgb = C;   m2 rgb = fp32(V_c * ((n - 1) / n)), so that the variance read from the output (m2 * n / (n - 1)) is V.
+ *             iterations == 0 copies the film.
+ * The delta form makes a constant neighbourhood exact; a film whose m2 is zero everywhere averages only pixels of EQUAL luminance.
+ * Limits: V' treats the pixels as independent and ignores the blur's bias, so it understates the true error (tenfold and more);
+ * the biweight rejects bright outliers, so the film's mean drops where the frame has fireflies; there is no depth or albedo guide: textures
+ * and coplanar depth edges are protected by luminance alone; nothing is temporal; a multi-GPU film must be reduced before the call (a
+ * rank's own film holds zeros in the pixels it does not own). */
+typedef struct phx_denoise {
+  uint32_t width, height;      /* 1 .. 65536 each */
+  uint32_t xstride;            /* floats per pixel of both films; >= 6 */
+  uint32_t normals_offset;     /* 0 = the film has no normals: w_n = 1 everywhere; else >= 3, normals_offset + 3 <= xstride */
+  uint32_t m2_offset;          /* required: >= 3, m2_offset + 3 <= xstride */
+  uint32_t samples_offset;     /* 0 = none: every pixel took spp samples; else >= 3, < xstride */
+  uint32_t spp;                /* >= 2 */
+  uint32_t iterations;         /* 0 .. 8; 0 copies the film */
+  float    sigma_l;            /* finite, > 0 */
+  uint32_t normal_power_log2;  /* 0 .. 10: w_n = (N.N')^(2^normal_power_log2); 7 is (N.N')^128 */
+  uint32_t on_device;          /* 0: both pointers are host memory, 1: both are device memory (HBM) */
+  uint32_t reserved[5];        /* must be 0 */
+} phx_denoise;
+
 /* ---- statistics ------------------------------------------------------------------------ */
 /* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
  * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
@@ -586,6 +636,17 @@ int phx_dev_adaptive_select(phx_device* dev, uint32_t num_active, const uint32_t
                             uint32_t num_rows, float* acc /* num_rows x 7: primary rgb, m2 rgb, samples; in and out */,
                             uint32_t samples_done, uint32_t spp, const phx_adaptive* a,
                             uint32_t* survivors /* num_active words */, uint32_t* num_survivors);
+
+/* The film denoiser (phx_denoise above states the rule): film_in -> film_out, both width x height x xstride floats, row-major; film_out may
+ * equal film_in, and must not overlap it otherwise.  Synchronous.  It needs a device but no scene.  Call it after phx_dev_join, and on
+ * several GPUs after the films are reduced.  PHX_ERR_STATE while a frame is started and not joined; PHX_ERR_ARG, with the field's name in
+ * the message, for a value outside the ranges stated at the struct, channels that overlap "primary" (floats 0 .. 2) or each other, a
+ * non-zero reserved word or a null pointer.  Its working memory (96 bytes a pixel) is allocated in the call and freed before it returns
+ * (PHX_ERR_OOM if it cannot be had): phx_stats.device_bytes and every later frame are what they were. */
+int phx_dev_denoise(phx_device* dev, const phx_denoise* d, const float* film_in, float* film_out);
+/* HIP-event times of the last phx_dev_denoise of this device in milliseconds: ms[0] the pack stage, ms[1 .. 8] the iterations (0 for those
+ * not run), ms[9] the unpack stage (with the film copy when film_out != film_in), ms[10] the whole call on the host's clock. */
+int phx_dev_denoise_times(const phx_device* dev, double* ms /* 11 */);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

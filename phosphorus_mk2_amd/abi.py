@@ -156,6 +156,15 @@ class Adaptive(C.Structure):
     _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32), ("step", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
+class Denoise(C.Structure):
+    """phx_denoise: the film denoiser's settings and the film's layout (phx_dev_denoise)"""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32), ("xstride", C.c_uint32), ("normals_offset", C.c_uint32), ("m2_offset", C.c_uint32),
+        ("samples_offset", C.c_uint32), ("spp", C.c_uint32), ("iterations", C.c_uint32), ("sigma_l", C.c_float),
+        ("normal_power_log2", C.c_uint32), ("on_device", C.c_uint32), ("reserved", C.c_uint32 * 5),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("camera_samples", C.c_uint64), ("rays_closest", C.c_uint64), ("rays_shadow", C.c_uint64),
@@ -182,7 +191,7 @@ EXPORTS = [
     "phx_tiles_free", "phx_dev_trace", "phx_dev_bsdf_f", "phx_dev_bsdf_sample", "phx_dev_copy_bvh",
     "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
     "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample", "phx_dev_film_moments",
-    "phx_dev_set_adaptive", "phx_dev_adaptive_select",
+    "phx_dev_set_adaptive", "phx_dev_adaptive_select", "phx_dev_denoise", "phx_dev_denoise_times",
 ]
 
 
@@ -217,5 +226,7 @@ def declare(lib):
     lib.phx_dev_set_adaptive.argtypes = [vp, C.POINTER(Adaptive)]; lib.phx_dev_set_adaptive.restype = C.c_int
     lib.phx_dev_adaptive_select.argtypes = [vp, C.c_uint32, u32p, C.c_uint32, f32p, C.c_uint32, C.c_uint32, C.POINTER(Adaptive), u32p, u32p]
     lib.phx_dev_adaptive_select.restype = C.c_int
+    lib.phx_dev_denoise.argtypes = [vp, C.POINTER(Denoise), vp, vp]; lib.phx_dev_denoise.restype = C.c_int  # the films: host or device addresses
+    lib.phx_dev_denoise_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_denoise_times.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

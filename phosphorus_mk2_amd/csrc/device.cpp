@@ -5,11 +5,13 @@
 // (cpu.cpp:223-238) — in batches of many tiles, each carried through the wavefront kernels of
 // trace.hip, shade_lambert.hip, shade_general.hip, film_hooks.hip — and hands finished tiles to the film sink (cpu.cpp:201), join() waits for it.
 // What needs no device lives beside this file: scene_flatten.cpp is the host-only half of preprocess, frame_plan.cpp that of the frame driver
-// (the film's pixel layout, the pixel cap, the batch cutter, the pass schedule); here are the allocations, the launches and the waits.
+// (the film's pixel layout, the pixel cap, the batch cutter, the pass schedule), denoise_check.cpp the argument check of the film denoiser
+// (denoise.hip, a post-process no frame launches); here are the allocations, the launches and the waits.
 // There is no CPU rendering path in this library: without a gfx950 device every entry point fails.
 #include "../../include/phx_xpu.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
+#include "denoise_check.h"
 #include "frame_plan.h"
 #include "kernels.h"
 #include "scene_flatten.h"
@@ -200,6 +202,7 @@ struct phx_device {
   DevBuf<float> w_acc; DevBuf<uint32_t> w_xy, sel_idx[2], sel_blocks;
   PinnedBuf<uint32_t> h_sel;
   phx_adaptive adaptive{}; bool adaptive_on = false;
+  double denoise_ms[11] = {};  // phx_dev_denoise_times: the last phx_dev_denoise's stages (it holds no device memory between calls)
 
   // frame
   phx_frame frame{};
@@ -590,6 +593,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 3: return sizeof(phx_face_set); case 4: return sizeof(phx_mesh); case 5: return sizeof(phx_camera);
     case 6: return sizeof(phx_scene); case 7: return sizeof(phx_tile); case 8: return sizeof(phx_frame);
     case 9: return sizeof(phx_stats); case 10: return sizeof(phx_texture); case 11: return sizeof(phx_adaptive);
+    case 13: return sizeof(phx_denoise);  // (12 stays unused: tests/test_adaptive_sampling.py pins it to 0)
     default: return 0;
   }
 }
@@ -740,6 +744,74 @@ int phx_dev_film_moments(phx_device* d, uint32_t num_pixels, uint32_t num_sample
     B.pr = const_cast<float4*>(pr); B.acc = a; B.num_pixels = num_pixels; B.num_samples = num_samples; B.xstride = 6;
     return s.run([&] { launch_film_moments(d->stream, B, num_samples, inv, samples_done, 3); });
   });
+}
+
+// (no stage_hook: the denoiser reads a film and no scene)
+int phx_dev_denoise(phx_device* d, const phx_denoise* q, const float* film_in, float* film_out) {
+  return guarded([&]() -> int {
+    if (!d) return fail(PHX_ERR_ARG, "denoise: null device");
+    if (d->running) return fail(PHX_ERR_STATE, "denoise while a frame is running");
+    if (!q) return fail(PHX_ERR_ARG, "denoise: null argument");
+    std::string why;
+    if (const int rc = denoise_check(*q, film_in, film_out, why)) return fail(rc, why);
+    const auto t0 = Clock::now();
+    DeviceScope on(d->hip_device);
+    if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+    std::fill(std::begin(d->denoise_ms), std::end(d->denoise_ms), 0.0);
+    const size_t npix = (size_t)q->width * q->height, film_bytes = npix * q->xstride * sizeof(float);
+    // everything the call holds on the device lives in these and goes with them, on every way out
+    DevBuf<float> staged; DevBuf<float4> c[2], v[2], n; DevBuf<double> e[2];
+    struct Events {
+      std::vector<hipEvent_t> ev;
+      ~Events() { for (hipEvent_t x : ev) (void)hipEventDestroy(x); }
+      int mark(hipStream_t s) { hipEvent_t x; HIPCHK(hipEventCreate(&x)); ev.push_back(x); HIPCHK(hipEventRecord(x, s)); return PHX_OK; }
+    } events;
+    const float* src = film_in; float* dst = film_out;
+    if (!q->on_device) {  // host films: one device copy, denoised in place
+      if (const int rc = staged.alloc(npix * q->xstride)) return rc;
+      HIPCHK(hipMemcpy(staged.p, film_in, film_bytes, hipMemcpyHostToDevice));
+      src = dst = staged.p;
+    }
+    if (q->iterations) {
+      for (int k = 0; k < 2; ++k) {
+        if (const int rc = c[k].alloc(npix)) return rc;
+        if (const int rc = v[k].alloc(npix)) return rc;
+        if (const int rc = e[k].alloc(npix)) return rc;
+      }
+      if (const int rc = n.alloc(npix)) return rc;
+      DenoiseArgs A{};
+      A.width = q->width; A.height = q->height; A.xstride = q->xstride; A.normals_offset = q->normals_offset; A.m2_offset = q->m2_offset;
+      A.samples_offset = q->samples_offset; A.spp = q->spp; A.normal_power_log2 = q->normal_power_log2; A.sigma_l = (double)q->sigma_l;
+      for (int k = 0; k < 2; ++k) { A.c[k] = c[k].p; A.v[k] = v[k].p; A.e[k] = e[k].p; }
+      A.n = n.p;
+      if (const int rc = events.mark(d->stream)) return rc;
+      launch_denoise_pack(d->stream, A, src);
+      if (const int rc = events.mark(d->stream)) return rc;
+      for (uint32_t i = 0; i < q->iterations; ++i) {
+        launch_denoise_iteration(d->stream, A, (int)(i & 1u), 1u << i);
+        if (const int rc = events.mark(d->stream)) return rc;
+      }
+      if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, film_bytes, hipMemcpyDeviceToDevice, d->stream));
+      launch_denoise_unpack(d->stream, A, (int)(q->iterations & 1u), dst);
+      if (const int rc = events.mark(d->stream)) return rc;
+    } else if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, film_bytes, hipMemcpyDeviceToDevice, d->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (!q->on_device) HIPCHK(hipMemcpy(film_out, staged.p, film_bytes, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k + 1 < events.ev.size(); ++k) {
+      float ms = 0.0f;
+      HIPCHK(hipEventElapsedTime(&ms, events.ev[k], events.ev[k + 1]));
+      d->denoise_ms[k == 0 ? 0 : k <= q->iterations ? k : 9] = ms;
+    }
+    d->denoise_ms[10] = ms_between(t0, Clock::now());
+    return PHX_OK;
+  });
+}
+
+int phx_dev_denoise_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "denoise_times: null argument");
+  std::copy(std::begin(d->denoise_ms), std::end(d->denoise_ms), ms);
+  return PHX_OK;
 }
 
 // (no stage_hook either: the selection reads no scene)

@@ -7,6 +7,7 @@
 //   shade_lambert.hip  k_shade<MATS, FIRST, LENS> (Lambert-only scenes), block_append2
 //   shade_general.hip  k_shade_g and its append ring; launch_shade (which reaches k_shade through shade_launch.h)
 //   film_hooks.hip     k_begin_pass, k_film, k_film_moments, k_scatter_film; k_adaptive_* (the selection of adaptive sampling); the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
+//   denoise.hip        k_denoise_pack, k_denoise_iteration, k_denoise_unpack: the film denoiser, a post-process no frame launches
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
 //
@@ -198,6 +199,23 @@ void launch_adaptive_move(hipStream_t stream, float* home, float* work, const ui
                           uint32_t xstride, int to_home);
 // channel "samples" = value in rows idx[0 .. n) of acc (idx == nullptr: rows 0 .. n - 1)
 void launch_adaptive_mark(hipStream_t stream, float* acc, uint32_t xstride, uint32_t samples_offset, const uint32_t* idx, uint32_t n, float value);
+
+// The film denoiser (phx_denoise in phx_xpu.h states the rule; denoise.hip).  Its state lives in working memory of the call, one
+// record per pixel and array, so that a tap is three 16-byte loads: c = (C.rgb, 0) and v = (V.rgb, 0), both ping-pong; e = the luminance
+// deviation e_x as the binary64 it is computed in (made once by the stage that writes V, read by the 3 x 3 of nine pixels), ping-pong;
+// n = (N.xyz, valid ? 1 : 0), constant.  96 bytes a pixel.
+struct DenoiseArgs {
+  uint32_t width, height, xstride, normals_offset, m2_offset, samples_offset, spp, normal_power_log2;
+  double sigma_l;
+  float4* c[2]; float4* v[2]; double* e[2]; float4* n;
+};
+enum { PHX_DENOISE_BX = 64, PHX_DENOISE_BY = 4 };  // a workgroup's pixels: 4 rows of 64, a wave per row
+// film -> state 0 (V from m2, valid, e)
+void launch_denoise_pack(hipStream_t stream, const DenoiseArgs& A, const float* film);
+// one iteration at step `step`: state `from` -> state `from ^ 1` (valid pixels only; the others' records are never read)
+void launch_denoise_iteration(hipStream_t stream, const DenoiseArgs& A, int from, uint32_t step);
+// state `from` -> "primary" and "m2" of the valid pixels of `film`, which holds the input film's floats
+void launch_denoise_unpack(hipStream_t stream, const DenoiseArgs& A, int from, float* film);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf

@@ -340,6 +340,30 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_set_adaptive(self._h, C.byref(a)), "phx_dev_set_adaptive")
         self._adaptive = True
 
+    def denoise(self, data, spp, primary_components=4, normals=False, adaptive=False, iterations=5, sigma_l=4.0, normal_power_log2=7, device_ptr=None):
+        """The film denoiser (phx_dev_denoise; include/phx_xpu.h states the rule): an edge-avoiding a-trous filter of a finished film
+        whose yardstick is the film's own error estimate, so the film must have been rendered with moments=True.  data (H, W, xstride) f32 as
+        render() returns it -> a new array of the same shape: "primary" filtered, "m2" the filtered value's variance estimate (read it with
+        film_variance as before), every other float untouched.  primary_components, normals and adaptive say how the pixel is laid out, as for
+        Film.  device_ptr: the address of a device-resident film of that layout, denoised IN PLACE; `data` then is only its shape (H, W,
+        xstride), and the call returns None.  Needs no scene; call it after join(), and after dist.reduce_film on several GPUs."""
+        shape = tuple(data) if device_ptr is not None and not hasattr(data, "shape") else data.shape
+        q = denoise_settings(shape, spp, primary_components, normals, adaptive, iterations, sigma_l, normal_power_log2)
+        if device_ptr is not None:
+            q.on_device = 1
+            _check(self._lib, self._lib.phx_dev_denoise(self._h, C.byref(q), device_ptr, device_ptr), "phx_dev_denoise")
+            return None
+        src = np.ascontiguousarray(data, np.float32)
+        out = np.empty_like(src)
+        _check(self._lib, self._lib.phx_dev_denoise(self._h, C.byref(q), src.ctypes.data, out.ctypes.data), "phx_dev_denoise")
+        return out
+
+    def denoise_times(self):
+        """HIP-event milliseconds of the last denoise(): dict of pack, iterations (list of 8, 0 for those not run), unpack, call (host clock)"""
+        ms = (C.c_double * 11)()
+        _check(self._lib, self._lib.phx_dev_denoise_times(self._h, ms), "phx_dev_denoise_times")
+        return {"pack": ms[0], "iterations": list(ms[1:9]), "unpack": ms[9], "call": ms[10]}
+
     # ---- stage-level hooks (parity tests) -------------------------------------------------------
     def adaptive_select(self, acc, samples_done, spp, threshold, floor=0.0, min_samples=16, step=16, active=None, num_active=None):
         """The selection of adaptive sampling behind a round that ended at samples_done of spp samples, on the caller's data
@@ -513,6 +537,22 @@ def film_variance(data, spp, primary_components=4, normals=False, adaptive=False
     return m2 * (spp / (spp - 1.0))
 
 
+def denoise_settings(shape, spp, primary_components=4, normals=False, adaptive=False, iterations=5, sigma_l=4.0, normal_power_log2=7):
+    """abi.Denoise for a film of `shape` (H, W, xstride) with the channels derived as Film derives them: "normals" behind "primary", "m2"
+    behind them, "samples" behind "m2".  ValueError for a film without the channel m2 (render it with moments=True)."""
+    if len(shape) != 3:
+        raise ValueError("denoise: the film must be (height, width, xstride)")
+    H, W, xstride = (int(v) for v in shape)
+    m2_offset = primary_components + (3 if normals else 0)
+    want = m2_offset + 3 + (1 if adaptive else 0)
+    if xstride != want:
+        raise ValueError(f"denoise: a film with the m2 channel has {want} floats per pixel in this layout, this one {xstride} "
+                         "(the denoiser needs a film rendered with moments=True)")
+    return abi.Denoise(width=W, height=H, xstride=xstride, normals_offset=primary_components if normals else 0, m2_offset=m2_offset,
+                       samples_offset=m2_offset + 3 if adaptive else 0, spp=int(spp), iterations=int(iterations), sigma_l=float(sigma_l),
+                       normal_power_log2=int(normal_power_log2), on_device=0)
+
+
 def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_sink=True, rank=0, world=1, moments=False, adaptive=False):
     """The reference's frame on SEVERAL devices in one process (src/core.cpp:103-115): every device is started on the SAME tile
     queue and the SAME film and joined in turn; no collective.  `devices` must have been preprocessed with `scene_desc`.
@@ -530,11 +570,15 @@ def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_s
 
 def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=32, rank=0, world=1, callback_tiles=False,
            samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference",
-           light_selection="uniform", environment_sampling=False, moments=False, adaptive=None):
+           light_selection="uniform", environment_sampling=False, moments=False, adaptive=None, denoise=None):
     """Convenience: the call sequence of session_t::render (plugins/blender/session.cpp:73-94):
     make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats).
     adaptive: a dict of HipDevice.set_adaptive's arguments (threshold=..., floor=, min_samples=, step=) turns adaptive sampling on; the film then
-    needs moments=True and carries the channel "samples"."""
+    needs moments=True and carries the channel "samples".
+    denoise: a dict of HipDevice.denoise's settings (iterations=, sigma_l=, normal_power_log2=; {} for the defaults) filters the film that is
+    returned; it needs moments=True."""
+    if denoise is not None and not moments:
+        raise ValueError("denoise needs moments=True: the filter's yardstick is the film's m2 channel")
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
                    tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling, light_selection=light_selection,
                    environment_sampling=environment_sampling)
@@ -558,6 +602,8 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
         film = Film(W, H, 4, normals, moments, adaptive is not None)
         dev.start(scene_desc, FrameState(seed, tiles, film, native_sink=native_sink))
         dev.join()
+        if denoise is not None:
+            return dev.denoise(film.data, spp, 4, normals, adaptive is not None, **denoise), dev.stats()
         return film.data, dev.stats()
     finally:
         dev.close()
