@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -18,6 +18,8 @@
  * denoise: the joined film goes through the film denoiser (phx_dev_denoise, 5 iterations, sigma_l 4; the film has no normals channel, so the
  * filter is guided by luminance alone) in place before it is written; the frame carries the error estimate, which is the filter's yardstick,
  * and the host prints the mean of the m2 channel before and after.  Without the keyword nothing of this runs.
+ * denoise-guided: the same, guided by the first hit's albedo: the host renders the guide film of the frame's seed (phx_dev_render_guides, 4 samples a
+ * pixel) and hands it to phx_dev_denoise_guided with PHX_GUIDE_DEMODULATE (the film has no normals channel, which PHX_GUIDE_PLANE would need).
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -86,8 +88,8 @@ int main(int argc, char** argv) {
       ad.threshold = (float)atof(argv[i + 1]); ad.floor = 0.0f; ad.min_samples = 4; ad.step = 2;
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
-    } else if (strcmp(argv[i], "denoise") == 0) {
-      denoise = 1;
+    } else if (strcmp(argv[i], "denoise") == 0 || strcmp(argv[i], "denoise-guided") == 0) {
+      denoise = strcmp(argv[i], "denoise") == 0 ? 1 : 2;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     } else if (strcmp(argv[i], "error-estimate") == 0) {
@@ -184,7 +186,21 @@ int main(int argc, char** argv) {
     dn.spp = opt.samples_per_pixel; dn.iterations = 5; dn.sigma_l = 4.0f; dn.normal_power_log2 = 7;
     double before = 0.0, after = 0.0;
     for (size_t p = 0; p < (size_t)W * H; ++p) for (int c = 0; c < 3; ++c) before += film[p * xstride + 4 + c];
-    if (phx_dev_denoise(devs[0], &dn, film, film) != PHX_OK) return fail("phx_dev_denoise");
+    if (denoise == 2) { /* the guides need the scene: a device that preprocessed it renders them, with the frame's seed */
+      float* guides = (float*)calloc((size_t)W * H * 8, sizeof(float));
+      phx_guides gp;
+      memset(&gp, 0, sizeof(gp));
+      gp.sampler_seed = frame.sampler_seed; gp.samples = 4;
+      if (!guides || phx_dev_render_guides(devs[0], &gp, guides) != PHX_OK) return fail("phx_dev_render_guides");
+      phx_denoise_guides dg;
+      memset(&dg, 0, sizeof(dg));
+      dg.guides = guides; dg.xstride = 8; dg.flags = PHX_GUIDE_DEMODULATE; dg.albedo_floor = 0.01f;
+      if (phx_dev_denoise_guided(devs[0], &dn, &dg, film, film) != PHX_OK) return fail("phx_dev_denoise_guided");
+      double cover = 0.0;
+      for (size_t p = 0; p < (size_t)W * H; ++p) cover += guides[p * 8 + 3];
+      printf("denoise-guided: %u guide samples, mean coverage %.4f\n", gp.samples, cover / (double)((size_t)W * H));
+      free(guides);
+    } else if (phx_dev_denoise(devs[0], &dn, film, film) != PHX_OK) return fail("phx_dev_denoise");
     for (size_t p = 0; p < (size_t)W * H; ++p) for (int c = 0; c < 3; ++c) after += film[p * xstride + 4 + c];
     printf("denoise: mean m2 %.6g -> %.6g\n", before / (3.0 * W * H), after / (3.0 * W * H));
   }

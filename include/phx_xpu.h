@@ -443,6 +443,62 @@ typedef struct phx_denoise {
   uint32_t reserved[5];        /* must be 0 */
 } phx_denoise;
 
+/* ---- first-hit guide channels: what the camera rays of a frame met, as a film of 8 floats a pixel ------------------------ */
+/* A pass of its own beside the frame (phx_dev_render_guides): camera rays are never stored, the ray of (seed, film pixel, absolute sample
+ * index) is rebuilt from the pixel and jitter tables, so the pass revisits exactly the first hits a frame with the same seed shades.  It
+ * launches none of the frame's kernels and changes no frame.  The film is W x H of the preprocessed scene's camera, the jitter table the one
+ * of the device's phx_options.samples_per_pixel (spp), 1 <= samples = G <= spp.  All arithmetic is fp32 without contraction, in the order
+ * written.  For pixel p and samples s = 0 .. G - 1, in this order:
+ *   ray       (o, d) = the camera ray of key (sampler_seed, p, s), pinhole or lens, as the frame builds it
+ *   hit       the closest hit along it, tmax = FLT_MAX, ties to the lowest primitive: the hit of phx_dev_trace and of the frame
+ *   albedo    a miss, and a hit on an is_emitter material, contribute (1, 1, 1); any other hit the sum over the material's lobes, in lobe
+ *             order and starting at (0, 0, 0), of the weight phx_dev_lobe_weights reports at that hit: weight * texel at the hit's
+ *             interpolated (s, t) = (w * uv0 + u * uv1) + v * uv2, w = (1 - u) - v, and (pre_weight * term) * that for Fresnel and image-mask
+ *             factors, with the shading normal the frame's "normals" channel holds for that sample and the view vector -d; a lobe that is
+ *             not there at the hit adds nothing
+ *   position  for a hit at distance t:  X_c = o_c + t * d_c  (one multiply, one add);  hits += 1
+ *   sums      albedo_sum += albedo (every sample);  X_sum += X and t_sum += t (hits only); per component, in sample order, from 0
+ * and the pixel's 8 floats are
+ *   0-2 albedo    albedo_sum_c * (1.0f / (float)G)
+ *   3   coverage  (float)hits * (1.0f / (float)G)
+ *   4-6 position  X_sum_c / (float)hits, or 0 when hits == 0
+ *   7   distance  t_sum / (float)hits, or 0 when hits == 0
+ * Limits: a mirror's or a glass pane's albedo is its own lobe weight, not what it reflects or shows; emitters and the sky count as white,
+ * so that demodulation leaves them alone; there are no normal maps; the guides of a multi-GPU frame are rendered whole by every rank. */
+typedef struct phx_guides {
+  uint64_t sampler_seed;       /* the frame's phx_frame.sampler_seed */
+  uint32_t samples;            /* G: 1 .. samples_per_pixel of the device */
+  uint32_t on_device;          /* 0: film is host memory, 1: device memory (HBM) */
+  uint32_t reserved[4];        /* must be 0 */
+} phx_guides;
+
+/* The guides of phx_dev_denoise_guided: phx_denoise's rule with the changes below.  binary64 without contraction in the order written, fp32
+ * values widened first, as there.  G_x are the 8 guide floats of pixel x (the layout above) at guides[x * xstride].
+ *   valid     additionally requires the pixel's 8 guide floats to be finite.
+ *   PHX_GUIDE_DEMODULATE   the filter runs on the film divided by the first hit's albedo, and multiplies it back:
+ *             D_c   = max((double)albedo_c, (double)albedo_floor)
+ *             init    C_c = fp32(primary_c / D_c);   V_c = fp32((m2_c * (n / (n - 1))) / (D_c * D_c))
+ *             output  primary_c = fp32(C_c * D_c);   m2_c = fp32(((V_c * D_c) * D_c) * ((n - 1) / n))
+ *             l_x, e_x, S_p and the biweight are those of the demodulated C and V.
+ *   PHX_GUIDE_PLANE        (needs normals_offset != 0) a non-centre tap's weight is w = ((h * w_n) * w_l) * w_x with
+ *             w_x = 1 if coverage_p == 0 and coverage_q == 0;  0 if exactly one of them is 0;  otherwise
+ *             r   = (N_x * dX_x + N_y * dX_y) + N_z * dX_z      N = p's film normal, dX_c = position_q,c - position_p,c
+ *             tol = (sigma_x * plane_scale) * distance_p;   u = fabs(r) / tol;   t = 1 - u * u;   w_x = u < 1 ? t * t : 0
+ *             and w_x = (r == 0 ? 1 : 0) when tol == 0.  plane_scale is the world size of one pixel at unit distance
+ *             (this camera's 1.12 * tan(fov / 2) / film_height, camera.hpp:113), so tol is sigma_x pixels' worth of surface at p's distance: q is kept when it lies on p's
+ *             tangent plane to within that.
+ * flags == 0 is phx_dev_denoise bit for bit, whatever the other fields hold (guides may then be NULL). */
+enum { PHX_GUIDE_DEMODULATE = 1, PHX_GUIDE_PLANE = 2 };
+typedef struct phx_denoise_guides {
+  const float* guides;         /* width x height x xstride floats, in the films' memory space (phx_denoise.on_device); not NULL unless flags == 0 */
+  uint32_t xstride;            /* floats per pixel of the guide film; >= 8 */
+  uint32_t flags;              /* PHX_GUIDE_* */
+  float    albedo_floor;       /* DEMODULATE: finite, > 0 */
+  float    sigma_x;            /* PLANE: finite, > 0 */
+  float    plane_scale;        /* PLANE: finite, > 0 */
+  uint32_t reserved[4];        /* must be 0 */
+} phx_denoise_guides;
+
 /* ---- statistics ------------------------------------------------------------------------ */
 /* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
  * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
@@ -647,6 +703,21 @@ int phx_dev_denoise(phx_device* dev, const phx_denoise* d, const float* film_in,
 /* HIP-event times of the last phx_dev_denoise of this device in milliseconds: ms[0] the pack stage, ms[1 .. 8] the iterations (0 for those
  * not run), ms[9] the unpack stage (with the film copy when film_out != film_in), ms[10] the whole call on the host's clock. */
 int phx_dev_denoise_times(const phx_device* dev, double* ms /* 11 */);
+
+/* The first-hit guide film of the preprocessed scene (phx_guides above states the rule): film receives W x H x 8 floats, row-major.
+ * Synchronous, on the device object's stream.  PHX_ERR_STATE without a preprocessed scene and while a frame is started and not joined;
+ * PHX_ERR_ARG, with the field's name in the message, for samples outside 1 .. samples_per_pixel, on_device above 1, a non-zero reserved
+ * word or a null film.  Its working memory (the film's pixel table, the jitter table and, for a host film, the film itself) is allocated
+ * in the call and freed before it returns: phx_stats.device_bytes and every later frame are what they were. */
+int phx_dev_render_guides(phx_device* dev, const phx_guides* g, float* film /* W * H * 8 fp32 */);
+/* Times of the last phx_dev_render_guides of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the host's clock
+ * (the tables' upload, the allocations and, for a host film, the download included). */
+int phx_dev_guides_times(const phx_device* dev, double* ms /* 2 */);
+/* phx_dev_denoise with guides (phx_denoise_guides above).  g == NULL or g->flags == 0: phx_dev_denoise itself.  Otherwise the same calls'
+ * checks, and PHX_ERR_ARG, with the field's name in the message, for unknown flags, PHX_GUIDE_PLANE without normals_offset, xstride < 8, a
+ * non-finite or non-positive albedo_floor (DEMODULATE) / sigma_x / plane_scale (PLANE), a non-zero reserved word or null guides.  Working
+ * memory: 96 bytes a pixel, 112 under PHX_GUIDE_PLANE, and the guide film's copy for host films.  phx_dev_denoise_times reports its stages. */
+int phx_dev_denoise_guided(phx_device* dev, const phx_denoise* d, const phx_denoise_guides* g, const float* film_in, float* film_out);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

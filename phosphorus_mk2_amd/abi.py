@@ -165,6 +165,23 @@ class Denoise(C.Structure):
     ]
 
 
+GUIDE_DEMODULATE, GUIDE_PLANE = 1, 2  # DenoiseGuides.flags (PHX_GUIDE_*)
+GUIDE_FLOATS = 8  # a pixel of the guide film: albedo rgb, coverage, position xyz, distance
+
+
+class Guides(C.Structure):
+    """phx_guides: the first-hit guide pass (phx_dev_render_guides)"""
+    _fields_ = [("sampler_seed", C.c_uint64), ("samples", C.c_uint32), ("on_device", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class DenoiseGuides(C.Structure):
+    """phx_denoise_guides: the guide film of a guided denoise call and what it is used for (phx_dev_denoise_guided)"""
+    _fields_ = [
+        ("guides", C.c_void_p), ("xstride", C.c_uint32), ("flags", C.c_uint32), ("albedo_floor", C.c_float), ("sigma_x", C.c_float),
+        ("plane_scale", C.c_float), ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("camera_samples", C.c_uint64), ("rays_closest", C.c_uint64), ("rays_shadow", C.c_uint64),
@@ -192,6 +209,7 @@ EXPORTS = [
     "phx_dev_texture_lookup", "phx_dev_environment_lookup", "phx_dev_lobe_weights",
     "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample", "phx_dev_film_moments",
     "phx_dev_set_adaptive", "phx_dev_adaptive_select", "phx_dev_denoise", "phx_dev_denoise_times",
+    "phx_dev_render_guides", "phx_dev_guides_times", "phx_dev_denoise_guided",
 ]
 
 
@@ -228,5 +246,8 @@ def declare(lib):
     lib.phx_dev_adaptive_select.restype = C.c_int
     lib.phx_dev_denoise.argtypes = [vp, C.POINTER(Denoise), vp, vp]; lib.phx_dev_denoise.restype = C.c_int  # the films: host or device addresses
     lib.phx_dev_denoise_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_denoise_times.restype = C.c_int
+    lib.phx_dev_render_guides.argtypes = [vp, C.POINTER(Guides), vp]; lib.phx_dev_render_guides.restype = C.c_int  # the film: a host or device address
+    lib.phx_dev_guides_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_guides_times.restype = C.c_int
+    lib.phx_dev_denoise_guided.argtypes = [vp, C.POINTER(Denoise), C.POINTER(DenoiseGuides), vp, vp]; lib.phx_dev_denoise_guided.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

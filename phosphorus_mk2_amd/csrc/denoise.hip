@@ -7,7 +7,15 @@
 //
 // One thread owns one pixel; the grid is 2-D over the film; no workgroup waits on another.  An edge is a skipped tap: a coordinate is tested
 // before it becomes an address.  All arithmetic is binary64 in the rule's order (the file is compiled without contraction, as every other).
+//
+// Each kernel is a template over GUIDE, the PHX_GUIDE_* flags of phx_denoise_guides.  GUIDE == 0 is the filter above and reads nothing
+// of its last argument; DEMODULATE divides the first hit's albedo out in the pack stage and multiplies it back in the unpack stage (both read the
+// guide film; nothing is kept per pixel); PLANE keeps x = (position, distance) per pixel, marks a valid pixel of coverage 0 with n.w = 2, and
+// multiplies a tap's weight by the biweight of its distance from p's tangent plane.
 #include "kernels.h"
+#include "../../include/phx_xpu.h"  // PHX_GUIDE_*
+
+#include <type_traits>
 
 namespace phx {
 
@@ -27,30 +35,49 @@ __device__ __forceinline__ double samples_of(const DenoiseArgs& A, const float* 
 
 }  // namespace
 
-__global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_pack(DenoiseArgs A, const float* __restrict__ film) {
+template <uint32_t GUIDE>
+__global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_pack(DenoiseArgs A, const float* __restrict__ film, DenoiseGuideArgs G) {
   int x, y; size_t p;
   if (!own_pixel(A, x, y, p)) return;
   const float* px = film + p * A.xstride;
-  const float c0 = px[0], c1 = px[1], c2 = px[2];
+  float c0 = px[0], c1 = px[1], c2 = px[2];
   const float m0 = px[A.m2_offset], m1 = px[A.m2_offset + 1], m2 = px[A.m2_offset + 2];
   float nx = 0.0f, ny = 0.0f, nz = 0.0f;
   if (A.normals_offset) { nx = px[A.normals_offset]; ny = px[A.normals_offset + 1]; nz = px[A.normals_offset + 2]; }
   const double n = samples_of(A, px);
-  const bool valid = isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(m0) && isfinite(m1) && isfinite(m2) && isfinite(nx) && isfinite(ny) && isfinite(nz) &&
-                     m0 >= 0.0f && m1 >= 0.0f && m2 >= 0.0f && isfinite(n) && n >= 2.0;
+  bool valid = isfinite(c0) && isfinite(c1) && isfinite(c2) && isfinite(m0) && isfinite(m1) && isfinite(m2) && isfinite(nx) && isfinite(ny) && isfinite(nz) &&
+               m0 >= 0.0f && m1 >= 0.0f && m2 >= 0.0f && isfinite(n) && n >= 2.0;
+  float g[8] = {};  // GUIDE: the pixel's guide floats (albedo, coverage, position, distance)
+  if constexpr (GUIDE != 0u) {
+    const float* gp = G.guides + p * G.xstride;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { g[k] = gp[k]; valid = valid && isfinite(g[k]); }
+  }
   float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f; double e = 0.0;
   if (valid) {
     const double q = n / (n - 1.0);
-    v0 = (float)((double)m0 * q); v1 = (float)((double)m1 * q); v2 = (float)((double)m2 * q);
+    if constexpr ((GUIDE & PHX_GUIDE_DEMODULATE) != 0u) {
+      const double d0 = fmax((double)g[0], G.albedo_floor), d1 = fmax((double)g[1], G.albedo_floor), d2 = fmax((double)g[2], G.albedo_floor);
+      c0 = (float)((double)c0 / d0); c1 = (float)((double)c1 / d1); c2 = (float)((double)c2 / d2);
+      v0 = (float)(((double)m0 * q) / (d0 * d0)); v1 = (float)(((double)m1 * q) / (d1 * d1)); v2 = (float)(((double)m2 * q) / (d2 * d2));
+    } else {
+      v0 = (float)((double)m0 * q); v1 = (float)((double)m1 * q); v2 = (float)((double)m2 * q);
+    }
     e = deviation(v0, v1, v2);
   }
   A.c[0][p] = make_float4(c0, c1, c2, 0.0f);
   A.v[0][p] = make_float4(v0, v1, v2, 0.0f);
   A.e[0][p] = e;
-  A.n[p] = make_float4(nx, ny, nz, valid ? 1.0f : 0.0f);
+  float flag = valid ? 1.0f : 0.0f;
+  if constexpr ((GUIDE & PHX_GUIDE_PLANE) != 0u) {
+    if (valid && g[3] == 0.0f) flag = 2.0f;  // no camera ray of the pixel hit anything
+    G.x[p] = make_float4(g[4], g[5], g[6], g[7]);
+  }
+  A.n[p] = make_float4(nx, ny, nz, flag);
 }
 
-__global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_iteration(DenoiseArgs A, int from, int step) {
+template <uint32_t GUIDE>
+__global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_iteration(DenoiseArgs A, int from, int step, DenoiseGuideArgs G) {
   int x, y; size_t p;
   if (!own_pixel(A, x, y, p)) return;
   const float4 Np = A.n[p];
@@ -83,6 +110,9 @@ __global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_ite
   const double sig = A.sigma_l * sqrt(sum_gee / sum_g);
 
   const bool p_missed = Np.x == 0.0f && Np.y == 0.0f && Np.z == 0.0f;
+  constexpr bool PLANE = (GUIDE & PHX_GUIDE_PLANE) != 0u;
+  float4 Xp = make_float4(0.0f, 0.0f, 0.0f, 0.0f); double tol = 0.0;  // PLANE: p's position and the plane tolerance at its distance
+  if constexpr (PLANE) { Xp = G.x[p]; tol = G.tol_scale * (double)Xp.w; }
   constexpr double k5[5] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
   double W = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0;
 #pragma unroll
@@ -115,6 +145,21 @@ __global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_ite
           wl = u < 1.0 ? t * t : 0.0;
         }
         w = (h * wn) * wl;
+        if constexpr (PLANE) {
+          double wx;
+          const bool p_open = Np.w == 2.0f, q_open = Nq.w == 2.0f;
+          if (p_open || q_open) wx = p_open && q_open ? 1.0 : 0.0;
+          else {
+            const float4 Xq = G.x[q];
+            const double r = ((double)Np.x * ((double)Xq.x - (double)Xp.x) + (double)Np.y * ((double)Xq.y - (double)Xp.y)) + (double)Np.z * ((double)Xq.z - (double)Xp.z);
+            if (tol == 0.0) wx = r == 0.0 ? 1.0 : 0.0;
+            else {
+              const double u = fabs(r) / tol, t = 1.0 - u * u;
+              wx = u < 1.0 ? t * t : 0.0;
+            }
+          }
+          w = w * wx;
+        }
       }
       W = W + w;
       a0 = a0 + w * ((double)Cq.x - cr); a1 = a1 + w * ((double)Cq.y - cg); a2 = a2 + w * ((double)Cq.z - cb);
@@ -130,7 +175,8 @@ __global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_ite
   A.e[to][p] = deviation(v0, v1, v2);
 }
 
-__global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_unpack(DenoiseArgs A, int from, float* __restrict__ film) {
+template <uint32_t GUIDE>
+__global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_unpack(DenoiseArgs A, int from, float* __restrict__ film, DenoiseGuideArgs G) {
   int x, y; size_t p;
   if (!own_pixel(A, x, y, p)) return;
   if (A.n[p].w == 0.0f) return;  // an invalid pixel keeps its input floats
@@ -138,8 +184,16 @@ __global__ void __launch_bounds__(PHX_DENOISE_BX * PHX_DENOISE_BY) k_denoise_unp
   const double n = samples_of(A, px);
   const double r = (n - 1.0) / n;
   const float4 Cp = A.c[from][p], Vp = A.v[from][p];
+  if constexpr ((GUIDE & PHX_GUIDE_DEMODULATE) != 0u) {
+    const float* gp = G.guides + p * G.xstride;
+    const double d0 = fmax((double)gp[0], G.albedo_floor), d1 = fmax((double)gp[1], G.albedo_floor), d2 = fmax((double)gp[2], G.albedo_floor);
+    px[0] = (float)((double)Cp.x * d0); px[1] = (float)((double)Cp.y * d1); px[2] = (float)((double)Cp.z * d2);
+    px[A.m2_offset] = (float)((((double)Vp.x * d0) * d0) * r); px[A.m2_offset + 1] = (float)((((double)Vp.y * d1) * d1) * r);
+    px[A.m2_offset + 2] = (float)((((double)Vp.z * d2) * d2) * r);
+  } else {
   px[0] = Cp.x; px[1] = Cp.y; px[2] = Cp.z;
   px[A.m2_offset] = (float)((double)Vp.x * r); px[A.m2_offset + 1] = (float)((double)Vp.y * r); px[A.m2_offset + 2] = (float)((double)Vp.z * r);
+  }
 }
 
 // ---- launches ---------------------------------------------------------------------------------------
@@ -149,13 +203,30 @@ const dim3 denoise_block(PHX_DENOISE_BX, PHX_DENOISE_BY);
 }  // namespace
 
 void launch_denoise_pack(hipStream_t stream, const DenoiseArgs& A, const float* film) {
-  hipLaunchKernelGGL(k_denoise_pack, denoise_grid(A), denoise_block, 0, stream, A, film);
+  hipLaunchKernelGGL(k_denoise_pack<0u>, denoise_grid(A), denoise_block, 0, stream, A, film, DenoiseGuideArgs{});
 }
 void launch_denoise_iteration(hipStream_t stream, const DenoiseArgs& A, int from, uint32_t step) {
-  hipLaunchKernelGGL(k_denoise_iteration, denoise_grid(A), denoise_block, 0, stream, A, from, (int)step);
+  hipLaunchKernelGGL(k_denoise_iteration<0u>, denoise_grid(A), denoise_block, 0, stream, A, from, (int)step, DenoiseGuideArgs{});
 }
 void launch_denoise_unpack(hipStream_t stream, const DenoiseArgs& A, int from, float* film) {
-  hipLaunchKernelGGL(k_denoise_unpack, denoise_grid(A), denoise_block, 0, stream, A, from, film);
+  hipLaunchKernelGGL(k_denoise_unpack<0u>, denoise_grid(A), denoise_block, 0, stream, A, from, film, DenoiseGuideArgs{});
+}
+
+// the guided instantiations: G.flags is 1, 2 or 3
+namespace {
+template <typename F> void with_guide_flags(uint32_t flags, F&& f) {
+  if (flags == 1u) f(std::integral_constant<uint32_t, 1u>{}); else if (flags == 2u) f(std::integral_constant<uint32_t, 2u>{}); else f(std::integral_constant<uint32_t, 3u>{});
+}
+}  // namespace
+void launch_denoise_pack_guided(hipStream_t stream, const DenoiseArgs& A, const DenoiseGuideArgs& G, const float* film) {
+  with_guide_flags(G.flags, [&](auto F) { hipLaunchKernelGGL(k_denoise_pack<decltype(F)::value>, denoise_grid(A), denoise_block, 0, stream, A, film, G); });
+}
+void launch_denoise_iteration_guided(hipStream_t stream, const DenoiseArgs& A, const DenoiseGuideArgs& G, int from, uint32_t step) {
+  // DEMODULATE alone filters the demodulated state by the unguided rule
+  with_guide_flags(G.flags, [&](auto F) { hipLaunchKernelGGL(k_denoise_iteration<(decltype(F)::value & PHX_GUIDE_PLANE)>, denoise_grid(A), denoise_block, 0, stream, A, from, (int)step, G); });
+}
+void launch_denoise_unpack_guided(hipStream_t stream, const DenoiseArgs& A, const DenoiseGuideArgs& G, int from, float* film) {
+  with_guide_flags(G.flags, [&](auto F) { hipLaunchKernelGGL(k_denoise_unpack<(decltype(F)::value & PHX_GUIDE_DEMODULATE)>, denoise_grid(A), denoise_block, 0, stream, A, from, film, G); });
 }
 
 }  // namespace phx

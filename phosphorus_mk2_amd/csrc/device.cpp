@@ -13,6 +13,7 @@
 #include "bvh_gpu.h"
 #include "denoise_check.h"
 #include "frame_plan.h"
+#include "guides_check.h"
 #include "kernels.h"
 #include "scene_flatten.h"
 
@@ -141,6 +142,26 @@ void adaptive_args(const phx_adaptive& a, uint32_t n, uint32_t spp, AdaptiveArgs
   A.k = (double)spp / (double)n;
   A.n = (float)n;
 }
+// The film jitter of sample index 0 .. spp - 1, shared by all pixels (run_frame and phx_dev_render_guides read the same table): sampler_t::preprocess
+// (sampling.cpp:98-112) with sample::stratified_2d (math/sampling.hpp:65-77), numbers from the counter sampler.  A cell past spp - 1 (spp is not a
+// square) is dropped, and an index no cell names keeps (0, 0).
+std::vector<float2> jitter_table(uint64_t seed, uint32_t spp) {
+  std::vector<float2> jit(spp, make_float2(0.0f, 0.0f));
+  const uint32_t spd = (uint32_t)std::lroundf(std::sqrt((float)spp));
+  const float step = 1.0f / (float)spd;
+  float dy = 0.0f;
+  for (uint32_t i = 0; i < spd; ++i, dy += step) {
+    float dx = 0.0f;
+    for (uint32_t j = 0; j < spd; ++j, dx += step) {
+      const uint32_t cell = j * spd + i;
+      const uint32_t key = path_key(seed, FILM_JITTER_STREAM, cell);
+      const float a = dx + draw_f32(key, 0) * step;
+      const float b = dy + draw_f32(key, 1) * step;
+      if (cell < spp) jit[cell] = make_float2(a, b);
+    }
+  }
+  return jit;
+}
 static_assert(PathQueues::bytes_per_path(false) == queue_bytes_per_path(false) && PathQueues::bytes_per_path(true) == queue_bytes_per_path(true),
               "what path_budget divides the device's memory by (frame_plan.h: FilmLayout::path_bytes)");
 
@@ -202,6 +223,7 @@ struct phx_device {
   DevBuf<float> w_acc; DevBuf<uint32_t> w_xy, sel_idx[2], sel_blocks;
   PinnedBuf<uint32_t> h_sel;
   phx_adaptive adaptive{}; bool adaptive_on = false;
+  double guides_ms[2] = {};    // phx_dev_guides_times: the last phx_dev_render_guides' kernel and call
   double denoise_ms[11] = {};  // phx_dev_denoise_times: the last phx_dev_denoise's stages (it holds no device memory between calls)
 
   // frame
@@ -594,6 +616,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 6: return sizeof(phx_scene); case 7: return sizeof(phx_tile); case 8: return sizeof(phx_frame);
     case 9: return sizeof(phx_stats); case 10: return sizeof(phx_texture); case 11: return sizeof(phx_adaptive);
     case 13: return sizeof(phx_denoise);  // (12 stays unused: tests/test_adaptive_sampling.py pins it to 0)
+    case 15: return sizeof(phx_guides); case 16: return sizeof(phx_denoise_guides);  // (14 likewise: tests/test_denoise.py)
     default: return 0;
   }
 }
@@ -747,20 +770,25 @@ int phx_dev_film_moments(phx_device* d, uint32_t num_pixels, uint32_t num_sample
 }
 
 // (no stage_hook: the denoiser reads a film and no scene)
-int phx_dev_denoise(phx_device* d, const phx_denoise* q, const float* film_in, float* film_out) {
+int phx_dev_denoise(phx_device* d, const phx_denoise* q, const float* film_in, float* film_out) { return phx_dev_denoise_guided(d, q, nullptr, film_in, film_out); }
+
+// g == nullptr or g->flags == 0: the unguided filter, by the launches it has always had
+int phx_dev_denoise_guided(phx_device* d, const phx_denoise* q, const phx_denoise_guides* g, const float* film_in, float* film_out) {
   return guarded([&]() -> int {
     if (!d) return fail(PHX_ERR_ARG, "denoise: null device");
     if (d->running) return fail(PHX_ERR_STATE, "denoise while a frame is running");
     if (!q) return fail(PHX_ERR_ARG, "denoise: null argument");
     std::string why;
     if (const int rc = denoise_check(*q, film_in, film_out, why)) return fail(rc, why);
+    if (g && !g->flags) g = nullptr;
+    if (g) if (const int rc = denoise_guides_check(*q, *g, why)) return fail(rc, why);
     const auto t0 = Clock::now();
     DeviceScope on(d->hip_device);
     if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
     std::fill(std::begin(d->denoise_ms), std::end(d->denoise_ms), 0.0);
     const size_t npix = (size_t)q->width * q->height, film_bytes = npix * q->xstride * sizeof(float);
     // everything the call holds on the device lives in these and goes with them, on every way out
-    DevBuf<float> staged; DevBuf<float4> c[2], v[2], n; DevBuf<double> e[2];
+    DevBuf<float> staged, gstaged; DevBuf<float4> c[2], v[2], n, gx; DevBuf<double> e[2];
     struct Events {
       std::vector<hipEvent_t> ev;
       ~Events() { for (hipEvent_t x : ev) (void)hipEventDestroy(x); }
@@ -779,20 +807,31 @@ int phx_dev_denoise(phx_device* d, const phx_denoise* q, const float* film_in, f
         if (const int rc = e[k].alloc(npix)) return rc;
       }
       if (const int rc = n.alloc(npix)) return rc;
+      DenoiseGuideArgs G{};
+      if (g) {
+        G.guides = g->guides; G.xstride = g->xstride; G.flags = g->flags;
+        G.albedo_floor = (double)g->albedo_floor; G.tol_scale = (double)g->sigma_x * (double)g->plane_scale;
+        if (!q->on_device) {  // host guides: a device copy, like the film's
+          if (const int rc = gstaged.alloc(npix * g->xstride)) return rc;
+          HIPCHK(hipMemcpy(gstaged.p, g->guides, npix * g->xstride * sizeof(float), hipMemcpyHostToDevice));
+          G.guides = gstaged.p;
+        }
+        if (g->flags & PHX_GUIDE_PLANE) { if (const int rc = gx.alloc(npix)) return rc; G.x = gx.p; }
+      }
       DenoiseArgs A{};
       A.width = q->width; A.height = q->height; A.xstride = q->xstride; A.normals_offset = q->normals_offset; A.m2_offset = q->m2_offset;
       A.samples_offset = q->samples_offset; A.spp = q->spp; A.normal_power_log2 = q->normal_power_log2; A.sigma_l = (double)q->sigma_l;
       for (int k = 0; k < 2; ++k) { A.c[k] = c[k].p; A.v[k] = v[k].p; A.e[k] = e[k].p; }
       A.n = n.p;
       if (const int rc = events.mark(d->stream)) return rc;
-      launch_denoise_pack(d->stream, A, src);
+      if (g) launch_denoise_pack_guided(d->stream, A, G, src); else launch_denoise_pack(d->stream, A, src);
       if (const int rc = events.mark(d->stream)) return rc;
       for (uint32_t i = 0; i < q->iterations; ++i) {
-        launch_denoise_iteration(d->stream, A, (int)(i & 1u), 1u << i);
+        if (g) launch_denoise_iteration_guided(d->stream, A, G, (int)(i & 1u), 1u << i); else launch_denoise_iteration(d->stream, A, (int)(i & 1u), 1u << i);
         if (const int rc = events.mark(d->stream)) return rc;
       }
       if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, film_bytes, hipMemcpyDeviceToDevice, d->stream));
-      launch_denoise_unpack(d->stream, A, (int)(q->iterations & 1u), dst);
+      if (g) launch_denoise_unpack_guided(d->stream, A, G, (int)(q->iterations & 1u), dst); else launch_denoise_unpack(d->stream, A, (int)(q->iterations & 1u), dst);
       if (const int rc = events.mark(d->stream)) return rc;
     } else if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, film_bytes, hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipGetLastError());
@@ -806,6 +845,54 @@ int phx_dev_denoise(phx_device* d, const phx_denoise* q, const float* film_in, f
     d->denoise_ms[10] = ms_between(t0, Clock::now());
     return PHX_OK;
   });
+}
+
+// The first-hit guide film (phx_guides; guides.hip).  Everything the call holds on the device lives in the DevBufs below and goes with them.
+int phx_dev_render_guides(phx_device* d, const phx_guides* g, float* film) {
+  return guarded([&]() -> int {
+    if (!d) return fail(PHX_ERR_ARG, "render_guides: null device");
+    if (!d->preprocessed) return fail(PHX_ERR_STATE, "render_guides before preprocess");
+    if (d->running) return fail(PHX_ERR_STATE, "render_guides while a frame is running");
+    if (!g) return fail(PHX_ERR_ARG, "render_guides: null argument");
+    const uint32_t W = d->scene.width, H = d->scene.height, spp = d->opt.samples_per_pixel;
+    std::string why;
+    if (const int rc = guides_check(*g, W, H, spp, film, why)) return fail(rc, why);
+    const auto t0 = Clock::now();
+    d->guides_ms[0] = d->guides_ms[1] = 0.0;
+    DeviceScope on(d->hip_device);
+    if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+    const size_t npix = (size_t)W * H;
+    std::vector<uint32_t> xy(npix);
+    for (uint32_t y = 0; y < H; ++y) for (uint32_t x = 0; x < W; ++x) xy[(size_t)y * W + x] = x | y << 16;
+    DevBuf<uint32_t> d_xy; DevBuf<float2> d_jit; DevBuf<float> staged;
+    if (const int rc = d_xy.upload(xy)) return rc;
+    if (const int rc = d_jit.upload(jitter_table(g->sampler_seed, spp))) return rc;
+    float* dst = film;
+    if (!g->on_device) { if (const int rc = staged.alloc(npix * 8)) return rc; dst = staged.p; }
+    PassBuffers B{};
+    B.pix_xy = d_xy.p; B.jitter = d_jit.p; B.num_pixels = (uint32_t)npix; B.num_samples = g->samples; B.seed = g->sampler_seed;
+    struct Events {
+      hipEvent_t ev[2] = {nullptr, nullptr};
+      ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    } events;
+    for (hipEvent_t& x : events.ev) HIPCHK(hipEventCreate(&x));
+    HIPCHK(hipEventRecord(events.ev[0], d->stream));
+    launch_guides(d->stream, d->scene, B, dst);
+    HIPCHK(hipEventRecord(events.ev[1], d->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (!g->on_device) HIPCHK(hipMemcpy(film, staged.p, npix * 8 * sizeof(float), hipMemcpyDeviceToHost));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, events.ev[0], events.ev[1]));
+    d->guides_ms[0] = ms; d->guides_ms[1] = ms_between(t0, Clock::now());
+    return PHX_OK;
+  });
+}
+
+int phx_dev_guides_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "guides_times: null argument");
+  ms[0] = d->guides_ms[0]; ms[1] = d->guides_ms[1];
+  return PHX_OK;
 }
 
 int phx_dev_denoise_times(const phx_device* d, double* ms) {
@@ -989,22 +1076,7 @@ int phx_device::run_frame() {
   // per-spp film jitter shared by all pixels: sampler_t::preprocess (sampling.cpp:98-112) with
   // sample::stratified_2d (math/sampling.hpp:65-77), numbers from the counter sampler
   const uint32_t spp = opt.samples_per_pixel;
-  std::vector<float2> jit(spp, make_float2(0.0f, 0.0f));
-  {
-    const uint32_t spd = (uint32_t)std::lroundf(std::sqrt((float)spp));
-    const float step = 1.0f / (float)spd;
-    float dy = 0.0f;
-    for (uint32_t i = 0; i < spd; ++i, dy += step) {
-      float dx = 0.0f;
-      for (uint32_t j = 0; j < spd; ++j, dx += step) {
-        const uint32_t cell = j * spd + i;
-        const uint32_t key = path_key(frame.sampler_seed, FILM_JITTER_STREAM, cell);
-        const float a = dx + draw_f32(key, 0) * step;
-        const float b = dy + draw_f32(key, 1) * step;
-        if (cell < spp) jit[cell] = make_float2(a, b);
-      }
-    }
-  }
+  const std::vector<float2> jit = jitter_table(frame.sampler_seed, spp);
   if (jitter_seed != frame.sampler_seed || jitter_spp != spp || !jitter.p) {  // a frame loop presents the same seed again and again
     if ((rc = jitter.upload(jit))) return rc;
     jitter_seed = frame.sampler_seed; jitter_spp = spp;

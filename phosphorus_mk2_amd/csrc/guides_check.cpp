@@ -1,0 +1,47 @@
+// guides_check.cpp — see guides_check.h.
+#include "guides_check.h"
+
+#include <cmath>
+#include <cstdint>
+
+namespace phx {
+
+namespace {
+bool positive(float v) { return std::isfinite(v) && v > 0.0f; }
+
+const char* guides_invalid(const phx_guides& g, uint32_t width, uint32_t height, uint32_t spp, const float* film) {
+  if (g.samples < 1u || g.samples > spp) return "samples";
+  if ((uint64_t)width * height * g.samples >= 0x7fffffffull) return "samples";  // path = pixel * samples + sample is a 32-bit word
+  if (g.on_device > 1u) return "on_device";
+  for (uint32_t w : g.reserved) if (w) return "reserved";
+  if (!film) return "film";
+  return nullptr;
+}
+const char* denoise_guides_invalid(const phx_denoise& d, const phx_denoise_guides& g) {
+  if (g.flags & ~(uint32_t)(PHX_GUIDE_DEMODULATE | PHX_GUIDE_PLANE)) return "flags";
+  if ((g.flags & PHX_GUIDE_PLANE) && !d.normals_offset) return "normals_offset";
+  if (g.xstride < 8u) return "xstride";
+  if ((g.flags & PHX_GUIDE_DEMODULATE) && !positive(g.albedo_floor)) return "albedo_floor";
+  if ((g.flags & PHX_GUIDE_PLANE) && !positive(g.sigma_x)) return "sigma_x";
+  if ((g.flags & PHX_GUIDE_PLANE) && !positive(g.plane_scale)) return "plane_scale";
+  for (uint32_t w : g.reserved) if (w) return "reserved";
+  if (!g.guides) return "guides";
+  return nullptr;
+}
+}  // namespace
+
+int guides_check(const phx_guides& g, uint32_t width, uint32_t height, uint32_t spp, const float* film, std::string& err) {
+  const char* field = guides_invalid(g, width, height, spp, film);
+  if (!field) return PHX_OK;
+  err = std::string("render_guides: ") + field + " is outside its range (phx_guides)";
+  return PHX_ERR_ARG;
+}
+
+int denoise_guides_check(const phx_denoise& d, const phx_denoise_guides& g, std::string& err) {
+  const char* field = denoise_guides_invalid(d, g);
+  if (!field) return PHX_OK;
+  err = std::string("denoise_guided: ") + field + " is outside its range (phx_denoise_guides)";
+  return PHX_ERR_ARG;
+}
+
+}  // namespace phx

@@ -8,6 +8,7 @@
 //   shade_general.hip  k_shade_g and its append ring; launch_shade (which reaches k_shade through shade_launch.h)
 //   film_hooks.hip     k_begin_pass, k_film, k_film_moments, k_scatter_film; k_adaptive_* (the selection of adaptive sampling); the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
 //   denoise.hip        k_denoise_pack, k_denoise_iteration, k_denoise_unpack: the film denoiser, a post-process no frame launches
+//   guides.hip         k_guides: the first-hit guide film (albedo, coverage, position, distance), a pass of its own no frame launches
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
 //
@@ -216,6 +217,23 @@ void launch_denoise_pack(hipStream_t stream, const DenoiseArgs& A, const float* 
 void launch_denoise_iteration(hipStream_t stream, const DenoiseArgs& A, int from, uint32_t step);
 // state `from` -> "primary" and "m2" of the valid pixels of `film`, which holds the input film's floats
 void launch_denoise_unpack(hipStream_t stream, const DenoiseArgs& A, int from, float* film);
+// The guided filter (phx_denoise_guides in phx_xpu.h): the same three stages, instantiated with the guides.  flags = PHX_GUIDE_* (never
+// 0 here: the launches above serve that).  DEMODULATE keeps nothing per pixel (the pack and unpack stages read the albedo from the guide film);
+// PLANE keeps x = (position.xyz, distance), constant, and n.w = 2 instead of 1 for a valid pixel of coverage 0: 112 bytes a pixel.
+struct DenoiseGuideArgs {
+  const float* guides; uint32_t xstride, flags;
+  double albedo_floor, tol_scale /* sigma_x * plane_scale */;
+  float4* x;
+};
+void launch_denoise_pack_guided(hipStream_t stream, const DenoiseArgs& A, const DenoiseGuideArgs& G, const float* film);
+void launch_denoise_iteration_guided(hipStream_t stream, const DenoiseArgs& A, const DenoiseGuideArgs& G, int from, uint32_t step);
+void launch_denoise_unpack_guided(hipStream_t stream, const DenoiseArgs& A, const DenoiseGuideArgs& G, int from, float* film);
+
+// The first-hit guide pass (phx_guides in phx_xpu.h; guides.hip): one launch, one thread per film pixel, 8 floats a pixel into `film`.
+// pb carries what camera_ray reads and nothing else: pix_xy (row-major over the film), jitter, num_samples = G, seed.
+void launch_guides(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, float* film);
+// its instantiations, for init_kernels_on_current_device (the per-lane traversal stack is dynamic LDS): -> how many were written to out[0 .. 3]
+uint32_t guides_kernels(const void** out);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf

@@ -661,6 +661,8 @@ void for_each_trace_kernel(F&& f) {
   };
   both(std::false_type{}); both(std::true_type{});
   f(reinterpret_cast<const void*>(&k_trace_rays<true>)); f(reinterpret_cast<const void*>(&k_trace_rays<false>));
+  const void* guides[4];  // guides.hip: k_guides keeps k_trace_rays' per-lane stack
+  for (uint32_t k = 0, n = guides_kernels(guides); k < n; ++k) f(guides[k]);
 }
 }  // namespace
 

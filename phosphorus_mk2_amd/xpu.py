@@ -15,6 +15,7 @@ The compute path is libphx_hip.so (hand-written HIP for gfx950).  There is no CP
 library is missing or no MI355X is visible, construction raises.
 """
 import ctypes as C
+import math
 import os
 import threading
 
@@ -340,22 +341,72 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_set_adaptive(self._h, C.byref(a)), "phx_dev_set_adaptive")
         self._adaptive = True
 
-    def denoise(self, data, spp, primary_components=4, normals=False, adaptive=False, iterations=5, sigma_l=4.0, normal_power_log2=7, device_ptr=None):
+    def render_guides(self, seed, samples, device_ptr=None):
+        """The first-hit guide film of the preprocessed scene (phx_dev_render_guides; include/phx_xpu.h states the rule): per pixel
+        albedo rgb, coverage, position xyz, distance over the first `samples` camera samples of a frame with sampler seed `seed` (1 <= samples <=
+        the device's samples_per_pixel) -> (H, W, 8) f32.  device_ptr: the address of a device-resident W * H * 8 fp32 film to fill instead;
+        the call then returns None."""
+        g = abi.Guides(sampler_seed=int(seed), samples=int(samples), on_device=0 if device_ptr is None else 1)
+        if device_ptr is not None:
+            _check(self._lib, self._lib.phx_dev_render_guides(self._h, C.byref(g), device_ptr), "phx_dev_render_guides")
+            return None
+        if self._scene is None:
+            _check(self._lib, self._lib.phx_dev_render_guides(self._h, C.byref(g), None), "phx_dev_render_guides")  # the device says why: no scene
+        H, W = self._scene.camera.height, self._scene.camera.width
+        out = np.zeros((H, W, abi.GUIDE_FLOATS), np.float32)
+        _check(self._lib, self._lib.phx_dev_render_guides(self._h, C.byref(g), out.ctypes.data), "phx_dev_render_guides")
+        return out
+
+    def guides_times(self):
+        """milliseconds of the last render_guides(): dict of kernel (HIP events) and call (host clock)"""
+        ms = (C.c_double * 2)()
+        _check(self._lib, self._lib.phx_dev_guides_times(self._h, ms), "phx_dev_guides_times")
+        return {"kernel": ms[0], "call": ms[1]}
+
+    def denoise(self, data, spp, primary_components=4, normals=False, adaptive=False, iterations=5, sigma_l=4.0, normal_power_log2=7, device_ptr=None,
+                guides=None, demodulate=True, plane=False, albedo_floor=0.01, sigma_x=1.0, plane_scale=None, guides_ptr=None):
         """The film denoiser (phx_dev_denoise; include/phx_xpu.h states the rule): an edge-avoiding a-trous filter of a finished film
         whose yardstick is the film's own error estimate, so the film must have been rendered with moments=True.  data (H, W, xstride) f32 as
         render() returns it -> a new array of the same shape: "primary" filtered, "m2" the filtered value's variance estimate (read it with
         film_variance as before), every other float untouched.  primary_components, normals and adaptive say how the pixel is laid out, as for
         Film.  device_ptr: the address of a device-resident film of that layout, denoised IN PLACE; `data` then is only its shape (H, W,
-        xstride), and the call returns None.  Needs no scene; call it after join(), and after dist.reduce_film on several GPUs."""
+        xstride), and the call returns None.  Needs no scene; call it after join(), and after dist.reduce_film on several GPUs.
+        guides: a guide film (H, W, >= 8) f32 as render_guides returns it (guides_ptr: its device address, with device_ptr, `guides` then its
+        shape) turns the guided filter on (phx_dev_denoise_guided): demodulate divides the first hit's albedo (floored at
+        albedo_floor) out before filtering and multiplies it back; plane (needs normals) also rejects taps farther than sigma_x pixels'
+        worth of surface from the pixel's tangent plane, plane_scale being the world size of a pixel at unit distance (guide_plane_scale;
+        default: that of the last preprocessed scene's camera)."""
         shape = tuple(data) if device_ptr is not None and not hasattr(data, "shape") else data.shape
         q = denoise_settings(shape, spp, primary_components, normals, adaptive, iterations, sigma_l, normal_power_log2)
+        if guides is None and guides_ptr is None:
+            gref, keep = None, None
+        else:
+            gshape = tuple(guides) if guides_ptr is not None and not hasattr(guides, "shape") else guides.shape
+            if len(gshape) != 3 or tuple(gshape[:2]) != tuple(shape[:2]):
+                raise ValueError(f"denoise: the guide film must be (height, width, >= 8) over the film's pixels, not {tuple(gshape)}")
+            if plane and plane_scale is None:
+                if self._scene is None:
+                    raise ValueError("denoise: plane=True needs plane_scale (guide_plane_scale(camera)) on a device without a preprocessed scene")
+                plane_scale = guide_plane_scale(self._scene.camera)
+            keep = None if guides_ptr is not None else np.ascontiguousarray(guides, np.float32)
+            g = abi.DenoiseGuides(guides=guides_ptr if guides_ptr is not None else keep.ctypes.data, xstride=int(gshape[2]),
+                                  flags=(abi.GUIDE_DEMODULATE if demodulate else 0) | (abi.GUIDE_PLANE if plane else 0),
+                                  albedo_floor=float(albedo_floor), sigma_x=float(sigma_x), plane_scale=float(plane_scale if plane_scale is not None else 0.0))
+            gref = C.byref(g)
+        call = (lambda a, b: self._lib.phx_dev_denoise(self._h, C.byref(q), a, b)) if gref is None else \
+               (lambda a, b: self._lib.phx_dev_denoise_guided(self._h, C.byref(q), gref, a, b))
+        what = "phx_dev_denoise" if gref is None else "phx_dev_denoise_guided"
         if device_ptr is not None:
+            if gref is not None and guides_ptr is None:
+                raise ValueError("denoise: a device-resident film needs device-resident guides (guides_ptr)")
             q.on_device = 1
-            _check(self._lib, self._lib.phx_dev_denoise(self._h, C.byref(q), device_ptr, device_ptr), "phx_dev_denoise")
+            _check(self._lib, call(device_ptr, device_ptr), what)
             return None
+        if guides_ptr is not None:
+            raise ValueError("denoise: device-resident guides (guides_ptr) need a device-resident film (device_ptr)")
         src = np.ascontiguousarray(data, np.float32)
         out = np.empty_like(src)
-        _check(self._lib, self._lib.phx_dev_denoise(self._h, C.byref(q), src.ctypes.data, out.ctypes.data), "phx_dev_denoise")
+        _check(self._lib, call(src.ctypes.data, out.ctypes.data), what)
         return out
 
     def denoise_times(self):
@@ -537,6 +588,12 @@ def film_variance(data, spp, primary_components=4, normals=False, adaptive=False
     return m2 * (spp / (spp - 1.0))
 
 
+def guide_plane_scale(camera):
+    """phx_denoise_guides.plane_scale of a camera (CameraDesc): the world size of one film pixel at unit distance.  The film's height at unit
+    distance is the camera kernel's zoom, 1.12 * tan(fov / 2) (camera.hpp:113)."""
+    return 1.12 * math.tan(0.5 * float(camera.fov)) / float(camera.height)
+
+
 def denoise_settings(shape, spp, primary_components=4, normals=False, adaptive=False, iterations=5, sigma_l=4.0, normal_power_log2=7):
     """abi.Denoise for a film of `shape` (H, W, xstride) with the channels derived as Film derives them: "normals" behind "primary", "m2"
     behind them, "samples" behind "m2".  ValueError for a film without the channel m2 (render it with moments=True)."""
@@ -576,7 +633,8 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
     adaptive: a dict of HipDevice.set_adaptive's arguments (threshold=..., floor=, min_samples=, step=) turns adaptive sampling on; the film then
     needs moments=True and carries the channel "samples".
     denoise: a dict of HipDevice.denoise's settings (iterations=, sigma_l=, normal_power_log2=; {} for the defaults) filters the film that is
-    returned; it needs moments=True."""
+    returned; it needs moments=True.  Its entry guides=dict(samples=4, demodulate=True, plane=False, albedo_floor=, sigma_x=) renders the
+    first-hit guide film with the frame's seed (HipDevice.render_guides) and runs the guided filter; plane=True needs normals=True."""
     if denoise is not None and not moments:
         raise ValueError("denoise needs moments=True: the filter's yardstick is the film's m2 channel")
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
@@ -603,6 +661,11 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
         dev.start(scene_desc, FrameState(seed, tiles, film, native_sink=native_sink))
         dev.join()
         if denoise is not None:
+            denoise = dict(denoise)
+            gset = denoise.pop("guides", None)
+            if gset is not None:
+                gset = dict(gset)
+                denoise.update(guides=dev.render_guides(seed, min(int(gset.pop("samples", 4)), spp)), **gset)
             return dev.denoise(film.data, spp, 4, normals, adaptive is not None, **denoise), dev.stats()
         return film.data, dev.stats()
     finally:
