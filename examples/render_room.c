@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -20,6 +20,9 @@
  * and the host prints the mean of the m2 channel before and after.  Without the keyword nothing of this runs.
  * denoise-guided: the same, guided by the first hit's albedo: the host renders the guide film of the frame's seed (phx_dev_render_guides, 4 samples a
  * pixel) and hands it to phx_dev_denoise_guided with PHX_GUIDE_DEMODULATE (the film has no normals channel, which PHX_GUIDE_PLANE would need).
+ * progressive K: K frames of 8 samples at seeds 7, 8, ... are pooled into one accumulator film (phx_dev_film_accumulate: primary rgba, m2 rgb, samples),
+ * each frame carrying the error estimate; after every frame the host prints the call's summary (the samples pooled so far and the pixels whose
+ * standard error is at most 0.05 * (|value| + 0.01)).  The accumulator is what the later steps (denoise) see and what is written.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -79,13 +82,18 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0, adaptive = 0, denoise = 0;
+  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0;
   phx_adaptive ad;
   memset(&ad, 0, sizeof(ad));
   for (int i = 2; i < argc; ++i)
     if (strcmp(argv[i], "adaptive") == 0 && i + 1 < argc) {  /* the keyword and its number */
       adaptive = 1;
       ad.threshold = (float)atof(argv[i + 1]); ad.floor = 0.0f; ad.min_samples = 4; ad.step = 2;
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else if (strcmp(argv[i], "progressive") == 0 && i + 1 < argc) {
+      progressive = atoi(argv[i + 1]);
+      if (progressive < 1 || progressive > 1024) progressive = 1;
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else if (strcmp(argv[i], "denoise") == 0 || strcmp(argv[i], "denoise-guided") == 0) {
@@ -135,8 +143,9 @@ int main(int argc, char** argv) {
     if (adaptive && phx_dev_set_adaptive(devs[i], &ad) != PHX_OK) return fail("phx_dev_set_adaptive"); /* the setting is the device's, not the frame's */
   }
 
-  if (adaptive || denoise) error_estimate = 1; /* the stopping rule and the denoiser read the estimate: such a frame must carry it */
-  const size_t xstride = 4 + (error_estimate ? 3 : 0) + (adaptive ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */
+  if (adaptive || denoise || progressive) error_estimate = 1; /* the stopping rule, the denoiser and the pooling read the estimate: such a frame must carry it */
+  int has_samples = adaptive; /* the film at hand carries the channel "samples" at float 7 */
+  size_t xstride = 4 + (error_estimate ? 3 : 0) + (adaptive ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */
   float* film = (float*)calloc((size_t)W * H * xstride, sizeof(float));
   phx_tiles* tiles = phx_tiles_make(W, H, 32, 0, 1); /* ONE job::tiles_t for all devices */
   phx_frame frame;
@@ -179,10 +188,37 @@ int main(int argc, char** argv) {
     printf("adaptive: mean samples per pixel %.4f of %u (camera_samples %llu)\n", taken / (double)((size_t)W * H), opt.samples_per_pixel,
            (unsigned long long)st.camera_samples);
   }
+  if (progressive) { /* after the join; with several ranks: after the film reduce.  Any device serves: the call reads two films, no scene */
+    const size_t xa = 8; /* primary rgba, m2 rgb, samples: an adaptive film's layout */
+    float* acc = (float*)calloc((size_t)W * H * xa, sizeof(float));
+    if (!acc) return 1;
+    phx_accumulate pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.width = W; pa.height = H; pa.xstride_a = (uint32_t)xa; pa.m2_offset_a = 4; pa.samples_offset_a = 7;
+    pa.xstride_b = (uint32_t)xstride; pa.m2_offset_b = 4; pa.samples_offset_b = adaptive ? 7 : 0; pa.spp_b = opt.samples_per_pixel;
+    pa.tau = 0.05f; pa.floor = 0.01f;
+    for (int k = 0; k < progressive; ++k) {
+      if (k > 0) { /* the next frame: the same film and queue, a NEW seed (the same seed would be the same samples again) */
+        memset(film, 0, (size_t)W * H * xstride * sizeof(float));
+        phx_tiles_reset(tiles);
+        frame.sampler_seed = 7 + (uint64_t)k;
+        for (int i = 0; i < num_devices; ++i)
+          if (phx_dev_start(devs[i], &frame) != PHX_OK) return fail("phx_dev_start");
+        for (int i = 0; i < num_devices; ++i)
+          if (phx_dev_join(devs[i]) != PHX_OK) return fail("phx_dev_join");
+      }
+      phx_accumulate_summary ps;
+      if (phx_dev_film_accumulate(devs[0], &pa, acc, film, &ps) != PHX_OK) return fail("phx_dev_film_accumulate");
+      printf("progressive: frame %d seed %llu samples %llu converged %llu of %llu invalid %llu\n", k + 1, (unsigned long long)frame.sampler_seed,
+             (unsigned long long)ps.samples, (unsigned long long)ps.converged, (unsigned long long)ps.pixels, (unsigned long long)ps.invalid);
+    }
+    free(film);
+    film = acc; xstride = xa; has_samples = 1;
+  }
   if (denoise) { /* after the join; with several ranks: after the film reduce.  Any device serves: the call reads the film, not the scene */
     phx_denoise dn;
     memset(&dn, 0, sizeof(dn));
-    dn.width = W; dn.height = H; dn.xstride = (uint32_t)xstride; dn.m2_offset = 4; dn.samples_offset = adaptive ? 7 : 0;
+    dn.width = W; dn.height = H; dn.xstride = (uint32_t)xstride; dn.m2_offset = 4; dn.samples_offset = has_samples ? 7 : 0;
     dn.spp = opt.samples_per_pixel; dn.iterations = 5; dn.sigma_l = 4.0f; dn.normal_power_log2 = 7;
     double before = 0.0, after = 0.0;
     for (size_t p = 0; p < (size_t)W * H; ++p) for (int c = 0; c < 3; ++c) before += film[p * xstride + 4 + c];

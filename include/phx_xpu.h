@@ -499,6 +499,65 @@ typedef struct phx_denoise_guides {
   uint32_t reserved[4];        /* must be 0 */
 } phx_denoise_guides;
 
+/* ---- film accumulation across frames: pooling finished films of different seeds into one ----------------------------------- */
+/* A pass of its own beside the frame (phx_dev_film_accumulate): it reads a finished film and the accumulator, launches none of the frame's
+ * kernels and changes no frame.  `acc` is in and out: a film with the channels "primary", optionally "normals", "m2" and ALWAYS "samples",
+ * the layout of an adaptive film, so that phx_dev_denoise and the variance identity below read it as it is.  `frame_film` is the finished
+ * film of ONE frame with "m2", with or without "samples" (samples_offset_b == 0: every pixel took spp_b samples).  The two films have their
+ * own strides and offsets (the fields ending in _a are acc's, in _b the frame film's) and live in the same memory space.
+ * Per pixel and colour, in binary64, without contraction, in the order written, fp32 inputs widened first:
+ *     n_a = (double)samples_a        n_b = samples_offset_b ? (double)samples_b : (double)spp_b
+ *     n   = n_a + n_b
+ *   a count (n_a or n_b) that is NaN, infinite or negative makes that pixel's primary rgb, m2 and samples NaN, and no other pixel's; its
+ *   normals stay acc's.  This is tested first.  Otherwise
+ *   n_b == 0:  the pixel of acc is not touched                  (a rank's unowned pixel, an empty frame)
+ *   n_a == 0:  primary rgb, m2 := the frame's floats bit for bit; samples := fp32(n_b)      (accumulating into a zeroed film is the copy)
+ *   otherwise
+ *     Q_a = (m2_a * n_a) * n_a       Q_b = (m2_b * n_b) * n_b   centred sums of squares of the unit-scale samples: m2 = Q / n^2 for uniform
+ *                                                               and for rescaled adaptive pixels alike (phx_adaptive, "variance")
+ *     d   = V_b - V_a                                           V = the pixel's "primary"
+ *     V   = fp32(V_a + (d * n_b) / n)
+ *     Q   = (Q_a + Q_b) + ((d * d) * (n_a * n_b)) / n           Chan's rule: the term in d is what "add the m2s" forgets
+ *     m2  = fp32((Q / n) / n)
+ *     samples = fp32(n)                                         exact up to 2^24 samples a pixel; beyond, the count is rounded: a stated limit
+ *   normals (when both films have them, and the pixel is touched: the two last cases): the frame's three floats if any of them != 0, else
+ *             acc's: "the last sample with a hit wins", as k_film has it.  A fourth component of primary stays acc's, as does every float
+ *             of acc's pixel outside the four channels.
+ *   Non-finite colours propagate through the arithmetic above into that pixel alone.
+ * After the call the unbiased variance of any pixel's value is m2 * n / (n - 1) with its own "samples": the identity the denoiser and
+ * phx_adaptive already rely on.
+ * The caller's part, which the call cannot check: the frames must come from different sampler_seeds (path keys and the jitter table both
+ * depend on the seed: the same seed twice is the same samples twice); the frames must share paths_per_sample and the scene; the pooled
+ * estimate treats all n samples as one sample set; a multi-GPU film must be reduced before it is accumulated (a rank's own film holds
+ * zeros in the pixels it does not own).
+ * summary (optional) is counted in the same launch from the floats acc's pixel holds AFTER the call: V_c its primary, m2_c, and
+ * n = (double)samples.  The counters are integers, so the result is exact and independent of the order of the reduction:
+ *     pixels     width * height
+ *     invalid    pixels with a non-finite primary rgb, m2 or n, an m2_c < 0 or n < 2
+ *     converged  valid pixels that meet the criterion of phx_adaptive at full exposure: per colour
+ *                    L = m2_c * (n / (n - 1));   b = tau * (fabs(V_c) + floor);   ok_c = L <= b * b
+ *                converged = ok_r && ok_g && ok_b        (tau = 0 is allowed: it counts the pixels with m2 == 0)
+ *     samples    the sum over the valid pixels of (uint64_t)min(n, 2^53), truncated, modulo 2^64 */
+typedef struct phx_accumulate {
+  uint32_t width, height;      /* 1 .. 65536 each */
+  uint32_t xstride_a;          /* floats per pixel of acc; 7 .. 24 */
+  uint32_t normals_offset_a;   /* 0 = acc has no normals; else >= 3, normals_offset_a + 3 <= xstride_a */
+  uint32_t m2_offset_a;        /* required: >= 3, m2_offset_a + 3 <= xstride_a */
+  uint32_t samples_offset_a;   /* required: >= 3, < xstride_a */
+  uint32_t xstride_b;          /* floats per pixel of frame_film; 6 .. 24 */
+  uint32_t normals_offset_b;   /* 0 = the frame film has no normals; else as for acc */
+  uint32_t m2_offset_b;        /* required, as for acc */
+  uint32_t samples_offset_b;   /* 0 = none: every pixel took spp_b samples; else >= 3, < xstride_b */
+  uint32_t spp_b;              /* >= 1 when samples_offset_b == 0; not read otherwise */
+  uint32_t on_device;          /* 0: both films are host memory, 1: both are device memory (HBM) */
+  float    tau;                /* the summary's threshold; finite, >= 0 */
+  float    floor;              /* the summary's floor in film units; finite, >= 0 */
+  uint32_t reserved[2];        /* must be 0 */
+} phx_accumulate;
+typedef struct phx_accumulate_summary {
+  uint64_t pixels, invalid, converged, samples;
+} phx_accumulate_summary;
+
 /* ---- statistics ------------------------------------------------------------------------ */
 /* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
  * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
@@ -718,6 +777,18 @@ int phx_dev_guides_times(const phx_device* dev, double* ms /* 2 */);
  * non-finite or non-positive albedo_floor (DEMODULATE) / sigma_x / plane_scale (PLANE), a non-zero reserved word or null guides.  Working
  * memory: 96 bytes a pixel, 112 under PHX_GUIDE_PLANE, and the guide film's copy for host films.  phx_dev_denoise_times reports its stages. */
 int phx_dev_denoise_guided(phx_device* dev, const phx_denoise* d, const phx_denoise_guides* g, const float* film_in, float* film_out);
+
+/* Film accumulation (phx_accumulate above states the rule): frame_film is pooled into acc, width x height pixels each, row-major, of
+ * xstride_a and xstride_b floats; summary may be NULL.  Synchronous, one kernel launch.  It needs a device but no scene.  Call it after
+ * phx_dev_join, and on several GPUs after the films are reduced.  PHX_ERR_STATE while a frame is started and not joined; PHX_ERR_ARG, with
+ * the field's name in the message, for a value outside the ranges stated at the struct, channels that overlap "primary" (floats 0 .. 2) or
+ * each other, samples_offset_a == 0, spp_b == 0 without a samples channel, a non-zero reserved word, a null pointer, or acc overlapping
+ * frame_film: acc is then untouched.  Its working memory (the counters and, for host films, the two films' copies) is allocated in the
+ * call and freed before it returns (PHX_ERR_OOM if it cannot be had): phx_stats.device_bytes and every later frame are what they were. */
+int phx_dev_film_accumulate(phx_device* dev, const phx_accumulate* a, float* acc, const float* frame_film, phx_accumulate_summary* summary /* may be NULL */);
+/* Times of the last phx_dev_film_accumulate of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the
+ * host's clock (the allocations and, for host films, the uploads and the download included). */
+int phx_dev_accumulate_times(const phx_device* dev, double* ms /* 2 */);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -182,6 +182,21 @@ class DenoiseGuides(C.Structure):
     ]
 
 
+class Accumulate(C.Structure):
+    """phx_accumulate: the two films' layouts and the summary's criterion (phx_dev_film_accumulate); _a is the accumulator, _b the frame film"""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("xstride_a", C.c_uint32), ("normals_offset_a", C.c_uint32), ("m2_offset_a", C.c_uint32), ("samples_offset_a", C.c_uint32),
+        ("xstride_b", C.c_uint32), ("normals_offset_b", C.c_uint32), ("m2_offset_b", C.c_uint32), ("samples_offset_b", C.c_uint32),
+        ("spp_b", C.c_uint32), ("on_device", C.c_uint32), ("tau", C.c_float), ("floor", C.c_float), ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class AccumulateSummary(C.Structure):
+    """phx_accumulate_summary: the counters of a phx_dev_film_accumulate call"""
+    _fields_ = [("pixels", C.c_uint64), ("invalid", C.c_uint64), ("converged", C.c_uint64), ("samples", C.c_uint64)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("camera_samples", C.c_uint64), ("rays_closest", C.c_uint64), ("rays_shadow", C.c_uint64),
@@ -210,6 +225,7 @@ EXPORTS = [
     "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample", "phx_dev_film_moments",
     "phx_dev_set_adaptive", "phx_dev_adaptive_select", "phx_dev_denoise", "phx_dev_denoise_times",
     "phx_dev_render_guides", "phx_dev_guides_times", "phx_dev_denoise_guided",
+    "phx_dev_film_accumulate", "phx_dev_accumulate_times",
 ]
 
 
@@ -249,5 +265,7 @@ def declare(lib):
     lib.phx_dev_render_guides.argtypes = [vp, C.POINTER(Guides), vp]; lib.phx_dev_render_guides.restype = C.c_int  # the film: a host or device address
     lib.phx_dev_guides_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_guides_times.restype = C.c_int
     lib.phx_dev_denoise_guided.argtypes = [vp, C.POINTER(Denoise), C.POINTER(DenoiseGuides), vp, vp]; lib.phx_dev_denoise_guided.restype = C.c_int
+    lib.phx_dev_film_accumulate.argtypes = [vp, C.POINTER(Accumulate), vp, vp, C.POINTER(AccumulateSummary)]; lib.phx_dev_film_accumulate.restype = C.c_int
+    lib.phx_dev_accumulate_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_accumulate_times.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

@@ -6,9 +6,10 @@
 // trace.hip, shade_lambert.hip, shade_general.hip, film_hooks.hip — and hands finished tiles to the film sink (cpu.cpp:201), join() waits for it.
 // What needs no device lives beside this file: scene_flatten.cpp is the host-only half of preprocess, frame_plan.cpp that of the frame driver
 // (the film's pixel layout, the pixel cap, the batch cutter, the pass schedule), denoise_check.cpp the argument check of the film denoiser
-// (denoise.hip, a post-process no frame launches); here are the allocations, the launches and the waits.
+// (denoise.hip, a post-process no frame launches), accumulate_check.cpp that of film accumulation (accumulate.hip, likewise); here are the allocations, the launches and the waits.
 // There is no CPU rendering path in this library: without a gfx950 device every entry point fails.
 #include "../../include/phx_xpu.h"
+#include "accumulate_check.h"
 #include "bvh_build.h"
 #include "bvh_gpu.h"
 #include "denoise_check.h"
@@ -224,6 +225,7 @@ struct phx_device {
   PinnedBuf<uint32_t> h_sel;
   phx_adaptive adaptive{}; bool adaptive_on = false;
   double guides_ms[2] = {};    // phx_dev_guides_times: the last phx_dev_render_guides' kernel and call
+  double accumulate_ms[2] = {};  // phx_dev_accumulate_times: the last phx_dev_film_accumulate's kernel and call
   double denoise_ms[11] = {};  // phx_dev_denoise_times: the last phx_dev_denoise's stages (it holds no device memory between calls)
 
   // frame
@@ -617,6 +619,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 9: return sizeof(phx_stats); case 10: return sizeof(phx_texture); case 11: return sizeof(phx_adaptive);
     case 13: return sizeof(phx_denoise);  // (12 stays unused: tests/test_adaptive_sampling.py pins it to 0)
     case 15: return sizeof(phx_guides); case 16: return sizeof(phx_denoise_guides);  // (14 likewise: tests/test_denoise.py)
+    case 18: return sizeof(phx_accumulate);  // (17 likewise: tests/test_guides.py)
     default: return 0;
   }
 }
@@ -887,6 +890,70 @@ int phx_dev_render_guides(phx_device* d, const phx_guides* g, float* film) {
     d->guides_ms[0] = ms; d->guides_ms[1] = ms_between(t0, Clock::now());
     return PHX_OK;
   });
+}
+
+// Film accumulation (phx_accumulate; accumulate.hip).  Everything the call holds on the device lives in the DevBufs below and goes with them.
+// (no stage_hook: the call reads two films and no scene)
+int phx_dev_film_accumulate(phx_device* d, const phx_accumulate* a, float* acc, const float* frame_film, phx_accumulate_summary* summary) {
+  return guarded([&]() -> int {
+    if (!d) return fail(PHX_ERR_ARG, "accumulate: null device");
+    if (d->running) return fail(PHX_ERR_STATE, "accumulate while a frame is running");
+    if (!a) return fail(PHX_ERR_ARG, "accumulate: null argument");
+    std::string why;
+    if (const int rc = accumulate_check(*a, acc, frame_film, why)) return fail(rc, why);
+    const auto t0 = Clock::now();
+    d->accumulate_ms[0] = d->accumulate_ms[1] = 0.0;
+    DeviceScope on(d->hip_device);
+    if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+    const size_t npix = (size_t)a->width * a->height, floats_a = npix * a->xstride_a, floats_b = npix * a->xstride_b;
+    const size_t slot_words = (size_t)PHX_ACCUMULATE_SLOTS * PHX_ACCUMULATE_SLOT_WORDS;
+    DevBuf<float> staged_a, staged_b; DevBuf<unsigned long long> counters;
+    float* dst = acc; const float* src = frame_film;
+    if (!a->on_device) {  // host films: device copies, acc's pooled in place and copied back
+      if (const int rc = staged_a.alloc(floats_a)) return rc;
+      if (const int rc = staged_b.alloc(floats_b)) return rc;
+      HIPCHK(hipMemcpy(staged_a.p, acc, floats_a * sizeof(float), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(staged_b.p, frame_film, floats_b * sizeof(float), hipMemcpyHostToDevice));
+      dst = staged_a.p; src = staged_b.p;
+    }
+    if (summary) {
+      if (const int rc = counters.alloc(slot_words)) return rc;
+      HIPCHK(hipMemsetAsync(counters.p, 0, slot_words * sizeof(unsigned long long), d->stream));
+    }
+    AccumulateArgs A{};
+    A.num_pixels = npix;
+    A.xstride_a = a->xstride_a; A.normals_offset_a = a->normals_offset_a; A.m2_offset_a = a->m2_offset_a; A.samples_offset_a = a->samples_offset_a;
+    A.xstride_b = a->xstride_b; A.normals_offset_b = a->normals_offset_b; A.m2_offset_b = a->m2_offset_b; A.samples_offset_b = a->samples_offset_b;
+    A.spp_b = a->spp_b; A.tau = (double)a->tau; A.floor = (double)a->floor;
+    struct Events {
+      hipEvent_t ev[2] = {nullptr, nullptr};
+      ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    } events;
+    for (hipEvent_t& x : events.ev) HIPCHK(hipEventCreate(&x));
+    HIPCHK(hipEventRecord(events.ev[0], d->stream));
+    launch_accumulate(d->stream, A, dst, src, counters.p);
+    HIPCHK(hipEventRecord(events.ev[1], d->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (!a->on_device) HIPCHK(hipMemcpy(acc, staged_a.p, floats_a * sizeof(float), hipMemcpyDeviceToHost));
+    if (summary) {
+      std::vector<unsigned long long> slots(slot_words);
+      HIPCHK(hipMemcpy(slots.data(), counters.p, slot_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};  // integers, modulo 2^64: whatever the order, the same sums
+      for (size_t s = 0; s < (size_t)PHX_ACCUMULATE_SLOTS; ++s) for (int k = 0; k < 4; ++k) c[k] += slots[s * PHX_ACCUMULATE_SLOT_WORDS + k];
+      summary->pixels = c[0]; summary->invalid = c[1]; summary->converged = c[2]; summary->samples = c[3];
+    }
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, events.ev[0], events.ev[1]));
+    d->accumulate_ms[0] = ms; d->accumulate_ms[1] = ms_between(t0, Clock::now());
+    return PHX_OK;
+  });
+}
+
+int phx_dev_accumulate_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "accumulate_times: null argument");
+  ms[0] = d->accumulate_ms[0]; ms[1] = d->accumulate_ms[1];
+  return PHX_OK;
 }
 
 int phx_dev_guides_times(const phx_device* d, double* ms) {

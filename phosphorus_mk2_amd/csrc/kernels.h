@@ -9,6 +9,7 @@
 //   film_hooks.hip     k_begin_pass, k_film, k_film_moments, k_scatter_film; k_adaptive_* (the selection of adaptive sampling); the hook kernels of the parity tests (phx_dev_*); the preprocess kernels
 //   denoise.hip        k_denoise_pack, k_denoise_iteration, k_denoise_unpack: the film denoiser, a post-process no frame launches
 //   guides.hip         k_guides: the first-hit guide film (albedo, coverage, position, distance), a pass of its own no frame launches
+//   accumulate.hip     k_accumulate: pools a finished film into an accumulator film and counts its summary, a pass of its own no frame launches
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
 //
@@ -234,6 +235,23 @@ void launch_denoise_unpack_guided(hipStream_t stream, const DenoiseArgs& A, cons
 void launch_guides(hipStream_t stream, const DevScene& sc, const PassBuffers& pb, float* film);
 // its instantiations, for init_kernels_on_current_device (the per-lane traversal stack is dynamic LDS): -> how many were written to out[0 .. 3]
 uint32_t guides_kernels(const void** out);
+
+// Film accumulation (phx_accumulate in phx_xpu.h states the rule; accumulate.hip): one launch, a workgroup per span of
+// PHX_ACCUMULATE_SPAN consecutive pixels.  The workgroup moves the span's floats of both films into LDS with coalesced 16-byte loads, a thread
+// pools one pixel, and the span of acc goes back the same way.  xstride_* <= PHX_ACCUMULATE_MAX_XSTRIDE (accumulate_check.h: the check
+// refuses more), which bounds the LDS of a launch: SPAN * 2 * MAX_XSTRIDE floats = 48 KB (accumulate.hip asserts it).
+struct AccumulateArgs {
+  uint64_t num_pixels;
+  uint32_t xstride_a, normals_offset_a, m2_offset_a, samples_offset_a;
+  uint32_t xstride_b, normals_offset_b, m2_offset_b, samples_offset_b;
+  uint32_t spp_b;
+  double tau, floor;
+};
+enum { PHX_ACCUMULATE_SPAN = 256, PHX_ACCUMULATE_SLOTS = 64, PHX_ACCUMULATE_SLOT_WORDS = 16 };
+// counters: nullptr, or PHX_ACCUMULATE_SLOTS zeroed slots of PHX_ACCUMULATE_SLOT_WORDS 64-bit words, a 128-byte line each (one line sustains
+// some 90 atomics a microsecond, and a 2160p film has 32 400 workgroups).  A workgroup adds pixels, invalid, converged, samples
+// (phx_accumulate_summary) to the first four words of slot (workgroup id % SLOTS); the caller sums the slots.
+void launch_accumulate(hipStream_t stream, const AccumulateArgs& A, float* acc, const float* frame_film, unsigned long long* counters);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf

@@ -415,6 +415,39 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_denoise_times(self._h, ms), "phx_dev_denoise_times")
         return {"pack": ms[0], "iterations": list(ms[1:9]), "unpack": ms[9], "call": ms[10]}
 
+    def accumulate(self, acc, frame_film, spp, primary_components=4, normals=False, frame_adaptive=False, threshold=None, floor=0.0, device_ptrs=None):
+        """Film accumulation across frames (phx_dev_film_accumulate; include/phx_xpu.h states the rule): frame_film, a finished film
+        of `spp` samples rendered with moments=True (frame_adaptive: under adaptive sampling, so that it carries its own "samples"), is pooled
+        into acc, a film in the accumulator's layout (accumulator(): the layout of an adaptive film) -> (acc, summary).  A C-contiguous float32
+        acc is pooled in place and returned; anything else is copied first.  summary is None unless threshold is given: then a dict of pixels,
+        invalid, converged (valid pixels whose standard error is at most threshold * (|value| + floor)) and samples, counted on the pooled
+        film.  The frames must come from different seeds.  device_ptrs: (acc address, frame film address) of device-resident films of these
+        layouts; acc and frame_film then are only their shapes (H, W, xstride), and the call returns (None, summary).  Needs no scene; call it
+        after join(), and after dist.reduce_film on several GPUs."""
+        on_device = device_ptrs is not None
+        shape_a = tuple(acc) if on_device and not hasattr(acc, "shape") else acc.shape
+        shape_b = tuple(frame_film) if on_device and not hasattr(frame_film, "shape") else frame_film.shape
+        q = accumulate_settings(shape_a, shape_b, spp, primary_components, normals, frame_adaptive, 0.0 if threshold is None else threshold, floor)
+        s = abi.AccumulateSummary() if threshold is not None else None
+        sref = C.byref(s) if s is not None else None
+        if on_device:
+            q.on_device = 1
+            pa, pb = (int(p) for p in device_ptrs)
+            out = keep = None
+        else:
+            out = acc if isinstance(acc, np.ndarray) and acc.dtype == np.float32 and acc.flags.c_contiguous and acc.flags.writeable else \
+                np.array(acc, np.float32, order="C")
+            keep = np.ascontiguousarray(frame_film, np.float32)
+            pa, pb = out.ctypes.data, keep.ctypes.data
+        _check(self._lib, self._lib.phx_dev_film_accumulate(self._h, C.byref(q), pa, pb, sref), "phx_dev_film_accumulate")
+        return out, (None if s is None else {k: int(getattr(s, k)) for k, _ in s._fields_})
+
+    def accumulate_times(self):
+        """milliseconds of the last accumulate(): dict of kernel (HIP events) and call (host clock)"""
+        ms = (C.c_double * 2)()
+        _check(self._lib, self._lib.phx_dev_accumulate_times(self._h, ms), "phx_dev_accumulate_times")
+        return {"kernel": ms[0], "call": ms[1]}
+
     # ---- stage-level hooks (parity tests) -------------------------------------------------------
     def adaptive_select(self, acc, samples_done, spp, threshold, floor=0.0, min_samples=16, step=16, active=None, num_active=None):
         """The selection of adaptive sampling behind a round that ended at samples_done of spp samples, on the caller's data
@@ -610,6 +643,81 @@ def denoise_settings(shape, spp, primary_components=4, normals=False, adaptive=F
                        normal_power_log2=int(normal_power_log2), on_device=0)
 
 
+def accumulator(width, height, primary_components=4, normals=False):
+    """A zeroed film in the accumulator's layout (HipDevice.accumulate): "primary", "normals" when asked for, "m2" and always "samples", which
+    is the layout of an adaptive film, so HipDevice.denoise(..., adaptive=True) and film_variance(..., adaptive=True) read it as it is
+    -> (H, W, xstride) f32.  Accumulating a frame into it is the copy."""
+    return Film(width, height, primary_components, normals, True, True).data
+
+
+def accumulate_settings(shape_a, shape_b, spp, primary_components=4, normals=False, frame_adaptive=False, threshold=0.0, floor=0.0):
+    """abi.Accumulate for an accumulator of shape_a and a frame film of shape_b (H, W, xstride each) with the channels derived as Film derives
+    them; both films have the same primary_components and normals, the accumulator always has "samples", the frame film when frame_adaptive.
+    ValueError for films of different sizes or without the channel m2 (render the frame with moments=True)."""
+    if len(shape_a) != 3 or len(shape_b) != 3:
+        raise ValueError("accumulate: both films must be (height, width, xstride)")
+    (H, W, xa), (Hb, Wb, xb) = ((int(v) for v in s) for s in (shape_a, shape_b))
+    if (H, W) != (Hb, Wb):
+        raise ValueError(f"accumulate: the accumulator is {W} x {H} pixels, the frame film {Wb} x {Hb}")
+    m2_offset = primary_components + (3 if normals else 0)
+    if xa != m2_offset + 4:
+        raise ValueError(f"accumulate: an accumulator has {m2_offset + 4} floats per pixel in this layout (xpu.accumulator), this one {xa}")
+    want = m2_offset + 3 + (1 if frame_adaptive else 0)
+    if xb != want:
+        raise ValueError(f"accumulate: a frame film with the m2 channel has {want} floats per pixel in this layout, this one {xb} "
+                         "(accumulation needs frames rendered with moments=True)")
+    no = primary_components if normals else 0
+    return abi.Accumulate(width=W, height=H, xstride_a=xa, normals_offset_a=no, m2_offset_a=m2_offset, samples_offset_a=m2_offset + 3,
+                          xstride_b=xb, normals_offset_b=no, m2_offset_b=m2_offset, samples_offset_b=m2_offset + 3 if frame_adaptive else 0,
+                          spp_b=int(spp), on_device=0, tau=float(threshold), floor=float(floor))
+
+
+def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None, adaptive=None, pps=1, depth=9, normals=False, tile_size=32,
+                       **options):
+    """Progressive rendering on ONE device: the scene is preprocessed once, then frame k = 0, 1, ... is rendered at `spp` samples
+    with sampler seed (seed + k) mod 2^64 and moments=True and pooled into an accumulator film (HipDevice.accumulate).  A generator: after
+    every frame it yields (film, summary, frames_done); film is the accumulator (H, W, xstride) f32 in xpu.accumulator's layout, a view that
+    the next frame changes: copy it to keep it.  It ends after `frames`, or, with stop=dict(threshold=, floor=0.0, coverage=0.95), once
+    pixels - invalid > 0 and converged >= coverage * (pixels - invalid) of the summary (HipDevice.accumulate states the criterion); summary is
+    None without stop.
+    denoise: a dict of HipDevice.denoise's settings; the yielded film then is a denoised COPY, the accumulator itself is never filtered.
+    Its entry guides=dict(samples=4, ...) renders the guide film once, with the first frame's seed.  adaptive: a dict of
+    HipDevice.set_adaptive's arguments for every frame.  options: further Options fields (samples_in_flight=, light_sampling=, ...)."""
+    if frames < 1:
+        raise ValueError("render_progressive: frames must be at least 1")
+    stop = dict(stop) if stop is not None else None
+    coverage = float(stop.pop("coverage", 0.95)) if stop is not None else None
+    if stop is not None and "threshold" not in stop:
+        raise ValueError("render_progressive: stop needs a threshold")
+    dev = HipDevice.make(Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, **options))
+    try:
+        if adaptive is not None:
+            dev.set_adaptive(**adaptive)
+        dev.preprocess(scene_desc)
+        W, H = scene_desc.camera.width, scene_desc.camera.height
+        acc = accumulator(W, H, 4, normals)
+        settings, guides = None, None
+        if denoise is not None:
+            settings = dict(denoise)
+            gset = settings.pop("guides", None)
+            if gset is not None:
+                gset = dict(gset)
+                guides = dev.render_guides(seed, min(int(gset.pop("samples", 4)), spp))
+                settings.update(gset)
+        for k in range(frames):
+            film = Film(W, H, 4, normals, True, adaptive is not None)
+            dev.start(scene_desc, FrameState((seed + k) % (1 << 64), Tiles.make(W, H, tile_size), film, native_sink=True))
+            dev.join()
+            _, summary = dev.accumulate(acc, film.data, spp, 4, normals, adaptive is not None, **(stop or {}))
+            out = acc if settings is None else dev.denoise(acc, spp, 4, normals, True, guides=guides, **settings)
+            yield out, summary, k + 1
+            valid = summary["pixels"] - summary["invalid"] if summary is not None else 0
+            if valid > 0 and summary["converged"] >= coverage * valid:  # (a film without one valid pixel, as any film of 1 spp, has not converged)
+                return
+    finally:
+        dev.close()
+
+
 def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_sink=True, rank=0, world=1, moments=False, adaptive=False):
     """The reference's frame on SEVERAL devices in one process (src/core.cpp:103-115): every device is started on the SAME tile
     queue and the SAME film and joined in turn; no collective.  `devices` must have been preprocessed with `scene_desc`.
@@ -627,16 +735,30 @@ def render_on(devices, scene_desc, seed=1, normals=False, tile_size=32, native_s
 
 def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=32, rank=0, world=1, callback_tiles=False,
            samples_in_flight=0, tiles_per_batch=0, native_sink=False, bvh_builder="auto", light_sampling="reference",
-           light_selection="uniform", environment_sampling=False, moments=False, adaptive=None, denoise=None):
+           light_selection="uniform", environment_sampling=False, moments=False, adaptive=None, denoise=None, progressive=None):
     """Convenience: the call sequence of session_t::render (plugins/blender/session.cpp:73-94):
     make -> preprocess -> tiles_t::make -> start -> join on ONE device.  Returns (film array HxWxC, stats).
     adaptive: a dict of HipDevice.set_adaptive's arguments (threshold=..., floor=, min_samples=, step=) turns adaptive sampling on; the film then
     needs moments=True and carries the channel "samples".
     denoise: a dict of HipDevice.denoise's settings (iterations=, sigma_l=, normal_power_log2=; {} for the defaults) filters the film that is
     returned; it needs moments=True.  Its entry guides=dict(samples=4, demodulate=True, plane=False, albedo_floor=, sigma_x=) renders the
-    first-hit guide film with the frame's seed (HipDevice.render_guides) and runs the guided filter; plane=True needs normals=True."""
+    first-hit guide film with the frame's seed (HipDevice.render_guides) and runs the guided filter; plane=True needs normals=True.
+    progressive: dict(frames=, stop=None) drains render_progressive (frames of spp samples at seeds seed, seed + 1, ... pooled into
+    one film, until `frames` are done or stop's coverage is met) and returns (the last film it yields, in xpu.accumulator's layout, the last
+    summary or None); it needs moments=True and renders the whole film on one device."""
     if denoise is not None and not moments:
         raise ValueError("denoise needs moments=True: the filter's yardstick is the film's m2 channel")
+    if progressive is not None:
+        if not moments:
+            raise ValueError("progressive needs moments=True: frames are pooled by their m2 channel")
+        if callback_tiles or (rank, world) != (0, 1):
+            raise ValueError("progressive renders whole films on one device: no callback_tiles, rank or world")
+        last = None
+        for last in render_progressive(scene_desc, spp, int(progressive["frames"]), seed, progressive.get("stop"), denoise, adaptive, pps, depth, normals,
+                                       tile_size, samples_in_flight=samples_in_flight, tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder,
+                                       light_sampling=light_sampling, light_selection=light_selection, environment_sampling=environment_sampling):
+            pass
+        return np.array(last[0]), last[1]
     opts = Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, samples_in_flight=samples_in_flight,
                    tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder, light_sampling=light_sampling, light_selection=light_selection,
                    environment_sampling=environment_sampling)
