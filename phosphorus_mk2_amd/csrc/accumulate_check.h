@@ -1,7 +1,7 @@
 // accumulate_check.h — the argument check of phx_dev_film_accumulate (phx_accumulate in phx_xpu.h states the ranges).
 //
 // Host-only, like denoise_check.h: the ABI's struct and nothing else, so the translation unit compiles with a plain host compiler
-// (tests/native/host_accumulate.cpp, tests/test_accumulate.py).  device.cpp calls it before it touches the device.
+// (tests/native/host_accumulate.cpp, tests/test_accumulate.py).  film_calls.cpp calls it before it touches the device.
 #pragma once
 #include "../../include/phx_xpu.h"
 

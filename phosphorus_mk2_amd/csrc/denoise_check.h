@@ -1,7 +1,7 @@
 // denoise_check.h — the argument check of phx_dev_denoise (phx_denoise in phx_xpu.h states the ranges).
 //
 // Host-only, like frame_plan.h: the ABI's struct and nothing else, so the translation unit compiles with a plain host compiler
-// (tests/native/host_denoise.cpp, tests/test_denoise.py).  device.cpp calls it before it touches the device.
+// (tests/native/host_denoise.cpp, tests/test_denoise.py).  film_calls.cpp calls it before it touches the device; what the checks share is film_checks.h.
 #pragma once
 #include "../../include/phx_xpu.h"
 

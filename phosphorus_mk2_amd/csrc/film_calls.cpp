@@ -1,0 +1,280 @@
+// film_calls.cpp — the entry points that work on a film and launch no frame: phx_dev_film_moments, phx_dev_denoise / _guided (denoise.hip),
+// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_adaptive_select and the three *_times getters.
+//
+// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp over film_checks.h)
+// and run before the device is selected; what the three large calls share — refusals, device, events, host-film staging, the wait and the
+// times — is FilmCall below.  phx_dev_film_moments and phx_dev_adaptive_select stage plain arrays, as the stage hooks do (Staging).
+#include "device_internal.h"
+#include "accumulate_check.h"
+#include "denoise_check.h"
+#include "film_checks.h"
+#include "guides_check.h"
+
+using namespace phx;
+
+namespace {
+
+// The refusals every film call opens with, in their order.  `args`: false when a pointer the call cannot do without is null.
+int refused(const phx_device* d, const char* call, bool args, bool needs_scene = false) {
+  auto no = [call](int code, const char* why) { return fail(code, std::string(call) + why); };  // (the text is built for a refusal only)
+  if (!d) return no(PHX_ERR_ARG, ": null device");
+  if (needs_scene && !d->preprocessed) return no(PHX_ERR_STATE, " before preprocess");
+  if (d->running) return no(PHX_ERR_STATE, " while a frame is running");
+  if (!args) return no(PHX_ERR_ARG, ": null argument");
+  return PHX_OK;
+}
+
+// One film call on the device, behind its argument check: begin() enters the device and zeroes the call's times, stage() gives a host film a
+// device copy, mark() records an event between launches, wait() waits and copies back, times() reads the events.  Everything it holds on the
+// device goes with it, on every way out, and the caller's device comes back.
+struct FilmCall {
+  phx_device* d; double* ms;  // ms: the call's times in the device object
+  Clock::time_point t0;
+  std::optional<DeviceScope> on;
+  std::deque<DevBuf<float>> staged;
+  struct Back { float* host; const float* dev; size_t bytes; };
+  std::vector<Back> back;
+  std::vector<hipEvent_t> ev;
+  ~FilmCall() { for (hipEvent_t x : ev) (void)hipEventDestroy(x); }
+
+  int begin(size_t num_times) {  // (a refused call never comes here: it leaves the caller's device and the previous call's times alone)
+    t0 = Clock::now();
+    if (!on.emplace(d->hip_device).ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+    std::fill(ms, ms + num_times, 0.0);
+    return PHX_OK;
+  }
+  // a host film of `floats` floats: `dev` becomes a device copy, filled from `from` (nullptr: left as allocated) and copied to `back_to` behind the wait (nullptr: not)
+  int stage(const float* from, size_t floats, float* back_to, float*& dev) {
+    staged.emplace_back();
+    if (const int rc = staged.back().alloc(floats)) return rc;
+    dev = staged.back().p;
+    if (from) HIPCHK(hipMemcpy(dev, from, floats * sizeof(float), hipMemcpyHostToDevice));
+    if (back_to) back.push_back({back_to, dev, floats * sizeof(float)});
+    return PHX_OK;
+  }
+  int mark() {
+    hipEvent_t x; HIPCHK(hipEventCreate(&x));
+    ev.push_back(x);
+    HIPCHK(hipEventRecord(x, d->stream));
+    return PHX_OK;
+  }
+  int wait() {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(d->stream));
+    for (const Back& b : back) HIPCHK(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+    return PHX_OK;
+  }
+  // behind wait(): the time between marks k and k + 1 into ms[slot(k)], the call's own since begin() into ms[call]
+  template <typename F> int times(size_t call, F&& slot) {
+    for (size_t k = 0; k + 1 < ev.size(); ++k) {
+      float t = 0.0f;
+      HIPCHK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+      ms[slot(k)] = t;
+    }
+    ms[call] = ms_between(t0, Clock::now());
+    return PHX_OK;
+  }
+  int kernel_and_call_times() { return times(1, [](size_t) { return (size_t)0; }); }  // two marks: (kernel, call)
+};
+
+}  // namespace
+
+extern "C" {
+
+// (no stage_hook: the film stage reads no scene, so a device that has preprocessed nothing serves)
+int phx_dev_film_moments(phx_device* d, uint32_t num_pixels, uint32_t num_samples, uint32_t samples_done, float inv, const float* radiance, float* acc) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "film_moments", true)) return rc;
+    if (num_pixels == 0 || num_samples == 0) return PHX_OK;
+    if (!radiance || !acc) return fail(PHX_ERR_ARG, "film_moments: null argument");
+    const size_t npaths = (size_t)num_pixels * num_samples;
+    if (npaths >= 0x7fffffffull) return fail(PHX_ERR_ARG, "film_moments: too many samples");
+    Staging s{d};
+    const float4* pr = reinterpret_cast<const float4*>(s.in(radiance, 4 * npaths));
+    float* a = s.out(acc, 6 * (size_t)num_pixels);
+    if (s.rc) return s.rc;
+    HIPCHK(hipMemcpy(a, acc, 6 * (size_t)num_pixels * sizeof(float), hipMemcpyHostToDevice));
+    PassBuffers B{};
+    B.pr = const_cast<float4*>(pr); B.acc = a; B.num_pixels = num_pixels; B.num_samples = num_samples; B.xstride = 6;
+    return s.run([&] { launch_film_moments(d->stream, B, num_samples, inv, samples_done, 3); });
+  });
+}
+
+// (no stage_hook: the denoiser reads a film and no scene)
+int phx_dev_denoise(phx_device* d, const phx_denoise* q, const float* film_in, float* film_out) { return phx_dev_denoise_guided(d, q, nullptr, film_in, film_out); }
+
+// g == nullptr or g->flags == 0: the unguided filter, by the launches it has always had
+int phx_dev_denoise_guided(phx_device* d, const phx_denoise* q, const phx_denoise_guides* g, const float* film_in, float* film_out) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "denoise", q != nullptr)) return rc;
+    std::string why;
+    if (const int rc = denoise_check(*q, film_in, film_out, why)) return fail(rc, why);
+    if (g && !g->flags) g = nullptr;
+    if (g) if (const int rc = denoise_guides_check(*q, *g, why)) return fail(rc, why);
+    FilmCall call{d, d->denoise_ms};
+    if (const int rc = call.begin(11)) return rc;
+    const size_t npix = (size_t)q->width * q->height, film_bytes = npix * q->xstride * sizeof(float);
+    // the working buffers live in these and go with them, on every way out
+    DevBuf<float4> c[2], v[2], n, gx; DevBuf<double> e[2];
+    const float* src = film_in; float* dst = film_out;
+    if (!q->on_device) {  // host films: one device copy, denoised in place
+      if (const int rc = call.stage(film_in, npix * q->xstride, film_out, dst)) return rc;
+      src = dst;
+    }
+    if (q->iterations) {
+      for (int k = 0; k < 2; ++k) {
+        if (const int rc = c[k].alloc(npix)) return rc;
+        if (const int rc = v[k].alloc(npix)) return rc;
+        if (const int rc = e[k].alloc(npix)) return rc;
+      }
+      if (const int rc = n.alloc(npix)) return rc;
+      DenoiseGuideArgs G{};
+      if (g) {
+        G.guides = g->guides; G.xstride = g->xstride; G.flags = g->flags;
+        G.albedo_floor = (double)g->albedo_floor; G.tol_scale = (double)g->sigma_x * (double)g->plane_scale;
+        if (!q->on_device) {  // host guides: a device copy, like the film's
+          float* copy = nullptr;
+          if (const int rc = call.stage(g->guides, npix * g->xstride, nullptr, copy)) return rc;
+          G.guides = copy;
+        }
+        if (g->flags & PHX_GUIDE_PLANE) { if (const int rc = gx.alloc(npix)) return rc; G.x = gx.p; }
+      }
+      DenoiseArgs A{};
+      A.width = q->width; A.height = q->height; A.xstride = q->xstride; A.normals_offset = q->normals_offset; A.m2_offset = q->m2_offset;
+      A.samples_offset = q->samples_offset; A.spp = q->spp; A.normal_power_log2 = q->normal_power_log2; A.sigma_l = (double)q->sigma_l;
+      for (int k = 0; k < 2; ++k) { A.c[k] = c[k].p; A.v[k] = v[k].p; A.e[k] = e[k].p; }
+      A.n = n.p;
+      if (const int rc = call.mark()) return rc;
+      if (g) launch_denoise_pack_guided(d->stream, A, G, src); else launch_denoise_pack(d->stream, A, src);
+      if (const int rc = call.mark()) return rc;
+      for (uint32_t i = 0; i < q->iterations; ++i) {
+        if (g) launch_denoise_iteration_guided(d->stream, A, G, (int)(i & 1u), 1u << i); else launch_denoise_iteration(d->stream, A, (int)(i & 1u), 1u << i);
+        if (const int rc = call.mark()) return rc;
+      }
+      if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, film_bytes, hipMemcpyDeviceToDevice, d->stream));
+      if (g) launch_denoise_unpack_guided(d->stream, A, G, (int)(q->iterations & 1u), dst); else launch_denoise_unpack(d->stream, A, (int)(q->iterations & 1u), dst);
+      if (const int rc = call.mark()) return rc;
+    } else if (dst != src) HIPCHK(hipMemcpyAsync(dst, src, film_bytes, hipMemcpyDeviceToDevice, d->stream));
+    if (const int rc = call.wait()) return rc;
+    // denoise_ms: 0 pack, 1 .. iterations the iterations, 9 unpack, 10 the call
+    return call.times(10, [&](size_t k) -> size_t { return k == 0 ? 0 : k <= q->iterations ? k : 9; });
+  });
+}
+
+// The first-hit guide film (phx_guides; guides.hip).
+int phx_dev_render_guides(phx_device* d, const phx_guides* g, float* film) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "render_guides", g != nullptr, true)) return rc;
+    const uint32_t W = d->scene.width, H = d->scene.height, spp = d->opt.samples_per_pixel;
+    std::string why;
+    if (const int rc = guides_check(*g, W, H, spp, film, why)) return fail(rc, why);
+    FilmCall call{d, d->guides_ms};
+    if (const int rc = call.begin(2)) return rc;
+    const size_t npix = (size_t)W * H;
+    std::vector<uint32_t> xy(npix);
+    for (uint32_t y = 0; y < H; ++y) for (uint32_t x = 0; x < W; ++x) xy[(size_t)y * W + x] = x | y << 16;
+    DevBuf<uint32_t> d_xy; DevBuf<float2> d_jit;
+    if (const int rc = d_xy.upload(xy)) return rc;
+    if (const int rc = d_jit.upload(jitter_table(g->sampler_seed, spp))) return rc;
+    float* dst = film;
+    if (!g->on_device) if (const int rc = call.stage(nullptr, npix * 8, film, dst)) return rc;
+    PassBuffers B{};
+    B.pix_xy = d_xy.p; B.jitter = d_jit.p; B.num_pixels = (uint32_t)npix; B.num_samples = g->samples; B.seed = g->sampler_seed;
+    if (const int rc = call.mark()) return rc;
+    launch_guides(d->stream, d->scene, B, dst);
+    if (const int rc = call.mark()) return rc;
+    if (const int rc = call.wait()) return rc;
+    return call.kernel_and_call_times();
+  });
+}
+
+// Film accumulation (phx_accumulate; accumulate.hip).
+// (no stage_hook: the call reads two films and no scene)
+int phx_dev_film_accumulate(phx_device* d, const phx_accumulate* a, float* acc, const float* frame_film, phx_accumulate_summary* summary) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "accumulate", a != nullptr)) return rc;
+    std::string why;
+    if (const int rc = accumulate_check(*a, acc, frame_film, why)) return fail(rc, why);
+    FilmCall call{d, d->accumulate_ms};
+    if (const int rc = call.begin(2)) return rc;
+    const size_t npix = (size_t)a->width * a->height;
+    const size_t slot_words = (size_t)PHX_ACCUMULATE_SLOTS * PHX_ACCUMULATE_SLOT_WORDS;
+    DevBuf<unsigned long long> counters;
+    float *dst = acc, *frame_copy = nullptr; const float* src = frame_film;
+    if (!a->on_device) {  // host films: device copies, acc's pooled in place and copied back
+      if (const int rc = call.stage(acc, npix * a->xstride_a, acc, dst)) return rc;
+      if (const int rc = call.stage(frame_film, npix * a->xstride_b, nullptr, frame_copy)) return rc;
+      src = frame_copy;
+    }
+    if (summary) {
+      if (const int rc = counters.alloc(slot_words)) return rc;
+      HIPCHK(hipMemsetAsync(counters.p, 0, slot_words * sizeof(unsigned long long), d->stream));
+    }
+    AccumulateArgs A{};
+    A.num_pixels = npix;
+    A.xstride_a = a->xstride_a; A.normals_offset_a = a->normals_offset_a; A.m2_offset_a = a->m2_offset_a; A.samples_offset_a = a->samples_offset_a;
+    A.xstride_b = a->xstride_b; A.normals_offset_b = a->normals_offset_b; A.m2_offset_b = a->m2_offset_b; A.samples_offset_b = a->samples_offset_b;
+    A.spp_b = a->spp_b; A.tau = (double)a->tau; A.floor = (double)a->floor;
+    if (const int rc = call.mark()) return rc;
+    launch_accumulate(d->stream, A, dst, src, counters.p);
+    if (const int rc = call.mark()) return rc;
+    if (const int rc = call.wait()) return rc;
+    if (summary) {
+      std::vector<unsigned long long> slots(slot_words);
+      HIPCHK(hipMemcpy(slots.data(), counters.p, slot_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};  // integers, modulo 2^64: whatever the order, the same sums
+      for (size_t s = 0; s < (size_t)PHX_ACCUMULATE_SLOTS; ++s) for (int k = 0; k < 4; ++k) c[k] += slots[s * PHX_ACCUMULATE_SLOT_WORDS + k];
+      summary->pixels = c[0]; summary->invalid = c[1]; summary->converged = c[2]; summary->samples = c[3];
+    }
+    return call.kernel_and_call_times();
+  });
+}
+
+int phx_dev_accumulate_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "accumulate_times: null argument");
+  ms[0] = d->accumulate_ms[0]; ms[1] = d->accumulate_ms[1];
+  return PHX_OK;
+}
+
+int phx_dev_guides_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "guides_times: null argument");
+  ms[0] = d->guides_ms[0]; ms[1] = d->guides_ms[1];
+  return PHX_OK;
+}
+
+int phx_dev_denoise_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "denoise_times: null argument");
+  std::copy(std::begin(d->denoise_ms), std::end(d->denoise_ms), ms);
+  return PHX_OK;
+}
+
+// (no stage_hook either: the selection reads no scene)
+int phx_dev_adaptive_select(phx_device* d, uint32_t num_active, const uint32_t* active, uint32_t num_rows, float* acc, uint32_t samples_done, uint32_t spp,
+                            const phx_adaptive* a, uint32_t* survivors, uint32_t* num_survivors) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "adaptive_select", acc && a && survivors && num_survivors)) return rc;
+    if (samples_done < 2u || samples_done >= spp) return fail(PHX_ERR_ARG, "adaptive_select: samples_done must be at least 2 and below spp");
+    if (const char* field = adaptive_invalid(*a)) return fail(PHX_ERR_ARG, outside_its_range("adaptive_select", field, "phx_adaptive"));
+    if (num_active > num_rows) return fail(PHX_ERR_ARG, "adaptive_select: more active rows than rows");
+    for (uint32_t i = 0; active && i < num_active; ++i) {
+      if (active[i] >= num_rows) return fail(PHX_ERR_ARG, "adaptive_select: an index past num_rows");
+      if (i && active[i] <= active[i - 1]) return fail(PHX_ERR_ARG, "adaptive_select: the indices must ascend strictly");
+    }
+    *num_survivors = 0;
+    if (num_active == 0) return PHX_OK;
+    Staging s{d};
+    const size_t nfl = 7 * (size_t)num_rows;
+    AdaptiveArgs A{};
+    A.acc = s.out(acc, nfl); A.xstride = 7; A.m2_offset = 3; A.samples_offset = 6;
+    A.active = active ? s.in(active, num_active) : nullptr; A.num_active = num_active;
+    adaptive_args(*a, samples_done, spp, A);
+    uint32_t* scratch = s.out<uint32_t>(nullptr, (num_active + PHX_ADAPTIVE_BLOCK - 1) / PHX_ADAPTIVE_BLOCK);
+    uint32_t *surv = s.out(survivors, num_active), *total = s.out(num_survivors, 1);
+    if (s.rc) return s.rc;
+    HIPCHK(hipMemcpy(A.acc, acc, nfl * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemsetAsync(surv, 0, (size_t)num_active * sizeof(uint32_t), d->stream));  // the words past the survivors: zeros, not what the allocation held
+    return s.run([&] { launch_adaptive_select(d->stream, A, scratch, surv, total); });
+  });
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 // tiles make the next batch, and the passes a batch is rendered in.
 //
 // Integer arithmetic on the ABI's structs and nothing else: no HIP call, no HIP header, no kernels.h, so the translation unit compiles with a
-// plain host compiler (tests/native/host_frame_plan.cpp, tests/test_frame_plan.py).  device.cpp asks the device how much memory is free
+// plain host compiler (tests/native/host_frame_plan.cpp, tests/test_frame_plan.py).  The frame driver (frame_driver.cpp) asks the device how much memory is free
 // (phx_device::path_budget), hands the answer in as a number of paths and drives the launches by what is decided here.
 #pragma once
 #include "../../include/phx_xpu.h"
@@ -14,7 +14,7 @@
 
 namespace phx {
 
-// what the queues + state of one path in flight take (device.cpp: PathQueues, whose static_assert holds the two to these figures)
+// what the queues + state of one path in flight take (device_internal.h: PathQueues, whose static_assert holds the two to these figures)
 constexpr size_t queue_bytes_per_path(bool normals) { return normals ? 192 : 176; }
 
 // The floats of one pixel in the batch buffer and in every film sink: "primary", then "normals", "m2" and "samples" where the frame has them

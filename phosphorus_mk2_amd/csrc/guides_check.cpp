@@ -1,8 +1,6 @@
 // guides_check.cpp — see guides_check.h.
 #include "guides_check.h"
-
-#include <cmath>
-#include <cstdint>
+#include "film_checks.h"
 
 namespace phx {
 
@@ -31,17 +29,11 @@ const char* denoise_guides_invalid(const phx_denoise& d, const phx_denoise_guide
 }  // namespace
 
 int guides_check(const phx_guides& g, uint32_t width, uint32_t height, uint32_t spp, const float* film, std::string& err) {
-  const char* field = guides_invalid(g, width, height, spp, film);
-  if (!field) return PHX_OK;
-  err = std::string("render_guides: ") + field + " is outside its range (phx_guides)";
-  return PHX_ERR_ARG;
+  return refusal("render_guides", guides_invalid(g, width, height, spp, film), "phx_guides", err);
 }
 
 int denoise_guides_check(const phx_denoise& d, const phx_denoise_guides& g, std::string& err) {
-  const char* field = denoise_guides_invalid(d, g);
-  if (!field) return PHX_OK;
-  err = std::string("denoise_guided: ") + field + " is outside its range (phx_denoise_guides)";
-  return PHX_ERR_ARG;
+  return refusal("denoise_guided", denoise_guides_invalid(d, g), "phx_denoise_guides", err);
 }
 
 }  // namespace phx

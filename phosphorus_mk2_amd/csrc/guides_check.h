@@ -2,7 +2,7 @@
 // state the ranges).
 //
 // Host-only, like denoise_check.h: the ABI's structs and nothing else, so the translation unit compiles with a plain host compiler
-// (tests/native/host_guides.cpp, tests/test_guides.py).  device.cpp calls them before it touches the device.
+// (tests/native/host_guides.cpp, tests/test_guides.py).  film_calls.cpp calls them before it touches the device.
 #pragma once
 #include "../../include/phx_xpu.h"
 

@@ -298,3 +298,15 @@ def check_cover(film, full, cover):
     assert same_bits(film[covered], full[covered])
     assert (film[~covered] == np.float32(SENTINEL)).all()
     assert not (full == np.float32(SENTINEL)).any()
+
+
+def current_hip_device(xpu):
+    """hipGetDevice of the calling thread, asked of the HIP runtime that the library itself runs on: the symbol is looked up through the
+    library's own handle, which finds it in the runtime the library was linked against, whatever its version (a pytest session may hold
+    torch's copy of the runtime as well)"""
+    import ctypes as C
+    dev = C.c_int(-1)
+    rc = xpu.load_library().hipGetDevice(C.byref(dev))
+    if rc != 0:
+        raise RuntimeError(f"hipGetDevice failed: {rc}")
+    return dev.value

@@ -197,6 +197,27 @@ def test_refusals_leave_acc_untouched_and_the_device_usable(xpu, dev):
     assert set(t) == {"kernel", "call"} and 0 < t["kernel"] <= t["call"]
 
 
+def test_a_call_the_check_refuses_leaves_films_times_and_device_alone(xpu, dev):
+    """behind a successful call, one the argument check refuses (on_device = 2): PHX_ERR_ARG with the check's text, both films and the summary
+    bit for bit what they were, the times still the successful call's, and the caller's current HIP device what it was
+    (On a machine with one GPU the current device is 0 before and after whatever the call does: that last assertion can fail only where
+    there are several.)"""
+    acc, frame, offs_a, offs_b, want, _ = case(8, 8)
+    dev.accumulate(acc.copy(), frame, SPP, 4, True, True, threshold=TAU, floor=FLOOR)
+    times = dev.accumulate_times()
+    assert 0 < times["kernel"] <= times["call"]
+    q = xpu.accumulate_settings(acc.shape, frame.shape, SPP, 4, True, True, TAU, FLOOR)
+    q.on_device = 2
+    a, b, s = acc.copy(), frame.copy(), xpu.abi.AccumulateSummary(pixels=7)
+    lib = xpu.load_library()
+    current = FC.current_hip_device(xpu)
+    rc = lib.phx_dev_film_accumulate(dev._h, C.byref(q), a.ctypes.data, b.ctypes.data, C.byref(s))
+    assert rc == PHX_ERR_ARG and lib.phx_last_error().decode() == "accumulate: on_device is outside its range (phx_accumulate)"
+    assert bits_equal(a, acc) and bits_equal(b, frame) and (s.pixels, s.invalid, s.converged, s.samples) == (7, 0, 0, 0)
+    assert dev.accumulate_times() == times
+    assert FC.current_hip_device(xpu) == current
+
+
 # ---- real frames ----------------------------------------------------------------------------------------------------------------------------
 W, H = 37, 29
 RENDER = dict(spp=SPP, depth=4, moments=True)

@@ -169,6 +169,28 @@ def test_stage_times_are_the_last_calls(dev):
     assert [v > 0 for v in t["iterations"]] == [True] * 3 + [False] * 5
 
 
+def test_a_call_the_check_refuses_leaves_films_times_and_device_alone(xpu, dev):
+    """behind a successful call, one the argument check refuses (on_device = 2): PHX_ERR_ARG with the check's text, both films bit for bit
+    what they were, the times still the successful call's, and the caller's current HIP device what it was
+    (On a machine with one GPU the current device is 0 before and after whatever the call does: that last assertion can fail only where
+    there are several.)"""
+    import ctypes as C
+    film, offs, _ = case(8, 8)
+    dev.denoise(film, SPP, 4, True, True, iterations=2)
+    times = dev.denoise_times()
+    assert times["pack"] > 0 and times["iterations"][1] > 0 and times["unpack"] > 0 and times["call"] > 0
+    q = xpu.denoise_settings(film.shape, SPP, 4, True, True)
+    q.on_device = 2
+    a, b = film.copy(), np.full(film.shape, FC.SENTINEL, F)
+    lib = xpu.load_library()
+    current = FC.current_hip_device(xpu)
+    rc = lib.phx_dev_denoise(dev._h, C.byref(q), a.ctypes.data, b.ctypes.data)
+    assert rc == 1 and lib.phx_last_error().decode() == "denoise: on_device is outside its range (phx_denoise)"  # PHX_ERR_ARG
+    assert bits_equal(a, film) and bits_equal(b, np.full(film.shape, FC.SENTINEL, F))
+    assert dev.denoise_times() == times
+    assert FC.current_hip_device(xpu) == current
+
+
 # ---- end to end ---------------------------------------------------------------------------------------------------------------------------
 RENDER = dict(spp=8, depth=5, normals=True, moments=True)
 ADAPTIVE = dict(threshold=0.2, min_samples=4, step=2)

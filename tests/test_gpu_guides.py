@@ -257,6 +257,28 @@ def test_device_film_repeats_and_seeds(xpu):
         dev.close()
 
 
+def test_a_call_the_check_refuses_leaves_film_times_and_device_alone(xpu):
+    """behind a successful call, one the argument check refuses (on_device = 2): PHX_ERR_ARG with the check's text, the film bit for bit what it
+    was, the times still the successful call's, and the caller's current HIP device what it was
+    (On a machine with one GPU the current device is 0 before and after whatever the call does: that last assertion can fail only where
+    there are several.)"""
+    dev = make_device(xpu, scene_of("cornell", 8, 8), 4)
+    try:
+        dev.render_guides(1, 2)
+        times = dev.guides_times()
+        assert 0 < times["kernel"] <= times["call"]
+        out = np.full((8, 8, 8), FC.SENTINEL, F)
+        g = xpu.abi.Guides(sampler_seed=1, samples=2, on_device=2)
+        current = FC.current_hip_device(xpu)
+        rc = dev._lib.phx_dev_render_guides(dev._h, C.byref(g), out.ctypes.data)
+        assert rc == 1 and dev._lib.phx_last_error().decode() == "render_guides: on_device is outside its range (phx_guides)"  # PHX_ERR_ARG
+        assert bits_equal(out, np.full((8, 8, 8), FC.SENTINEL, F))
+        assert dev.guides_times() == times
+        assert FC.current_hip_device(xpu) == current
+    finally:
+        dev.close()
+
+
 # ---- 3. state and memory -------------------------------------------------------------------------------------------------------------------------
 def test_state_refusals_memory_and_the_next_frame(xpu):
     scene = scene_of("cornell")
