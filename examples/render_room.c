@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K] [display [auto]]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -23,6 +23,9 @@
  * progressive K: K frames of 8 samples at seeds 7, 8, ... are pooled into one accumulator film (phx_dev_film_accumulate: primary rgba, m2 rgb, samples),
  * each frame carrying the error estimate; after every frame the host prints the call's summary (the samples pooled so far and the pixels whose
  * standard error is at most 0.05 * (|value| + 0.01)).  The accumulator is what the later steps (denoise) see and what is written.
+ * display [auto]: after every other step the film at hand goes through the display pass (phx_dev_film_display: exposure 1, or with `auto` taken from
+ * the film's own luminance histogram so that its logarithmic mean between the 50th and 95th percentile lands on 0.18; the ACES curve, the sRGB
+ * transfer function, ordered dither) and the 8-bit image is written to argv[1] + ".ppm"; the host prints the scale and the call's counters.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -82,7 +85,7 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0;
+  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0;
   phx_adaptive ad;
   memset(&ad, 0, sizeof(ad));
   for (int i = 2; i < argc; ++i)
@@ -96,6 +99,11 @@ int main(int argc, char** argv) {
       if (progressive < 1 || progressive > 1024) progressive = 1;
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
+    } else if (strcmp(argv[i], "display") == 0) {  /* the keyword and, optionally, `auto` */
+      const int take = i + 1 < argc && strcmp(argv[i + 1], "auto") == 0 ? 2 : 1;
+      display = take;
+      for (int k = i; k + take < argc; ++k) argv[k] = argv[k + take];
+      argc -= take; --i;
     } else if (strcmp(argv[i], "denoise") == 0 || strcmp(argv[i], "denoise-guided") == 0) {
       denoise = strcmp(argv[i], "denoise") == 0 ? 1 : 2;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
@@ -246,6 +254,27 @@ int main(int argc, char** argv) {
     for (size_t p = 0; ok && p < (size_t)W * H; ++p) ok = fwrite(film + p * xstride, sizeof(float), 4, f) == 4; /* H x W x 4 whatever the film holds */
     if (!ok) { fprintf(stderr, "cannot write %s\n", argv[1]); return 1; }
     fclose(f);
+  }
+  if (display && argc > 1) { /* the last step: what the other steps left in `film`, 4 bytes a pixel.  Any device serves: the call reads the film, not the scene */
+    phx_display dp;
+    phx_display_summary ds;
+    memset(&dp, 0, sizeof(dp));
+    dp.width = W; dp.height = H; dp.xstride = (uint32_t)xstride;
+    dp.flags = PHX_DISPLAY_DITHER | (display == 2 ? PHX_DISPLAY_AUTO_EXPOSURE : 0); dp.tone = PHX_TONE_ACES; dp.scale = 1.0f;
+    dp.key = 0.18f; dp.low_q16 = 32768; dp.high_q16 = 62259; dp.min_scale = 1.0f / 4096.0f; dp.max_scale = 4096.0f;
+    uint8_t* image = (uint8_t*)malloc((size_t)W * H * 4);
+    char* name = (char*)malloc(strlen(argv[1]) + 5);
+    if (!image || !name) return 1;
+    if (phx_dev_film_display(devs[0], &dp, film, image, &ds, NULL) != PHX_OK) return fail("phx_dev_film_display");
+    printf("display: scale %.9g from_histogram %u pixels %llu invalid %llu unlit %llu counted %llu\n", (double)ds.scale, ds.from_histogram,
+           (unsigned long long)ds.pixels, (unsigned long long)ds.invalid, (unsigned long long)ds.unlit, (unsigned long long)ds.counted);
+    strcpy(name, argv[1]); strcat(name, ".ppm");
+    FILE* f = fopen(name, "wb");
+    int ok = f != NULL && fprintf(f, "P6\n%d %d\n255\n", W, H) > 0;
+    for (size_t p = 0; ok && p < (size_t)W * H; ++p) ok = fwrite(image + 4 * p, 1, 3, f) == 3; /* alpha is dropped */
+    if (!ok) { fprintf(stderr, "cannot write %s\n", name); return 1; }
+    fclose(f);
+    free(name); free(image);
   }
   phx_tiles_free(tiles);
   for (int i = 0; i < num_devices; ++i) phx_dev_destroy(devs[i]);

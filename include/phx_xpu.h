@@ -558,6 +558,67 @@ typedef struct phx_accumulate_summary {
   uint64_t pixels, invalid, converged, samples;
 } phx_accumulate_summary;
 
+/* ---- the display pass: a film's linear radiance -> an 8-bit sRGB image, with the exposure taken from the film itself -------- */
+/* A pass of its own beside the frame (phx_dev_film_display): it reads a finished film of ANY layout (only the first three floats of a pixel,
+ * "primary" rgb), launches none of the frame's kernels and changes no film.  The image is width x height pixels of 4 bytes, R, G, B, 255,
+ * row-major, rows image_pitch bytes apart.  Pixel i is (x, y) = (i mod width, i div width).  Nothing in the rule is implementation-defined:
+ * integer operations, fp32 arithmetic without contraction in the order written, two binary64 steps that are spelled out, and powf_ (the
+ * library's own deterministic pow: a binary64 log and exp kernel of + - * / fma, rounded to fp32 once).
+ * Histogram: made iff PHX_DISPLAY_AUTO_EXPOSURE is set, or summary is given, or histogram is given.
+ *     a pixel is `invalid` when r, g or b is not finite.  Otherwise
+ *     Y = fp32((0.2126 * r + 0.7152 * g) + 0.0722 * b)      in binary64, fp32 inputs widened first: the denoiser's weights in its order
+ *     Y <= 0 counts as `unlit`.  Otherwise
+ *     bin = clamp((bits(Y) >> 20) - 888, 0, 255)            8 bins an octave over [2^-16, 2^16), the ends open-ended, in integer operations
+ *     counted = the sum of the bins = pixels - invalid - unlit
+ *   The counts are 64-bit integers, exact in any order.  A bin is linear inside its octave and is read below as if it were logarithmic: bin
+ *   k stands for 2^((2k + 1) / 16 - 16), the logarithmic middle of [2^(k / 8 - 16), 2^((k + 1) / 8 - 16)), so the estimate can be off by up
+ *   to 0.09 stop.
+ * Exposure (PHX_DISPLAY_AUTO_EXPOSURE; N = counted, C_k = h_0 + ... + h_(k-1)):
+ *     N == 0:  scale := the struct's scale, from_histogram = 0       (a film with no lit pixel)
+ *     otherwise, from_histogram = 1 and
+ *     c_lo = (N * low_q16) >> 16        c_hi = (N * high_q16 + 65535) >> 16            ranks, 64-bit integers
+ *     w_k  = the overlap of bin k's rank range [C_k, C_k + h_k) with [c_lo, c_hi)
+ *     W = sum of w_k                    S = sum of w_k * (2k + 1)
+ *     p = fp32((double)S / (double)(16 * W) - 16.0)                  the mean log2 luminance between the percentiles
+ *     Ybar = powf_(2.0f, p)
+ *     scale = fminf(fmaxf(key / Ybar, min_scale), max_scale)
+ *   Without the flag scale := the struct's scale and from_histogram = 0.
+ * Encode, per colour c of every pixel (an invalid pixel by the same rule: NaN -> 0, +inf -> white), fp32:
+ *     x = scale * v_c;  if !(x > 0) then x = 0  (NaN, negatives, -0, -inf);  x = fminf(x, 65536.0f)
+ *     PHX_TONE_CLAMP:     t = x
+ *     PHX_TONE_REINHARD:  t = (x * (1 + x / (white * white))) / (1 + x)
+ *     PHX_TONE_ACES:      t = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)
+ *     t = fminf(t, 1.0f)
+ *     e = t <= 0.0031308f ? 12.92f * t : 1.055f * powf_(t, 1.0f / 2.4f) - 0.055f                  the sRGB transfer function
+ *     q = 255.0f * e + d       d = 0.5f, or under PHX_DISPLAY_DITHER d = (B[y & 3][x & 3] + 0.5f) / 16.0f with the 4 x 4 ordered matrix
+ *                              B = {{0, 8, 2, 10}, {12, 4, 14, 6}, {3, 11, 1, 9}, {15, 7, 13, 5}}
+ *     code = (uint8_t)(int)q   q lies in [0, 256)
+ * Out of scope: colour management beyond the sRGB curve, hue-preserving and local operators, temporal smoothing of the exposure (feed
+ * summary.scale of one call back as the next one's scale, min_scale and max_scale), outputs of more than 8 bits. */
+enum { PHX_DISPLAY_DITHER = 1, PHX_DISPLAY_AUTO_EXPOSURE = 2 };            /* phx_display.flags */
+enum { PHX_TONE_CLAMP = 0, PHX_TONE_REINHARD = 1, PHX_TONE_ACES = 2 };     /* phx_display.tone */
+typedef struct phx_display {
+  uint32_t width, height;      /* 1 .. 65536 each */
+  uint32_t xstride;            /* floats per film pixel; 3 .. 24.  Only the first three are read */
+  uint32_t image_pitch;        /* bytes per image row; 0 = 4 * width, else a multiple of 4 and >= 4 * width.  Bytes past 4 * width of a row are never written */
+  uint32_t on_device;          /* 0: film and image are host memory, 1: both are device memory (HBM), 2: the film is device memory, the image host memory (the preview) */
+  uint32_t flags;              /* PHX_DISPLAY_*; other bits are refused */
+  uint32_t tone;               /* PHX_TONE_* */
+  float    scale;              /* the exposure multiplier; finite, > 0.  Under AUTO_EXPOSURE the fallback */
+  float    white;              /* PHX_TONE_REINHARD only: finite, > 0 */
+  float    key;                /* AUTO_EXPOSURE only: finite, > 0 */
+  uint32_t low_q16;            /* AUTO_EXPOSURE only: the percentiles in units of 1 / 65536, low_q16 < high_q16 */
+  uint32_t high_q16;           /* <= 65536 */
+  float    min_scale;          /* AUTO_EXPOSURE only: finite, > 0 */
+  float    max_scale;          /* finite, >= min_scale */
+  uint32_t reserved[2];        /* must be 0 */
+} phx_display;
+typedef struct phx_display_summary {
+  uint64_t pixels, invalid, unlit, counted;
+  float    scale;              /* the multiplier the image was encoded with */
+  uint32_t from_histogram;     /* 1: scale came from the histogram, 0: it is the struct's */
+} phx_display_summary;
+
 /* ---- statistics ------------------------------------------------------------------------ */
 /* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
  * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
@@ -789,6 +850,20 @@ int phx_dev_film_accumulate(phx_device* dev, const phx_accumulate* a, float* acc
 /* Times of the last phx_dev_film_accumulate of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the
  * host's clock (the allocations and, for host films, the uploads and the download included). */
 int phx_dev_accumulate_times(const phx_device* dev, double* ms /* 2 */);
+
+/* The display pass (phx_display above states the rule): film, width x height pixels of xstride floats, row-major, becomes image, height
+ * rows of width RGBA8 pixels image_pitch bytes apart; image must be 4-byte aligned, and film and image must not share a byte.  summary and
+ * histogram (256 counts) are host memory whatever on_device says, and either may be NULL.  Synchronous: at most three kernel launches
+ * (histogram, exposure, encode) with no host round trip between them.  It needs a device but no scene.  PHX_ERR_STATE while a frame is
+ * started and not joined; PHX_ERR_ARG, with the field's name in the message, for a value outside the ranges stated at the struct, unknown
+ * flags, a non-zero reserved word, a null or misaligned pointer, or film overlapping image: image, summary and histogram are then
+ * untouched.  Its working memory (the counters and, for host memory, the copies of film and image) is allocated in the call and freed
+ * before it returns (PHX_ERR_OOM if it cannot be had): phx_stats.device_bytes and every later frame are what they were. */
+int phx_dev_film_display(phx_device* dev, const phx_display* p, const float* film, uint8_t* image,
+                         phx_display_summary* summary /* may be NULL */, uint64_t* histogram /* 256, may be NULL */);
+/* Times of the last phx_dev_film_display of this device in milliseconds: ms[0] histogram + exposure and ms[1] the encode (HIP events; 0 for
+ * a stage not run), ms[2] the whole call on the host's clock (the allocations, uploads and the image's download included). */
+int phx_dev_display_times(const phx_device* dev, double* ms /* 3: histogram + exposure, encode, call */);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

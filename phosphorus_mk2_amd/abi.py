@@ -197,6 +197,25 @@ class AccumulateSummary(C.Structure):
     _fields_ = [("pixels", C.c_uint64), ("invalid", C.c_uint64), ("converged", C.c_uint64), ("samples", C.c_uint64)]
 
 
+DISPLAY_DITHER, DISPLAY_AUTO_EXPOSURE = 1, 2  # Display.flags (PHX_DISPLAY_*)
+TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2  # Display.tone (PHX_TONE_*)
+
+
+class Display(C.Structure):
+    """phx_display: the film's and the image's layout, the exposure and the tone curve of the display pass (phx_dev_film_display)"""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32), ("xstride", C.c_uint32), ("image_pitch", C.c_uint32), ("on_device", C.c_uint32),
+        ("flags", C.c_uint32), ("tone", C.c_uint32), ("scale", C.c_float), ("white", C.c_float), ("key", C.c_float),
+        ("low_q16", C.c_uint32), ("high_q16", C.c_uint32), ("min_scale", C.c_float), ("max_scale", C.c_float), ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class DisplaySummary(C.Structure):
+    """phx_display_summary: the counters and the scale of a phx_dev_film_display call"""
+    _fields_ = [("pixels", C.c_uint64), ("invalid", C.c_uint64), ("unlit", C.c_uint64), ("counted", C.c_uint64), ("scale", C.c_float),
+                ("from_histogram", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [
         ("camera_samples", C.c_uint64), ("rays_closest", C.c_uint64), ("rays_shadow", C.c_uint64),
@@ -225,7 +244,7 @@ EXPORTS = [
     "phx_dev_light_sample", "phx_dev_light_emission", "phx_dev_environment_sample", "phx_dev_film_moments",
     "phx_dev_set_adaptive", "phx_dev_adaptive_select", "phx_dev_denoise", "phx_dev_denoise_times",
     "phx_dev_render_guides", "phx_dev_guides_times", "phx_dev_denoise_guided",
-    "phx_dev_film_accumulate", "phx_dev_accumulate_times",
+    "phx_dev_film_accumulate", "phx_dev_accumulate_times", "phx_dev_film_display", "phx_dev_display_times",
 ]
 
 
@@ -267,5 +286,7 @@ def declare(lib):
     lib.phx_dev_denoise_guided.argtypes = [vp, C.POINTER(Denoise), C.POINTER(DenoiseGuides), vp, vp]; lib.phx_dev_denoise_guided.restype = C.c_int
     lib.phx_dev_film_accumulate.argtypes = [vp, C.POINTER(Accumulate), vp, vp, C.POINTER(AccumulateSummary)]; lib.phx_dev_film_accumulate.restype = C.c_int
     lib.phx_dev_accumulate_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_accumulate_times.restype = C.c_int
+    lib.phx_dev_film_display.argtypes = [vp, C.POINTER(Display), vp, vp, C.POINTER(DisplaySummary), C.POINTER(C.c_uint64)]; lib.phx_dev_film_display.restype = C.c_int
+    lib.phx_dev_display_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_display_times.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

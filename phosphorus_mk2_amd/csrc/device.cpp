@@ -338,6 +338,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 13: return sizeof(phx_denoise);  // (12 stays unused: tests/test_adaptive_sampling.py pins it to 0)
     case 15: return sizeof(phx_guides); case 16: return sizeof(phx_denoise_guides);  // (14 likewise: tests/test_denoise.py)
     case 18: return sizeof(phx_accumulate);  // (17 likewise: tests/test_guides.py)
+    case 19: return sizeof(phx_display); case 20: return sizeof(phx_display_summary);
     default: return 0;
   }
 }

@@ -1,12 +1,14 @@
 // film_calls.cpp — the entry points that work on a film and launch no frame: phx_dev_film_moments, phx_dev_denoise / _guided (denoise.hip),
-// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_adaptive_select and the three *_times getters.
+// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the
+// four *_times getters.
 //
-// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp over film_checks.h)
+// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp, display_check.cpp over film_checks.h)
 // and run before the device is selected; what the three large calls share — refusals, device, events, host-film staging, the wait and the
 // times — is FilmCall below.  phx_dev_film_moments and phx_dev_adaptive_select stage plain arrays, as the stage hooks do (Staging).
 #include "device_internal.h"
 #include "accumulate_check.h"
 #include "denoise_check.h"
+#include "display_check.h"
 #include "film_checks.h"
 #include "guides_check.h"
 
@@ -233,6 +235,63 @@ int phx_dev_film_accumulate(phx_device* d, const phx_accumulate* a, float* acc, 
 int phx_dev_accumulate_times(const phx_device* d, double* ms) {
   if (!d || !ms) return fail(PHX_ERR_ARG, "accumulate_times: null argument");
   ms[0] = d->accumulate_ms[0]; ms[1] = d->accumulate_ms[1];
+  return PHX_OK;
+}
+
+// The display pass (phx_display; display.hip).
+// (no stage_hook: the call reads a film and no scene)
+int phx_dev_film_display(phx_device* d, const phx_display* p, const float* film, uint8_t* image, phx_display_summary* summary, uint64_t* histogram) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "display", p != nullptr)) return rc;
+    std::string why;
+    if (const int rc = display_check(*p, film, image, why)) return fail(rc, why);
+    FilmCall call{d, d->display_ms};
+    if (const int rc = call.begin(3)) return rc;
+    const size_t npix = (size_t)p->width * p->height;
+    const bool counts = (p->flags & PHX_DISPLAY_AUTO_EXPOSURE) || summary || histogram;
+    const float* src = film; uint32_t* dst = reinterpret_cast<uint32_t*>(image);
+    DisplayArgs A{};
+    A.num_pixels = npix; A.width = p->width; A.xstride = p->xstride; A.pitch_words = (uint32_t)(display_pitch(*p) / 4u); A.flags = p->flags; A.tone = p->tone;
+    A.scale = p->scale; A.white = p->white; A.key = p->key; A.min_scale = p->min_scale; A.max_scale = p->max_scale; A.low_q16 = p->low_q16; A.high_q16 = p->high_q16;
+    if (p->on_device == 0u) {  // a host film: a device copy
+      float* copy = nullptr;
+      if (const int rc = call.stage(film, npix * p->xstride, nullptr, copy)) return rc;
+      src = copy;
+    }
+    if (p->on_device != 1u) {  // a host image: a device image of 4 * width bytes a row, copied back row by row behind the wait
+      float* words = nullptr;
+      if (const int rc = call.stage(nullptr, npix, nullptr, words)) return rc;
+      dst = reinterpret_cast<uint32_t*>(words); A.pitch_words = p->width;
+    }
+    DevBuf<unsigned long long> slots; DevBuf<DisplayBlock> block;
+    int num_cus = 0;
+    if (counts) {
+      const size_t slot_words = (size_t)PHX_DISPLAY_SLOTS * PHX_DISPLAY_SLOT_WORDS;
+      if (const int rc = slots.alloc(slot_words)) return rc;
+      if (const int rc = block.alloc(1)) return rc;
+      HIPCHK(hipMemsetAsync(slots.p, 0, slot_words * sizeof(unsigned long long), d->stream));
+      HIPCHK(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, d->hip_device));
+    }
+    if (const int rc = call.mark()) return rc;
+    if (counts) launch_display_histogram(d->stream, A, (uint32_t)std::max(num_cus, 1), src, slots.p, block.p);
+    if (const int rc = call.mark()) return rc;
+    launch_display_encode(d->stream, A, src, block.p, dst);
+    if (const int rc = call.mark()) return rc;
+    if (const int rc = call.wait()) return rc;
+    if (p->on_device != 1u) HIPCHK(hipMemcpy2D(image, display_pitch(*p), dst, 4ull * p->width, 4ull * p->width, p->height, hipMemcpyDeviceToHost));
+    if (summary || histogram) {
+      DisplayBlock b;
+      HIPCHK(hipMemcpy(&b, block.p, sizeof b, hipMemcpyDeviceToHost));
+      if (histogram) std::copy(b.histogram, b.histogram + 256, histogram);
+      if (summary) { summary->pixels = b.pixels; summary->invalid = b.invalid; summary->unlit = b.unlit; summary->counted = b.counted; summary->scale = b.scale; summary->from_histogram = b.from_histogram; }
+    }
+    return call.times(2, [](size_t k) { return k; });  // display_ms: 0 histogram + exposure, 1 encode, 2 the call
+  });
+}
+
+int phx_dev_display_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "display_times: null argument");
+  std::copy(std::begin(d->display_ms), std::end(d->display_ms), ms);
   return PHX_OK;
 }
 

@@ -10,6 +10,7 @@
 //   denoise.hip        k_denoise_pack, k_denoise_iteration, k_denoise_unpack: the film denoiser, a post-process no frame launches
 //   guides.hip         k_guides: the first-hit guide film (albedo, coverage, position, distance), a pass of its own no frame launches
 //   accumulate.hip     k_accumulate: pools a finished film into an accumulator film and counts its summary, a pass of its own no frame launches
+//   display.hip        k_display_histogram, k_display_exposure, k_display_encode: a film's radiance to an RGBA8 sRGB image, a pass of its own no frame launches
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
 //
@@ -252,6 +253,29 @@ enum { PHX_ACCUMULATE_SPAN = 256, PHX_ACCUMULATE_SLOTS = 64, PHX_ACCUMULATE_SLOT
 // some 90 atomics a microsecond, and a 2160p film has 32 400 workgroups).  A workgroup adds pixels, invalid, converged, samples
 // (phx_accumulate_summary) to the first four words of slot (workgroup id % SLOTS); the caller sums the slots.
 void launch_accumulate(hipStream_t stream, const AccumulateArgs& A, float* acc, const float* frame_film, unsigned long long* counters);
+
+// The display pass (phx_display in phx_xpu.h states the rule; display.hip, over display_rule.h): up to three launches on one stream
+// with no host round trip between them.
+//   launch_display_histogram  k_display_histogram: a grid sized by the device's compute units (at most PHX_DISPLAY_HIST_MAX_GROUPS workgroups,
+//                             display_check.h) strides over spans of PHX_DISPLAY_SPAN pixels, counts into 258 LDS counters (the 256 bins,
+//                             invalid, unlit) and adds the non-zero ones to slot (workgroup id % PHX_DISPLAY_SLOTS) of `slots`;
+//                             k_display_exposure: one workgroup sums the slots and runs the exposure rule into `block`
+//   launch_display_encode     k_display_encode: a thread per pixel, one 32-bit store per pixel, the scale read from `block` (nullptr: A.scale)
+struct DisplayArgs {
+  uint64_t num_pixels;
+  uint32_t width, xstride, pitch_words /* 32-bit words per image row */, flags, tone;
+  float scale, white, key, min_scale, max_scale;
+  uint32_t low_q16, high_q16;
+};
+enum { PHX_DISPLAY_SPAN = 256, PHX_DISPLAY_SLOTS = 16, PHX_DISPLAY_SLOT_WORDS = 272 /* 258 counts, padded to whole 128-byte lines */ };
+// what k_display_exposure leaves for the encode and for the host (phx_display_summary and the histogram)
+struct DisplayBlock {
+  unsigned long long histogram[256], pixels, invalid, unlit, counted;
+  float scale; uint32_t from_histogram;
+};
+// slots: PHX_DISPLAY_SLOTS * PHX_DISPLAY_SLOT_WORDS zeroed 64-bit words; num_cus: the device's compute units
+void launch_display_histogram(hipStream_t stream, const DisplayArgs& A, uint32_t num_cus, const float* film, unsigned long long* slots, DisplayBlock* block);
+void launch_display_encode(hipStream_t stream, const DisplayArgs& A, const float* film, const DisplayBlock* block, uint32_t* image);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf

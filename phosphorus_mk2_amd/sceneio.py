@@ -312,6 +312,16 @@ def save_pfm(path, rgb):
         f.write(img.tobytes())
 
 
+def save_ppm(path, image):
+    """an 8-bit image (H, W, 3 or 4) uint8, as HipDevice.display returns it, as binary PPM (P6); alpha is dropped.  load_ppm reads it back."""
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError("save_ppm: the image must be (height, width, 3 or 4) uint8")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        f.write(np.ascontiguousarray(img[:, :, :3]).tobytes())
+
+
 def save_exr(path, film):
     """film::file_t::finalize (src/film/file.cpp:27-46) writes the 4-component float image as OpenEXR through OpenImageIO;
     this writes the same image as an uncompressed scanline OpenEXR 2 file (FLOAT channels A, B, G, R; a film without

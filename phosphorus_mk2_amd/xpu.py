@@ -448,6 +448,46 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_accumulate_times(self._h, ms), "phx_dev_accumulate_times")
         return {"kernel": ms[0], "call": ms[1]}
 
+    def display(self, film, exposure=1.0, tone="aces", white=4.0, dither=True, key=0.18, percentiles=(0.5, 0.95), scale_range=(2.0 ** -12, 2.0 ** 12),
+                summary=False, device_ptr=None, image_on_host=True, image_ptr=None, image_pitch=0, fallback=1.0):
+        """The display pass (phx_dev_film_display; include/phx_xpu.h states the rule): film (H, W, xstride) f32 of any layout, of
+        which "primary" rgb is read, -> an (H, W, 4) uint8 image R, G, B, 255: radiance times the exposure, through the tone curve ("clamp",
+        "reinhard" with its `white`, "aces") and the sRGB transfer function, rounded to 8 bits with a 4 x 4 ordered dither (dither=False:
+        plain rounding).  exposure: the multiplier, or "auto": the device takes it from the film's own luminance histogram, so that the
+        logarithmic mean between the two `percentiles` lands on `key`, within scale_range; a film without a lit pixel is shown at `fallback`.
+        summary=True: -> (image, summary), a dict of pixels, invalid, unlit, counted, scale,
+        from_histogram and histogram, the 256 counts.
+        device_ptr: the address of a device-resident film; `film` then is only its shape (H, W, xstride).  With image_on_host (the preview:
+        4 bytes a pixel come back instead of the film) the image is returned as above; otherwise image_ptr is the address of a
+        device-resident image of image_pitch bytes a row (0: 4 * W), and None is returned in the image's place.  Needs no scene."""
+        shape = tuple(film) if device_ptr is not None and not hasattr(film, "shape") else film.shape
+        q = display_settings(shape, exposure, tone, white, dither, key, percentiles, scale_range, fallback)
+        s, h = (abi.DisplaySummary(), (C.c_uint64 * 256)()) if summary else (None, None)
+        if device_ptr is not None and not image_on_host:
+            if image_ptr is None:
+                raise ValueError("display: a device-resident image needs its address (image_ptr)")
+            q.on_device, q.image_pitch = 1, int(image_pitch)
+            src, out, dst = int(device_ptr), None, int(image_ptr)
+        else:
+            if image_ptr is not None:
+                raise ValueError("display: image_ptr is a device address: it needs device_ptr and image_on_host=False")
+            q.on_device = 0 if device_ptr is None else 2
+            keep = None if device_ptr is not None else np.ascontiguousarray(film, np.float32)
+            out = np.empty((q.height, q.width, 4), np.uint8)
+            src, dst = int(device_ptr) if device_ptr is not None else keep.ctypes.data, out.ctypes.data
+        _check(self._lib, self._lib.phx_dev_film_display(self._h, C.byref(q), src, dst, C.byref(s) if summary else None, h), "phx_dev_film_display")
+        if not summary:
+            return out
+        info = {k: int(getattr(s, k)) for k in ("pixels", "invalid", "unlit", "counted", "from_histogram")}
+        info.update(scale=float(s.scale), histogram=np.array(h[:], np.uint64))
+        return out, info
+
+    def display_times(self):
+        """milliseconds of the last display(): dict of histogram (with the exposure) and encode (HIP events) and call (host clock)"""
+        ms = (C.c_double * 3)()
+        _check(self._lib, self._lib.phx_dev_display_times(self._h, ms), "phx_dev_display_times")
+        return {"histogram": ms[0], "encode": ms[1], "call": ms[2]}
+
     # ---- stage-level hooks (parity tests) -------------------------------------------------------
     def adaptive_select(self, acc, samples_done, spp, threshold, floor=0.0, min_samples=16, step=16, active=None, num_active=None):
         """The selection of adaptive sampling behind a round that ended at samples_done of spp samples, on the caller's data
@@ -672,8 +712,41 @@ def accumulate_settings(shape_a, shape_b, spp, primary_components=4, normals=Fal
                           spp_b=int(spp), on_device=0, tau=float(threshold), floor=float(floor))
 
 
+TONES = {"clamp": abi.TONE_CLAMP, "reinhard": abi.TONE_REINHARD, "aces": abi.TONE_ACES}
+
+
+def display_settings(shape, exposure=1.0, tone="aces", white=4.0, dither=True, key=0.18, percentiles=(0.5, 0.95), scale_range=(2.0 ** -12, 2.0 ** 12),
+                     fallback=1.0):
+    """abi.Display for a film of `shape` (H, W, xstride) in host memory and a tightly packed host image (HipDevice.display sets on_device and
+    image_pitch).  exposure: the multiplier, or "auto", which reads key, percentiles (fractions, held in units of 1 / 65536), scale_range
+    and `fallback`, the multiplier of a film without a lit pixel.  ValueError for a shape that is no film or an unknown tone."""
+    if len(shape) != 3:
+        raise ValueError("display: the film must be (height, width, xstride)")
+    H, W, xstride = (int(v) for v in shape)
+    if tone not in TONES:
+        raise ValueError(f"display: tone must be one of {sorted(TONES)}, not {tone!r}")
+    auto = isinstance(exposure, str)
+    if auto and exposure != "auto":
+        raise ValueError(f'display: exposure must be a number or "auto", not {exposure!r}')
+    lo, hi = (int(round(float(v) * 65536.0)) for v in percentiles)
+    return abi.Display(width=W, height=H, xstride=xstride, image_pitch=0, on_device=0,
+                       flags=(abi.DISPLAY_DITHER if dither else 0) | (abi.DISPLAY_AUTO_EXPOSURE if auto else 0), tone=TONES[tone],
+                       scale=float(fallback if auto else exposure), white=float(white), key=float(key), low_q16=lo, high_q16=hi,
+                       min_scale=float(scale_range[0]), max_scale=float(scale_range[1]))
+
+
+def display(film, **settings):
+    """HipDevice.display on a device made for the call (no scene is needed) and closed behind it: film (H, W, xstride) f32 -> (H, W, 4) uint8,
+    or (image, summary) with summary=True."""
+    dev = HipDevice.make(Options(samples_per_pixel=1, paths_per_sample=1, path_depth=1))
+    try:
+        return dev.display(film, **settings)
+    finally:
+        dev.close()
+
+
 def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None, adaptive=None, pps=1, depth=9, normals=False, tile_size=32,
-                       **options):
+                       display=None, **options):
     """Progressive rendering on ONE device: the scene is preprocessed once, then frame k = 0, 1, ... is rendered at `spp` samples
     with sampler seed (seed + k) mod 2^64 and moments=True and pooled into an accumulator film (HipDevice.accumulate).  A generator: after
     every frame it yields (film, summary, frames_done); film is the accumulator (H, W, xstride) f32 in xpu.accumulator's layout, a view that
@@ -682,7 +755,9 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
     None without stop.
     denoise: a dict of HipDevice.denoise's settings; the yielded film then is a denoised COPY, the accumulator itself is never filtered.
     Its entry guides=dict(samples=4, ...) renders the guide film once, with the first frame's seed.  adaptive: a dict of
-    HipDevice.set_adaptive's arguments for every frame.  options: further Options fields (samples_in_flight=, light_sampling=, ...)."""
+    HipDevice.set_adaptive's arguments for every frame.  display: a dict of HipDevice.display's settings ({} for the defaults); the generator
+    then yields (film, summary, frames_done, image), the image (or (image, summary) under summary=True) of the film it yields: with denoise,
+    of the denoised copy.  options: further Options fields (samples_in_flight=, light_sampling=, ...)."""
     if frames < 1:
         raise ValueError("render_progressive: frames must be at least 1")
     stop = dict(stop) if stop is not None else None
@@ -710,7 +785,10 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
             dev.join()
             _, summary = dev.accumulate(acc, film.data, spp, 4, normals, adaptive is not None, **(stop or {}))
             out = acc if settings is None else dev.denoise(acc, spp, 4, normals, True, guides=guides, **settings)
-            yield out, summary, k + 1
+            if display is None:
+                yield out, summary, k + 1
+            else:
+                yield out, summary, k + 1, dev.display(out, **display)
             valid = summary["pixels"] - summary["invalid"] if summary is not None else 0
             if valid > 0 and summary["converged"] >= coverage * valid:  # (a film without one valid pixel, as any film of 1 spp, has not converged)
                 return
