@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K] [display [auto]]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K] [display [auto]] [orbit K]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -26,6 +26,10 @@
  * display [auto]: after every other step the film at hand goes through the display pass (phx_dev_film_display: exposure 1, or with `auto` taken from
  * the film's own luminance histogram so that its logarithmic mean between the 50th and 95th percentile lands on 0.18; the ACES curve, the sRGB
  * transfer function, ordered dither) and the 8-bit image is written to argv[1] + ".ppm"; the host prints the scale and the call's counters.
+ * orbit K: instead of the steps above, K cameras on an arc about the room's middle, one frame of 8 samples each at seeds 7, 8, ... on ONE device that
+ * preprocessed once: per camera phx_dev_set_camera, the guide film (phx_dev_render_guides), from the second camera on phx_dev_film_reproject of the
+ * accumulator (the host prints its summary), the frame, phx_dev_film_accumulate and the display pass into argv[1] + ".orbit<k>.ppm" (DESIGN 22).
+ * The last accumulator is what is written to argv[1].
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -43,6 +47,77 @@
 static int fail(const char* what) {
   fprintf(stderr, "%s: %s\n", what, phx_last_error());
   return 1;
+}
+
+/* orbit K on a device that has preprocessed `scene`: see the head of the file.  Frames carry normals and the error estimate (10 floats a pixel),
+ * the accumulator also "samples" (11): the layouts phx_reproject reads. */
+static int orbit(phx_device* dev, const phx_scene* scene, const phx_options* opt, int count, const char* path) {
+  const size_t xf = 10, xa = 11, npix = (size_t)W * H;
+  float* film = (float*)calloc(npix * xf, sizeof(float));
+  float* acc = (float*)calloc(npix * xa, sizeof(float));
+  float* next = (float*)calloc(npix * xa, sizeof(float));
+  float* guides[2] = {(float*)calloc(npix * 8, sizeof(float)), (float*)calloc(npix * 8, sizeof(float))};
+  uint8_t* image = (uint8_t*)malloc(npix * 4);
+  char* name = (char*)malloc(strlen(path) + 32);
+  phx_tiles* tiles = phx_tiles_make(W, H, 32, 0, 1);
+  if (!film || !acc || !next || !guides[0] || !guides[1] || !image || !name || !tiles) return 1;
+  phx_camera before = scene->camera;
+  for (int k = 0; k < count; ++k) {
+    phx_camera cam = scene->camera; /* on an arc about (0, 0, -3), looking at it: rows of to_world are the camera's axes, then its origin */
+    const float a = 0.08f * (float)k, c = cosf(a), s = sinf(a);
+    memset(cam.to_world, 0, sizeof(cam.to_world));
+    cam.to_world[0] = c; cam.to_world[2] = -s; cam.to_world[5] = 1.0f; cam.to_world[8] = s; cam.to_world[10] = c; cam.to_world[15] = 1.0f;
+    cam.to_world[12] = 3.0f * s; cam.to_world[14] = -3.0f + 3.0f * c;
+    if (phx_dev_set_camera(dev, &cam) != PHX_OK) return fail("phx_dev_set_camera");
+    phx_guides gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.sampler_seed = 7 + (uint64_t)k; gp.samples = 4;
+    if (phx_dev_render_guides(dev, &gp, guides[k & 1]) != PHX_OK) return fail("phx_dev_render_guides");
+    if (k > 0) { /* carry the accumulator to this camera */
+      phx_reproject rp;
+      phx_reproject_summary rs;
+      memset(&rp, 0, sizeof(rp));
+      rp.width = W; rp.height = H; rp.xstride_a = (uint32_t)xa; rp.normals_offset_a = 4; rp.m2_offset_a = 7; rp.samples_offset_a = 10; rp.xstride_g = 8;
+      rp.from = before; rp.to = cam; rp.sigma_plane = 1.0f; rp.sigma_dist = 4.0f; rp.max_history = 64;
+      if (phx_dev_film_reproject(dev, &rp, acc, guides[(k - 1) & 1], guides[k & 1], next, &rs) != PHX_OK) return fail("phx_dev_film_reproject");
+      printf("orbit: camera %d reused %llu no_geometry %llu disoccluded %llu of %llu samples %llu\n", k + 1, (unsigned long long)rs.reused,
+             (unsigned long long)rs.no_geometry, (unsigned long long)rs.disoccluded, (unsigned long long)rs.pixels, (unsigned long long)rs.samples);
+      float* t = acc; acc = next; next = t;
+    }
+    phx_frame frame;
+    memset(&frame, 0, sizeof(frame));
+    memset(film, 0, npix * xf * sizeof(float));
+    phx_tiles_reset(tiles);
+    frame.tiles_user = tiles; frame.next_tile = phx_tiles_next; frame.sampler_seed = 7 + (uint64_t)k; frame.primary_components = 4;
+    frame.normals_channel = 1; frame.moments_channel = 1; frame.host_film = film;
+    if (phx_dev_start(dev, &frame) != PHX_OK) return fail("phx_dev_start");
+    if (phx_dev_join(dev) != PHX_OK) return fail("phx_dev_join");
+    phx_accumulate pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.width = W; pa.height = H; pa.xstride_a = (uint32_t)xa; pa.normals_offset_a = 4; pa.m2_offset_a = 7; pa.samples_offset_a = 10;
+    pa.xstride_b = (uint32_t)xf; pa.normals_offset_b = 4; pa.m2_offset_b = 7; pa.spp_b = opt->samples_per_pixel;
+    if (phx_dev_film_accumulate(dev, &pa, acc, film, NULL) != PHX_OK) return fail("phx_dev_film_accumulate");
+    phx_display dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.width = W; dp.height = H; dp.xstride = (uint32_t)xa; dp.flags = PHX_DISPLAY_DITHER; dp.tone = PHX_TONE_ACES; dp.scale = 1.0f;
+    dp.key = 0.18f; dp.low_q16 = 32768; dp.high_q16 = 62259; dp.min_scale = 1.0f / 4096.0f; dp.max_scale = 4096.0f;
+    if (phx_dev_film_display(dev, &dp, acc, image, NULL, NULL) != PHX_OK) return fail("phx_dev_film_display");
+    sprintf(name, "%s.orbit%d.ppm", path, k + 1);
+    FILE* f = fopen(name, "wb");
+    int ok = f != NULL && fprintf(f, "P6\n%d %d\n255\n", W, H) > 0;
+    for (size_t p = 0; ok && p < npix; ++p) ok = fwrite(image + 4 * p, 1, 3, f) == 3; /* alpha is dropped */
+    if (!ok) { fprintf(stderr, "cannot write %s\n", name); return 1; }
+    fclose(f);
+    before = cam;
+  }
+  FILE* f = fopen(path, "wb");
+  int ok = f != NULL;
+  for (size_t p = 0; ok && p < npix; ++p) ok = fwrite(acc + p * xa, sizeof(float), 4, f) == 4;
+  if (!ok) { fprintf(stderr, "cannot write %s\n", path); return 1; }
+  fclose(f);
+  phx_tiles_free(tiles);
+  free(film); free(acc); free(next); free(guides[0]); free(guides[1]); free(image); free(name);
+  return 0;
 }
 
 int main(int argc, char** argv) {
@@ -85,7 +160,7 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0;
+  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0, orbit_cameras = 0;
   phx_adaptive ad;
   memset(&ad, 0, sizeof(ad));
   for (int i = 2; i < argc; ++i)
@@ -97,6 +172,11 @@ int main(int argc, char** argv) {
     } else if (strcmp(argv[i], "progressive") == 0 && i + 1 < argc) {
       progressive = atoi(argv[i + 1]);
       if (progressive < 1 || progressive > 1024) progressive = 1;
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
+    } else if (strcmp(argv[i], "orbit") == 0 && i + 1 < argc) {
+      orbit_cameras = atoi(argv[i + 1]);
+      if (orbit_cameras < 1 || orbit_cameras > 1024) orbit_cameras = 1;
       for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
       argc -= 2; --i;
     } else if (strcmp(argv[i], "display") == 0) {  /* the keyword and, optionally, `auto` */
@@ -151,6 +231,11 @@ int main(int argc, char** argv) {
     if (adaptive && phx_dev_set_adaptive(devs[i], &ad) != PHX_OK) return fail("phx_dev_set_adaptive"); /* the setting is the device's, not the frame's */
   }
 
+  if (orbit_cameras) { /* a path of cameras on the first device, in place of the one frame below */
+    const int rc = argc > 1 ? orbit(devs[0], &scene, &opt, orbit_cameras, argv[1]) : 1;
+    for (int i = 0; i < num_devices; ++i) phx_dev_destroy(devs[i]);
+    return rc;
+  }
   if (adaptive || denoise || progressive) error_estimate = 1; /* the stopping rule, the denoiser and the pooling read the estimate: such a frame must carry it */
   int has_samples = adaptive; /* the film at hand carries the channel "samples" at float 7 */
   size_t xstride = 4 + (error_estimate ? 3 : 0) + (adaptive ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */

@@ -427,7 +427,8 @@ typedef struct phx_adaptive {
  * The delta form makes a constant neighbourhood exact; a film whose m2 is zero everywhere averages only pixels of EQUAL luminance.
  * Limits: V' treats the pixels as independent and ignores the blur's bias, so it understates the true error (tenfold and more);
  * the biweight rejects bright outliers, so the film's mean drops where the frame has fireflies; there is no depth or albedo guide: textures
- * and coplanar depth edges are protected by luminance alone; nothing is temporal; a multi-GPU film must be reduced before the call (a
+ * and coplanar depth edges are protected by luminance alone; nothing is temporal here (what carries a film across a camera move is
+ * phx_reproject); a multi-GPU film must be reduced before the call (a
  * rank's own film holds zeros in the pixels it does not own). */
 typedef struct phx_denoise {
   uint32_t width, height;      /* 1 .. 65536 each */
@@ -619,6 +620,79 @@ typedef struct phx_display_summary {
   uint32_t from_histogram;     /* 1: scale came from the histogram, 0: it is the struct's */
 } phx_display_summary;
 
+/* ---- reprojection: carrying an accumulator film from one camera of a static scene to another ------------------------------- */
+/* A pass of its own beside the frame (phx_dev_film_reproject): it reads the accumulator under the old camera (acc_from), the guide films
+ * (phx_guides) under the old and the new camera (guides_from, guides_to) and the two cameras; it writes EVERY float of acc_to, a film of
+ * acc_from's layout.  It reads no scene, launches none of the frame's kernels and changes no frame.  The layout fields are those of
+ * phx_accumulate's acc ("primary", "normals", "m2", "samples"; here the normals are required: the plane test reads them); both guide films
+ * have 8 floats a pixel at xstride_g floats apart.  All four films are width x height pixels, row-major, in the same memory space.
+ * All arithmetic is binary64, without contraction, in the order written; fp32 inputs are widened first; a result is rounded to fp32 once,
+ * where fp32(...) says so.
+ * Cameras (derived once, on the host, for `from` and `to` alike; M = to_world, row-vector convention, M[4 * i + j] = x[i][j]):
+ *     O     = (M[12], M[13], M[14])                                      the origin; a lens camera is projected as the pinhole through O
+ *     a b c = M[0] M[1] M[2];  d e f = M[4] M[5] M[6];  g h k = M[8] M[9] M[10]
+ *     A = e * k - f * h;   B = f * g - d * k;   C = d * h - e * g;       det = (a * A + b * B) + c * C
+ *     I     = | A / det   (c * h - b * k) / det   (b * f - c * e) / det |    the inverse of the upper 3 x 3: adjugate over determinant
+ *             | B / det   (a * k - c * g) / det   (c * d - a * f) / det |
+ *             | C / det   (b * g - a * h) / det   (a * e - b * d) / det |
+ *     zoom  = 1.12 * tan((double)fov * 0.5)       ratio = W / H       W = (double)film_width, H = (double)film_height
+ *   det == 0, or a non-finite det, O, I or zoom, or zoom == 0, is refused ("from" / "to"), as is a film size other than width x height.
+ *   What is inverted is the camera ray of the frame (camera.hpp:113-139): camera-space direction (nx * ratio * zoom, ny * zoom, -1) through
+ *   M.  The frame's own zoom and ratio are fp32; the difference cancels below, like everything that both projections share.
+ *     project(K, X):   D = X - O_K (per component);   c_j = (D_x * I_0j + D_y * I_1j) + D_z * I_2j,  j = x, y, z
+ *                      behind the camera unless c_z < 0 (a NaN is behind it).  t = -c_z
+ *                      fx = ((c_x / t) / (ratio * zoom) + 0.5) * W;    fy = (0.5 - (c_y / t) / zoom) * H
+ * Output pixel p = (x, y), G = its 8 floats of guides_to:
+ *   no history      every float of acc_to's pixel := 0.  (phx_accumulate's n_a == 0 case then makes the next frame the copy there.)
+ *   coverage_p > 0 is false (the sky, a NaN):  no history, counted as no_geometry.  Otherwise X = G's position and
+ *     project(from, X), project(to, X); X behind either camera: no history (counted, like every case below, as disoccluded)
+ *     sx = x + (fx_from - fx_to);   sy = y + (fy_from - fy_to)         motion, not position: under from == to, sx == x and sy == y exactly,
+ *                                                                      wherever inside the pixel the mean hit position lies
+ *     unless sx > -1 && sx < W && sy > -1 && sy < H (false for a NaN):  no history
+ *     x0 = floor(sx);  y0 = floor(sy);  tx = sx - x0;  ty = sy - y0
+ *   taps, in this order:  (x0, y0) w = (1 - tx) * (1 - ty);  (x0 + 1, y0) w = tx * (1 - ty);  (x0, y0 + 1) w = (1 - tx) * ty;
+ *                         (x0 + 1, y0 + 1) w = tx * ty
+ *     A tap q counts only if  w > 0;  q is inside the film;  acc_from's pixel q is valid by phx_denoise's definition with its own samples
+ *     (primary rgb, m2 and N finite, every m2 >= 0, n finite and >= 2);  q's 8 floats of guides_from are finite;  coverage_q > 0;  and q
+ *     is the same surface:  with dX = X - position_q (per component), N = q's normal in acc_from and
+ *         tol = plane_scale_from * distance_q        plane_scale_from = zoom_from / H: a pixel's world size at unit distance
+ *         r = (N_x * dX_x + N_y * dX_y) + N_z * dX_z;          fabs(r) <= sigma_plane * tol
+ *         dd = (dX_x * dX_x + dX_y * dX_y) + dX_z * dX_z;      lim = sigma_dist * tol;   dd <= lim * lim
+ *     (a NaN fails either test).  No tap counts: no history.
+ *   result, over the taps that count, in tap order; every sum STARTS AT its first term (not at 0.0):
+ *     Wsum = sum of w_i;   u_i = w_i / Wsum
+ *     n   = sum of u_i * n_i;   V_c = sum of u_i * V_i,c;   m_c = sum of (u_i * u_i) * m2_i,c      the denoiser's B / W^2: taps as independent
+ *     n_out = min(n, (double)max_history);   if n > n_out:  m_c = m_c * (n / n_out)     the history claims no more confidence than
+ *                                                                                      max_history samples of the same spread
+ *     primary rgb = fp32(V_c);   m2 = fp32(m_c);   samples = fp32(n_out)
+ *     every other float of the pixel (the normals, a fourth component of primary, ...) is that of the counting tap of largest w, ties to
+ *     the first in tap order.
+ *   So one tap of weight 1 with n <= max_history is the copy of acc_from's pixel bit for bit (u = 1; 1 * v == v, -0 included), and a
+ *   non-finite value of a pixel of acc_from or guides_from makes that pixel no tap and reaches no other pixel.
+ * summary (optional), integers counted in the same launch, exact in any order:  pixels = width * height = reused + no_geometry +
+ *   disoccluded;  samples = the sum over the reused pixels of (uint64_t) of the "samples" float written, truncated, modulo 2^64.
+ * Limits: view-dependent shading (glossy, mirror, glass) is carried as if it were diffuse; the sky and whatever is seen through a specular
+ * path get no history (the guides hold the FIRST hit); the lens is projected as a pinhole, so out-of-focus regions smear; m2 of a bilinear
+ * mix treats the taps as independent and understates the variance of the result; objects do not move; nothing clamps the history against
+ * the new frame; the film size cannot change with the camera; a multi-GPU film is reduced first. */
+typedef struct phx_reproject {
+  uint32_t   width, height;      /* 1 .. 65536 each */
+  uint32_t   xstride_a;          /* floats per pixel of acc_from and acc_to; 10 .. 24 */
+  uint32_t   normals_offset_a;   /* required: >= 3, normals_offset_a + 3 <= xstride_a */
+  uint32_t   m2_offset_a;        /* required: >= 3, m2_offset_a + 3 <= xstride_a */
+  uint32_t   samples_offset_a;   /* required: >= 3, < xstride_a */
+  uint32_t   xstride_g;          /* floats per pixel of guides_from and guides_to; 8 .. 64 */
+  uint32_t   on_device;          /* 0: the four films are host memory, 1: all are device memory (HBM) */
+  phx_camera from, to;           /* film_width x film_height of both must be width x height */
+  float      sigma_plane;        /* finite, > 0: the tangent-plane tolerance in pixels' worth of surface */
+  float      sigma_dist;         /* finite, > 0: the distance tolerance, likewise */
+  uint32_t   max_history;        /* >= 2: the most samples a reprojected pixel may claim */
+  uint32_t   reserved[3];        /* must be 0 */
+} phx_reproject;
+typedef struct phx_reproject_summary {
+  uint64_t pixels, reused, no_geometry, disoccluded, samples;
+} phx_reproject_summary;
+
 /* ---- statistics ------------------------------------------------------------------------ */
 /* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
  * phx_stats::shade_kernels has bit (family * PHX_SHADE_PASSES + pass) set for every one the last frame launched. */
@@ -726,6 +800,13 @@ int         phx_dev_get_stats(const phx_device* dev, phx_stats* out);
  * scene.  PHX_ERR_STATE while a frame is started and not yet joined; PHX_ERR_ARG, with the field's name in the message, for a value outside
  * the ranges stated at the struct or a non-zero reserved word: the previous setting then stays in force. */
 int         phx_dev_set_adaptive(phx_device* dev, const phx_adaptive* a /* NULL: off */);
+/* Replaces the camera of the preprocessed scene and nothing else: no validation of the scene, no tree, no upload.  Every later
+ * frame, guide pass and stage hook is what it would be on a device preprocessed with the same scene under this camera, bit for bit: the
+ * kernels rebuild their camera rays from the camera's fields on each launch and pick the lens or pinhole instantiation then.
+ * PHX_ERR_STATE without a preprocessed scene and while a frame is started and not joined; PHX_ERR_ARG for a camera phx_dev_preprocess would
+ * refuse, with its text, and for a film_width or film_height other than the preprocessed scene's (the film, the tile plan and the pixel
+ * tables are sized by them).  A refused call leaves the device as it was. */
+int         phx_dev_set_camera(phx_device* dev, const phx_camera* camera);
 
 /* ---- native tile queue: job::tiles_t (src/jobs/tiles.hpp:10-90) ----------------------- */
 /* make(): row-major tile_size x tile_size tiles with edge remainders (tiles.hpp:49-89);
@@ -864,6 +945,19 @@ int phx_dev_film_display(phx_device* dev, const phx_display* p, const float* fil
 /* Times of the last phx_dev_film_display of this device in milliseconds: ms[0] histogram + exposure and ms[1] the encode (HIP events; 0 for
  * a stage not run), ms[2] the whole call on the host's clock (the allocations, uploads and the image's download included). */
 int phx_dev_display_times(const phx_device* dev, double* ms /* 3: histogram + exposure, encode, call */);
+
+/* Reprojection (phx_reproject above states the rule): acc_from, guides_from and guides_to are read, every float of acc_to is written;
+ * summary may be NULL.  Synchronous, one kernel launch.  It needs a device but no scene.  PHX_ERR_STATE while a frame is started and not
+ * joined; PHX_ERR_ARG, with the field's name in the message, for a value outside the ranges stated at the struct, channels that overlap
+ * "primary" or each other, a camera whose film is not width x height or whose matrix is singular or not finite ("from" / "to"), a
+ * non-zero reserved word, a null pointer, or acc_to sharing a byte with any of the three inputs: acc_to is then untouched.  Its working
+ * memory (the counters and, for host films, the four films' copies) is allocated in the call and freed before it returns (PHX_ERR_OOM if
+ * it cannot be had): phx_stats.device_bytes and every later frame are what they were. */
+int phx_dev_film_reproject(phx_device* dev, const phx_reproject* r, const float* acc_from, const float* guides_from, const float* guides_to,
+                           float* acc_to, phx_reproject_summary* summary /* may be NULL */);
+/* Times of the last phx_dev_film_reproject of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the
+ * host's clock (the allocations and, for host films, the uploads and the download included). */
+int phx_dev_reproject_times(const phx_device* dev, double* ms /* 2 */);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

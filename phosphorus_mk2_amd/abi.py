@@ -197,6 +197,21 @@ class AccumulateSummary(C.Structure):
     _fields_ = [("pixels", C.c_uint64), ("invalid", C.c_uint64), ("converged", C.c_uint64), ("samples", C.c_uint64)]
 
 
+class Reproject(C.Structure):
+    """phx_reproject: the accumulator films' and the guide films' layout, the two cameras and the settings of phx_dev_film_reproject"""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("xstride_a", C.c_uint32), ("normals_offset_a", C.c_uint32), ("m2_offset_a", C.c_uint32), ("samples_offset_a", C.c_uint32),
+        ("xstride_g", C.c_uint32), ("on_device", C.c_uint32), ("from", Camera), ("to", Camera),  # (`from` is a keyword: getattr(q, "from"))
+        ("sigma_plane", C.c_float), ("sigma_dist", C.c_float), ("max_history", C.c_uint32), ("reserved", C.c_uint32 * 3),
+    ]
+
+
+class ReprojectSummary(C.Structure):
+    """phx_reproject_summary: the counters of a phx_dev_film_reproject call"""
+    _fields_ = [("pixels", C.c_uint64), ("reused", C.c_uint64), ("no_geometry", C.c_uint64), ("disoccluded", C.c_uint64), ("samples", C.c_uint64)]
+
+
 DISPLAY_DITHER, DISPLAY_AUTO_EXPOSURE = 1, 2  # Display.flags (PHX_DISPLAY_*)
 TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2  # Display.tone (PHX_TONE_*)
 
@@ -245,6 +260,7 @@ EXPORTS = [
     "phx_dev_set_adaptive", "phx_dev_adaptive_select", "phx_dev_denoise", "phx_dev_denoise_times",
     "phx_dev_render_guides", "phx_dev_guides_times", "phx_dev_denoise_guided",
     "phx_dev_film_accumulate", "phx_dev_accumulate_times", "phx_dev_film_display", "phx_dev_display_times",
+    "phx_dev_set_camera", "phx_dev_film_reproject", "phx_dev_reproject_times",
 ]
 
 
@@ -288,5 +304,8 @@ def declare(lib):
     lib.phx_dev_accumulate_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_accumulate_times.restype = C.c_int
     lib.phx_dev_film_display.argtypes = [vp, C.POINTER(Display), vp, vp, C.POINTER(DisplaySummary), C.POINTER(C.c_uint64)]; lib.phx_dev_film_display.restype = C.c_int
     lib.phx_dev_display_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_display_times.restype = C.c_int
+    lib.phx_dev_set_camera.argtypes = [vp, C.POINTER(Camera)]; lib.phx_dev_set_camera.restype = C.c_int
+    lib.phx_dev_film_reproject.argtypes = [vp, C.POINTER(Reproject), vp, vp, vp, vp, C.POINTER(ReprojectSummary)]; lib.phx_dev_film_reproject.restype = C.c_int
+    lib.phx_dev_reproject_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_reproject_times.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

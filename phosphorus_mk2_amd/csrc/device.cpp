@@ -275,6 +275,23 @@ int phx_dev_preprocess(phx_device* d, const phx_scene* s) {
   });
 }
 
+// The camera is nine host-side words of d->scene (scene_flatten.cpp: flatten_camera) and nothing on the device: every launch takes the
+// scene by value, rebuilds its camera rays from those words and picks its lens or pinhole instantiation then (launch_trace_primary,
+// launch_shade, launch_guides); trace_plan reads the tree alone, and the pixel, tile and jitter tables the film's size and the seed.
+int phx_dev_set_camera(phx_device* d, const phx_camera* c) {
+  return guarded([&]() -> int {
+    if (!d || !c) return fail(PHX_ERR_ARG, "set_camera: null argument");
+    if (!d->preprocessed) return fail(PHX_ERR_STATE, "set_camera before preprocess");
+    if (d->running) return fail(PHX_ERR_STATE, "set_camera while a frame is running");
+    DevScene sc = d->scene; std::string why;
+    if (const int rc = flatten_camera(*c, sc, why)) return fail(rc, why);
+    if (sc.width != d->scene.width || sc.height != d->scene.height)
+      return fail(PHX_ERR_ARG, "set_camera: the film size must stay the preprocessed scene's (" + std::to_string(d->scene.width) + " x " + std::to_string(d->scene.height) + ")");
+    d->scene = sc;
+    return PHX_OK;
+  });
+}
+
 int phx_dev_start(phx_device* d, const phx_frame* f) {
   if (!d || !f) return fail(PHX_ERR_ARG, "start: null argument");
   if (!d->preprocessed) return fail(PHX_ERR_STATE, "start before preprocess");
@@ -339,6 +356,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 15: return sizeof(phx_guides); case 16: return sizeof(phx_denoise_guides);  // (14 likewise: tests/test_denoise.py)
     case 18: return sizeof(phx_accumulate);  // (17 likewise: tests/test_guides.py)
     case 19: return sizeof(phx_display); case 20: return sizeof(phx_display_summary);
+    case 21: return sizeof(phx_reproject); case 22: return sizeof(phx_reproject_summary);
     default: return 0;
   }
 }

@@ -1,9 +1,9 @@
 // film_calls.cpp — the entry points that work on a film and launch no frame: phx_dev_film_moments, phx_dev_denoise / _guided (denoise.hip),
-// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the
-// four *_times getters.
+// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_reproject (reproject.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the
+// five *_times getters.
 //
-// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp, display_check.cpp over film_checks.h)
-// and run before the device is selected; what the three large calls share — refusals, device, events, host-film staging, the wait and the
+// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp, display_check.cpp, reproject_check.cpp over film_checks.h)
+// and run before the device is selected; what the large calls share — refusals, device, events, host-film staging, the wait and the
 // times — is FilmCall below.  phx_dev_film_moments and phx_dev_adaptive_select stage plain arrays, as the stage hooks do (Staging).
 #include "device_internal.h"
 #include "accumulate_check.h"
@@ -11,6 +11,7 @@
 #include "display_check.h"
 #include "film_checks.h"
 #include "guides_check.h"
+#include "reproject_check.h"
 
 using namespace phx;
 
@@ -235,6 +236,58 @@ int phx_dev_film_accumulate(phx_device* d, const phx_accumulate* a, float* acc, 
 int phx_dev_accumulate_times(const phx_device* d, double* ms) {
   if (!d || !ms) return fail(PHX_ERR_ARG, "accumulate_times: null argument");
   ms[0] = d->accumulate_ms[0]; ms[1] = d->accumulate_ms[1];
+  return PHX_OK;
+}
+
+// Reprojection (phx_reproject; reproject.hip).
+// (no stage_hook: the call reads four films and two cameras of its own, and no scene)
+int phx_dev_film_reproject(phx_device* d, const phx_reproject* r, const float* acc_from, const float* guides_from, const float* guides_to, float* acc_to,
+                           phx_reproject_summary* summary) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "reproject", r != nullptr)) return rc;
+    std::string why;
+    ReprojectArgs A{};
+    if (const int rc = reproject_check(*r, acc_from, guides_from, guides_to, acc_to, A.from, A.to, why)) return fail(rc, why);
+    FilmCall call{d, d->reproject_ms};
+    if (const int rc = call.begin(2)) return rc;
+    const size_t npix = (size_t)r->width * r->height;
+    const size_t slot_words = (size_t)PHX_REPROJECT_SLOTS * PHX_REPROJECT_SLOT_WORDS;
+    DevBuf<unsigned long long> counters;
+    const float *src = acc_from, *gf = guides_from, *gt = guides_to; float* dst = acc_to;
+    if (!r->on_device) {  // host films: device copies of the three inputs, and acc_to's copied back behind the wait
+      float *c0 = nullptr, *c1 = nullptr, *c2 = nullptr;
+      if (const int rc = call.stage(acc_from, npix * r->xstride_a, nullptr, c0)) return rc;
+      if (const int rc = call.stage(guides_from, npix * r->xstride_g, nullptr, c1)) return rc;
+      if (const int rc = call.stage(guides_to, npix * r->xstride_g, nullptr, c2)) return rc;
+      if (const int rc = call.stage(nullptr, npix * r->xstride_a, acc_to, dst)) return rc;
+      src = c0; gf = c1; gt = c2;
+    }
+    if (summary) {
+      if (const int rc = counters.alloc(slot_words)) return rc;
+      HIPCHK(hipMemsetAsync(counters.p, 0, slot_words * sizeof(unsigned long long), d->stream));
+    }
+    A.num_pixels = npix; A.width = r->width; A.height = r->height;
+    A.xstride_a = r->xstride_a; A.normals_offset_a = r->normals_offset_a; A.m2_offset_a = r->m2_offset_a; A.samples_offset_a = r->samples_offset_a;
+    A.xstride_g = r->xstride_g;
+    A.sigma_plane = (double)r->sigma_plane; A.sigma_dist = (double)r->sigma_dist; A.max_history = (double)r->max_history;
+    if (const int rc = call.mark()) return rc;
+    launch_reproject(d->stream, A, src, gf, gt, dst, counters.p);
+    if (const int rc = call.mark()) return rc;
+    if (const int rc = call.wait()) return rc;
+    if (summary) {
+      std::vector<unsigned long long> slots(slot_words);
+      HIPCHK(hipMemcpy(slots.data(), counters.p, slot_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      unsigned long long c[5] = {0ull, 0ull, 0ull, 0ull, 0ull};  // integers, modulo 2^64: whatever the order, the same sums
+      for (size_t s = 0; s < (size_t)PHX_REPROJECT_SLOTS; ++s) for (int k = 0; k < 5; ++k) c[k] += slots[s * PHX_REPROJECT_SLOT_WORDS + k];
+      summary->pixels = c[0]; summary->reused = c[1]; summary->no_geometry = c[2]; summary->disoccluded = c[3]; summary->samples = c[4];
+    }
+    return call.kernel_and_call_times();
+  });
+}
+
+int phx_dev_reproject_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "reproject_times: null argument");
+  ms[0] = d->reproject_ms[0]; ms[1] = d->reproject_ms[1];
   return PHX_OK;
 }
 

@@ -10,6 +10,7 @@
 //   denoise.hip        k_denoise_pack, k_denoise_iteration, k_denoise_unpack: the film denoiser, a post-process no frame launches
 //   guides.hip         k_guides: the first-hit guide film (albedo, coverage, position, distance), a pass of its own no frame launches
 //   accumulate.hip     k_accumulate: pools a finished film into an accumulator film and counts its summary, a pass of its own no frame launches
+//   reproject.hip      k_reproject: carries an accumulator film from one camera to another by the guide films' first hits, a pass of its own no frame launches
 //   display.hip        k_display_histogram, k_display_exposure, k_display_encode: a film's radiance to an RGBA8 sRGB image, a pass of its own no frame launches
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
@@ -28,6 +29,7 @@
 #pragma once
 #include "bsdf.h"
 #include "bvh8.h"
+#include "reproject_check.h"  // ReprojectCamera (host-only)
 
 #include <hip/hip_runtime.h>
 
@@ -276,6 +278,22 @@ struct DisplayBlock {
 // slots: PHX_DISPLAY_SLOTS * PHX_DISPLAY_SLOT_WORDS zeroed 64-bit words; num_cus: the device's compute units
 void launch_display_histogram(hipStream_t stream, const DisplayArgs& A, uint32_t num_cus, const float* film, unsigned long long* slots, DisplayBlock* block);
 void launch_display_encode(hipStream_t stream, const DisplayArgs& A, const float* film, const DisplayBlock* block, uint32_t* image);
+
+// Reprojection (phx_reproject in phx_xpu.h states the rule; reproject.hip): one launch, one thread per output pixel in binary64,
+// workgroups of PHX_REPROJECT_BLOCK consecutive pixels.  The four taps are gathered straight from memory: neighbouring threads share them.
+// ReprojectCamera: a camera as reproject_check.cpp derives it on the host (reproject_check.h).
+struct ReprojectArgs {
+  ReprojectCamera from, to;
+  uint64_t num_pixels;
+  uint32_t width, height, xstride_a, normals_offset_a, m2_offset_a, samples_offset_a, xstride_g;
+  double sigma_plane, sigma_dist, max_history;
+};
+enum { PHX_REPROJECT_BLOCK = 256, PHX_REPROJECT_SLOTS = 64, PHX_REPROJECT_SLOT_WORDS = 16 };
+// counters: nullptr, or PHX_REPROJECT_SLOTS zeroed slots of PHX_REPROJECT_SLOT_WORDS 64-bit words (a 128-byte line each, as for
+// launch_accumulate).  A workgroup adds pixels, reused, no_geometry, disoccluded, samples (phx_reproject_summary) to the first five words
+// of slot (workgroup id % SLOTS); the caller sums the slots.
+void launch_reproject(hipStream_t stream, const ReprojectArgs& A, const float* acc_from, const float* guides_from, const float* guides_to, float* acc_to,
+                      unsigned long long* counters);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf

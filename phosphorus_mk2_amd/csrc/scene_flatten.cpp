@@ -172,15 +172,30 @@ void environment_tables(const phx_scene& s, FlatScene& out) {
 
 }  // namespace
 
+int flatten_camera(const phx_camera& c, DevScene& sc, std::string& err) {
+  auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
+  // (camera_t's constructor leaves focal_distance uninitialised, entities/camera.hpp:31-36: it means something only behind a lens)
+  if (!(std::fabs(c.aperture_radius) <= FLT_MAX) || (c.aperture_radius != 0.0f && !(std::fabs(c.focal_distance) <= FLT_MAX)))
+    return refuse("camera: aperture radius / focal distance not finite");
+  if (c.film_width == 0 || c.film_height == 0 || c.film_width > 65535 || c.film_height > 65535)
+    return refuse("film size out of range");
+  std::memcpy(sc.cam_m, c.to_world, sizeof(sc.cam_m));
+  sc.zoom = 1.12f * std::tan(c.fov * 0.5f);  // camera.hpp:113
+  sc.stepx = 1.0f / (float)c.film_width; sc.stepy = 1.0f / (float)c.film_height;
+  sc.ratio = (float)c.film_width / (float)c.film_height;
+  sc.width = c.film_width; sc.height = c.film_height;
+  sc.aperture_radius = c.aperture_radius; sc.focal_distance = c.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
+  return PHX_OK;
+}
+
 int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err) {
   auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
   auto material = [](uint32_t i) { return "material " + std::to_string(i); };
   if (!s.meshes || !s.materials || s.num_materials == 0) return refuse("scene without meshes/materials");
-  // (camera_t's constructor leaves focal_distance uninitialised, entities/camera.hpp:31-36: it means something only behind a lens)
-  if (!(std::fabs(s.camera.aperture_radius) <= FLT_MAX) || (s.camera.aperture_radius != 0.0f && !(std::fabs(s.camera.focal_distance) <= FLT_MAX)))
-    return refuse("camera: aperture radius / focal distance not finite");
-  if (s.camera.film_width == 0 || s.camera.film_height == 0 || s.camera.film_width > 65535 || s.camera.film_height > 65535)
-    return refuse("film size out of range");
+  {  // the camera's refusals come here, its fields at the end, where `out` has been reset: one function states both
+    DevScene checked{};
+    if (const int rc = flatten_camera(s.camera, checked, err)) return rc;
+  }
   if (s.environment_material >= (int32_t)s.num_materials) return refuse("environment material out of range");
   // the packed word: the triangle pick in the low byte, the light's selection above it, the environment's bit above that.  Valid: 0, 1, 0x101 and 0x301
   if (PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) > PHX_LIGHTS_BY_AREA) return refuse("unknown light_sampling");
@@ -378,13 +393,7 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
 
   sc.num_lights = (uint32_t)out.lights.size();
   sc.max_depth = opt.path_depth;
-  std::memcpy(sc.cam_m, s.camera.to_world, sizeof(sc.cam_m));
-  sc.zoom = 1.12f * std::tan(s.camera.fov * 0.5f);  // camera.hpp:113
-  sc.stepx = 1.0f / (float)s.camera.film_width; sc.stepy = 1.0f / (float)s.camera.film_height;
-  sc.ratio = (float)s.camera.film_width / (float)s.camera.film_height;
-  sc.width = s.camera.film_width; sc.height = s.camera.film_height;
-  sc.aperture_radius = s.camera.aperture_radius; sc.focal_distance = s.camera.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
-  return PHX_OK;
+  return flatten_camera(s.camera, sc, err);  // (accepted above)
 }
 
 }  // namespace phx

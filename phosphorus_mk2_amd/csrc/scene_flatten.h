@@ -44,6 +44,10 @@ struct FlatScene {
   DevScene scene{};
 };
 
+// The one statement of how a phx_camera becomes DevScene's camera fields (cam_m, zoom, stepx, stepy, ratio, width, height, aperture_radius,
+// focal_distance), with the camera's refusals: flatten_scene and phx_dev_set_camera both read it.  PHX_ERR_ARG leaves `sc` untouched.
+int flatten_camera(const phx_camera& c, DevScene& sc, std::string& err);
+
 // PHX_OK, or PHX_ERR_ARG with the reason in `err`; `out` is meaningful only after PHX_OK
 int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err);
 

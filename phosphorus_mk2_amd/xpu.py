@@ -230,6 +230,7 @@ class HipDevice:
         self._h, self._lib, self.options = handle, lib, options
         self._keep = None
         self._scene = None
+        self._camera = None  # the camera of the last set_camera behind the last preprocess; None: the scene's own
         self._adaptive = False  # set_adaptive is on: this device's frames carry the channel "samples"
 
     @staticmethod
@@ -264,7 +265,16 @@ class HipDevice:
     def preprocess(self, scene_desc):
         s, keep = scene_desc.pack()
         _check(self._lib, self._lib.phx_dev_preprocess(self._h, C.byref(s)), "phx_dev_preprocess")
-        self._scene = scene_desc
+        self._scene, self._camera = scene_desc, None
+
+    def set_camera(self, camera):
+        """Replaces the camera of the preprocessed scene and nothing else (phx_dev_set_camera): camera is a CameraDesc of the
+        preprocessed scene's film size.  Every later frame and guide film is what a device preprocessed with the scene under this camera
+        renders, bit for bit, at none of preprocess's cost.  The scene description is not changed: start() still takes the one that was
+        preprocessed."""
+        c = pack_camera(camera)
+        _check(self._lib, self._lib.phx_dev_set_camera(self._h, C.byref(c)), "phx_dev_set_camera")
+        self._camera = camera
 
     def start(self, scene_desc, frame):
         assert scene_desc is self._scene, "start() must get the scene that was preprocessed"
@@ -387,7 +397,7 @@ class HipDevice:
             if plane and plane_scale is None:
                 if self._scene is None:
                     raise ValueError("denoise: plane=True needs plane_scale (guide_plane_scale(camera)) on a device without a preprocessed scene")
-                plane_scale = guide_plane_scale(self._scene.camera)
+                plane_scale = guide_plane_scale(self._camera or self._scene.camera)
             keep = None if guides_ptr is not None else np.ascontiguousarray(guides, np.float32)
             g = abi.DenoiseGuides(guides=guides_ptr if guides_ptr is not None else keep.ctypes.data, xstride=int(gshape[2]),
                                   flags=(abi.GUIDE_DEMODULATE if demodulate else 0) | (abi.GUIDE_PLANE if plane else 0),
@@ -446,6 +456,37 @@ class HipDevice:
         """milliseconds of the last accumulate(): dict of kernel (HIP events) and call (host clock)"""
         ms = (C.c_double * 2)()
         _check(self._lib, self._lib.phx_dev_accumulate_times(self._h, ms), "phx_dev_accumulate_times")
+        return {"kernel": ms[0], "call": ms[1]}
+
+    def reproject(self, acc, guides_from, guides_to, camera_from, camera_to, sigma_plane=1.0, sigma_dist=4.0, max_history=64, primary_components=4,
+                  summary=True, device_ptrs=None):
+        """Reprojection (phx_dev_film_reproject; include/phx_xpu.h states the rule): acc, an accumulator film with normals
+        (accumulator(..., normals=True)) under camera_from, is carried to camera_to by the two cameras' guide films (render_guides under
+        each) -> (film, summary): a new film of acc's layout, in which a pixel whose first hit was seen before holds the bilinear mix of the
+        old pixels that are the same surface (to within sigma_plane pixels' worth of surface off the tangent plane and sigma_dist of
+        distance), its "samples" capped at max_history, and every other pixel is zero, so that accumulate() starts it afresh.  summary: a
+        dict of pixels, reused, no_geometry, disoccluded and samples (None with summary=False).  The defaults are settings, not
+        measurements.  device_ptrs: (acc, guides_from, guides_to, out) addresses of device-resident films; acc, guides_from and guides_to
+        then are only their shapes, and the call returns (None, summary).  Needs no scene."""
+        on_device = device_ptrs is not None
+        shapes = [tuple(a) if on_device and not hasattr(a, "shape") else a.shape for a in (acc, guides_from, guides_to)]
+        q = reproject_settings(shapes[0], shapes[1], shapes[2], camera_from, camera_to, sigma_plane, sigma_dist, max_history, primary_components)
+        s = abi.ReprojectSummary() if summary else None
+        if on_device:
+            q.on_device = 1
+            ptrs, out, keep = [int(p) for p in device_ptrs], None, None
+        else:
+            keep = [np.ascontiguousarray(a, np.float32) for a in (acc, guides_from, guides_to)]
+            out = np.empty(shapes[0], np.float32)
+            ptrs = [k.ctypes.data for k in keep] + [out.ctypes.data]
+        _check(self._lib, self._lib.phx_dev_film_reproject(self._h, C.byref(q), ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(s) if s is not None else None),
+               "phx_dev_film_reproject")
+        return out, (None if s is None else {k: int(getattr(s, k)) for k, _ in s._fields_})
+
+    def reproject_times(self):
+        """milliseconds of the last reproject(): dict of kernel (HIP events) and call (host clock)"""
+        ms = (C.c_double * 2)()
+        _check(self._lib, self._lib.phx_dev_reproject_times(self._h, ms), "phx_dev_reproject_times")
         return {"kernel": ms[0], "call": ms[1]}
 
     def display(self, film, exposure=1.0, tone="aces", white=4.0, dither=True, key=0.18, percentiles=(0.5, 0.95), scale_range=(2.0 ** -12, 2.0 ** 12),
@@ -712,6 +753,37 @@ def accumulate_settings(shape_a, shape_b, spp, primary_components=4, normals=Fal
                           spp_b=int(spp), on_device=0, tau=float(threshold), floor=float(floor))
 
 
+def pack_camera(camera):
+    """abi.Camera of a CameraDesc, field by field as SceneDesc.pack fills the scene's"""
+    c = abi.Camera()
+    c.to_world[:] = [float(x) for x in camera.to_world.reshape(-1)]
+    c.fov, c.focal_distance, c.aperture_radius = camera.fov, camera.focal_distance, camera.aperture_radius
+    c.film_width, c.film_height = camera.width, camera.height
+    return c
+
+
+def reproject_settings(shape_a, shape_gf, shape_gt, camera_from, camera_to, sigma_plane=1.0, sigma_dist=4.0, max_history=64, primary_components=4):
+    """abi.Reproject for an accumulator film of shape_a (H, W, xstride) WITH normals, laid out as xpu.accumulator(W, H, primary_components,
+    True) lays it out, and two guide films (H, W, >= 8) of one stride.  ValueError for films of different sizes, an accumulator without
+    normals or guide films of different strides."""
+    if len(shape_a) != 3 or len(shape_gf) != 3 or len(shape_gt) != 3:
+        raise ValueError("reproject: the films must be (height, width, xstride)")
+    H, W, xa = (int(v) for v in shape_a)
+    if tuple(shape_gf[:2]) != (H, W) or tuple(shape_gt[:2]) != (H, W):
+        raise ValueError(f"reproject: the accumulator is {W} x {H} pixels, the guide films {shape_gf[1]} x {shape_gf[0]} and {shape_gt[1]} x {shape_gt[0]}")
+    if int(shape_gf[2]) != int(shape_gt[2]):
+        raise ValueError(f"reproject: the two guide films must have one stride, not {shape_gf[2]} and {shape_gt[2]}")
+    m2_offset = primary_components + 3
+    if xa != m2_offset + 4:
+        raise ValueError(f"reproject: an accumulator with normals has {m2_offset + 4} floats per pixel in this layout "
+                         f"(xpu.accumulator(..., normals=True): the plane test reads them), this one {xa}")
+    q = abi.Reproject(width=W, height=H, xstride_a=xa, normals_offset_a=primary_components, m2_offset_a=m2_offset, samples_offset_a=m2_offset + 3,
+                      xstride_g=int(shape_gf[2]), on_device=0, to=pack_camera(camera_to), sigma_plane=float(sigma_plane), sigma_dist=float(sigma_dist),
+                      max_history=int(max_history))
+    setattr(q, "from", pack_camera(camera_from))
+    return q
+
+
 TONES = {"clamp": abi.TONE_CLAMP, "reinhard": abi.TONE_REINHARD, "aces": abi.TONE_ACES}
 
 
@@ -792,6 +864,60 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
             valid = summary["pixels"] - summary["invalid"] if summary is not None else 0
             if valid > 0 and summary["converged"] >= coverage * valid:  # (a film without one valid pixel, as any film of 1 spp, has not converged)
                 return
+    finally:
+        dev.close()
+
+
+def render_camera_path(scene_desc, cameras, spp, frames_per_camera=1, seed=1, guide_samples=4, reproject=None, denoise=None, display=None,
+                       pps=1, depth=9, tile_size=32, **options):
+    """A camera path through a static scene on ONE device: the scene is preprocessed once; then, per camera of `cameras`
+    (CameraDescs of the scene's film size): set_camera; the guide film (guide_samples samples, the seed of the camera's first frame); from
+    the second camera on the accumulator is carried over by HipDevice.reproject (`reproject`: a dict of its settings, sigma_plane=,
+    sigma_dist=, max_history=); then frames_per_camera frames of `spp` samples with seeds (seed + k) mod 2^64, k counting frames over the
+    whole path, each pooled by HipDevice.accumulate.  A generator: after every frame it yields (film, summary, frames_done, reprojection),
+    as render_progressive yields (summary is None: there is no stop) plus the summary of the reprojection that led to this camera (None at
+    the first); with display, (..., reprojection, image).  film is the accumulator (H, W, 14) f32 in xpu.accumulator's layout with
+    normals, replaced at every camera: copy it to keep it.  denoise, display, options: as for render_progressive; the guided denoiser
+    reads this camera's guide film (no entry `guides` is needed: guides=dict(...) carries its settings)."""
+    if frames_per_camera < 1:
+        raise ValueError("render_camera_path: frames_per_camera must be at least 1")
+    dev = HipDevice.make(Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, **options))
+    try:
+        dev.preprocess(scene_desc)
+        W, H = scene_desc.camera.width, scene_desc.camera.height
+        acc = accumulator(W, H, 4, True)
+        settings, guided = None, False
+        if denoise is not None:
+            settings = dict(denoise)
+            gset = settings.pop("guides", None)
+            if gset is not None:
+                gset = dict(gset)
+                gset.pop("samples", None)
+                settings.update(gset)
+                guided = True
+        k, previous, guides_before = 0, None, None
+        for camera in cameras:
+            dev.set_camera(camera)
+            guides = dev.render_guides((seed + k) % (1 << 64), min(int(guide_samples), spp))
+            moved = None
+            if previous is not None:
+                acc, moved = dev.reproject(acc, guides_before, guides, previous, camera, **(reproject or {}))
+            for _ in range(frames_per_camera):
+                film = Film(W, H, 4, True, True, False)
+                dev.start(scene_desc, FrameState((seed + k) % (1 << 64), Tiles.make(W, H, tile_size), film, native_sink=True))
+                dev.join()
+                k += 1
+                dev.accumulate(acc, film.data, spp, 4, True, False)
+                if settings is None:
+                    out = acc
+                else:
+                    out = dev.denoise(acc, spp, 4, True, True, guides=guides if guided else None,
+                                      **({"plane_scale": guide_plane_scale(camera), **settings} if guided else settings))
+                if display is None:
+                    yield out, None, k, moved
+                else:
+                    yield out, None, k, moved, dev.display(out, **display)
+            previous, guides_before = camera, guides
     finally:
         dev.close()
 
