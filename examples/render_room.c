@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K] [display [auto]] [orbit K]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K] [display [auto]] [despeckle] [orbit K [clamp]]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -30,6 +30,12 @@
  * preprocessed once: per camera phx_dev_set_camera, the guide film (phx_dev_render_guides), from the second camera on phx_dev_film_reproject of the
  * accumulator (the host prints its summary), the frame, phx_dev_film_accumulate and the display pass into argv[1] + ".orbit<k>.ppm" (DESIGN 22).
  * The last accumulator is what is written to argv[1].
+ * orbit K clamp: that, and from the second camera on the reprojected accumulator is clamped against the neighbourhoods of this camera's frame film
+ * before the frame is pooled (phx_dev_film_outlier_clamp: radius 1, two-sided, the centre included, gamma 3, a clamped pixel claims at most 8 samples;
+ * DESIGN 23); the host prints the call's summary.
+ * despeckle: every joined frame film is clamped in place against its own neighbourhoods before anything else reads it (phx_dev_film_outlier_clamp:
+ * radius 2, the centre excluded, upper only, gamma 4, the 2 brightest taps left out); the frame carries the error estimate, which is scaled with a
+ * clamped colour, and the host prints the call's summary.  The clamp is biased: what the fireflies carried is gone from the film.
  * With N > 1 it is the reference's multi-device mechanism (src/core.cpp:103-115): N devices — one per GPU that phx_discover
  * reports, wrapping around when the box has fewer — are all started on ONE tile queue and ONE film, and joined in turn.
  * No collective: whoever renders a tile writes it into the shared film.
@@ -51,7 +57,7 @@ static int fail(const char* what) {
 
 /* orbit K on a device that has preprocessed `scene`: see the head of the file.  Frames carry normals and the error estimate (10 floats a pixel),
  * the accumulator also "samples" (11): the layouts phx_reproject reads. */
-static int orbit(phx_device* dev, const phx_scene* scene, const phx_options* opt, int count, const char* path) {
+static int orbit(phx_device* dev, const phx_scene* scene, const phx_options* opt, int count, int clamp, const char* path) {
   const size_t xf = 10, xa = 11, npix = (size_t)W * H;
   float* film = (float*)calloc(npix * xf, sizeof(float));
   float* acc = (float*)calloc(npix * xa, sizeof(float));
@@ -92,6 +98,17 @@ static int orbit(phx_device* dev, const phx_scene* scene, const phx_options* opt
     frame.normals_channel = 1; frame.moments_channel = 1; frame.host_film = film;
     if (phx_dev_start(dev, &frame) != PHX_OK) return fail("phx_dev_start");
     if (phx_dev_join(dev) != PHX_OK) return fail("phx_dev_join");
+    if (clamp && k > 0) { /* the history against what this camera's first frame shows, before that frame is pooled into it */
+      phx_outlier_clamp oc;
+      phx_outlier_clamp_summary os;
+      memset(&oc, 0, sizeof(oc));
+      oc.width = W; oc.height = H; oc.xstride_a = (uint32_t)xa; oc.m2_offset_a = 7; oc.samples_offset_a = 10; oc.xstride_b = (uint32_t)xf;
+      oc.radius = 1; oc.trim = 0; oc.min_taps = 4; oc.gamma = 3.0f; oc.clamped_history = 8;
+      if (phx_dev_film_outlier_clamp(dev, &oc, acc, film, acc, &os) != PHX_OK) return fail("phx_dev_film_outlier_clamp");
+      printf("orbit: camera %d clamped %llu capped %llu inside %llu skipped %llu unbounded %llu of %llu\n", k + 1, (unsigned long long)os.clamped,
+             (unsigned long long)os.capped, (unsigned long long)os.inside, (unsigned long long)os.skipped, (unsigned long long)os.unbounded,
+             (unsigned long long)os.pixels);
+    }
     phx_accumulate pa;
     memset(&pa, 0, sizeof(pa));
     pa.width = W; pa.height = H; pa.xstride_a = (uint32_t)xa; pa.normals_offset_a = 4; pa.m2_offset_a = 7; pa.samples_offset_a = 10;
@@ -117,6 +134,23 @@ static int orbit(phx_device* dev, const phx_scene* scene, const phx_options* opt
   fclose(f);
   phx_tiles_free(tiles);
   free(film); free(acc); free(next); free(guides[0]); free(guides[1]); free(image); free(name);
+  return 0;
+}
+
+/* despeckle: a joined frame film of `xstride` floats a pixel (primary rgba, m2 rgb [, samples]) against its own neighbourhoods, in place */
+static int despeckle_film(phx_device* dev, float* film, size_t xstride, int has_samples, int frame_number) {
+  phx_outlier_clamp oc;
+  phx_outlier_clamp_summary os;
+  memset(&oc, 0, sizeof(oc));
+  oc.width = W; oc.height = H; oc.xstride_a = oc.xstride_b = (uint32_t)xstride; oc.m2_offset_a = 4; oc.samples_offset_a = has_samples ? 7 : 0;
+  oc.flags = PHX_OUTLIER_EXCLUDE_CENTRE | PHX_OUTLIER_UPPER_ONLY; oc.radius = 2; oc.trim = 2; oc.min_taps = 4; oc.gamma = 4.0f;
+  double before = 0.0, after = 0.0;
+  for (size_t p = 0; p < (size_t)W * H; ++p) for (int c = 0; c < 3; ++c) before += film[p * xstride + c];
+  if (phx_dev_film_outlier_clamp(dev, &oc, film, film, film, &os) != PHX_OK) return fail("phx_dev_film_outlier_clamp");
+  for (size_t p = 0; p < (size_t)W * H; ++p) for (int c = 0; c < 3; ++c) after += film[p * xstride + c];
+  printf("despeckle: frame %d clamped %llu inside %llu skipped %llu unbounded %llu of %llu film mean %.6g -> %.6g\n", frame_number, (unsigned long long)os.clamped,
+         (unsigned long long)os.inside, (unsigned long long)os.skipped, (unsigned long long)os.unbounded, (unsigned long long)os.pixels,
+         before / (3.0 * W * H), after / (3.0 * W * H));
   return 0;
 }
 
@@ -160,7 +194,7 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0, orbit_cameras = 0;
+  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0, orbit_cameras = 0, orbit_clamp = 0, despeckle = 0;
   phx_adaptive ad;
   memset(&ad, 0, sizeof(ad));
   for (int i = 2; i < argc; ++i)
@@ -177,8 +211,10 @@ int main(int argc, char** argv) {
     } else if (strcmp(argv[i], "orbit") == 0 && i + 1 < argc) {
       orbit_cameras = atoi(argv[i + 1]);
       if (orbit_cameras < 1 || orbit_cameras > 1024) orbit_cameras = 1;
-      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
-      argc -= 2; --i;
+      const int take = i + 2 < argc && strcmp(argv[i + 2], "clamp") == 0 ? 3 : 2;  /* the keyword, its number and, optionally, `clamp` */
+      orbit_clamp = take == 3;
+      for (int k = i; k + take < argc; ++k) argv[k] = argv[k + take];
+      argc -= take; --i;
     } else if (strcmp(argv[i], "display") == 0) {  /* the keyword and, optionally, `auto` */
       const int take = i + 1 < argc && strcmp(argv[i + 1], "auto") == 0 ? 2 : 1;
       display = take;
@@ -186,6 +222,10 @@ int main(int argc, char** argv) {
       argc -= take; --i;
     } else if (strcmp(argv[i], "denoise") == 0 || strcmp(argv[i], "denoise-guided") == 0) {
       denoise = strcmp(argv[i], "denoise") == 0 ? 1 : 2;
+      for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+      --argc; --i;
+    } else if (strcmp(argv[i], "despeckle") == 0) {
+      despeckle = 1;
       for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
       --argc; --i;
     } else if (strcmp(argv[i], "error-estimate") == 0) {
@@ -232,11 +272,11 @@ int main(int argc, char** argv) {
   }
 
   if (orbit_cameras) { /* a path of cameras on the first device, in place of the one frame below */
-    const int rc = argc > 1 ? orbit(devs[0], &scene, &opt, orbit_cameras, argv[1]) : 1;
+    const int rc = argc > 1 ? orbit(devs[0], &scene, &opt, orbit_cameras, orbit_clamp, argv[1]) : 1;
     for (int i = 0; i < num_devices; ++i) phx_dev_destroy(devs[i]);
     return rc;
   }
-  if (adaptive || denoise || progressive) error_estimate = 1; /* the stopping rule, the denoiser and the pooling read the estimate: such a frame must carry it */
+  if (adaptive || denoise || progressive || despeckle) error_estimate = 1; /* the stopping rule, the denoiser and the pooling read the estimate: such a frame must carry it */
   int has_samples = adaptive; /* the film at hand carries the channel "samples" at float 7 */
   size_t xstride = 4 + (error_estimate ? 3 : 0) + (adaptive ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */
   float* film = (float*)calloc((size_t)W * H * xstride, sizeof(float));
@@ -251,6 +291,8 @@ int main(int argc, char** argv) {
     if (phx_dev_start(devs[i], &frame) != PHX_OK) return fail("phx_dev_start");
   for (int i = 0; i < num_devices; ++i)
     if (phx_dev_join(devs[i]) != PHX_OK) return fail("phx_dev_join");
+
+  if (despeckle && despeckle_film(devs[0], film, xstride, adaptive, 1)) return 1; /* before anything else reads the film */
 
   phx_stats st, sum;
   memset(&sum, 0, sizeof(sum));
@@ -299,6 +341,7 @@ int main(int argc, char** argv) {
           if (phx_dev_start(devs[i], &frame) != PHX_OK) return fail("phx_dev_start");
         for (int i = 0; i < num_devices; ++i)
           if (phx_dev_join(devs[i]) != PHX_OK) return fail("phx_dev_join");
+        if (despeckle && despeckle_film(devs[0], film, xstride, adaptive, k + 1)) return 1;
       }
       phx_accumulate_summary ps;
       if (phx_dev_film_accumulate(devs[0], &pa, acc, film, &ps) != PHX_OK) return fail("phx_dev_film_accumulate");

@@ -673,8 +673,8 @@ typedef struct phx_display_summary {
  *   disoccluded;  samples = the sum over the reused pixels of (uint64_t) of the "samples" float written, truncated, modulo 2^64.
  * Limits: view-dependent shading (glossy, mirror, glass) is carried as if it were diffuse; the sky and whatever is seen through a specular
  * path get no history (the guides hold the FIRST hit); the lens is projected as a pinhole, so out-of-focus regions smear; m2 of a bilinear
- * mix treats the taps as independent and understates the variance of the result; objects do not move; nothing clamps the history against
- * the new frame; the film size cannot change with the camera; a multi-GPU film is reduced first. */
+ * mix treats the taps as independent and understates the variance of the result; objects do not move; nothing here clamps the history against
+ * the new frame (phx_outlier_clamp, DESIGN 23, is a pass of its own for that); the film size cannot change with the camera; a multi-GPU film is reduced first. */
 typedef struct phx_reproject {
   uint32_t   width, height;      /* 1 .. 65536 each */
   uint32_t   xstride_a;          /* floats per pixel of acc_from and acc_to; 10 .. 24 */
@@ -692,6 +692,74 @@ typedef struct phx_reproject {
 typedef struct phx_reproject_summary {
   uint64_t pixels, reused, no_geometry, disoccluded, samples;
 } phx_reproject_summary;
+
+/* ---- the outlier clamp: pulling a film's pixels back to what a neighbourhood can justify ----------------------------------- */
+/* A pass of its own beside the frame (phx_dev_film_outlier_clamp): film A is clamped, pixel by pixel and colour by colour, against bounds
+ * taken from the neighbourhood of the same pixel in a reference film B, into film_out, a film of A's layout.  Two uses of the one rule:
+ *   despeckle      B is A itself: a finished frame film against its own neighbourhood, before it is pooled or filtered
+ *                  (PHX_OUTLIER_EXCLUDE_CENTRE | PHX_OUTLIER_UPPER_ONLY: a firefly does not vouch for itself, and nothing is brightened)
+ *   history clamp  A is a reprojected accumulator (phx_reproject), B the first frame film under the new camera, before that frame is
+ *                  pooled into A: the variance clipping of temporal filters.  It also bounds phx_reproject's "carried as if it were
+ *                  diffuse" limit: a carried value cannot leave what the new frame's neighbourhood shows.
+ * It reads no scene, launches none of the frame's kernels and changes no frame.  A has xstride_a floats a pixel, "primary" rgb first, "m2"
+ * (3 floats) at m2_offset_a and "samples" (1 float) at samples_offset_a, each 0 = none; B has xstride_b floats a pixel, of which only the
+ * first three, "primary" rgb, are read.  The films are width x height pixels, row-major, in the same memory space.
+ * All arithmetic is binary64, without contraction, in the order written; fp32 inputs are widened first; a result is rounded to fp32 once,
+ * where fp32(...) says so.  Pixel p = (x, y), A_c its colour c of A, n its samples float:
+ *   skipped        A_r, A_g or A_b is not finite, or A has "samples" and n is not a finite number > 0:  every float of the pixel is A's.
+ *                  (A pixel without history is all zero after phx_reproject, and stays so: phx_accumulate then starts it afresh.)
+ *   taps           q = p + (dx, dy), dy = -r .. r outer, dx = -r .. r inner, r = radius; under PHX_OUTLIER_EXCLUDE_CENTRE without (0, 0).
+ *                  A tap counts if q is inside the film and B_q's r, g and b are finite.
+ *   luminance      l_q = (0.2126 * R + 0.7152 * G) + 0.0722 * B      of B_q: the denoiser's weights in its order
+ *   trim           `trim` times: the counting tap of largest l_q is dropped, among equals the earlier one in tap order.  (A second
+ *                  firefly in the window would otherwise widen the bounds that should catch the first.)
+ *   k              the number of taps left.  k < min_taps: the pixel is untouched and counted as unbounded.
+ *   bounds         per colour c, sums starting at 0.0 and running over the taps left in tap order:
+ *                      mu = (sum of B_q,c) / k
+ *                      s  = (sum of (B_q,c - mu) * (B_q,c - mu)) / k
+ *                      w  = gamma * sqrt(s) + floor
+ *                      hi = mu + w;   lo = mu - w
+ *   clamp          A_c > hi:  A'_c = fp32(hi).   A_c < lo and PHX_OUTLIER_UPPER_ONLY is not set:  A'_c = fp32(lo).   Otherwise the float
+ *                  keeps its bits.  The pixel is counted as clamped if any colour was, else as inside.
+ *   m2             (when A has it)  v = m2_c.  If colour c was clamped and A_c != 0:  f = A'_c / A_c;  if 0 <= f < 1:  v = (v * f) * f, as
+ *                  if every sample of the pixel had been scaled by f.
+ *   samples cap    if clamped_history > 0, the pixel was clamped in any colour and n > clamped_history:  samples := fp32(clamped_history)
+ *                  and, with n_out = (double)clamped_history, v = v * (n / n_out) for all three colours, as phx_reproject's cap does: a
+ *                  history that had to be clamped claims no more confidence than clamped_history samples.  Counted as capped.
+ *   rounding       m2_c = fp32(v) where either step applied to it; otherwise the float keeps its bits.  Every other float of the pixel
+ *                  is A's.
+ * So a constant film comes back bit for bit (s = 0, hi = lo = mu = the value: neither comparison holds), and with B = A, the centre
+ * included, trim = 0 and floor = 0 no pixel is clamped once gamma >= sqrt(k - 1) (Samuelson's inequality; k <= 49).
+ * summary (optional), integers counted in the same launch, exact in any order:  pixels = width * height = skipped + unbounded + inside +
+ *   clamped;  capped counts the pixels whose samples were cut.
+ * Aliasing: film_out may be film exactly (the same address) or share no byte with it; ref may be film exactly (then xstride_b must be
+ *   xstride_a) or share no byte with it; film_out may be ref exactly or share no byte with it.  Any partial overlap is refused.  Where
+ *   film_out shares bytes with ref the call works from a device copy of ref, made inside the call and released before it returns, so
+ *   every bound is taken from B as it was before the call.
+ * Limits: the clamp is BIASED: it removes the energy the outliers carried (a film whose fireflies hold 10 % of its mean comes back some
+ *   10 % darker), and a true small highlight narrower than the window is cut like a firefly; the taps know no surface (no normals or
+ *   guides in the window), so bounds taken across an edge are wide; colours are clamped one by one, so a clamped pixel can change hue;
+ *   objects do not move; a multi-GPU film is reduced first. */
+enum { PHX_OUTLIER_EXCLUDE_CENTRE = 1, PHX_OUTLIER_UPPER_ONLY = 2 };       /* phx_outlier_clamp.flags */
+typedef struct phx_outlier_clamp {
+  uint32_t width, height;      /* 1 .. 65536 each */
+  uint32_t xstride_a;          /* floats per pixel of film and film_out; 3 .. 24 */
+  uint32_t m2_offset_a;        /* 0 = A has no m2; else >= 3, m2_offset_a + 3 <= xstride_a */
+  uint32_t samples_offset_a;   /* 0 = A has no samples; else >= 3, < xstride_a, outside m2 */
+  uint32_t xstride_b;          /* floats per pixel of ref; 3 .. 24.  Only the first three are read */
+  uint32_t on_device;          /* 0: the three films are host memory, 1: all are device memory (HBM) */
+  uint32_t flags;              /* PHX_OUTLIER_*; other bits are refused */
+  uint32_t radius;             /* 1 .. 3: the window is (2 * radius + 1) pixels square */
+  uint32_t trim;               /* 0 .. 3: the brightest taps left out of the bounds */
+  uint32_t min_taps;           /* 1 .. (2 * radius + 1)^2: fewer taps left bound nothing */
+  float    gamma;              /* finite, >= 0: the bounds' half width in standard deviations of the taps */
+  float    floor;              /* finite, >= 0: added to the half width, in film units */
+  uint32_t clamped_history;    /* 0 = no cap; else the most samples a clamped pixel may claim (needs samples_offset_a) */
+  uint32_t reserved[2];        /* must be 0 */
+} phx_outlier_clamp;
+typedef struct phx_outlier_clamp_summary {
+  uint64_t pixels, skipped, unbounded, inside, clamped, capped;
+} phx_outlier_clamp_summary;
 
 /* ---- statistics ------------------------------------------------------------------------ */
 /* The shade kernels (shade_general.hip: launch_shade picks one per launch from the scene's closures, images and lens and from the pass).
@@ -958,6 +1026,20 @@ int phx_dev_film_reproject(phx_device* dev, const phx_reproject* r, const float*
 /* Times of the last phx_dev_film_reproject of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the
  * host's clock (the allocations and, for host films, the uploads and the download included). */
 int phx_dev_reproject_times(const phx_device* dev, double* ms /* 2 */);
+
+/* The outlier clamp (phx_outlier_clamp above states the rule): film is clamped against ref's neighbourhoods into film_out; summary may be
+ * NULL.  Synchronous, one kernel launch.  It needs a device but no scene.  PHX_ERR_STATE while a frame is started and not joined;
+ * PHX_ERR_ARG, with the field's name in the message, for a value outside the ranges stated at the struct, channels that overlap
+ * "primary" or each other, unknown flags, clamped_history without a samples channel, a non-zero reserved word, a null pointer ("film",
+ * "ref", "film_out") or a partial overlap of two films ("ref": with film; "film_out": with film or ref): film_out and summary are then
+ * untouched.  Its working memory (the counters, ref's copy where film_out shares bytes with ref and, for host films, the films' copies)
+ * is allocated in the call and freed before it returns (PHX_ERR_OOM if it cannot be had): phx_stats.device_bytes and every later frame
+ * are what they were. */
+int phx_dev_film_outlier_clamp(phx_device* dev, const phx_outlier_clamp* c, const float* film, const float* ref, float* film_out,
+                               phx_outlier_clamp_summary* summary /* may be NULL */);
+/* Times of the last phx_dev_film_outlier_clamp of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the
+ * host's clock (the allocations, ref's copy and, for host films, the uploads and the download included). */
+int phx_dev_outlier_clamp_times(const phx_device* dev, double* ms /* 2 */);
 
 /* The acceleration structure of the preprocessed scene as the traversal kernels read it (a parity hook: the tests check that every box the
  * device builder stored contains what hangs below it).  Copies min(capacity, size) bytes of the pool of 64-byte elements (csrc/bvh8.h:

@@ -212,6 +212,24 @@ class ReprojectSummary(C.Structure):
     _fields_ = [("pixels", C.c_uint64), ("reused", C.c_uint64), ("no_geometry", C.c_uint64), ("disoccluded", C.c_uint64), ("samples", C.c_uint64)]
 
 
+OUTLIER_EXCLUDE_CENTRE, OUTLIER_UPPER_ONLY = 1, 2  # OutlierClamp.flags (PHX_OUTLIER_*)
+
+
+class OutlierClamp(C.Structure):
+    """phx_outlier_clamp: the layouts of the film (_a) and of the reference film (_b) and the settings of phx_dev_film_outlier_clamp"""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32), ("xstride_a", C.c_uint32), ("m2_offset_a", C.c_uint32), ("samples_offset_a", C.c_uint32),
+        ("xstride_b", C.c_uint32), ("on_device", C.c_uint32), ("flags", C.c_uint32), ("radius", C.c_uint32), ("trim", C.c_uint32),
+        ("min_taps", C.c_uint32), ("gamma", C.c_float), ("floor", C.c_float), ("clamped_history", C.c_uint32), ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class OutlierClampSummary(C.Structure):
+    """phx_outlier_clamp_summary: the counters of a phx_dev_film_outlier_clamp call"""
+    _fields_ = [("pixels", C.c_uint64), ("skipped", C.c_uint64), ("unbounded", C.c_uint64), ("inside", C.c_uint64), ("clamped", C.c_uint64),
+                ("capped", C.c_uint64)]
+
+
 DISPLAY_DITHER, DISPLAY_AUTO_EXPOSURE = 1, 2  # Display.flags (PHX_DISPLAY_*)
 TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2  # Display.tone (PHX_TONE_*)
 
@@ -261,6 +279,7 @@ EXPORTS = [
     "phx_dev_render_guides", "phx_dev_guides_times", "phx_dev_denoise_guided",
     "phx_dev_film_accumulate", "phx_dev_accumulate_times", "phx_dev_film_display", "phx_dev_display_times",
     "phx_dev_set_camera", "phx_dev_film_reproject", "phx_dev_reproject_times",
+    "phx_dev_film_outlier_clamp", "phx_dev_outlier_clamp_times",
 ]
 
 
@@ -307,5 +326,7 @@ def declare(lib):
     lib.phx_dev_set_camera.argtypes = [vp, C.POINTER(Camera)]; lib.phx_dev_set_camera.restype = C.c_int
     lib.phx_dev_film_reproject.argtypes = [vp, C.POINTER(Reproject), vp, vp, vp, vp, C.POINTER(ReprojectSummary)]; lib.phx_dev_film_reproject.restype = C.c_int
     lib.phx_dev_reproject_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_reproject_times.restype = C.c_int
+    lib.phx_dev_film_outlier_clamp.argtypes = [vp, C.POINTER(OutlierClamp), vp, vp, vp, C.POINTER(OutlierClampSummary)]; lib.phx_dev_film_outlier_clamp.restype = C.c_int
+    lib.phx_dev_outlier_clamp_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_outlier_clamp_times.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

@@ -357,6 +357,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 18: return sizeof(phx_accumulate);  // (17 likewise: tests/test_guides.py)
     case 19: return sizeof(phx_display); case 20: return sizeof(phx_display_summary);
     case 21: return sizeof(phx_reproject); case 22: return sizeof(phx_reproject_summary);
+    case 23: return sizeof(phx_outlier_clamp); case 24: return sizeof(phx_outlier_clamp_summary);
     default: return 0;
   }
 }

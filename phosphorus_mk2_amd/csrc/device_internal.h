@@ -167,6 +167,7 @@ struct phx_device {
   double guides_ms[2] = {};    // phx_dev_guides_times: the last phx_dev_render_guides' kernel and call
   double accumulate_ms[2] = {};  // phx_dev_accumulate_times: the last phx_dev_film_accumulate's kernel and call
   double reproject_ms[2] = {};   // phx_dev_reproject_times: the last phx_dev_film_reproject's kernel and call
+  double outlier_clamp_ms[2] = {};  // phx_dev_outlier_clamp_times: the last phx_dev_film_outlier_clamp's kernel and call
   double display_ms[3] = {};   // phx_dev_display_times: the last phx_dev_film_display's histogram + exposure, encode and call
   double denoise_ms[11] = {};  // phx_dev_denoise_times: the last phx_dev_denoise's stages (it holds no device memory between calls)
 

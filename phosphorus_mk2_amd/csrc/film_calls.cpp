@@ -1,8 +1,8 @@
 // film_calls.cpp — the entry points that work on a film and launch no frame: phx_dev_film_moments, phx_dev_denoise / _guided (denoise.hip),
-// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_reproject (reproject.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the
-// five *_times getters.
+// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_reproject (reproject.hip), phx_dev_film_outlier_clamp (outlier_clamp.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the
+// six *_times getters.
 //
-// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp, display_check.cpp, reproject_check.cpp over film_checks.h)
+// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp, display_check.cpp, reproject_check.cpp, outlier_clamp_check.cpp over film_checks.h)
 // and run before the device is selected; what the large calls share — refusals, device, events, host-film staging, the wait and the
 // times — is FilmCall below.  phx_dev_film_moments and phx_dev_adaptive_select stage plain arrays, as the stage hooks do (Staging).
 #include "device_internal.h"
@@ -11,6 +11,7 @@
 #include "display_check.h"
 #include "film_checks.h"
 #include "guides_check.h"
+#include "outlier_clamp_check.h"
 #include "reproject_check.h"
 
 using namespace phx;
@@ -288,6 +289,60 @@ int phx_dev_film_reproject(phx_device* d, const phx_reproject* r, const float* a
 int phx_dev_reproject_times(const phx_device* d, double* ms) {
   if (!d || !ms) return fail(PHX_ERR_ARG, "reproject_times: null argument");
   ms[0] = d->reproject_ms[0]; ms[1] = d->reproject_ms[1];
+  return PHX_OK;
+}
+
+// The outlier clamp (phx_outlier_clamp; outlier_clamp.hip).
+// (no stage_hook: the call reads two films and no scene)
+int phx_dev_film_outlier_clamp(phx_device* d, const phx_outlier_clamp* c, const float* film, const float* ref, float* film_out, phx_outlier_clamp_summary* summary) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "outlier_clamp", c != nullptr)) return rc;
+    std::string why;
+    bool ref_needs_copy = false;
+    if (const int rc = outlier_clamp_check(*c, film, ref, film_out, ref_needs_copy, why)) return fail(rc, why);
+    FilmCall call{d, d->outlier_clamp_ms};
+    if (const int rc = call.begin(2)) return rc;
+    const size_t npix = (size_t)c->width * c->height, floats_b = npix * c->xstride_b;
+    const size_t slot_words = (size_t)PHX_OUTLIER_SLOTS * PHX_OUTLIER_SLOT_WORDS;
+    DevBuf<unsigned long long> counters; DevBuf<float> ref_copy;
+    const float *src = film, *bounds = ref; float* dst = film_out;
+    if (!c->on_device) {  // host films: a device copy of film, clamped in place and copied back to film_out, and one of ref
+      float* copy = nullptr;
+      if (const int rc = call.stage(film, npix * c->xstride_a, film_out, dst)) return rc;
+      if (const int rc = call.stage(ref, floats_b, nullptr, copy)) return rc;
+      src = dst; bounds = copy;
+    } else if (ref_needs_copy) {  // film_out is ref: the bounds come from ref as it was
+      if (const int rc = ref_copy.alloc(floats_b)) return rc;
+      HIPCHK(hipMemcpyAsync(ref_copy.p, ref, floats_b * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
+      bounds = ref_copy.p;
+    }
+    if (summary) {
+      if (const int rc = counters.alloc(slot_words)) return rc;
+      HIPCHK(hipMemsetAsync(counters.p, 0, slot_words * sizeof(unsigned long long), d->stream));
+    }
+    OutlierClampArgs A{};
+    A.width = c->width; A.height = c->height; A.xstride_a = c->xstride_a; A.m2_offset_a = c->m2_offset_a; A.samples_offset_a = c->samples_offset_a;
+    A.xstride_b = c->xstride_b; A.flags = c->flags; A.radius = c->radius; A.trim = c->trim; A.min_taps = c->min_taps;
+    A.a_is_b = ref == film ? 1u : 0u;  // (the check: then of one stride; a copy of ref holds what film holds)
+    A.gamma = (double)c->gamma; A.floor = (double)c->floor; A.clamped_history = (double)c->clamped_history;
+    if (const int rc = call.mark()) return rc;
+    launch_outlier_clamp(d->stream, A, src, bounds, dst, counters.p);
+    if (const int rc = call.mark()) return rc;
+    if (const int rc = call.wait()) return rc;
+    if (summary) {
+      std::vector<unsigned long long> slots(slot_words);
+      HIPCHK(hipMemcpy(slots.data(), counters.p, slot_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      unsigned long long s[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};  // integers, modulo 2^64: whatever the order, the same sums
+      for (size_t k = 0; k < (size_t)PHX_OUTLIER_SLOTS; ++k) for (int i = 0; i < 6; ++i) s[i] += slots[k * PHX_OUTLIER_SLOT_WORDS + i];
+      summary->pixels = s[0]; summary->skipped = s[1]; summary->unbounded = s[2]; summary->inside = s[3]; summary->clamped = s[4]; summary->capped = s[5];
+    }
+    return call.kernel_and_call_times();
+  });
+}
+
+int phx_dev_outlier_clamp_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "outlier_clamp_times: null argument");
+  ms[0] = d->outlier_clamp_ms[0]; ms[1] = d->outlier_clamp_ms[1];
   return PHX_OK;
 }
 

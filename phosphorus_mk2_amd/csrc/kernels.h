@@ -11,6 +11,7 @@
 //   guides.hip         k_guides: the first-hit guide film (albedo, coverage, position, distance), a pass of its own no frame launches
 //   accumulate.hip     k_accumulate: pools a finished film into an accumulator film and counts its summary, a pass of its own no frame launches
 //   reproject.hip      k_reproject: carries an accumulator film from one camera to another by the guide films' first hits, a pass of its own no frame launches
+//   outlier_clamp.hip  k_outlier_clamp: clamps a film's pixels to bounds taken from a reference film's neighbourhoods (despeckle, history clamp), a pass of its own no frame launches
 //   display.hip        k_display_histogram, k_display_exposure, k_display_encode: a film's radiance to an RGBA8 sRGB image, a pass of its own no frame launches
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
@@ -294,6 +295,23 @@ enum { PHX_REPROJECT_BLOCK = 256, PHX_REPROJECT_SLOTS = 64, PHX_REPROJECT_SLOT_W
 // of slot (workgroup id % SLOTS); the caller sums the slots.
 void launch_reproject(hipStream_t stream, const ReprojectArgs& A, const float* acc_from, const float* guides_from, const float* guides_to, float* acc_to,
                       unsigned long long* counters);
+
+// The outlier clamp (phx_outlier_clamp in phx_xpu.h states the rule; outlier_clamp.hip): one launch, a workgroup per tile of
+// PHX_OUTLIER_TILE x PHX_OUTLIER_TILE output pixels, one thread per pixel in binary64.  The workgroup moves the rows of ref that its tile
+// and a halo of `radius` pixels cover into LDS as they lie in memory (16-byte accesses where a row's range allows them), and every tap is
+// read from there.  xstride_b <= PHX_OUTLIER_MAX_XSTRIDE and radius <= PHX_OUTLIER_MAX_RADIUS (outlier_clamp_check.h: the check refuses
+// more) bound the LDS of a launch: 22 rows of at most 22 * 24 + 4 floats = 47 KB (outlier_clamp.hip asserts it).
+struct OutlierClampArgs {
+  uint32_t width, height, xstride_a, m2_offset_a, samples_offset_a, xstride_b;
+  uint32_t flags, radius, trim, min_taps;
+  uint32_t a_is_b;  // ref is film (or the call's copy of it): a thread reads its own pixel of A out of the tile in LDS
+  double gamma, floor, clamped_history;
+};
+enum { PHX_OUTLIER_TILE = 16, PHX_OUTLIER_SLOTS = 64, PHX_OUTLIER_SLOT_WORDS = 16 };
+// film_out may be film; ref shares no byte with film_out.  counters: nullptr, or PHX_OUTLIER_SLOTS zeroed slots of PHX_OUTLIER_SLOT_WORDS
+// 64-bit words (a 128-byte line each, as for launch_accumulate).  A workgroup adds pixels, skipped, unbounded, inside, clamped, capped
+// (phx_outlier_clamp_summary) to the first six words of slot (workgroup id % SLOTS); the caller sums the slots.
+void launch_outlier_clamp(hipStream_t stream, const OutlierClampArgs& A, const float* film, const float* ref, float* film_out, unsigned long long* counters);
 
 // stage-level entry points (synchronous helpers for the parity tests)
 // light_pick + triangle_t::sample as k_shade_g's next-event block runs them: per item u3 = (pick, lu, lv) -> light, triangle inside it, (bu, bv), P, lpdf

@@ -489,6 +489,52 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_reproject_times(self._h, ms), "phx_dev_reproject_times")
         return {"kernel": ms[0], "call": ms[1]}
 
+    def clamp_outliers(self, film, ref=None, radius=2, gamma=4.0, floor=0.0, trim=2, min_taps=4, exclude_centre=True, upper_only=True, clamped_history=0,
+                       primary_components=4, normals=False, moments=True, samples=False, m2_offset=None, samples_offset=None, summary=True, out=None,
+                       device_ptrs=None):
+        """The outlier clamp (phx_dev_film_outlier_clamp; include/phx_xpu.h states the rule): every colour of every pixel of film is
+        clamped to mean +- (gamma standard deviations + floor) of the (2 radius + 1)^2 window around the same pixel of ref ("primary" rgb of
+        it; None: film itself), the `trim` brightest taps left out, a pixel with fewer than min_taps taps left alone -> (film, summary).
+        The defaults are the despeckle of a frame film against itself: the centre excluded, upper only.  For a history clamp pass the
+        reprojected accumulator as film, the new camera's first frame film as ref, exclude_centre=False, upper_only=False and
+        clamped_history, the most samples a clamped pixel may go on claiming (0: no cap; needs samples).  "m2" is scaled with a clamped
+        colour.  The clamp is BIASED: it removes the energy the outliers carried.  The defaults are settings, not measurements.
+        film's layout is derived as Film derives it from primary_components, normals, moments and samples, or given by m2_offset and
+        samples_offset (0: none).  A C-contiguous float32 film is clamped in place and returned; anything else is copied first; out: an
+        array of film's shape that receives the result instead (it may be ref), film is then left alone.  summary: a dict of pixels,
+        skipped, unbounded, inside, clamped and capped (None with summary=False).  device_ptrs: (film, ref, out) addresses of
+        device-resident films (ref may be film's, out may be film's or ref's); film and ref then are only their shapes, and the call
+        returns (None, summary).  Needs no scene."""
+        on_device = device_ptrs is not None
+        shape_a = tuple(film) if on_device and not hasattr(film, "shape") else film.shape
+        shape_b = shape_a if ref is None else tuple(ref) if on_device and not hasattr(ref, "shape") else ref.shape
+        q = outlier_clamp_settings(shape_a, shape_b, radius, gamma, floor, trim, min_taps, exclude_centre, upper_only, clamped_history, primary_components,
+                                   normals, moments, samples, m2_offset, samples_offset)
+        s = abi.OutlierClampSummary() if summary else None
+        if on_device:
+            q.on_device = 1
+            (pa, pb, po), res, keep = (int(p) for p in device_ptrs), None, None
+        else:
+            def writable(a):
+                return isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable
+            if out is not None and (not writable(out) or out.shape != tuple(shape_a)):
+                raise ValueError("clamp_outliers: out must be a writable C-contiguous float32 array of film's shape")
+            if out is None:
+                src = res = film if writable(film) else np.array(film, np.float32, order="C")
+            else:
+                src, res = np.ascontiguousarray(film, np.float32), out
+            keep = src if ref is None or ref is film else out if ref is out else np.ascontiguousarray(ref, np.float32)
+            pa, pb, po = src.ctypes.data, keep.ctypes.data, res.ctypes.data
+        _check(self._lib, self._lib.phx_dev_film_outlier_clamp(self._h, C.byref(q), pa, pb, po, C.byref(s) if s is not None else None),
+               "phx_dev_film_outlier_clamp")
+        return res, (None if s is None else {k: int(getattr(s, k)) for k, _ in s._fields_})
+
+    def outlier_clamp_times(self):
+        """milliseconds of the last clamp_outliers(): dict of kernel (HIP events) and call (host clock)"""
+        ms = (C.c_double * 2)()
+        _check(self._lib, self._lib.phx_dev_outlier_clamp_times(self._h, ms), "phx_dev_outlier_clamp_times")
+        return {"kernel": ms[0], "call": ms[1]}
+
     def display(self, film, exposure=1.0, tone="aces", white=4.0, dither=True, key=0.18, percentiles=(0.5, 0.95), scale_range=(2.0 ** -12, 2.0 ** 12),
                 summary=False, device_ptr=None, image_on_host=True, image_ptr=None, image_pitch=0, fallback=1.0):
         """The display pass (phx_dev_film_display; include/phx_xpu.h states the rule): film (H, W, xstride) f32 of any layout, of
@@ -784,6 +830,30 @@ def reproject_settings(shape_a, shape_gf, shape_gt, camera_from, camera_to, sigm
     return q
 
 
+def outlier_clamp_settings(shape_a, shape_b, radius=2, gamma=4.0, floor=0.0, trim=2, min_taps=4, exclude_centre=True, upper_only=True, clamped_history=0,
+                           primary_components=4, normals=False, moments=True, samples=False, m2_offset=None, samples_offset=None):
+    """abi.OutlierClamp for a film of shape_a and a reference film of shape_b (H, W, xstride each) in host memory.  The film's "m2" and
+    "samples" are where Film puts them for primary_components, normals, moments and samples ("samples" behind "m2", so an accumulator is
+    moments=True, samples=True), unless m2_offset / samples_offset say otherwise (0: none).  ValueError for films of different sizes or a
+    film narrower than the derived layout."""
+    if len(shape_a) != 3 or len(shape_b) != 3:
+        raise ValueError("clamp_outliers: both films must be (height, width, xstride)")
+    (H, W, xa), (Hb, Wb, xb) = ((int(v) for v in s) for s in (shape_a, shape_b))
+    if (H, W) != (Hb, Wb):
+        raise ValueError(f"clamp_outliers: the film is {W} x {H} pixels, the reference film {Wb} x {Hb}")
+    behind = primary_components + (3 if normals else 0)
+    if m2_offset is None:
+        m2_offset = behind if moments else 0
+    if samples_offset is None:
+        samples_offset = (behind + (3 if moments else 0)) if samples else 0
+    if max(behind, m2_offset + 3 if m2_offset else 0, samples_offset + 1 if samples_offset else 0) > xa:
+        raise ValueError(f"clamp_outliers: this layout needs {max(behind, m2_offset + 3, samples_offset + 1)} floats per pixel, the film has {xa}")
+    return abi.OutlierClamp(width=W, height=H, xstride_a=xa, m2_offset_a=int(m2_offset), samples_offset_a=int(samples_offset), xstride_b=xb, on_device=0,
+                            flags=(abi.OUTLIER_EXCLUDE_CENTRE if exclude_centre else 0) | (abi.OUTLIER_UPPER_ONLY if upper_only else 0),
+                            radius=int(radius), trim=int(trim), min_taps=int(min_taps), gamma=float(gamma), floor=float(floor),
+                            clamped_history=int(clamped_history))
+
+
 TONES = {"clamp": abi.TONE_CLAMP, "reinhard": abi.TONE_REINHARD, "aces": abi.TONE_ACES}
 
 
@@ -818,7 +888,7 @@ def display(film, **settings):
 
 
 def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None, adaptive=None, pps=1, depth=9, normals=False, tile_size=32,
-                       display=None, **options):
+                       display=None, despeckle=None, **options):
     """Progressive rendering on ONE device: the scene is preprocessed once, then frame k = 0, 1, ... is rendered at `spp` samples
     with sampler seed (seed + k) mod 2^64 and moments=True and pooled into an accumulator film (HipDevice.accumulate).  A generator: after
     every frame it yields (film, summary, frames_done); film is the accumulator (H, W, xstride) f32 in xpu.accumulator's layout, a view that
@@ -829,7 +899,10 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
     Its entry guides=dict(samples=4, ...) renders the guide film once, with the first frame's seed.  adaptive: a dict of
     HipDevice.set_adaptive's arguments for every frame.  display: a dict of HipDevice.display's settings ({} for the defaults); the generator
     then yields (film, summary, frames_done, image), the image (or (image, summary) under summary=True) of the film it yields: with denoise,
-    of the denoised copy.  options: further Options fields (samples_in_flight=, light_sampling=, ...)."""
+    of the denoised copy (DESIGN 21).  despeckle: a dict of HipDevice.clamp_outliers' settings (radius=, gamma=, floor=, trim=, min_taps=;
+    {} for the defaults): every frame film is then clamped in place against its own neighbourhoods, the centre excluded and upper only,
+    before it is pooled (biased: the fireflies' energy is gone).  options: further Options fields (samples_in_flight=,
+    light_sampling=, ...)."""
     if frames < 1:
         raise ValueError("render_progressive: frames must be at least 1")
     stop = dict(stop) if stop is not None else None
@@ -855,6 +928,9 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
             film = Film(W, H, 4, normals, True, adaptive is not None)
             dev.start(scene_desc, FrameState((seed + k) % (1 << 64), Tiles.make(W, H, tile_size), film, native_sink=True))
             dev.join()
+            if despeckle is not None:
+                dev.clamp_outliers(film.data, **{**despeckle, "exclude_centre": True, "upper_only": True, "primary_components": 4, "normals": normals,
+                                                 "moments": True, "samples": adaptive is not None, "summary": False})
             _, summary = dev.accumulate(acc, film.data, spp, 4, normals, adaptive is not None, **(stop or {}))
             out = acc if settings is None else dev.denoise(acc, spp, 4, normals, True, guides=guides, **settings)
             if display is None:
@@ -869,7 +945,7 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
 
 
 def render_camera_path(scene_desc, cameras, spp, frames_per_camera=1, seed=1, guide_samples=4, reproject=None, denoise=None, display=None,
-                       pps=1, depth=9, tile_size=32, **options):
+                       pps=1, depth=9, tile_size=32, history_clamp=None, **options):
     """A camera path through a static scene on ONE device: the scene is preprocessed once; then, per camera of `cameras`
     (CameraDescs of the scene's film size): set_camera; the guide film (guide_samples samples, the seed of the camera's first frame); from
     the second camera on the accumulator is carried over by HipDevice.reproject (`reproject`: a dict of its settings, sigma_plane=,
@@ -878,7 +954,10 @@ def render_camera_path(scene_desc, cameras, spp, frames_per_camera=1, seed=1, gu
     as render_progressive yields (summary is None: there is no stop) plus the summary of the reprojection that led to this camera (None at
     the first); with display, (..., reprojection, image).  film is the accumulator (H, W, 14) f32 in xpu.accumulator's layout with
     normals, replaced at every camera: copy it to keep it.  denoise, display, options: as for render_progressive; the guided denoiser
-    reads this camera's guide film (no entry `guides` is needed: guides=dict(...) carries its settings)."""
+    reads this camera's guide film (no entry `guides` is needed: guides=dict(...) carries its settings).  history_clamp: a dict of
+    HipDevice.clamp_outliers' settings (radius=, gamma=, floor=, trim=, min_taps=, clamped_history=; {} for the defaults): from the second
+    camera on the reprojected accumulator is clamped, two-sided and with the centre included, against the neighbourhoods of that camera's
+    first frame film before that frame is pooled."""
     if frames_per_camera < 1:
         raise ValueError("render_camera_path: frames_per_camera must be at least 1")
     dev = HipDevice.make(Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, **options))
@@ -902,11 +981,14 @@ def render_camera_path(scene_desc, cameras, spp, frames_per_camera=1, seed=1, gu
             moved = None
             if previous is not None:
                 acc, moved = dev.reproject(acc, guides_before, guides, previous, camera, **(reproject or {}))
-            for _ in range(frames_per_camera):
+            for first in [True] + [False] * (frames_per_camera - 1):
                 film = Film(W, H, 4, True, True, False)
                 dev.start(scene_desc, FrameState((seed + k) % (1 << 64), Tiles.make(W, H, tile_size), film, native_sink=True))
                 dev.join()
                 k += 1
+                if history_clamp is not None and previous is not None and first:
+                    dev.clamp_outliers(acc, film.data, **{**history_clamp, "exclude_centre": False, "upper_only": False, "primary_components": 4,
+                                                          "normals": True, "moments": True, "samples": True, "summary": False})
                 dev.accumulate(acc, film.data, spp, 4, True, False)
                 if settings is None:
                     out = acc

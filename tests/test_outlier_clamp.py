@@ -1,0 +1,463 @@
+"""The outlier clamp (phx_outlier_clamp) without a GPU: the ABI and the header's text, every refusal of the argument check and every
+way two films can share a byte (csrc/outlier_clamp_check.cpp through tests/native/host_outlier_clamp.cpp), the Python layout helper, and
+the float64 model of the rule (tests/outlier_clamp64.py): constants, Samuelson's bound, bounds derived by hand, trimming, m2, the cap,
+non-finite and skipped pixels, the film's edges, min_taps, UPPER_ONLY, the synthetic payoff and the history case.  The device is held to
+the same model bit for bit in tests/test_gpu_outlier_clamp.py."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import outlier_clamp64 as oc
+import outlier_clamp_cases as OC
+from conftest import ROOT
+
+F, D = np.float32, np.float64
+NATIVE = os.path.join(ROOT, "tests", "native")
+CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
+HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off"]
+SOURCES = [os.path.join(NATIVE, "host_outlier_clamp.cpp"), os.path.join(CSRC, "outlier_clamp_check.cpp")]
+ERR_ARG = 1
+FIELDS = ["width", "height", "xstride_a", "m2_offset_a", "samples_offset_a", "xstride_b", "on_device", "flags", "radius", "trim", "min_taps", "gamma", "floor",
+          "clamped_history", "reserved"]
+SUMMARY = ["pixels", "skipped", "unbounded", "inside", "clamped", "capped"]
+EX, UP = oc.EXCLUDE_CENTRE, oc.UPPER_ONLY
+
+
+# ---- 1. the ABI and the header ------------------------------------------------------------------------------------------------------------
+def test_struct_size_and_field_offsets():
+    from phosphorus_mk2_amd import abi
+    assert C.sizeof(abi.OutlierClamp) == 64
+    assert [f for f, _ in abi.OutlierClamp._fields_] == FIELDS
+    assert [getattr(abi.OutlierClamp, f).offset for f in FIELDS] == [4 * i for i in range(15)]
+    assert abi.OutlierClamp.reserved.size == 8
+    assert [f for f, _ in abi.OutlierClampSummary._fields_] == SUMMARY and C.sizeof(abi.OutlierClampSummary) == 48
+    assert (abi.OUTLIER_EXCLUDE_CENTRE, abi.OUTLIER_UPPER_ONLY) == (EX, UP) == (1, 2)
+    for name in ("phx_dev_film_outlier_clamp", "phx_dev_outlier_clamp_times"):
+        assert name in abi.EXPORTS
+
+
+def test_struct_size_is_the_librarys():
+    from phosphorus_mk2_amd import abi, xpu
+    if not os.path.exists(xpu.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    lib = xpu.load_library()
+    assert lib.phx_abi_sizeof(23) == C.sizeof(abi.OutlierClamp) == 64 and lib.phx_abi_sizeof(24) == C.sizeof(abi.OutlierClampSummary) == 48
+    assert lib.phx_abi_sizeof(21) == C.sizeof(abi.Reproject) and lib.phx_abi_sizeof(22) == C.sizeof(abi.ReprojectSummary)  # the earlier indices stay
+
+
+def test_header_states_the_struct_and_the_rule():
+    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
+    body = re.search(r"typedef struct phx_outlier_clamp \{(.*?)\} phx_outlier_clamp;", hdr, re.S).group(1)
+    names = re.findall(r"\b(\w+)(?:\[2\])?\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert names == FIELDS
+    assert re.search(r"uint64_t\s+pixels,\s*skipped,\s*unbounded,\s*inside,\s*clamped,\s*capped;\s*\} phx_outlier_clamp_summary;", hdr)
+    assert re.search(r"enum \{ PHX_OUTLIER_EXCLUDE_CENTRE = 1, PHX_OUTLIER_UPPER_ONLY = 2 \};", hdr)
+    assert re.search(r"int\s+phx_dev_film_outlier_clamp\(phx_device\* dev, const phx_outlier_clamp\* c, const float\* film, const float\* ref, float\* film_out,"
+                     r"\s+phx_outlier_clamp_summary\* summary", hdr)
+    assert re.search(r"int\s+phx_dev_outlier_clamp_times\(const phx_device\* dev, double\* ms", hdr)
+    rule = hdr[hdr.index("the outlier clamp (DESIGN 23)"):hdr.index("typedef struct phx_outlier_clamp {")]
+    flat = " ".join(rule.replace("*", " ").split())
+    for phrase in ["binary64, without contraction", "dy = -r .. r outer, dx = -r .. r inner", "l_q = (0.2126 R + 0.7152 G) + 0.0722 B",
+                   "among equals the earlier one in tap order", "k < min_taps", "sums starting at 0.0", "mu = (sum of B_q,c) / k",
+                   "s = (sum of (B_q,c - mu) (B_q,c - mu)) / k", "w = gamma sqrt(s) + floor", "hi = mu + w; lo = mu - w", "A'_c = fp32(hi)",
+                   "A'_c = fp32(lo)", "f = A'_c / A_c", "v = (v f) f", "samples := fp32(clamped_history)", "v = v (n / n_out)",
+                   "Any partial overlap is refused", "device copy of ref", "BIASED", "removes the energy", "Samuelson"]:
+        assert " ".join(phrase.split()) in flat, phrase
+
+
+def test_python_settings_derive_the_layout_as_film_does():
+    from phosphorus_mk2_amd import abi, xpu
+    q = xpu.outlier_clamp_settings((5, 7, 7), (5, 7, 7))                                     # a frame film with moments: rgba, m2
+    assert (q.width, q.height, q.xstride_a, q.m2_offset_a, q.samples_offset_a, q.xstride_b, q.on_device) == (7, 5, 7, 4, 0, 7, 0)
+    assert (q.flags, q.radius, q.trim, q.min_taps, q.gamma, q.floor, q.clamped_history, list(q.reserved)) == (EX | UP, 2, 2, 4, 4.0, 0.0, 0, [0, 0])
+    acc = xpu.accumulator(7, 5, 4, True)
+    q = xpu.outlier_clamp_settings(acc.shape, (5, 7, 10), 1, 2.5, 0.125, 0, 9, False, False, 8, 4, True, True, True)
+    assert (q.xstride_a, q.m2_offset_a, q.samples_offset_a, q.xstride_b) == (11, 7, 10, 10)
+    assert (q.flags, q.radius, q.trim, q.min_taps, q.gamma, q.floor, q.clamped_history) == (0, 1, 0, 9, 2.5, 0.125, 8)
+    q = xpu.outlier_clamp_settings((5, 7, 24), (5, 7, 3), m2_offset=17, samples_offset=5)
+    assert (q.m2_offset_a, q.samples_offset_a, q.xstride_b) == (17, 5, 3)
+    q = xpu.outlier_clamp_settings((5, 7, 3), (5, 7, 3), primary_components=3, moments=False)
+    assert (q.xstride_a, q.m2_offset_a, q.samples_offset_a) == (3, 0, 0)
+    with pytest.raises(ValueError, match="pixels"):
+        xpu.outlier_clamp_settings((5, 7, 7), (5, 8, 7))
+    with pytest.raises(ValueError, match="floats per pixel"):
+        xpu.outlier_clamp_settings((5, 7, 6), (5, 7, 6))
+
+
+# ---- 2. the refusals ----------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def host():
+    from phosphorus_mk2_amd import abi
+    so = os.path.join(NATIVE, "libhost_outlier_clamp.so")
+    hdr = [os.path.join(CSRC, "outlier_clamp_check.h"), os.path.join(CSRC, "film_checks.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + hdr):
+        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
+    lib = C.CDLL(so)
+    lib.ho_check.argtypes = [C.POINTER(abi.OutlierClamp)] + [C.c_void_p] * 3 + [C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]; lib.ho_check.restype = C.c_int
+    lib.ho_sizeof.restype = C.c_uint32; lib.ho_sizeof_summary.restype = C.c_uint32
+    assert lib.ho_sizeof() == C.sizeof(abi.OutlierClamp) and lib.ho_sizeof_summary() == C.sizeof(abi.OutlierClampSummary)
+    return lib
+
+
+FAR = (1 << 40, 2 << 40, 3 << 40)  # film, ref, film_out far apart: the largest film is 2^32 pixels of 96 bytes
+
+
+@pytest.fixture(scope="module")
+def check(host):
+    def run(q, ptrs=FAR, copy=False):
+        err, cp = C.create_string_buffer(256), C.c_int(-1)
+        rc = host.ho_check(C.byref(q), *ptrs, err, 256, C.byref(cp))
+        return (rc, err.value.decode(), cp.value) if copy else (rc, err.value.decode())
+    return run
+
+
+def good(**kw):
+    from phosphorus_mk2_amd import xpu
+    W, H = kw.get("width", 64), kw.get("height", 48)
+    q = xpu.outlier_clamp_settings((H, W, 11), (H, W, 11), m2_offset=7, samples_offset=10)
+    for k, v in kw.items():
+        setattr(q, k, v)
+    return q
+
+
+NAN, INF = float("nan"), float("inf")
+ACCEPTED = [dict(), dict(width=1, height=1), dict(width=65536, height=65536), dict(on_device=1), dict(xstride_a=24, xstride_b=24), dict(xstride_b=3),
+            dict(xstride_a=3, m2_offset_a=0, samples_offset_a=0), dict(m2_offset_a=0), dict(samples_offset_a=0), dict(m2_offset_a=8, samples_offset_a=7),
+            dict(m2_offset_a=3, samples_offset_a=6), dict(flags=0), dict(flags=1), dict(flags=2), dict(flags=3), dict(radius=1, min_taps=9),
+            dict(radius=3, min_taps=49), dict(trim=0), dict(trim=3), dict(min_taps=1), dict(min_taps=25), dict(gamma=0.0), dict(gamma=1e30, floor=1e30),
+            dict(clamped_history=1), dict(clamped_history=0xffffffff)]
+REFUSED = [("width", dict(width=0)), ("width", dict(width=65537)), ("height", dict(height=0)), ("height", dict(height=65537)),
+           ("xstride_a", dict(xstride_a=2)), ("xstride_a", dict(xstride_a=25)),
+           ("m2_offset_a", dict(m2_offset_a=2)), ("m2_offset_a", dict(m2_offset_a=9)), ("m2_offset_a", dict(m2_offset_a=0xfffffffe)),
+           ("samples_offset_a", dict(samples_offset_a=2)), ("samples_offset_a", dict(samples_offset_a=11)), ("samples_offset_a", dict(samples_offset_a=7)),
+           ("samples_offset_a", dict(samples_offset_a=9)), ("samples_offset_a", dict(samples_offset_a=0xffffffff)),
+           ("xstride_b", dict(xstride_b=2)), ("xstride_b", dict(xstride_b=25)), ("on_device", dict(on_device=2)),
+           ("flags", dict(flags=4)), ("flags", dict(flags=0x80000001)), ("radius", dict(radius=0)), ("radius", dict(radius=4)), ("trim", dict(trim=4)),
+           ("min_taps", dict(min_taps=0)), ("min_taps", dict(min_taps=26)), ("min_taps", dict(radius=1, min_taps=10)), ("min_taps", dict(radius=3, min_taps=50)),
+           ("gamma", dict(gamma=-1.0)), ("gamma", dict(gamma=NAN)), ("gamma", dict(gamma=INF)), ("floor", dict(floor=-1e-30)), ("floor", dict(floor=NAN)),
+           ("floor", dict(floor=INF)), ("clamped_history", dict(samples_offset_a=0, clamped_history=1))]
+
+
+def ident(kw):
+    return ",".join(f"{k}={v}" for k, v in kw.items()) or "defaults"
+
+
+@pytest.mark.parametrize("kw", ACCEPTED, ids=[ident(kw) for kw in ACCEPTED])
+def test_check_accepts(check, kw):
+    assert check(good(**kw)) == (0, "")
+
+
+@pytest.mark.parametrize("field,kw", REFUSED, ids=[ident(kw) for _, kw in REFUSED])
+def test_check_refuses_and_names_the_field(check, field, kw):
+    rc, msg = check(good(**kw))
+    assert rc == ERR_ARG and msg == f"outlier_clamp: {field} is outside its range (phx_outlier_clamp)", (rc, msg)
+
+
+def test_the_refusals_come_in_the_fields_order(check):
+    """every field wrong at once, then mended one by one from the front: the check names the first that is still wrong"""
+    q = good(width=0, height=0, xstride_a=2, m2_offset_a=2, samples_offset_a=2, xstride_b=2, on_device=2, flags=4, radius=0, trim=4, min_taps=0, gamma=-1.0,
+             floor=-1.0, clamped_history=1)
+    q.reserved[0] = 1
+    fixes = [("width", dict(width=64)), ("height", dict(height=48)), ("xstride_a", dict(xstride_a=11)), ("m2_offset_a", dict(m2_offset_a=7)),
+             ("samples_offset_a", dict(samples_offset_a=0)), ("xstride_b", dict(xstride_b=11)), ("on_device", dict(on_device=0)), ("flags", dict(flags=3)),
+             ("radius", dict(radius=2)), ("trim", dict(trim=3)), ("min_taps", dict(min_taps=25)), ("gamma", dict(gamma=4.0)), ("floor", dict(floor=0.0)),
+             ("clamped_history", dict(samples_offset_a=10)), ("reserved", None)]
+    for field, fix in fixes:
+        assert re.search(rf": {field} is outside", check(q)[1]), (field, check(q))
+        for k, v in (fix or {}).items():
+            setattr(q, k, v)
+        if fix is None:
+            q.reserved[0] = 0
+    assert check(q) == (0, "")
+    for ptrs, field in (((0, FAR[1], FAR[2]), "film"), ((FAR[0], 0, FAR[2]), "ref"), ((FAR[0], FAR[1], 0), "film_out"), ((0, 0, 0), "film")):
+        q.reserved[1] = 0
+        assert re.search(rf": {field} is outside", check(q, ptrs)[1]), field
+        q.reserved[1] = 1
+        assert "reserved" in check(q, ptrs)[1]            # the struct's words before the pointers
+
+
+def test_every_way_two_films_can_share_a_byte(check):
+    q = good()
+    n = 64 * 48 * 11 * 4                                   # bytes of either film
+    a, b, o = 0x1000000, 0x1000000 + n, 0x1000000 + 2 * n  # back to back: no byte shared
+    ok = lambda ptrs, copy: check(q, ptrs, True) == (0, "", copy)
+    no = lambda ptrs, field: check(q, ptrs, True)[0] == ERR_ARG and re.search(rf": {field} is outside", check(q, ptrs)[1])
+    assert ok((a, b, o), 0) and ok((o, a, b), 0) and ok((b, o, a), 0)
+    assert ok((a, b, a), 0)          # in place
+    assert ok((a, a, o), 0)          # ref is film
+    assert ok((a, a, a), 1)          # both: the bounds come from a copy
+    assert ok((a, b, b), 1)          # film_out is ref
+    for d in (4, n - 4, -4, -n + 4, n // 2):
+        assert no((a, a + d, o + n), "ref"), d                       # ref overlaps film partially
+        assert no((a, b + n, a + d), "film_out"), d                  # film_out overlaps film partially
+        assert no((a, b, b + d), "film_out"), d                      # film_out overlaps ref (or, from below, film) partially
+        assert no((a, o + n, o + n + d), "film_out"), d              # film_out overlaps ref partially from either side, clear of film
+        assert no((a, a + d, a), "ref"), d                           # in place with a shifted ref
+    # ref at film's address but of another stride is a partial overlap; so is film_out at ref's
+    q3 = good(xstride_b=3)
+    assert re.search(r": ref is outside", check(q3, (a, a, o))[1]) and re.search(r": film_out is outside", check(q3, (a, o, o))[1])
+    assert check(q3, (a, b, a), True) == (0, "", 0)
+    # the first and the last byte: [p, p + n) against [p + n, ...) and [p - n, p)
+    assert ok((a, a + n, a + 2 * n), 0) and ok((a + 2 * n, a + n, a), 0)
+    assert no((a, a + n - 1, a + 2 * n), "ref") and no((a, a + n, a + 2 * n - 1), "film_out") and no((a + 1, a + 4 * n, a - n + 2), "film_out")
+
+
+def test_the_check_under_the_sanitizers(tmp_path):
+    """host_outlier_clamp.cpp's own main() under AddressSanitizer and UBSan: its cases get the answers above, and the program ends without a report"""
+    exe = str(tmp_path / "host_outlier_clamp_asan")
+    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_OUTLIER_CLAMP_MAIN"] +
+                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
+    got = {l.split()[0]: (int(l.split()[1]), int(l.split()[2]), l) for l in r.stdout.splitlines()}
+    want = {"good": (None, 0), "in-place": (None, 0), "self": (None, 0), "self-in-place": (None, 1), "out-is-ref": (None, 1),
+            "ref-overlaps-film": ("ref", 0), "out-overlaps-film": ("film_out", 0), "out-overlaps-ref": ("film_out", 0), "null-film": ("film", 0),
+            "null-ref": ("ref", 0), "null-out": ("film_out", 0), "self-other-stride": ("ref", 0), "width": ("width", 0), "height": ("height", 0),
+            "xstride-a": ("xstride_a", 0), "m2-wrap": ("m2_offset_a", 0), "samples-in-m2": ("samples_offset_a", 0), "xstride-b": ("xstride_b", 0),
+            "on-device": ("on_device", 0), "flags": ("flags", 0), "radius": ("radius", 0), "trim": ("trim", 0), "min-taps": ("min_taps", 0),
+            "gamma": ("gamma", 0), "floor": ("floor", 0), "clamped-history": ("clamped_history", 0), "reserved": ("reserved", 0)}
+    assert set(want) == set(got)
+    for name, (field, copy) in want.items():
+        rc, cp, line = got[name]
+        assert cp == copy, line
+        assert (rc == 0 and line.split()[3:] == []) if field is None else (rc == ERR_ARG and re.search(rf": {field} is outside", line)), line
+
+
+# ---- 3. properties of the model -----------------------------------------------------------------------------------------------------------
+def rgb_film(values):
+    """(H, W) -> a grey film (H, W, 3) f32"""
+    return np.repeat(np.asarray(values, F)[..., None], 3, -1)
+
+
+def test_a_constant_film_comes_back_bit_for_bit():
+    for value in (0.0, 0.3, 1e-30, 7e30, -2.5):
+        for r in (1, 2, 3):
+            for flags in (0, EX, UP, EX | UP):
+                for trim in (0, 3):
+                    A = np.full((9, 11, 7), F(value)); A[..., 6] = 4
+                    out, s, _ = oc.clamp(A, A, 3, 6, r, 4.0, 0.0, trim, 1, flags, 2)
+                    assert oc.same(out, A) and s["inside"] + s["unbounded"] == s["pixels"] == 99 and s["clamped"] == s["capped"] == 0, (value, r, flags, trim)
+                    assert s["unbounded"] == (0 if trim == 0 or r > 1 or not flags & EX else 4), (r, flags, trim)   # a corner of radius 1 has 3 taps without its centre
+
+
+def test_samuelson_no_pixel_of_a_film_leaves_its_own_windows_bounds():
+    """A = B, the centre included, floor = 0, trim = 0: a sample lies at most sqrt(k - 1) deviations from the mean of the k it belongs to
+    (Samuelson's inequality), k <= 49, sqrt(48) < 7.  The margin 7 - sqrt(48) = 0.07 deviations is some 1e14 times the rounding error of
+    49 binary64 additions"""
+    rng = np.random.default_rng(5)
+    A = OC.heavy(rng, 41, 33, 7, 3, 6, specials=False)
+    for r in (1, 2, 3):
+        out, s, _ = oc.clamp(A, A, 3, 6, r, 7.0, 0.0, 0, 1, 0, 1)
+        assert oc.same(out, A) and s["inside"] == 41 * 33 and s["clamped"] == 0, r
+    out, s, _ = oc.clamp(A, A, 3, 6, 2, 0.5, 0.0, 0, 1, 0)    # and the film is not one the clamp leaves alone anyway
+    assert s["clamped"] > 100
+
+
+def one_spike():
+    """a 9 x 9 film of short mantissas: 1 everywhere, 3 in a plus around the centre, a spike of 1000 at the centre"""
+    g = np.ones((9, 9))
+    g[4, 4] = 1000.0
+    for dy, dx in ((0, 1), (0, -1), (1, 0), (-1, 0)):
+        g[4 + dy, 4 + dx] = 3.0
+    return rgb_film(g)
+
+
+def test_one_spike_is_pulled_to_the_bound_derived_by_hand():
+    """radius 1, the centre excluded, trim 0: the spike's eight taps are four 3s and four 1s: mu = 16 / 8 = 2, every deviation is 1, s = 8 / 8 = 1,
+    w = gamma * 1 + floor.  gamma = 2.5, floor = 0.25: hi = 4.75.  No other pixel changes a bit under UPPER_ONLY: the spike is excluded from no
+    neighbour's window, so each neighbour's own bound is far above its value"""
+    A = one_spike()
+    out, s, cls = oc.clamp(A, A, 0, 0, 1, 2.5, 0.25, 0, 1, EX | UP)
+    assert out[4, 4].tolist() == [4.75] * 3
+    changed = ~(out.view(np.uint32) == A.view(np.uint32)).all(-1)
+    assert changed.sum() == 1 and changed[4, 4]
+    assert s == {"pixels": 81, "skipped": 0, "unbounded": 0, "inside": 80, "clamped": 1, "capped": 0} and cls[4, 4] == 3
+    # why the despeckle excludes the centre: with its own value among the nine taps the spike lies sqrt(8) = 2.83 deviations above their mean
+    # (Samuelson's bound, reached by one outlier among equals), so gamma = 3 already lets it through
+    out2, _, _ = oc.clamp(A, A, 0, 0, 1, 3.0, 0.25, 0, 1, 0)
+    v = np.array([1, 3, 1, 3, 1000, 3, 1, 3, 1], D)
+    mu = v.sum() / 9
+    assert 1000.0 <= mu + 3.0 * math.sqrt(((v - mu) ** 2).sum() / 9) + 0.25 and out2[4, 4, 0] == 1000.0 and out2[0, 0].tolist() == [1.0] * 3
+
+
+def test_two_adjacent_spikes_need_the_trim():
+    """spikes of 1000 at (4, 4) and (4, 5) on a film of 1s, radius 1, the centre excluded, gamma = 2, floor = 0.5.
+    trim 0: each spike's eight taps are seven 1s and the other spike: mu = 1007 / 8 = 125.875; the deviations are -124.875 seven times and 874.125
+    once; s = (7 * 124.875^2 + 874.125^2) / 8; hi = mu + 2 sqrt(s) + 0.5: the weak bound, some 787.
+    trim 1: the other spike is dropped, seven 1s are left: mu = 1, s = 0, hi = 1.5: the clean neighbourhood's bound."""
+    g = np.ones((9, 10))
+    g[4, 4] = g[4, 5] = 1000.0
+    A = rgb_film(g)
+    mu = D(1007.0) / 8
+    s = (7 * (1 - mu) * (1 - mu) + (1000 - mu) * (1000 - mu)) / 8
+    weak = F(mu + 2.0 * np.sqrt(s) + 0.5)
+    assert 780 < weak < 790
+    out0, s0, _ = oc.clamp(A, A, 0, 0, 1, 2.0, 0.5, 0, 1, EX | UP)
+    assert out0[4, 4].tolist() == [weak] * 3 and out0[4, 5].tolist() == [weak] * 3 and s0["clamped"] == 2
+    out1, s1, _ = oc.clamp(A, A, 0, 0, 1, 2.0, 0.5, 1, 1, EX | UP)
+    assert out1[4, 4].tolist() == [1.5] * 3 and out1[4, 5].tolist() == [1.5] * 3 and s1["clamped"] == 2
+    for out in (out0, out1):
+        rest = np.ones((9, 10), bool); rest[4, 4] = rest[4, 5] = False
+        assert oc.same(out[rest], A[rest])
+    # among equals the EARLIER tap goes: at (4, 3) the window holds one spike, at (3, 4) two; with trim 1 and two equal maxima the first in
+    # tap order, (4, 4), is dropped and (4, 5) stays: seven taps of 1 and one of 1000 are left of nine
+    k, lo, hi = oc.bounds((9, 10), A, 1, 2.0, 0.5, 1, 0)
+    assert k[3, 4] == 8 and hi[3, 4, 0] == mu + 2.0 * np.sqrt(s) + 0.5
+
+
+def test_m2_scaling_and_the_samples_cap_exactly():
+    """the spike 1000 -> 4.75 of test_one_spike...: f = 4.75 / 1000 in binary64, m2 = fp32((m2 * f) * f); with clamped_history = 8 and n = 32 samples
+    := 8 and m2 is multiplied by 32 / 8 = 4 as well, for all three colours; a pixel that is not clamped keeps m2 and samples bit for bit"""
+    rgb = one_spike()
+    A = np.zeros((9, 9, 8), F)
+    A[..., :3] = rgb
+    A[..., 3] = 0.123                                     # a fourth component: nobody's business
+    A[..., 4:7] = [3.0, 5.0, 7.0]
+    A[..., 7] = 32
+    A[4, 4, 1] = 2.0                                      # the green of the spike lies inside the bounds: not clamped, but capped with the pixel
+    f = D(F(4.75)) / D(1000.0)
+    out, s, _ = oc.clamp(A, A, 4, 7, 1, 2.5, 0.25, 0, 1, EX | UP)
+    assert out[4, 4, :4].tolist() == [4.75, 2.0, 4.75, F(0.123)] and out[4, 4, 7] == 32
+    assert out[4, 4, 4:7].tolist() == [F((3.0 * f) * f), 5.0, F((7.0 * f) * f)] and s["capped"] == 0
+    out, s, _ = oc.clamp(A, A, 4, 7, 1, 2.5, 0.25, 0, 1, EX | UP, clamped_history=8)
+    assert out[4, 4, 7] == 8 and s["capped"] == 1 and s["clamped"] == 1
+    assert out[4, 4, 4:7].tolist() == [F(((3.0 * f) * f) * 4.0), F(5.0 * 4.0), F(((7.0 * f) * f) * 4.0)]
+    rest = np.ones((9, 9), bool); rest[4, 4] = False
+    assert oc.same(out[rest], A[rest])
+    out, s, _ = oc.clamp(A, A, 4, 7, 1, 2.5, 0.25, 0, 1, EX | UP, clamped_history=32)    # n > clamped_history is false: no cap
+    assert out[4, 4, 7] == 32 and s["capped"] == 0
+    # a colour clamped from a negative value up to a positive bound, or from 0: f is outside [0, 1) or undefined, m2 keeps its bits
+    B = A.copy(); B[4, 4, :3] = [-1000.0, 0.0, 1000.0]
+    ref = A.copy(); ref[..., :3] = 2.0
+    out, s, _ = oc.clamp(B, ref, 4, 7, 1, 0.0, 0.5, 0, 1, 0)
+    assert out[4, 4, :3].tolist() == [1.5, 1.5, 2.5] and oc.same(out[4, 4, 4:6], B[4, 4, 4:6]) and out[4, 4, 6] == F((7.0 * (2.5 / 1000.0)) * (2.5 / 1000.0))
+
+
+def test_a_non_finite_pixel_of_b_is_no_tap_and_reaches_only_its_window():
+    rng = np.random.default_rng(2)
+    A = OC.heavy(rng, 15, 13, 7, 3, 6, specials=False)
+    B = OC.heavy(rng, 15, 13, 4, specials=False)
+    clean, s0, _ = oc.clamp(A, B, 3, 6, 2, 1.0, 0.0, 1, 4, 0)
+    for ch, v in ((0, np.nan), (1, np.inf), (2, -np.inf)):
+        B2 = B.copy(); B2[6, 7, ch] = v
+        out, s, _ = oc.clamp(A, B2, 3, 6, 2, 1.0, 0.0, 1, 4, 0)
+        changed = ~(out.view(np.uint32) == clean.view(np.uint32)).all(-1)
+        ys, xs = np.nonzero(changed)
+        assert len(ys) > 0 and (np.abs(ys - 6) <= 2).all() and (np.abs(xs - 7) <= 2).all() and np.isfinite(out[..., :3]).all()
+        k, _, _ = oc.bounds((13, 15), B2, 2, 1.0, 0.0, 0, 0)
+        assert k[6, 7] == 24 and k[5, 6] == 24 and k[0, 0] == 9 and k[6, 10] == 25
+    B3 = np.full_like(B, np.nan)
+    out, s, _ = oc.clamp(A, B3, 3, 6, 2, 1.0, 0.0, 0, 1, 0)
+    assert oc.same(out, A) and s["unbounded"] == 15 * 13               # no tap anywhere
+
+
+def test_a_skipped_pixel_stays_as_it_was():
+    rng = np.random.default_rng(3)
+    A = OC.heavy(rng, 12, 10, 7, 3, 6, specials=False)
+    A[..., :3] = np.abs(A[..., :3]) + 100.0                              # far above the reference: every pixel that is not skipped is clamped
+    B = np.ones((10, 12, 3), F)
+    A[2, 3, 1] = np.nan; A[4, 5, 0] = np.inf; A[5, 5, 6] = 0.0; A[6, 6, 6] = np.nan; A[7, 7, 6] = -4.0; A[8, 8, 6] = np.inf
+    A[9, 9] = 0.0                                                        # reprojection's pixel without history
+    out, s, cls = oc.clamp(A, B, 3, 6, 1, 4.0, 0.0, 0, 1, 0, 2)
+    skipped = [(2, 3), (4, 5), (5, 5), (6, 6), (7, 7), (8, 8), (9, 9)]
+    for y, x in skipped:
+        assert oc.same(out[y, x], A[y, x]) and cls[y, x] == 0
+    assert s["skipped"] == 7 and s["clamped"] == 120 - 7 and not out[9, 9].any()
+    assert (out[..., 0][cls == 3] == 1.0).all()
+    # a film without a samples channel skips on its colours alone
+    out, s, cls = oc.clamp(A, B, 3, 0, 1, 4.0, 0.0, 0, 1, 0)
+    assert s["skipped"] == 2 and cls[5, 5] == 3
+
+
+def test_windows_cut_by_each_of_the_four_edges():
+    """B = 10 * y + x, a plane in small integers: every sum is exact, and the test computes mu and s of each cut window itself"""
+    H, W = 8, 9
+    ys, xs = np.mgrid[0:H, 0:W]
+    B = rgb_film(10.0 * ys + xs)
+    A = rgb_film(np.full((H, W), 1e6))
+    for r in (1, 2, 3):
+        out, s, _ = oc.clamp(A, B, 0, 0, r, 1.5, 0.0, 0, 1, 0)
+        for (y, x) in ((0, 4), (H - 1, 4), (4, 0), (4, W - 1), (0, 0), (H - 1, W - 1), (0, W - 1), (H - 1, 0), (4, 4), (1, 1)):
+            win = B[max(y - r, 0):y + r + 1, max(x - r, 0):x + r + 1, 0].astype(D).ravel()
+            mu = win.sum() / len(win)
+            want = F(mu + 1.5 * np.sqrt(((win - mu) ** 2).sum() / len(win)))
+            assert out[y, x, 0] == want, (r, y, x)
+        k, _, _ = oc.bounds((H, W), B, r, 1.5, 0.0, 0, 0)
+        assert k[0, 0] == (r + 1) ** 2 and k[0, 4] == (r + 1) * min(2 * r + 1, W) and k[4, 4] == min(2 * r + 1, H) * min(2 * r + 1, W)
+        assert s["clamped"] == H * W
+
+
+def test_min_taps_is_respected():
+    A = rgb_film(np.full((6, 6), 50.0))
+    B = rgb_film(np.ones((6, 6)))
+    for r, flags, trim in ((1, 0, 0), (1, EX, 0), (2, EX, 2), (3, 0, 3)):
+        k, _, _ = oc.bounds((6, 6), B, r, 4.0, 0.0, trim, flags)
+        for min_taps in (1, 4, 6, 9, (2 * r + 1) ** 2):
+            out, s, cls = oc.clamp(A, B, 0, 0, r, 4.0, 0.0, trim, min_taps, flags)
+            assert ((cls == 1) == (k < min_taps)).all() and ((cls == 3) == (k >= min_taps)).all()
+            assert oc.same(out[cls == 1], A[cls == 1]) and (out[cls == 3] == 1.0).all()
+            assert s["unbounded"] == int((k < min_taps).sum())
+    k, _, _ = oc.bounds((1, 1), B[:1, :1], 2, 4.0, 0.0, 0, EX)
+    assert k[0, 0] == 0                                                  # a 1 x 1 film without its centre: nothing bounds it
+
+
+def test_upper_only_never_raises_a_value_and_two_sided_does():
+    rng = np.random.default_rng(7)
+    A = OC.heavy(rng, 21, 17, 6, 3, 0)
+    B = OC.heavy(rng, 21, 17, 3)
+    out, s, _ = oc.clamp(A, B, 3, 0, 2, 0.5, 0.0, 1, 3, UP)
+    fin = np.isfinite(A[..., :3]).all(-1)
+    assert (out[..., :3][fin] <= A[..., :3][fin]).all() and s["clamped"] > 20
+    out2, s2, _ = oc.clamp(A, B, 3, 0, 2, 0.5, 0.0, 1, 3, 0)
+    assert (out2[..., :3][fin] > A[..., :3][fin]).any() and s2["clamped"] > s["clamped"]
+    up = out[..., :3] < A[..., :3]
+    assert oc.same(out2[..., :3][up], out[..., :3][up])                 # where the upper bound bit, both agree
+
+
+# ---- 4. what it is for ----------------------------------------------------------------------------------------------------------------------
+PAYOFF_RATIO = 0.0132   # MSE after / before on seed 19 at (radius 2, gamma 4, trim 2, min_taps 4), measured with this model
+
+
+def test_synthetic_payoff(capsys):
+    """DESIGN 23's film: a 128 x 128 ramp, 16 exponential samples a pixel, one sample in 10^4 a firefly worth 1000 x the mean.  Seed 19 is
+    asserted at 1.5 x the ratio measured when this test was written (the margin is for a change of numpy's generator), and in
+    any case below 1; seeds 1 .. 4 and the untrimmed clamp are reported"""
+    assert 1.5 * PAYOFF_RATIO < 1.0
+    rows = []
+    for seed in (19, 1, 2, 3, 4):
+        film, truth = OC.fireflies(seed)
+        before = OC.mse(film, truth)
+        out, s, _ = oc.clamp(film, film, 0, 0, 2, 4.0, 0.0, 2, 4, EX | UP)
+        out0, _, _ = oc.clamp(film, film, 0, 0, 2, 4.0, 0.0, 0, 4, EX | UP)
+        rows.append((seed, before, OC.mse(out, truth) / before, OC.mse(out0, truth) / before, float(out.astype(D).mean() / film.astype(D).mean()), s["clamped"]))
+    with capsys.disabled():
+        for seed, before, ratio, ratio0, mean, clamped in rows:
+            print(f"\n  outlier clamp payoff seed {seed}: MSE before {before:.4g}, after / before {ratio:.4f} (trim 0: {ratio0:.4f}), film mean x {mean:.4f}, {clamped} pixels clamped", end="")
+    assert rows[0][2] <= 1.5 * PAYOFF_RATIO, rows[0]
+    assert all(r[4] < 1.0 for r in rows)                                 # the stated limit: the clamp is biased, the fireflies' energy is gone
+
+
+def test_history_case_a_carried_spike_ends_inside_the_new_frames_bounds():
+    """an accumulator of 64 samples carries a spike the new frame does not show: after the clamp, two-sided and with the centre, the pixel lies
+    within [lo, hi] of the new frame's window (to the fp32 rounding of a bound below 2: 1e-6 covers half an ulp, 6e-8), claims clamped_history
+    samples, and is counted as capped; its neighbours keep their history"""
+    rng = np.random.default_rng(23)
+    H, W = 12, 14
+    new = np.zeros((H, W, 7), F)
+    new[..., :3] = (1.0 + 0.1 * rng.normal(size=(H, W, 1))).astype(F)
+    acc = np.zeros((H, W, 11), F)
+    acc[..., :3] = 1.0; acc[..., 7:10] = 0.01; acc[..., 10] = 64
+    acc[5, 6, :3] = [40.0, 35.0, 50.0]
+    acc[8, 2] = 0.0                                                     # a disoccluded pixel
+    out, s, cls = oc.clamp(acc, new, 7, 10, 1, 3.0, 0.0, 0, 4, 0, clamped_history=4)
+    k, lo, hi = oc.bounds((H, W), new, 1, 3.0, 0.0, 0, 0)
+    assert k[5, 6] == 9 and (lo[5, 6] <= out[5, 6, :3] + 1e-6).all() and (out[5, 6, :3] <= hi[5, 6] + 1e-6).all() and (hi[5, 6] < 2.0).all()
+    assert out[5, 6, 10] == 4 and cls[5, 6] == 3 and s["capped"] == s["clamped"] == 1 and s["skipped"] == 1
+    rest = np.ones((H, W), bool); rest[5, 6] = False
+    assert oc.same(out[rest], acc[rest]) and not out[8, 2].any()
