@@ -11,7 +11,7 @@
 // for an odd xstride (7, 11), 2-way for 6 and 10 and 8-way for 8, on some thirty 4-byte accesses a pixel (at strides 8 + 7 and 11 + 10 the kernel runs at a device copy's rate).
 // An untouched pixel is written back with the bits it had.
 // All arithmetic is binary64 in the rule's order (the file is compiled without contraction, as every other).
-#include "kernels.h"
+#include "film_pass.h"
 #include "accumulate_check.h"  // PHX_ACCUMULATE_MAX_XSTRIDE
 
 namespace phx {
@@ -28,12 +28,6 @@ __device__ __forceinline__ void move_span(const float* __restrict__ from, float*
   const uint32_t nvec = aligned ? count >> 2 : 0u;
   for (uint32_t v = threadIdx.x; v < nvec; v += SPAN) reinterpret_cast<float4*>(to)[v] = reinterpret_cast<const float4*>(from)[v];
   for (uint32_t i = (nvec << 2) + threadIdx.x; i < count; i += SPAN) to[i] = from[i];
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
 }
 
 }  // namespace
@@ -90,8 +84,7 @@ __global__ void __launch_bounds__(PHX_ACCUMULATE_SPAN) k_accumulate(AccumulateAr
     }
     if (counters) {  // the summary, from the floats the pixel holds now
       const double n = (double)a[A.samples_offset_a];
-      valid = isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]) && isfinite(am[0]) && isfinite(am[1]) && isfinite(am[2]) &&
-              am[0] >= 0.0f && am[1] >= 0.0f && am[2] >= 0.0f && isfinite(n) && n >= 2.0;
+      valid = accumulator_pixel_valid(a, am, n);
       if (valid) {
         const double q = n / (n - 1.0);
         converged = true;
@@ -106,19 +99,12 @@ __global__ void __launch_bounds__(PHX_ACCUMULATE_SPAN) k_accumulate(AccumulateAr
     }
   }
   if (counters) {  // (wave-uniform) ballots and one sum per wave, then one vector atomic of four lanes per workgroup
-    const unsigned long long pixels = (unsigned long long)__popcll(__ballot(live)), invalid = (unsigned long long)__popcll(__ballot(live && !valid)),
-                             conv = (unsigned long long)__popcll(__ballot(converged)), samples = wave_sum(ns);
-    if ((t & 63u) == 0u) { unsigned long long* p = part[t >> 6]; p[0] = pixels; p[1] = invalid; p[2] = conv; p[3] = samples; }
+    const unsigned long long counts[4] = {wave_count(live), wave_count(live && !valid), wave_count(converged), wave_sum(ns)};  // pixels, invalid, converged, samples
+    store_wave_counts(part, t, counts);
   }
-  __syncthreads();
+  __syncthreads();  // the one barrier behind the pixels: for the span's way back and for the counts
   move_span(sa, ga, floats_a, aligned_a);
-  if (counters && t < 4u) {
-    unsigned long long v = 0ull;
-#pragma unroll
-    for (uint32_t w = 0; w < SPAN / 64u; ++w) v += part[w][t];
-    // one line of counters per slot, the slot by workgroup id: 32 400 workgroups on ONE line took longer than the rest of the kernel
-    atomicAdd(counters + (size_t)(blockIdx.x % PHX_ACCUMULATE_SLOTS) * PHX_ACCUMULATE_SLOT_WORDS + t, v);
-  }
+  if (counters) add_workgroup_counts(part, t, blockIdx.x, counters);
 }
 
 void launch_accumulate(hipStream_t stream, const AccumulateArgs& A, float* acc, const float* frame_film, unsigned long long* counters) {

@@ -7,15 +7,14 @@ namespace phx {
 namespace {
 const char* denoise_invalid(const phx_denoise& d, const float* film_in, const float* film_out) {
   static const char* const layout[4] = {"xstride", "normals_offset", "m2_offset", "samples_offset"};
-  if (d.width < 1u || d.width > 65536u) return "width";
-  if (d.height < 1u || d.height > 65536u) return "height";
+  if (const char* field = film_size_invalid(d.width, d.height)) return field;
   if (const int k = film_layout_invalid(d.xstride, d.normals_offset, d.m2_offset, d.samples_offset, 6u, ~0u, false); k >= 0) return layout[k];
   if (d.spp < 2u) return "spp";
   if (d.iterations > 8u) return "iterations";
-  if (!std::isfinite(d.sigma_l) || !(d.sigma_l > 0.0f)) return "sigma_l";
+  if (!finite_positive(d.sigma_l)) return "sigma_l";
   if (d.normal_power_log2 > 10u) return "normal_power_log2";
   if (d.on_device > 1u) return "on_device";
-  for (uint32_t w : d.reserved) if (w) return "reserved";
+  if (any_reserved(d.reserved)) return "reserved";
   if (!film_in) return "film_in";
   if (!film_out) return "film_out";
   const uint64_t bytes = (uint64_t)d.width * d.height * d.xstride * sizeof(float);

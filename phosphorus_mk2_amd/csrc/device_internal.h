@@ -164,12 +164,11 @@ struct phx_device {
   phx::DevBuf<float> w_acc; phx::DevBuf<uint32_t> w_xy, sel_idx[2], sel_blocks;
   phx::PinnedBuf<uint32_t> h_sel;
   phx_adaptive adaptive{}; bool adaptive_on = false;
-  double guides_ms[2] = {};    // phx_dev_guides_times: the last phx_dev_render_guides' kernel and call
-  double accumulate_ms[2] = {};  // phx_dev_accumulate_times: the last phx_dev_film_accumulate's kernel and call
-  double reproject_ms[2] = {};   // phx_dev_reproject_times: the last phx_dev_film_reproject's kernel and call
-  double outlier_clamp_ms[2] = {};  // phx_dev_outlier_clamp_times: the last phx_dev_film_outlier_clamp's kernel and call
-  double display_ms[3] = {};   // phx_dev_display_times: the last phx_dev_film_display's histogram + exposure, encode and call
-  double denoise_ms[11] = {};  // phx_dev_denoise_times: the last phx_dev_denoise's stages (it holds no device memory between calls)
+  // the milliseconds of each film call's last run (film_calls.cpp: FilmCall writes them, a phx_dev_*_times getter copies its array out whole,
+  // times_of): kernel and call; the display's histogram + exposure, encode and call; the denoiser's pack, iterations 1 .. 8, unpack and call
+  double guides_ms[2] = {}, accumulate_ms[2] = {}, reproject_ms[2] = {}, outlier_clamp_ms[2] = {};
+  double display_ms[3] = {};
+  double denoise_ms[11] = {};
 
   // frame
   phx_frame frame{};

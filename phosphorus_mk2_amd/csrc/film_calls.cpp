@@ -1,10 +1,11 @@
 // film_calls.cpp — the entry points that work on a film and launch no frame: phx_dev_film_moments, phx_dev_denoise / _guided (denoise.hip),
-// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_reproject (reproject.hip), phx_dev_film_outlier_clamp (outlier_clamp.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the
-// six *_times getters.
+// phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_reproject (reproject.hip),
+// phx_dev_film_outlier_clamp (outlier_clamp.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the six *_times getters.
 //
-// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (denoise_check.cpp, guides_check.cpp, accumulate_check.cpp, display_check.cpp, reproject_check.cpp, outlier_clamp_check.cpp over film_checks.h)
-// and run before the device is selected; what the large calls share — refusals, device, events, host-film staging, the wait and the
-// times — is FilmCall below.  phx_dev_film_moments and phx_dev_adaptive_select stage plain arrays, as the stage hooks do (Staging).
+// None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (the *_check.cpp
+// files over film_checks.h) and run before the device is selected.  What the large calls share is stated once below: the refusals (refused);
+// device, events, host-film staging, the wait and the times (FilmCall); the summary's counters (SummarySlots, the host's side of film_pass.h);
+// the times getters (times_of).  phx_dev_film_moments and phx_dev_adaptive_select stage plain arrays, as the stage hooks do (Staging).
 #include "device_internal.h"
 #include "accumulate_check.h"
 #include "denoise_check.h"
@@ -29,7 +30,7 @@ int refused(const phx_device* d, const char* call, bool args, bool needs_scene =
 }
 
 // One film call on the device, behind its argument check: begin() enters the device and zeroes the call's times, stage() gives a host film a
-// device copy, mark() records an event between launches, wait() waits and copies back, times() reads the events.  Everything it holds on the
+// device copy, mark() records an event between launches, wait() waits and copies back, run() is both around one kernel, times() reads the events.  Everything it holds on the
 // device goes with it, on every way out, and the caller's device comes back.
 struct FilmCall {
   phx_device* d; double* ms;  // ms: the call's times in the device object
@@ -78,8 +79,40 @@ struct FilmCall {
     ms[call] = ms_between(t0, Clock::now());
     return PHX_OK;
   }
+  // a call of one kernel: a mark on either side of the launch, then the wait
+  template <typename F> int run(F&& launch) {
+    if (const int rc = mark()) return rc;
+    launch();
+    if (const int rc = mark()) return rc;
+    return wait();
+  }
   int kernel_and_call_times() { return times(1, [](size_t) { return (size_t)0; }); }  // two marks: (kernel, call)
 };
+
+// The counters behind a summary (kernels.h: summary slots).  zero(): before the launch, only for a caller who asked for a summary (a kernel given
+// p == nullptr counts nothing).  read(): behind FilmCall::wait(); out[k], k < n: the slots' k-th words summed, modulo 2^64 whatever the order.
+struct SummarySlots : DevBuf<unsigned long long> {
+  static constexpr size_t WORDS = (size_t)PHX_SUMMARY_SLOTS * PHX_SUMMARY_SLOT_WORDS;
+  int zero(hipStream_t stream) {
+    if (const int rc = alloc(WORDS)) return rc;
+    HIPCHK(hipMemsetAsync(p, 0, WORDS * sizeof(unsigned long long), stream));
+    return PHX_OK;
+  }
+  int read(uint64_t* out, int n) const {
+    std::vector<unsigned long long> slots(WORDS);
+    HIPCHK(hipMemcpy(slots.data(), p, WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::fill(out, out + n, (uint64_t)0);
+    for (size_t s = 0; s < (size_t)PHX_SUMMARY_SLOTS; ++s) for (int k = 0; k < n; ++k) out[k] += slots[s * PHX_SUMMARY_SLOT_WORDS + k];
+    return PHX_OK;
+  }
+};
+
+// a *_times getter: `text` for a null argument, else a copy of the device object's array
+template <size_t N> int times_of(const phx_device* d, double (phx_device::*ms)[N], double* out, const char* text) {
+  if (!d || !out) return fail(PHX_ERR_ARG, text);
+  std::copy(std::begin(d->*ms), std::end(d->*ms), out);
+  return PHX_OK;
+}
 
 }  // namespace
 
@@ -184,10 +217,7 @@ int phx_dev_render_guides(phx_device* d, const phx_guides* g, float* film) {
     if (!g->on_device) if (const int rc = call.stage(nullptr, npix * 8, film, dst)) return rc;
     PassBuffers B{};
     B.pix_xy = d_xy.p; B.jitter = d_jit.p; B.num_pixels = (uint32_t)npix; B.num_samples = g->samples; B.seed = g->sampler_seed;
-    if (const int rc = call.mark()) return rc;
-    launch_guides(d->stream, d->scene, B, dst);
-    if (const int rc = call.mark()) return rc;
-    if (const int rc = call.wait()) return rc;
+    if (const int rc = call.run([&] { launch_guides(d->stream, d->scene, B, dst); })) return rc;
     return call.kernel_and_call_times();
   });
 }
@@ -202,43 +232,30 @@ int phx_dev_film_accumulate(phx_device* d, const phx_accumulate* a, float* acc, 
     FilmCall call{d, d->accumulate_ms};
     if (const int rc = call.begin(2)) return rc;
     const size_t npix = (size_t)a->width * a->height;
-    const size_t slot_words = (size_t)PHX_ACCUMULATE_SLOTS * PHX_ACCUMULATE_SLOT_WORDS;
-    DevBuf<unsigned long long> counters;
+    SummarySlots counters;
     float *dst = acc, *frame_copy = nullptr; const float* src = frame_film;
     if (!a->on_device) {  // host films: device copies, acc's pooled in place and copied back
       if (const int rc = call.stage(acc, npix * a->xstride_a, acc, dst)) return rc;
       if (const int rc = call.stage(frame_film, npix * a->xstride_b, nullptr, frame_copy)) return rc;
       src = frame_copy;
     }
-    if (summary) {
-      if (const int rc = counters.alloc(slot_words)) return rc;
-      HIPCHK(hipMemsetAsync(counters.p, 0, slot_words * sizeof(unsigned long long), d->stream));
-    }
+    if (summary) if (const int rc = counters.zero(d->stream)) return rc;
     AccumulateArgs A{};
     A.num_pixels = npix;
     A.xstride_a = a->xstride_a; A.normals_offset_a = a->normals_offset_a; A.m2_offset_a = a->m2_offset_a; A.samples_offset_a = a->samples_offset_a;
     A.xstride_b = a->xstride_b; A.normals_offset_b = a->normals_offset_b; A.m2_offset_b = a->m2_offset_b; A.samples_offset_b = a->samples_offset_b;
     A.spp_b = a->spp_b; A.tau = (double)a->tau; A.floor = (double)a->floor;
-    if (const int rc = call.mark()) return rc;
-    launch_accumulate(d->stream, A, dst, src, counters.p);
-    if (const int rc = call.mark()) return rc;
-    if (const int rc = call.wait()) return rc;
+    if (const int rc = call.run([&] { launch_accumulate(d->stream, A, dst, src, counters.p); })) return rc;
     if (summary) {
-      std::vector<unsigned long long> slots(slot_words);
-      HIPCHK(hipMemcpy(slots.data(), counters.p, slot_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      unsigned long long c[4] = {0ull, 0ull, 0ull, 0ull};  // integers, modulo 2^64: whatever the order, the same sums
-      for (size_t s = 0; s < (size_t)PHX_ACCUMULATE_SLOTS; ++s) for (int k = 0; k < 4; ++k) c[k] += slots[s * PHX_ACCUMULATE_SLOT_WORDS + k];
+      uint64_t c[4];
+      if (const int rc = counters.read(c, 4)) return rc;
       summary->pixels = c[0]; summary->invalid = c[1]; summary->converged = c[2]; summary->samples = c[3];
     }
     return call.kernel_and_call_times();
   });
 }
 
-int phx_dev_accumulate_times(const phx_device* d, double* ms) {
-  if (!d || !ms) return fail(PHX_ERR_ARG, "accumulate_times: null argument");
-  ms[0] = d->accumulate_ms[0]; ms[1] = d->accumulate_ms[1];
-  return PHX_OK;
-}
+int phx_dev_accumulate_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::accumulate_ms, ms, "accumulate_times: null argument"); }
 
 // Reprojection (phx_reproject; reproject.hip).
 // (no stage_hook: the call reads four films and two cameras of its own, and no scene)
@@ -252,8 +269,7 @@ int phx_dev_film_reproject(phx_device* d, const phx_reproject* r, const float* a
     FilmCall call{d, d->reproject_ms};
     if (const int rc = call.begin(2)) return rc;
     const size_t npix = (size_t)r->width * r->height;
-    const size_t slot_words = (size_t)PHX_REPROJECT_SLOTS * PHX_REPROJECT_SLOT_WORDS;
-    DevBuf<unsigned long long> counters;
+    SummarySlots counters;
     const float *src = acc_from, *gf = guides_from, *gt = guides_to; float* dst = acc_to;
     if (!r->on_device) {  // host films: device copies of the three inputs, and acc_to's copied back behind the wait
       float *c0 = nullptr, *c1 = nullptr, *c2 = nullptr;
@@ -263,34 +279,22 @@ int phx_dev_film_reproject(phx_device* d, const phx_reproject* r, const float* a
       if (const int rc = call.stage(nullptr, npix * r->xstride_a, acc_to, dst)) return rc;
       src = c0; gf = c1; gt = c2;
     }
-    if (summary) {
-      if (const int rc = counters.alloc(slot_words)) return rc;
-      HIPCHK(hipMemsetAsync(counters.p, 0, slot_words * sizeof(unsigned long long), d->stream));
-    }
+    if (summary) if (const int rc = counters.zero(d->stream)) return rc;
     A.num_pixels = npix; A.width = r->width; A.height = r->height;
     A.xstride_a = r->xstride_a; A.normals_offset_a = r->normals_offset_a; A.m2_offset_a = r->m2_offset_a; A.samples_offset_a = r->samples_offset_a;
     A.xstride_g = r->xstride_g;
     A.sigma_plane = (double)r->sigma_plane; A.sigma_dist = (double)r->sigma_dist; A.max_history = (double)r->max_history;
-    if (const int rc = call.mark()) return rc;
-    launch_reproject(d->stream, A, src, gf, gt, dst, counters.p);
-    if (const int rc = call.mark()) return rc;
-    if (const int rc = call.wait()) return rc;
+    if (const int rc = call.run([&] { launch_reproject(d->stream, A, src, gf, gt, dst, counters.p); })) return rc;
     if (summary) {
-      std::vector<unsigned long long> slots(slot_words);
-      HIPCHK(hipMemcpy(slots.data(), counters.p, slot_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      unsigned long long c[5] = {0ull, 0ull, 0ull, 0ull, 0ull};  // integers, modulo 2^64: whatever the order, the same sums
-      for (size_t s = 0; s < (size_t)PHX_REPROJECT_SLOTS; ++s) for (int k = 0; k < 5; ++k) c[k] += slots[s * PHX_REPROJECT_SLOT_WORDS + k];
+      uint64_t c[5];
+      if (const int rc = counters.read(c, 5)) return rc;
       summary->pixels = c[0]; summary->reused = c[1]; summary->no_geometry = c[2]; summary->disoccluded = c[3]; summary->samples = c[4];
     }
     return call.kernel_and_call_times();
   });
 }
 
-int phx_dev_reproject_times(const phx_device* d, double* ms) {
-  if (!d || !ms) return fail(PHX_ERR_ARG, "reproject_times: null argument");
-  ms[0] = d->reproject_ms[0]; ms[1] = d->reproject_ms[1];
-  return PHX_OK;
-}
+int phx_dev_reproject_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::reproject_ms, ms, "reproject_times: null argument"); }
 
 // The outlier clamp (phx_outlier_clamp; outlier_clamp.hip).
 // (no stage_hook: the call reads two films and no scene)
@@ -303,8 +307,7 @@ int phx_dev_film_outlier_clamp(phx_device* d, const phx_outlier_clamp* c, const 
     FilmCall call{d, d->outlier_clamp_ms};
     if (const int rc = call.begin(2)) return rc;
     const size_t npix = (size_t)c->width * c->height, floats_b = npix * c->xstride_b;
-    const size_t slot_words = (size_t)PHX_OUTLIER_SLOTS * PHX_OUTLIER_SLOT_WORDS;
-    DevBuf<unsigned long long> counters; DevBuf<float> ref_copy;
+    SummarySlots counters; DevBuf<float> ref_copy;
     const float *src = film, *bounds = ref; float* dst = film_out;
     if (!c->on_device) {  // host films: a device copy of film, clamped in place and copied back to film_out, and one of ref
       float* copy = nullptr;
@@ -316,35 +319,23 @@ int phx_dev_film_outlier_clamp(phx_device* d, const phx_outlier_clamp* c, const 
       HIPCHK(hipMemcpyAsync(ref_copy.p, ref, floats_b * sizeof(float), hipMemcpyDeviceToDevice, d->stream));
       bounds = ref_copy.p;
     }
-    if (summary) {
-      if (const int rc = counters.alloc(slot_words)) return rc;
-      HIPCHK(hipMemsetAsync(counters.p, 0, slot_words * sizeof(unsigned long long), d->stream));
-    }
+    if (summary) if (const int rc = counters.zero(d->stream)) return rc;
     OutlierClampArgs A{};
     A.width = c->width; A.height = c->height; A.xstride_a = c->xstride_a; A.m2_offset_a = c->m2_offset_a; A.samples_offset_a = c->samples_offset_a;
     A.xstride_b = c->xstride_b; A.flags = c->flags; A.radius = c->radius; A.trim = c->trim; A.min_taps = c->min_taps;
     A.a_is_b = ref == film ? 1u : 0u;  // (the check: then of one stride; a copy of ref holds what film holds)
     A.gamma = (double)c->gamma; A.floor = (double)c->floor; A.clamped_history = (double)c->clamped_history;
-    if (const int rc = call.mark()) return rc;
-    launch_outlier_clamp(d->stream, A, src, bounds, dst, counters.p);
-    if (const int rc = call.mark()) return rc;
-    if (const int rc = call.wait()) return rc;
+    if (const int rc = call.run([&] { launch_outlier_clamp(d->stream, A, src, bounds, dst, counters.p); })) return rc;
     if (summary) {
-      std::vector<unsigned long long> slots(slot_words);
-      HIPCHK(hipMemcpy(slots.data(), counters.p, slot_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      unsigned long long s[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};  // integers, modulo 2^64: whatever the order, the same sums
-      for (size_t k = 0; k < (size_t)PHX_OUTLIER_SLOTS; ++k) for (int i = 0; i < 6; ++i) s[i] += slots[k * PHX_OUTLIER_SLOT_WORDS + i];
+      uint64_t s[6];
+      if (const int rc = counters.read(s, 6)) return rc;
       summary->pixels = s[0]; summary->skipped = s[1]; summary->unbounded = s[2]; summary->inside = s[3]; summary->clamped = s[4]; summary->capped = s[5];
     }
     return call.kernel_and_call_times();
   });
 }
 
-int phx_dev_outlier_clamp_times(const phx_device* d, double* ms) {
-  if (!d || !ms) return fail(PHX_ERR_ARG, "outlier_clamp_times: null argument");
-  ms[0] = d->outlier_clamp_ms[0]; ms[1] = d->outlier_clamp_ms[1];
-  return PHX_OK;
-}
+int phx_dev_outlier_clamp_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::outlier_clamp_ms, ms, "outlier_clamp_times: null argument"); }
 
 // The display pass (phx_display; display.hip).
 // (no stage_hook: the call reads a film and no scene)
@@ -397,23 +388,9 @@ int phx_dev_film_display(phx_device* d, const phx_display* p, const float* film,
   });
 }
 
-int phx_dev_display_times(const phx_device* d, double* ms) {
-  if (!d || !ms) return fail(PHX_ERR_ARG, "display_times: null argument");
-  std::copy(std::begin(d->display_ms), std::end(d->display_ms), ms);
-  return PHX_OK;
-}
-
-int phx_dev_guides_times(const phx_device* d, double* ms) {
-  if (!d || !ms) return fail(PHX_ERR_ARG, "guides_times: null argument");
-  ms[0] = d->guides_ms[0]; ms[1] = d->guides_ms[1];
-  return PHX_OK;
-}
-
-int phx_dev_denoise_times(const phx_device* d, double* ms) {
-  if (!d || !ms) return fail(PHX_ERR_ARG, "denoise_times: null argument");
-  std::copy(std::begin(d->denoise_ms), std::end(d->denoise_ms), ms);
-  return PHX_OK;
-}
+int phx_dev_display_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::display_ms, ms, "display_times: null argument"); }
+int phx_dev_guides_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::guides_ms, ms, "guides_times: null argument"); }
+int phx_dev_denoise_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::denoise_ms, ms, "denoise_times: null argument"); }
 
 // (no stage_hook either: the selection reads no scene)
 int phx_dev_adaptive_select(phx_device* d, uint32_t num_active, const uint32_t* active, uint32_t num_rows, float* acc, uint32_t samples_done, uint32_t spp,

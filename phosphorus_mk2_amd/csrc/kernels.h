@@ -13,6 +13,7 @@
 //   reproject.hip      k_reproject: carries an accumulator film from one camera to another by the guide films' first hits, a pass of its own no frame launches
 //   outlier_clamp.hip  k_outlier_clamp: clamps a film's pixels to bounds taken from a reference film's neighbourhoods (despeckle, history clamp), a pass of its own no frame launches
 //   display.hip        k_display_histogram, k_display_exposure, k_display_encode: a film's radiance to an RGBA8 sRGB image, a pass of its own no frame launches
+//   film_pass.h        what the film passes with a summary share: the counter path (wave_count, wave_sum, store_wave_counts, add_workgroup_counts), accumulator_pixel_valid
 //   shade_common.h     the device functions two or more of them share: camera_ray, shading_normal, light_pick, env_sample, light_emission, ...
 // A family's code can change another's only through a shared header.
 //
@@ -240,6 +241,12 @@ void launch_guides(hipStream_t stream, const DevScene& sc, const PassBuffers& pb
 // its instantiations, for init_kernels_on_current_device (the per-lane traversal stack is dynamic LDS): -> how many were written to out[0 .. 3]
 uint32_t guides_kernels(const void** out);
 
+// Summary slots: the `counters` of launch_accumulate, launch_reproject and launch_outlier_clamp (film_pass.h has the device's side,
+// film_calls.cpp's SummarySlots the host's).  nullptr, or PHX_SUMMARY_SLOTS zeroed slots of PHX_SUMMARY_SLOT_WORDS 64-bit words, a 128-byte
+// line each: a workgroup adds its counts, in the order of the call's summary struct, to the first words of slot (workgroup id % SLOTS), and
+// the caller sums the slots.  One line sustains some 90 atomics a microsecond, and a 2160p film has 32 400 workgroups.
+enum { PHX_SUMMARY_SLOTS = 64, PHX_SUMMARY_SLOT_WORDS = 16 };
+
 // Film accumulation (phx_accumulate in phx_xpu.h states the rule; accumulate.hip): one launch, a workgroup per span of
 // PHX_ACCUMULATE_SPAN consecutive pixels.  The workgroup moves the span's floats of both films into LDS with coalesced 16-byte loads, a thread
 // pools one pixel, and the span of acc goes back the same way.  xstride_* <= PHX_ACCUMULATE_MAX_XSTRIDE (accumulate_check.h: the check
@@ -251,10 +258,8 @@ struct AccumulateArgs {
   uint32_t spp_b;
   double tau, floor;
 };
-enum { PHX_ACCUMULATE_SPAN = 256, PHX_ACCUMULATE_SLOTS = 64, PHX_ACCUMULATE_SLOT_WORDS = 16 };
-// counters: nullptr, or PHX_ACCUMULATE_SLOTS zeroed slots of PHX_ACCUMULATE_SLOT_WORDS 64-bit words, a 128-byte line each (one line sustains
-// some 90 atomics a microsecond, and a 2160p film has 32 400 workgroups).  A workgroup adds pixels, invalid, converged, samples
-// (phx_accumulate_summary) to the first four words of slot (workgroup id % SLOTS); the caller sums the slots.
+enum { PHX_ACCUMULATE_SPAN = 256 };
+// counters: summary slots (above); pixels, invalid, converged, samples (phx_accumulate_summary)
 void launch_accumulate(hipStream_t stream, const AccumulateArgs& A, float* acc, const float* frame_film, unsigned long long* counters);
 
 // The display pass (phx_display in phx_xpu.h states the rule; display.hip, over display_rule.h): up to three launches on one stream
@@ -289,10 +294,8 @@ struct ReprojectArgs {
   uint32_t width, height, xstride_a, normals_offset_a, m2_offset_a, samples_offset_a, xstride_g;
   double sigma_plane, sigma_dist, max_history;
 };
-enum { PHX_REPROJECT_BLOCK = 256, PHX_REPROJECT_SLOTS = 64, PHX_REPROJECT_SLOT_WORDS = 16 };
-// counters: nullptr, or PHX_REPROJECT_SLOTS zeroed slots of PHX_REPROJECT_SLOT_WORDS 64-bit words (a 128-byte line each, as for
-// launch_accumulate).  A workgroup adds pixels, reused, no_geometry, disoccluded, samples (phx_reproject_summary) to the first five words
-// of slot (workgroup id % SLOTS); the caller sums the slots.
+enum { PHX_REPROJECT_BLOCK = 256 };
+// counters: summary slots (above); pixels, reused, no_geometry, disoccluded, samples (phx_reproject_summary)
 void launch_reproject(hipStream_t stream, const ReprojectArgs& A, const float* acc_from, const float* guides_from, const float* guides_to, float* acc_to,
                       unsigned long long* counters);
 
@@ -307,10 +310,9 @@ struct OutlierClampArgs {
   uint32_t a_is_b;  // ref is film (or the call's copy of it): a thread reads its own pixel of A out of the tile in LDS
   double gamma, floor, clamped_history;
 };
-enum { PHX_OUTLIER_TILE = 16, PHX_OUTLIER_SLOTS = 64, PHX_OUTLIER_SLOT_WORDS = 16 };
-// film_out may be film; ref shares no byte with film_out.  counters: nullptr, or PHX_OUTLIER_SLOTS zeroed slots of PHX_OUTLIER_SLOT_WORDS
-// 64-bit words (a 128-byte line each, as for launch_accumulate).  A workgroup adds pixels, skipped, unbounded, inside, clamped, capped
-// (phx_outlier_clamp_summary) to the first six words of slot (workgroup id % SLOTS); the caller sums the slots.
+enum { PHX_OUTLIER_TILE = 16 };
+// film_out may be film; ref shares no byte with film_out.  counters: summary slots (above); pixels, skipped, unbounded, inside, clamped,
+// capped (phx_outlier_clamp_summary)
 void launch_outlier_clamp(hipStream_t stream, const OutlierClampArgs& A, const float* film, const float* ref, float* film_out, unsigned long long* counters);
 
 // stage-level entry points (synchronous helpers for the parity tests)

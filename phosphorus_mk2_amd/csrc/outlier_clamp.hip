@@ -14,7 +14,7 @@
 // The pixel's code is compiled once per radius, so the window's loops unroll and a tap's index is a constant; which taps count is one 64-bit
 // mask, and the trimming keeps the three brightest taps' indices in named registers: nothing is indexed at run time.
 // All arithmetic is binary64 in the rule's order (the file is compiled without contraction, as every other).
-#include "kernels.h"
+#include "film_pass.h"
 #include "outlier_clamp_check.h"  // PHX_OUTLIER_MAX_XSTRIDE, PHX_OUTLIER_MAX_RADIUS
 
 namespace phx {
@@ -183,17 +183,11 @@ __global__ void __launch_bounds__(PHX_OUTLIER_TILE * PHX_OUTLIER_TILE) k_outlier
     else clamp_pixel<3>(A, T, px, py, film, film_out, cls, capped);
   }
   if (counters) {  // (wave-uniform) ballots, then one vector atomic of six lanes per workgroup
-    const unsigned long long pixels = (unsigned long long)__popcll(__ballot(live)), skipped = (unsigned long long)__popcll(__ballot(cls == 0)),
-                             unbounded = (unsigned long long)__popcll(__ballot(cls == 1)), inside = (unsigned long long)__popcll(__ballot(cls == 2)),
-                             clamped = (unsigned long long)__popcll(__ballot(cls == 3)), cut = (unsigned long long)__popcll(__ballot(capped));
-    if (lane == 0u) { unsigned long long* w = part[wave]; w[0] = pixels; w[1] = skipped; w[2] = unbounded; w[3] = inside; w[4] = clamped; w[5] = cut; }
+    // pixels, skipped, unbounded, inside, clamped, capped
+    const unsigned long long counts[6] = {wave_count(live), wave_count(cls == 0), wave_count(cls == 1), wave_count(cls == 2), wave_count(cls == 3), wave_count(capped)};
+    store_wave_counts(part, t, counts);
     __syncthreads();
-    if (t < 6u) {
-      unsigned long long sum = 0ull;
-#pragma unroll
-      for (uint32_t w = 0; w < WAVES; ++w) sum += part[w][t];
-      atomicAdd(counters + (size_t)((blockIdx.y * gridDim.x + blockIdx.x) % PHX_OUTLIER_SLOTS) * PHX_OUTLIER_SLOT_WORDS + t, sum);
-    }
+    add_workgroup_counts(part, t, blockIdx.y * gridDim.x + blockIdx.x, counters);
   }
 }
 

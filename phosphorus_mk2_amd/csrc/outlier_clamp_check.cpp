@@ -6,12 +6,9 @@ namespace phx {
 
 namespace {
 const char* outlier_clamp_invalid(const phx_outlier_clamp& c, const float* film, const float* ref, const float* film_out, bool& ref_needs_copy) {
-  if (c.width < 1u || c.width > 65536u) return "width";
-  if (c.height < 1u || c.height > 65536u) return "height";
-  if (c.xstride_a < 3u || c.xstride_a > (uint32_t)PHX_OUTLIER_MAX_XSTRIDE) return "xstride_a";
-  if (c.m2_offset_a && !channel_fits(c.m2_offset_a, 3u, c.xstride_a)) return "m2_offset_a";
-  if (c.samples_offset_a && (!channel_fits(c.samples_offset_a, 1u, c.xstride_a) || (c.m2_offset_a && channels_overlap(c.samples_offset_a, 1u, c.m2_offset_a, 3u))))
-    return "samples_offset_a";
+  static const char* const names_a[4] = {"xstride_a", nullptr /* the clamp reads no normals */, "m2_offset_a", "samples_offset_a"};
+  if (const char* field = film_size_invalid(c.width, c.height)) return field;
+  if (const int k = film_layout_invalid(c.xstride_a, 0u, c.m2_offset_a, c.samples_offset_a, 3u, (uint32_t)PHX_OUTLIER_MAX_XSTRIDE, false, false); k >= 0) return names_a[k];
   if (c.xstride_b < 3u || c.xstride_b > (uint32_t)PHX_OUTLIER_MAX_XSTRIDE) return "xstride_b";
   if (c.on_device > 1u) return "on_device";
   if (c.flags & ~(uint32_t)(PHX_OUTLIER_EXCLUDE_CENTRE | PHX_OUTLIER_UPPER_ONLY)) return "flags";
@@ -19,10 +16,10 @@ const char* outlier_clamp_invalid(const phx_outlier_clamp& c, const float* film,
   if (c.trim > 3u) return "trim";
   const uint32_t side = 2u * c.radius + 1u;
   if (c.min_taps < 1u || c.min_taps > side * side) return "min_taps";
-  if (!std::isfinite(c.gamma) || c.gamma < 0.0f) return "gamma";
-  if (!std::isfinite(c.floor) || c.floor < 0.0f) return "floor";
+  if (!finite_nonneg(c.gamma)) return "gamma";
+  if (!finite_nonneg(c.floor)) return "floor";
   if (c.clamped_history && !c.samples_offset_a) return "clamped_history";
-  for (uint32_t w : c.reserved) if (w) return "reserved";
+  if (any_reserved(c.reserved)) return "reserved";
   if (!film) return "film";
   if (!ref) return "ref";
   if (!film_out) return "film_out";

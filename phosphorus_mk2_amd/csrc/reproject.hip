@@ -9,19 +9,13 @@
 // threads sample neighbouring points, so a wave's taps are a few rows of consecutive pixels that L1 / L2 serve (DESIGN 22 has the measured
 // rate beside a device copy's); there is no LDS staging.  Every index is tested against the film before it is formed.
 // All arithmetic is binary64 in the rule's order (the file is compiled without contraction, as every other).
-#include "kernels.h"
+#include "film_pass.h"
 
 namespace phx {
 
 namespace {
 
 constexpr uint32_t BLOCK = PHX_REPROJECT_BLOCK;
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // project(K, X) of the rule: false for a point behind the camera (a NaN is behind it)
 __device__ __forceinline__ bool project(const ReprojectCamera& K, double X, double Y, double Z, double& fx, double& fy) {
@@ -71,10 +65,7 @@ __global__ void __launch_bounds__(PHX_REPROJECT_BLOCK) k_reproject(ReprojectArgs
             const float* a = acc_from + q * A.xstride_a;
             const float* am = a + A.m2_offset_a; const float* an = a + A.normals_offset_a;
             const double n = (double)a[A.samples_offset_a];
-            const bool valid = isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]) && isfinite(am[0]) && isfinite(am[1]) && isfinite(am[2]) &&
-                               isfinite(an[0]) && isfinite(an[1]) && isfinite(an[2]) && am[0] >= 0.0f && am[1] >= 0.0f && am[2] >= 0.0f &&
-                               isfinite(n) && n >= 2.0;
-            if (!valid) continue;
+            if (!(accumulator_pixel_valid(a, am, n) && isfinite(an[0]) && isfinite(an[1]) && isfinite(an[2]))) continue;
             const float* g = guides_from + q * A.xstride_g;
             bool finite = true;
 #pragma unroll
@@ -131,17 +122,11 @@ __global__ void __launch_bounds__(PHX_REPROJECT_BLOCK) k_reproject(ReprojectArgs
     }
   }
   if (counters) {  // (wave-uniform) ballots and one sum per wave, then one vector atomic of five lanes per workgroup
-    const unsigned long long pixels = (unsigned long long)__popcll(__ballot(live)), reu = (unsigned long long)__popcll(__ballot(reused)),
-                             nogeo = (unsigned long long)__popcll(__ballot(no_geometry)),
-                             dis = (unsigned long long)__popcll(__ballot(live && !reused && !no_geometry)), samples = wave_sum(ns);
-    if ((t & 63u) == 0u) { unsigned long long* w = part[t >> 6]; w[0] = pixels; w[1] = reu; w[2] = nogeo; w[3] = dis; w[4] = samples; }
+    // pixels, reused, no_geometry, disoccluded, samples
+    const unsigned long long counts[5] = {wave_count(live), wave_count(reused), wave_count(no_geometry), wave_count(live && !reused && !no_geometry), wave_sum(ns)};
+    store_wave_counts(part, t, counts);
     __syncthreads();
-    if (t < 5u) {
-      unsigned long long v = 0ull;
-#pragma unroll
-      for (uint32_t w = 0; w < BLOCK / 64u; ++w) v += part[w][t];
-      atomicAdd(counters + (size_t)(blockIdx.x % PHX_REPROJECT_SLOTS) * PHX_REPROJECT_SLOT_WORDS + t, v);
-    }
+    add_workgroup_counts(part, t, blockIdx.x, counters);
   }
 }
 

@@ -27,18 +27,17 @@ namespace {
 const char* reproject_invalid(const phx_reproject& r, const float* acc_from, const float* guides_from, const float* guides_to, const float* acc_to,
                               ReprojectCamera& from, ReprojectCamera& to) {
   static const char* const names[4] = {"xstride_a", "normals_offset_a", "m2_offset_a", "samples_offset_a"};
-  if (r.width < 1u || r.width > 65536u) return "width";
-  if (r.height < 1u || r.height > 65536u) return "height";
+  if (const char* field = film_size_invalid(r.width, r.height)) return field;
   if (const int k = film_layout_invalid(r.xstride_a, r.normals_offset_a, r.m2_offset_a, r.samples_offset_a, 10u, (uint32_t)PHX_REPROJECT_MAX_XSTRIDE, true); k >= 0) return names[k];
   if (!r.normals_offset_a) return "normals_offset_a";
   if (r.xstride_g < 8u || r.xstride_g > (uint32_t)PHX_REPROJECT_MAX_GUIDE_XSTRIDE) return "xstride_g";
   if (r.on_device > 1u) return "on_device";
   if (r.from.film_width != r.width || r.from.film_height != r.height || !reproject_camera(r.from, from)) return "from";
   if (r.to.film_width != r.width || r.to.film_height != r.height || !reproject_camera(r.to, to)) return "to";
-  if (!std::isfinite(r.sigma_plane) || !(r.sigma_plane > 0.0f)) return "sigma_plane";
-  if (!std::isfinite(r.sigma_dist) || !(r.sigma_dist > 0.0f)) return "sigma_dist";
+  if (!finite_positive(r.sigma_plane)) return "sigma_plane";
+  if (!finite_positive(r.sigma_dist)) return "sigma_dist";
   if (r.max_history < 2u) return "max_history";
-  for (uint32_t w : r.reserved) if (w) return "reserved";
+  if (any_reserved(r.reserved)) return "reserved";
   if (!acc_from) return "acc_from";
   if (!guides_from) return "guides_from";
   if (!guides_to) return "guides_to";

@@ -151,6 +151,29 @@ class CallbackTiles:
         return None
 
 
+def film_layout(primary_components=4, normals=False, moments=False, samples=False):
+    """The channel order of a film's pixel, derived here and nowhere else: "primary", then "normals" (3 floats), "m2" (3 floats) and "samples"
+    (1 float), each only when asked for -> (normals_offset, m2_offset, samples_offset, xstride); the offset of a channel that is not there
+    is 0, as in the structs of include/phx_xpu.h."""
+    xstride, offsets = primary_components, []
+    for there, floats in ((normals, 3), (moments, 3), (samples, 1)):
+        offsets.append(xstride if there else 0)
+        xstride += floats if there else 0
+    return offsets[0], offsets[1], offsets[2], xstride
+
+
+def _film_shape(film, on_device):  # a device-resident film is given by its shape, or by an array of it
+    return tuple(film) if on_device and not hasattr(film, "shape") else film.shape
+
+
+def _writable_f32(a):  # an array a film call can work on in place
+    return isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable
+
+
+def _summary_dict(s):  # a summary struct of counts, or None
+    return None if s is None else {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+
 class Film:
     """An in-memory film sink: film_t<>::add_tile copies a tile's render buffer into a full frame
     (what film::file_t / the Blender sink do, src/film/file.cpp:27-41)."""
@@ -160,11 +183,10 @@ class Film:
             raise ValueError("a film of adaptive sampling needs moments=True (phx_dev_start refuses the frame otherwise)")
         self.width, self.height = width, height
         self.primary_components, self.normals, self.moments, self.adaptive = primary_components, normals, moments, adaptive
-        # channel "m2" (phx_frame.moments_channel), when asked for, sits behind "primary" and "normals"
-        self.m2_offset = primary_components + (3 if normals else 0)
-        # channel "samples" (adaptive sampling: the device adds it to every frame started while HipDevice.set_adaptive is on) sits behind "m2"
-        self.samples_offset = self.m2_offset + 3
-        self.xstride = self.m2_offset + (3 if moments else 0) + (1 if adaptive else 0)
+        # channel "m2" (phx_frame.moments_channel), when asked for, sits behind "primary" and "normals"; channel "samples" (adaptive sampling:
+        # the device adds it to every frame started while HipDevice.set_adaptive is on) behind "m2".  A film without them says where they would be
+        _, self.m2_offset, self.samples_offset, _ = film_layout(primary_components, normals, True, True)
+        self.xstride = film_layout(primary_components, normals, moments, adaptive)[3]
         self.data = np.zeros((height, width, self.xstride), np.float32)
         self.tiles = 0
         self._lock = threading.Lock()
@@ -367,11 +389,15 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_render_guides(self._h, C.byref(g), out.ctypes.data), "phx_dev_render_guides")
         return out
 
+    def _times(self, getter, n, keys=None):
+        """a phx_dev_*_times getter of n doubles -> dict by keys, or the list"""
+        ms = (C.c_double * n)()
+        _check(self._lib, getattr(self._lib, getter)(self._h, ms), getter)
+        return list(ms) if keys is None else dict(zip(keys, ms))
+
     def guides_times(self):
         """milliseconds of the last render_guides(): dict of kernel (HIP events) and call (host clock)"""
-        ms = (C.c_double * 2)()
-        _check(self._lib, self._lib.phx_dev_guides_times(self._h, ms), "phx_dev_guides_times")
-        return {"kernel": ms[0], "call": ms[1]}
+        return self._times("phx_dev_guides_times", 2, ("kernel", "call"))
 
     def denoise(self, data, spp, primary_components=4, normals=False, adaptive=False, iterations=5, sigma_l=4.0, normal_power_log2=7, device_ptr=None,
                 guides=None, demodulate=True, plane=False, albedo_floor=0.01, sigma_x=1.0, plane_scale=None, guides_ptr=None):
@@ -386,12 +412,12 @@ class HipDevice:
         albedo_floor) out before filtering and multiplies it back; plane (needs normals) also rejects taps farther than sigma_x pixels'
         worth of surface from the pixel's tangent plane, plane_scale being the world size of a pixel at unit distance (guide_plane_scale;
         default: that of the last preprocessed scene's camera)."""
-        shape = tuple(data) if device_ptr is not None and not hasattr(data, "shape") else data.shape
+        shape = _film_shape(data, device_ptr is not None)
         q = denoise_settings(shape, spp, primary_components, normals, adaptive, iterations, sigma_l, normal_power_log2)
         if guides is None and guides_ptr is None:
             gref, keep = None, None
         else:
-            gshape = tuple(guides) if guides_ptr is not None and not hasattr(guides, "shape") else guides.shape
+            gshape = _film_shape(guides, guides_ptr is not None)
             if len(gshape) != 3 or tuple(gshape[:2]) != tuple(shape[:2]):
                 raise ValueError(f"denoise: the guide film must be (height, width, >= 8) over the film's pixels, not {tuple(gshape)}")
             if plane and plane_scale is None:
@@ -421,9 +447,8 @@ class HipDevice:
 
     def denoise_times(self):
         """HIP-event milliseconds of the last denoise(): dict of pack, iterations (list of 8, 0 for those not run), unpack, call (host clock)"""
-        ms = (C.c_double * 11)()
-        _check(self._lib, self._lib.phx_dev_denoise_times(self._h, ms), "phx_dev_denoise_times")
-        return {"pack": ms[0], "iterations": list(ms[1:9]), "unpack": ms[9], "call": ms[10]}
+        ms = self._times("phx_dev_denoise_times", 11)
+        return {"pack": ms[0], "iterations": ms[1:9], "unpack": ms[9], "call": ms[10]}
 
     def accumulate(self, acc, frame_film, spp, primary_components=4, normals=False, frame_adaptive=False, threshold=None, floor=0.0, device_ptrs=None):
         """Film accumulation across frames (phx_dev_film_accumulate; include/phx_xpu.h states the rule): frame_film, a finished film
@@ -435,9 +460,8 @@ class HipDevice:
         layouts; acc and frame_film then are only their shapes (H, W, xstride), and the call returns (None, summary).  Needs no scene; call it
         after join(), and after dist.reduce_film on several GPUs."""
         on_device = device_ptrs is not None
-        shape_a = tuple(acc) if on_device and not hasattr(acc, "shape") else acc.shape
-        shape_b = tuple(frame_film) if on_device and not hasattr(frame_film, "shape") else frame_film.shape
-        q = accumulate_settings(shape_a, shape_b, spp, primary_components, normals, frame_adaptive, 0.0 if threshold is None else threshold, floor)
+        q = accumulate_settings(_film_shape(acc, on_device), _film_shape(frame_film, on_device), spp, primary_components, normals, frame_adaptive,
+                                0.0 if threshold is None else threshold, floor)
         s = abi.AccumulateSummary() if threshold is not None else None
         sref = C.byref(s) if s is not None else None
         if on_device:
@@ -445,18 +469,15 @@ class HipDevice:
             pa, pb = (int(p) for p in device_ptrs)
             out = keep = None
         else:
-            out = acc if isinstance(acc, np.ndarray) and acc.dtype == np.float32 and acc.flags.c_contiguous and acc.flags.writeable else \
-                np.array(acc, np.float32, order="C")
+            out = acc if _writable_f32(acc) else np.array(acc, np.float32, order="C")
             keep = np.ascontiguousarray(frame_film, np.float32)
             pa, pb = out.ctypes.data, keep.ctypes.data
         _check(self._lib, self._lib.phx_dev_film_accumulate(self._h, C.byref(q), pa, pb, sref), "phx_dev_film_accumulate")
-        return out, (None if s is None else {k: int(getattr(s, k)) for k, _ in s._fields_})
+        return out, _summary_dict(s)
 
     def accumulate_times(self):
         """milliseconds of the last accumulate(): dict of kernel (HIP events) and call (host clock)"""
-        ms = (C.c_double * 2)()
-        _check(self._lib, self._lib.phx_dev_accumulate_times(self._h, ms), "phx_dev_accumulate_times")
-        return {"kernel": ms[0], "call": ms[1]}
+        return self._times("phx_dev_accumulate_times", 2, ("kernel", "call"))
 
     def reproject(self, acc, guides_from, guides_to, camera_from, camera_to, sigma_plane=1.0, sigma_dist=4.0, max_history=64, primary_components=4,
                   summary=True, device_ptrs=None):
@@ -469,7 +490,7 @@ class HipDevice:
         measurements.  device_ptrs: (acc, guides_from, guides_to, out) addresses of device-resident films; acc, guides_from and guides_to
         then are only their shapes, and the call returns (None, summary).  Needs no scene."""
         on_device = device_ptrs is not None
-        shapes = [tuple(a) if on_device and not hasattr(a, "shape") else a.shape for a in (acc, guides_from, guides_to)]
+        shapes = [_film_shape(a, on_device) for a in (acc, guides_from, guides_to)]
         q = reproject_settings(shapes[0], shapes[1], shapes[2], camera_from, camera_to, sigma_plane, sigma_dist, max_history, primary_components)
         s = abi.ReprojectSummary() if summary else None
         if on_device:
@@ -481,13 +502,11 @@ class HipDevice:
             ptrs = [k.ctypes.data for k in keep] + [out.ctypes.data]
         _check(self._lib, self._lib.phx_dev_film_reproject(self._h, C.byref(q), ptrs[0], ptrs[1], ptrs[2], ptrs[3], C.byref(s) if s is not None else None),
                "phx_dev_film_reproject")
-        return out, (None if s is None else {k: int(getattr(s, k)) for k, _ in s._fields_})
+        return out, _summary_dict(s)
 
     def reproject_times(self):
         """milliseconds of the last reproject(): dict of kernel (HIP events) and call (host clock)"""
-        ms = (C.c_double * 2)()
-        _check(self._lib, self._lib.phx_dev_reproject_times(self._h, ms), "phx_dev_reproject_times")
-        return {"kernel": ms[0], "call": ms[1]}
+        return self._times("phx_dev_reproject_times", 2, ("kernel", "call"))
 
     def clamp_outliers(self, film, ref=None, radius=2, gamma=4.0, floor=0.0, trim=2, min_taps=4, exclude_centre=True, upper_only=True, clamped_history=0,
                        primary_components=4, normals=False, moments=True, samples=False, m2_offset=None, samples_offset=None, summary=True, out=None,
@@ -506,8 +525,8 @@ class HipDevice:
         device-resident films (ref may be film's, out may be film's or ref's); film and ref then are only their shapes, and the call
         returns (None, summary).  Needs no scene."""
         on_device = device_ptrs is not None
-        shape_a = tuple(film) if on_device and not hasattr(film, "shape") else film.shape
-        shape_b = shape_a if ref is None else tuple(ref) if on_device and not hasattr(ref, "shape") else ref.shape
+        shape_a = _film_shape(film, on_device)
+        shape_b = shape_a if ref is None else _film_shape(ref, on_device)
         q = outlier_clamp_settings(shape_a, shape_b, radius, gamma, floor, trim, min_taps, exclude_centre, upper_only, clamped_history, primary_components,
                                    normals, moments, samples, m2_offset, samples_offset)
         s = abi.OutlierClampSummary() if summary else None
@@ -515,25 +534,21 @@ class HipDevice:
             q.on_device = 1
             (pa, pb, po), res, keep = (int(p) for p in device_ptrs), None, None
         else:
-            def writable(a):
-                return isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous and a.flags.writeable
-            if out is not None and (not writable(out) or out.shape != tuple(shape_a)):
+            if out is not None and (not _writable_f32(out) or out.shape != tuple(shape_a)):
                 raise ValueError("clamp_outliers: out must be a writable C-contiguous float32 array of film's shape")
             if out is None:
-                src = res = film if writable(film) else np.array(film, np.float32, order="C")
+                src = res = film if _writable_f32(film) else np.array(film, np.float32, order="C")
             else:
                 src, res = np.ascontiguousarray(film, np.float32), out
             keep = src if ref is None or ref is film else out if ref is out else np.ascontiguousarray(ref, np.float32)
             pa, pb, po = src.ctypes.data, keep.ctypes.data, res.ctypes.data
         _check(self._lib, self._lib.phx_dev_film_outlier_clamp(self._h, C.byref(q), pa, pb, po, C.byref(s) if s is not None else None),
                "phx_dev_film_outlier_clamp")
-        return res, (None if s is None else {k: int(getattr(s, k)) for k, _ in s._fields_})
+        return res, _summary_dict(s)
 
     def outlier_clamp_times(self):
         """milliseconds of the last clamp_outliers(): dict of kernel (HIP events) and call (host clock)"""
-        ms = (C.c_double * 2)()
-        _check(self._lib, self._lib.phx_dev_outlier_clamp_times(self._h, ms), "phx_dev_outlier_clamp_times")
-        return {"kernel": ms[0], "call": ms[1]}
+        return self._times("phx_dev_outlier_clamp_times", 2, ("kernel", "call"))
 
     def display(self, film, exposure=1.0, tone="aces", white=4.0, dither=True, key=0.18, percentiles=(0.5, 0.95), scale_range=(2.0 ** -12, 2.0 ** 12),
                 summary=False, device_ptr=None, image_on_host=True, image_ptr=None, image_pitch=0, fallback=1.0):
@@ -547,7 +562,7 @@ class HipDevice:
         device_ptr: the address of a device-resident film; `film` then is only its shape (H, W, xstride).  With image_on_host (the preview:
         4 bytes a pixel come back instead of the film) the image is returned as above; otherwise image_ptr is the address of a
         device-resident image of image_pitch bytes a row (0: 4 * W), and None is returned in the image's place.  Needs no scene."""
-        shape = tuple(film) if device_ptr is not None and not hasattr(film, "shape") else film.shape
+        shape = _film_shape(film, device_ptr is not None)
         q = display_settings(shape, exposure, tone, white, dither, key, percentiles, scale_range, fallback)
         s, h = (abi.DisplaySummary(), (C.c_uint64 * 256)()) if summary else (None, None)
         if device_ptr is not None and not image_on_host:
@@ -571,9 +586,7 @@ class HipDevice:
 
     def display_times(self):
         """milliseconds of the last display(): dict of histogram (with the exposure) and encode (HIP events) and call (host clock)"""
-        ms = (C.c_double * 3)()
-        _check(self._lib, self._lib.phx_dev_display_times(self._h, ms), "phx_dev_display_times")
-        return {"histogram": ms[0], "encode": ms[1], "call": ms[2]}
+        return self._times("phx_dev_display_times", 3, ("histogram", "encode", "call"))
 
     # ---- stage-level hooks (parity tests) -------------------------------------------------------
     def adaptive_select(self, acc, samples_done, spp, threshold, floor=0.0, min_samples=16, step=16, active=None, num_active=None):
@@ -735,12 +748,12 @@ def film_variance(data, spp, primary_components=4, normals=False, adaptive=False
     adaptive=True: a film of adaptive sampling (one more float per pixel, "samples"): m2 * n / (n - 1) from the pixel's OWN n, which holds
     after the rescale of a pixel that stopped as well; inf where n <= 1.  spp is not used then."""
     data = np.asarray(data)
-    off = primary_components + (3 if normals else 0)
-    if data.shape[-1] != off + 3 + (1 if adaptive else 0):
-        raise ValueError(f"film_variance: a film with the m2 channel has {off + 3 + (1 if adaptive else 0)} floats per pixel, this one {data.shape[-1]}")
+    _, off, samples_offset, want = film_layout(primary_components, normals, True, adaptive)
+    if data.shape[-1] != want:
+        raise ValueError(f"film_variance: a film with the m2 channel has {want} floats per pixel, this one {data.shape[-1]}")
     m2 = data[..., off:off + 3].astype(np.float64)
     if adaptive:
-        n = data[..., off + 3].astype(np.float64)[..., None]
+        n = data[..., samples_offset].astype(np.float64)[..., None]
         with np.errstate(divide="ignore", invalid="ignore"):
             return np.where(n > 1, m2 * (n / (n - 1.0)), np.inf)
     if spp <= 1:
@@ -760,13 +773,12 @@ def denoise_settings(shape, spp, primary_components=4, normals=False, adaptive=F
     if len(shape) != 3:
         raise ValueError("denoise: the film must be (height, width, xstride)")
     H, W, xstride = (int(v) for v in shape)
-    m2_offset = primary_components + (3 if normals else 0)
-    want = m2_offset + 3 + (1 if adaptive else 0)
+    normals_offset, m2_offset, samples_offset, want = film_layout(primary_components, normals, True, adaptive)
     if xstride != want:
         raise ValueError(f"denoise: a film with the m2 channel has {want} floats per pixel in this layout, this one {xstride} "
                          "(the denoiser needs a film rendered with moments=True)")
-    return abi.Denoise(width=W, height=H, xstride=xstride, normals_offset=primary_components if normals else 0, m2_offset=m2_offset,
-                       samples_offset=m2_offset + 3 if adaptive else 0, spp=int(spp), iterations=int(iterations), sigma_l=float(sigma_l),
+    return abi.Denoise(width=W, height=H, xstride=xstride, normals_offset=normals_offset, m2_offset=m2_offset,
+                       samples_offset=samples_offset, spp=int(spp), iterations=int(iterations), sigma_l=float(sigma_l),
                        normal_power_log2=int(normal_power_log2), on_device=0)
 
 
@@ -786,16 +798,15 @@ def accumulate_settings(shape_a, shape_b, spp, primary_components=4, normals=Fal
     (H, W, xa), (Hb, Wb, xb) = ((int(v) for v in s) for s in (shape_a, shape_b))
     if (H, W) != (Hb, Wb):
         raise ValueError(f"accumulate: the accumulator is {W} x {H} pixels, the frame film {Wb} x {Hb}")
-    m2_offset = primary_components + (3 if normals else 0)
-    if xa != m2_offset + 4:
-        raise ValueError(f"accumulate: an accumulator has {m2_offset + 4} floats per pixel in this layout (xpu.accumulator), this one {xa}")
-    want = m2_offset + 3 + (1 if frame_adaptive else 0)
+    no, m2_offset, samples_offset, want_a = film_layout(primary_components, normals, True, True)
+    if xa != want_a:
+        raise ValueError(f"accumulate: an accumulator has {want_a} floats per pixel in this layout (xpu.accumulator), this one {xa}")
+    _, _, samples_offset_b, want = film_layout(primary_components, normals, True, frame_adaptive)
     if xb != want:
         raise ValueError(f"accumulate: a frame film with the m2 channel has {want} floats per pixel in this layout, this one {xb} "
                          "(accumulation needs frames rendered with moments=True)")
-    no = primary_components if normals else 0
-    return abi.Accumulate(width=W, height=H, xstride_a=xa, normals_offset_a=no, m2_offset_a=m2_offset, samples_offset_a=m2_offset + 3,
-                          xstride_b=xb, normals_offset_b=no, m2_offset_b=m2_offset, samples_offset_b=m2_offset + 3 if frame_adaptive else 0,
+    return abi.Accumulate(width=W, height=H, xstride_a=xa, normals_offset_a=no, m2_offset_a=m2_offset, samples_offset_a=samples_offset,
+                          xstride_b=xb, normals_offset_b=no, m2_offset_b=m2_offset, samples_offset_b=samples_offset_b,
                           spp_b=int(spp), on_device=0, tau=float(threshold), floor=float(floor))
 
 
@@ -819,11 +830,11 @@ def reproject_settings(shape_a, shape_gf, shape_gt, camera_from, camera_to, sigm
         raise ValueError(f"reproject: the accumulator is {W} x {H} pixels, the guide films {shape_gf[1]} x {shape_gf[0]} and {shape_gt[1]} x {shape_gt[0]}")
     if int(shape_gf[2]) != int(shape_gt[2]):
         raise ValueError(f"reproject: the two guide films must have one stride, not {shape_gf[2]} and {shape_gt[2]}")
-    m2_offset = primary_components + 3
-    if xa != m2_offset + 4:
-        raise ValueError(f"reproject: an accumulator with normals has {m2_offset + 4} floats per pixel in this layout "
+    normals_offset, m2_offset, samples_offset, want = film_layout(primary_components, True, True, True)
+    if xa != want:
+        raise ValueError(f"reproject: an accumulator with normals has {want} floats per pixel in this layout "
                          f"(xpu.accumulator(..., normals=True): the plane test reads them), this one {xa}")
-    q = abi.Reproject(width=W, height=H, xstride_a=xa, normals_offset_a=primary_components, m2_offset_a=m2_offset, samples_offset_a=m2_offset + 3,
+    q = abi.Reproject(width=W, height=H, xstride_a=xa, normals_offset_a=normals_offset, m2_offset_a=m2_offset, samples_offset_a=samples_offset,
                       xstride_g=int(shape_gf[2]), on_device=0, to=pack_camera(camera_to), sigma_plane=float(sigma_plane), sigma_dist=float(sigma_dist),
                       max_history=int(max_history))
     setattr(q, "from", pack_camera(camera_from))
@@ -841,11 +852,10 @@ def outlier_clamp_settings(shape_a, shape_b, radius=2, gamma=4.0, floor=0.0, tri
     (H, W, xa), (Hb, Wb, xb) = ((int(v) for v in s) for s in (shape_a, shape_b))
     if (H, W) != (Hb, Wb):
         raise ValueError(f"clamp_outliers: the film is {W} x {H} pixels, the reference film {Wb} x {Hb}")
-    behind = primary_components + (3 if normals else 0)
-    if m2_offset is None:
-        m2_offset = behind if moments else 0
-    if samples_offset is None:
-        samples_offset = (behind + (3 if moments else 0)) if samples else 0
+    _, derived_m2, derived_samples, _ = film_layout(primary_components, normals, moments, samples)
+    behind = film_layout(primary_components, normals)[3]  # "primary" and "normals": what the film holds at least
+    m2_offset = derived_m2 if m2_offset is None else m2_offset
+    samples_offset = derived_samples if samples_offset is None else samples_offset
     if max(behind, m2_offset + 3 if m2_offset else 0, samples_offset + 1 if samples_offset else 0) > xa:
         raise ValueError(f"clamp_outliers: this layout needs {max(behind, m2_offset + 3, samples_offset + 1)} floats per pixel, the film has {xa}")
     return abi.OutlierClamp(width=W, height=H, xstride_a=xa, m2_offset_a=int(m2_offset), samples_offset_a=int(samples_offset), xstride_b=xb, on_device=0,

@@ -1,7 +1,8 @@
 """The one film-layout rule of the argument checks (csrc/film_checks.h: film_layout_invalid) without a GPU, exhaustively: every small layout
-and the wrap-around offsets, asked of denoise_check and of accumulate_check for either film through the wrappers of tests/test_denoise.py and
-tests/test_accumulate.py, against a restatement in Python integers of the ranges include/phx_xpu.h states for phx_denoise and phx_accumulate.
-tests/test_denoise.py and tests/test_accumulate.py hold the listed cases of every other field."""
+and the wrap-around offsets, asked of denoise_check, of accumulate_check for either film and of outlier_clamp_check for its film through the
+wrappers of tests/test_denoise.py, tests/test_accumulate.py and tests/test_outlier_clamp.py, against a restatement in Python integers of the
+ranges include/phx_xpu.h states for phx_denoise, phx_accumulate and phx_outlier_clamp.  Those three modules hold the listed cases of every
+other field."""
 import ctypes as C
 import itertools
 import os
@@ -12,6 +13,7 @@ import pytest
 
 import test_accumulate as TA
 import test_denoise as TD
+import test_outlier_clamp as TO
 from conftest import ROOT
 
 NATIVE, CSRC, HOST_FLAGS = TD.NATIVE, TD.CSRC, TD.HOST_FLAGS
@@ -22,12 +24,15 @@ OFFSETS = list(range(0, 13)) + WRAP
 NO_MAX = 0xffffffff
 # (smallest xstride, largest xstride, samples required): phx_denoise; acc and the frame film of phx_accumulate
 DENOISE, ACC, FRAME = (6, NO_MAX, False), (7, 24, True), (6, 24, False)
+# ... and (m2 required): the film of phx_outlier_clamp, which has no normals; its xstrides reach past both ends of the range
+CLAMP = (3, 24, False, False)
+CLAMP_XSTRIDES = [0, 2] + XSTRIDES + [24, 25, 0xffffffff]
 
 
-def first_invalid(xstride, normals, m2, samples, lo, hi, samples_required):
-    """include/phx_xpu.h, in Python integers: xstride within its range; m2 required, >= 3, m2 + 3 <= xstride; normals 0 or >= 3 and normals + 3 <=
-    xstride; samples 0 (unless required) or >= 3 and < xstride; no two channels share a float.  -> the first field outside its range in the
-    order xstride, m2, normals, samples, or None"""
+def first_invalid(xstride, normals, m2, samples, lo, hi, samples_required, m2_required=True):
+    """include/phx_xpu.h, in Python integers: xstride within its range; m2 (0: none, unless required) >= 3, m2 + 3 <= xstride; normals 0 or >= 3
+    and normals + 3 <= xstride; samples 0 (unless required) or >= 3 and < xstride; no two channels share a float.  -> the first field outside
+    its range in the order xstride, m2, normals, samples, or None"""
     def inside(off, length):
         return off >= 3 and off + length <= xstride
 
@@ -35,13 +40,13 @@ def first_invalid(xstride, normals, m2, samples, lo, hi, samples_required):
         return a + alen <= b or b + blen <= a
     if not lo <= xstride <= hi:
         return "xstride"
-    if not inside(m2, 3):
+    if not (inside(m2, 3) if m2 else not m2_required):
         return "m2_offset"
-    if normals and not (inside(normals, 3) and disjoint(normals, 3, m2, 3)):
+    if normals and not (inside(normals, 3) and (not m2 or disjoint(normals, 3, m2, 3))):
         return "normals_offset"
     if not samples:
         return "samples_offset" if samples_required else None
-    if not (inside(samples, 1) and disjoint(samples, 1, m2, 3) and (not normals or disjoint(samples, 1, normals, 3))):
+    if not (inside(samples, 1) and (not m2 or disjoint(samples, 1, m2, 3)) and (not normals or disjoint(samples, 1, normals, 3))):
         return "samples_offset"
     return None
 
@@ -89,6 +94,19 @@ def test_every_small_layout_and_the_wrapping_offsets():
     assert cases == len(XSTRIDES) * len(OFFSETS) ** 3 == 33750
     for k in refused:  # the grid reaches every answer of every check
         assert set(refused[k]) == {None, "xstride", "m2_offset", "normals_offset", "samples_offset"}, (k, refused[k])
+    # the clamp's film: no normals, m2 optional
+    ho = wrapper("host_outlier_clamp", TO.SOURCES)
+    ho.ho_check.argtypes = [C.POINTER(abi.OutlierClamp)] + [C.c_void_p] * 3 + [C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
+    c, copy = TO.good(), C.c_int(0)
+    assert ho.ho_check(C.byref(c), *TO.FAR, err, 256, C.byref(copy)) == 0
+    refused["clamp"] = {}
+    for xs, m2, s in itertools.product(CLAMP_XSTRIDES, OFFSETS, OFFSETS):
+        c.xstride_a, c.m2_offset_a, c.samples_offset_a = xs, m2, s
+        got = answer(ho.ho_check(C.byref(c), *TO.FAR, err, 256, C.byref(copy)), err.value.decode(), "outlier_clamp", "phx_outlier_clamp", "_a")
+        assert got == first_invalid(xs, 0, m2, s, *CLAMP), (xs, m2, s, got)
+        refused["clamp"][got] = refused["clamp"].get(got, 0) + 1
+    assert sum(refused["clamp"].values()) == len(CLAMP_XSTRIDES) * len(OFFSETS) ** 2 == 3375
+    assert set(refused["clamp"]) == {None, "xstride", "m2_offset", "samples_offset"}, refused["clamp"]
     print("film layout grid:", cases, "cases;", {k: {str(f): c for f, c in v.items()} for k, v in refused.items()})
 
 
@@ -106,4 +124,4 @@ def test_the_corner_cases_under_the_sanitizers(tmp_path):
     assert len(lines) == 8 * 13 ** 3
     for line in lines:
         xs, n, m2, s, *got = (int(w) for w in line.split())
-        assert got == [index[first_invalid(xs, n, m2, s, *rule)] for rule in (DENOISE, ACC, FRAME)], line
+        assert got == [index[first_invalid(xs, n, m2, s, *rule)] for rule in (DENOISE, ACC, FRAME)] + [index[first_invalid(xs, 0, m2, s, *CLAMP)]], line

@@ -88,6 +88,18 @@ def test_pixel_counts_around_the_span(dev, count):
     run(dev, count, 1)
 
 
+def summary_slots():
+    """PHX_SUMMARY_SLOTS (csrc/kernels.h): a workgroup adds its counts to slot (workgroup id % slots)"""
+    return int(re.search(r"PHX_SUMMARY_SLOTS = (\d+)", open(os.path.join(ROOT, "phosphorus_mk2_amd", "csrc", "kernels.h")).read()).group(1))
+
+
+def test_more_workgroups_than_summary_slots(dev):
+    """66 workgroups, the last of 3 pixels: the slots are gone round once and two of them are added to twice"""
+    count = 65 * SPAN + 3
+    assert -(-count // SPAN) > summary_slots() == 64
+    run(dev, count, 1)
+
+
 @pytest.mark.parametrize("width,height", SHAPES)
 def test_shapes(dev, width, height):
     acc, want = run(dev, width, height)

@@ -107,6 +107,15 @@ def test_sizes_and_radii(dev, width, height, radius):
         assert s["skipped"] + s["unbounded"] + s["inside"] + s["clamped"] == 1
 
 
+def test_more_workgroups_than_summary_slots(dev):
+    """9 x 8 = 72 ragged tiles over the 64 slots a workgroup adds its counts to by (linear workgroup id % PHX_SUMMARY_SLOTS)"""
+    width, height = 141, 123
+    src = open(os.path.join(ROOT, "phosphorus_mk2_amd", "csrc", "kernels.h")).read()
+    assert -(-width // TILE) * -(-height // TILE) == 72 > int(re.search(r"PHX_SUMMARY_SLOTS = (\d+)", src).group(1)) == 64
+    s = run(dev, width, height, radius=2)
+    assert s["pixels"] == width * height == s["skipped"] + s["unbounded"] + s["inside"] + s["clamped"]
+
+
 @pytest.mark.parametrize("width,height", OC.SIZES)
 def test_a_film_against_itself_in_place(dev, width, height):
     """the despeckle: B is A, film_out is film, the centre excluded and upper only: the bounds come from the film as it was"""

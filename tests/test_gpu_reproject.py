@@ -96,6 +96,15 @@ def test_pixel_counts_around_the_block(dev, count):
     assert s["reused"] > count // 2
 
 
+def test_more_workgroups_than_summary_slots(dev):
+    """66 workgroups, the last of 3 pixels, over the 64 slots a workgroup adds its counts to by (workgroup id % PHX_SUMMARY_SLOTS)"""
+    count = 65 * BLOCK + 3
+    src = open(os.path.join(ROOT, "phosphorus_mk2_amd", "csrc", "kernels.h")).read()
+    assert -(-count // BLOCK) > int(re.search(r"PHX_SUMMARY_SLOTS = (\d+)", src).group(1)) == 64
+    want, s = run(dev, count, 1, "translation")
+    assert s["reused"] > count // 2
+
+
 @pytest.mark.parametrize("width,height", SHAPES)
 def test_shapes(dev, width, height):
     run(dev, width, height, "translation")

@@ -4,6 +4,7 @@ the float64 model of the rule (tests/outlier_clamp64.py): constants, Samuelson's
 non-finite and skipped pixels, the film's edges, min_taps, UPPER_ONLY, the synthetic payoff and the history case.  The device is held to
 the same model bit for bit in tests/test_gpu_outlier_clamp.py."""
 import ctypes as C
+import itertools
 import math
 import os
 import re
@@ -88,6 +89,19 @@ def test_python_settings_derive_the_layout_as_film_does():
         xpu.outlier_clamp_settings((5, 7, 7), (5, 8, 7))
     with pytest.raises(ValueError, match="floats per pixel"):
         xpu.outlier_clamp_settings((5, 7, 6), (5, 7, 6))
+
+
+def test_film_layout_is_the_layout_film_has():
+    """xpu.film_layout, the one derivation of the channel order, against Film for every film there is: an offset where the channel is, 0 where not"""
+    from phosphorus_mk2_amd import xpu
+    for pc, normals, moments, samples in itertools.product((3, 4), (False, True), (False, True), (False, True)):
+        no, mo, so, xstride = xpu.film_layout(pc, normals, moments, samples)
+        assert no == (pc if normals else 0)
+        if samples and not moments:   # no Film carries "samples" without "m2": the channel then sits where a film without it ends
+            assert (mo, so, xstride) == (0, xpu.Film(3, 2, pc, normals).xstride, xpu.Film(3, 2, pc, normals).xstride + 1)
+            continue
+        film = xpu.Film(3, 2, pc, normals, moments, samples)
+        assert (mo, so) == (film.m2_offset if moments else 0, film.samples_offset if samples else 0) and xstride == film.xstride == film.data.shape[2]
 
 
 # ---- 2. the refusals ----------------------------------------------------------------------------------------------------------------------
