@@ -143,11 +143,16 @@ PHX_HD bool mt_intersect(const TriRec& T, const v3& o, const v3& wi, float tmax,
   us = sdot(t, p) * ood;
   vs = sdot(wi, q) * ood;
   ds = sdot(e1, q) * ood;
-  const bool xmask = (det > 0.00000001f) || (det < -0.00000001f);
+  // The reference's predicate — |det| > eps, us >= 0, vs >= 0, us + vs <= 1, ds >= 0, ds < tmax (or the tie) — with "vs >= 0 and ds >= 0" as ONE
+  // compare of their minimum, and without short-circuits (every operand is computed anyway; the compiler otherwise narrows the exec mask term by
+  // term).  minNum drops a NaN operand, which changes nothing: a NaN vs makes us + vs NaN and fails smask, a NaN ds fails both compares of dmask;
+  // min(-0, x >= 0) is -0 or +0 and passes ">= 0" like both of its operands.
+  const bool xmask = (det > 0.00000001f) | (det < -0.00000001f);
   const bool umask = us >= 0.0f;
-  const bool vmask = (vs >= 0.0f) && ((us + vs) <= 1.0f);
-  const bool dmask = (ds >= 0.0f) && ((ds < tmax) || (ds == tmax && T.prim < best_prim));
-  return vmask && umask && dmask && xmask;
+  const bool vdmask = fminf(vs, ds) >= 0.0f;
+  const bool smask = (us + vs) <= 1.0f;
+  const bool dmask = (ds < tmax) | ((ds == tmax) & (T.prim < best_prim));
+  return umask & vdmask & smask & dmask & xmask;
 }
 
 struct RayCtx {

@@ -91,6 +91,14 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
   const float4* __restrict__ ro = pb.ro[q];
   const float4* __restrict__ rd = pb.rd[q];
   uint32_t dlo = 0, dhi = 0;  // the wave's current chunk [dlo, dhi)
+  // Element i of the pool.  Every instantiation but the unpacked SPILL one runs on pools of < 2^26 elements only (trace_plan), whose byte offsets
+  // fit 32 bits: the fetch is then global_load v, s[pool] with ONE 32-bit shift per lane, where the 64-bit address costs a 64-bit shift and a
+  // 64-bit add per lane and fetch (-1.3 % of k_trace, profiles/r08_ktrace_select_ab.log)
+  constexpr bool OFF32 = !(SPILL && !PACKED);
+  auto pool_elem = [&](uint32_t i) {
+    if constexpr (OFF32) return reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(sc.pool) + (i << 6));
+    else return reinterpret_cast<const uint4*>(sc.pool) + (size_t)i * 4u;
+  };
 #if PHX_COUNT
   uint32_t cnt_lds[2] = {0, 0}, cnt_mem[2] = {0, 0}, cnt_tri[2] = {0, 0};  // instrumented build: this lane's traversal work
   uint32_t cnt_iter = 0, cnt_nb = 0, cnt_tb = 0, cnt_refill = 0;              // ... and the wave's (wave-uniform)
@@ -233,7 +241,7 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
         for (int k = 0; k < 4; ++k) { const uint4 v = s4[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
       }
       if (!in_lds) {
-        const uint4* s4 = reinterpret_cast<const uint4*>(sc.pool) + (size_t)ni * 4u;
+        const uint4* s4 = pool_elem(ni);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { const uint4 v = s4[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
       }
@@ -263,7 +271,7 @@ __device__ __forceinline__ void trace_stream(const DevScene& sc, const PassBuffe
       const uint32_t k = 23u - (uint32_t)__clz((int)(tg & TG_PENDING));  // slot of the highest pending triangle (bits 8..15 -> 7..0)
       tg &= ~(0x100u << k);
       const uint32_t ti = tg_base + (uint32_t)__popc(tg & 0xffu & ~(0xffffffffu << k));
-      const uint4* t4 = reinterpret_cast<const uint4*>(sc.pool) + (size_t)ti * 4u;
+      const uint4* t4 = pool_elem(ti);
       const uint4 t0 = t4[0], t1 = t4[1], t2 = t4[2];  // three of the record's four words: v0, e0, e1, prim
       TriRec T;
       T.v0x = u2f(t0.x); T.v0y = u2f(t0.y); T.v0z = u2f(t0.z); T.e0x = u2f(t0.w);
@@ -679,6 +687,11 @@ hipError_t init_kernels_on_current_device() {
   return rc;
 }
 
+// k_trace addresses the pool with 32-bit byte offsets (trace_stream: pool_elem) in every instantiation but <1024, SPILL, unpacked>, which keeps
+// 64-bit addresses: a pool of 2^26 elements or more (4 GB) runs that one whatever its depth (with every level in LDS it never touches the spill
+// area, and such a pool is never packed: PHX_STACK_PACKED needs < 2^24 elements)
+static bool trace_pool_is_wide(const DevScene& sc) { return sc.num_elems >= (1u << 26); }
+
 // What a k_trace launch on this scene looks like: workgroup size, nodelets staged in LDS, stack levels, LDS bytes.
 TracePlan trace_plan(const DevScene& sc) {
   const TraceEnv& E = trace_env();
@@ -696,6 +709,7 @@ TracePlan trace_plan(const DevScene& sc) {
     P.lds_levels = std::max(2u, std::min(P.levels, want));
   }
   const bool spill = P.lds_levels < P.levels;
+  const bool wide = trace_pool_is_wide(sc);
   // nodelets staged in LDS: whatever the per-lane stacks leave of the workgroup's share of the CU's 160 KB at full occupancy
   // (32 waves per CU); 9 (root + one level) when the stacks alone do not fit, and occupancy then follows from the LDS
   // 5-byte stack entries (PHX_STACK_PACKED): for the SPILL plan, when the pool's indices fit 24 bits
@@ -713,8 +727,8 @@ TracePlan trace_plan(const DevScene& sc) {
   };
   // 1024-thread workgroups share one copy of the staged nodelets among 16 waves; a deep tree (levels >= 10: the stacks alone
   // exceed the CU's LDS at full occupancy) is better served by smaller workgroups, whose LDS granularity wastes less
-  P.block = E.block_env ? E.block_env : 1024u;
-  if (E.block_env || spill) P.wg_per_cu = plan(P.block, P.ntop, P.lds_bytes);  // spilling exists for 1024-thread workgroups only
+  P.block = E.block_env && !wide ? E.block_env : 1024u;
+  if (E.block_env || spill || wide) P.wg_per_cu = plan(P.block, P.ntop, P.lds_bytes);  // spilling exists for 1024-thread workgroups only
   else {
     uint32_t best_waves = 0;
     for (uint32_t blk = 1024u; blk >= 256u; blk >>= 1) {
@@ -742,7 +756,7 @@ void launch_trace(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
   // UV: the pass has a barycentrics stream exactly when the committed scene reads them (device.cpp), so its presence picks the instantiation
   with_flag(pb.hit_uv != nullptr, [&](auto UV) {
     constexpr bool uv = decltype(UV)::value;
-    if (P.lds_levels < P.levels) { if (P.packed) go(&k_trace<1024, true, true, uv>); else go(&k_trace<1024, true, false, uv>); }  // deep tree: 1024-thread workgroups, the stack's deep levels in HBM
+    if (P.lds_levels < P.levels || trace_pool_is_wide(sc)) { if (P.packed) go(&k_trace<1024, true, true, uv>); else go(&k_trace<1024, true, false, uv>); }  // deep tree: 1024-thread workgroups, the stack's deep levels in HBM
     else if (block == 256) go(&k_trace<256, false, false, uv>);
     else if (block == 512) go(&k_trace<512, false, false, uv>);
     else go(&k_trace<1024, false, false, uv>);

@@ -13,6 +13,7 @@ instructions, not by label numbers (those change from build to build):
   tail      exec-mask merges of the structured control flow back to the loop head
 Every VALU instruction is priced with the issue costs MEASURED on gfx950 (profiles/r02_valu_ops.json, scripts/micro/valu_ops.hip):
 VOP2 integer / fp32 add, sub, mul, fmac, and, or, shifts: 2 clocks per wave-instruction and SIMD; v_fma_f32 2.6; v_rcp_f32 8;
+v_bitop3_b32 2.24 (profiles/r05_valu_ops.json);
 everything else (VOP3 encodings, conversions, min/max, compares, selects, bit-field ops) 4.  The table is an issue-time
 estimate for ONE wave with all its lanes in the block — it says where the instructions are, not how long a launch takes.
 """
@@ -32,6 +33,8 @@ def clocks(op):
         return 2.07
     if op in ("v_fma_f32",):
         return 2.61
+    if op.startswith("v_bitop3_b32"):
+        return 2.24  # profiles/r05_valu_ops.json
     if op.startswith("v_rcp") or op.startswith("v_div_scale") or op.startswith("v_div_fmas") or op.startswith("v_div_fixup"):
         return 8.05 if op.startswith("v_rcp") else 4.1
     return 4.1
@@ -93,9 +96,15 @@ def main():
         raise SystemExit("marker not found")
 
     # the loop head: the watchdog counter (s_add_i32 sN, sN, -1 followed by s_cmp_lg_u32 sN, 0)
-    head = find(lambda o, s: o == "s_add_i32" and s.endswith(", -1"))
-    while not ops[head + 1][1].startswith("s_cmp_lg"):
-        head = find(lambda o, s: o == "s_add_i32" and s.endswith(", -1"), head + 1)
+    # ... or, when the compiler counts upwards, the compare with PHX_TRACE_WATCHDOG itself (s_cmp_* sN, 0x400000, or s_mov_b32 sM, 0x400000
+    # in front of a v_cmp when it keeps the counter in a VGPR)
+    up = [k for k in range(len(ops)) if (ops[k][1].startswith("s_cmp_") or ops[k][1] == "s_mov_b32") and ops[k][2].endswith(", 0x400000")]
+    if up:
+        head = up[0]
+    else:
+        head = find(lambda o, s: o == "s_add_i32" and s.endswith(", -1"))
+        while not ops[head + 1][1].startswith("s_cmp_lg"):
+            head = find(lambda o, s: o == "s_add_i32" and s.endswith(", -1"), head + 1)
     refill = find(lambda o, s: o == "s_bcnt1_i32_b64", head)           # popcount of the idle ballot
     ray_fetch = find(lambda o, s: o.startswith("v_rcp_f32"), refill)     # make_ray_ctx
     node = find(lambda o, s: o == "v_ffbh_u32_e32", ray_fetch)           # highest pending inner child
@@ -153,7 +162,7 @@ def main():
             hist[o] = hist.get(o, 0) + 1
     print("| opcode | count | clocks each | clocks |\n|---|---|---|---|")
     for o, n in sorted(hist.items(), key=lambda x: -x[1]):
-        cl = clocks(o if o in ("v_fma_f32",) else o + "_e32")
+        cl = clocks(o if o in ("v_fma_f32", "v_bitop3_b32") else o + "_e32")
         print(f"| {o} | {n} | {cl:.2f} | {n * cl:.0f} |")
 
 

@@ -97,6 +97,9 @@ def ktrace_node_test(asm, kernel="_ZN3phx7k_traceILi1024ELb0E"):
     # five register moves and the lane's group bookkeeping behind it are the loop's, not the test's)
     tload = next(i for i in range(end, len(kl)) if "global_load_dwordx2" in kl[i])
     tend = next(i for i in range(tload, len(kl)) if re.match(r"^\s+v_cmp_gt_f32\S*\s+.*\|v\d+\|", kl[i]))
+    # ... or the last compare of the accept, when the compiler schedules |det| among the others: everything up to the s_and_saveexec that applies it
+    applied = next(i for i in range(tend, len(kl)) if re.match(r"^\s+s_and_saveexec_b64", kl[i]))
+    tend = max(i for i in range(tend, applied) if re.match(r"^\s+v_", kl[i]))
     return node, count(kl[tload + 1:tend + 1])
 
 
