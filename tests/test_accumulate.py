@@ -5,21 +5,17 @@ oracle's films of two seeds.  The device is held to the same model bit for bit i
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import accumulate64 as ac
 import frame_cases as FC
-from conftest import ROOT, bits_equal
+import native_lib as NL
+from conftest import bits_equal
+from native_lib import CSRC, ERR_ARG
 
 F, D = np.float32, np.float64
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
-HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off"]
-SOURCES = [os.path.join(NATIVE, "host_accumulate.cpp"), os.path.join(CSRC, "accumulate_check.cpp")]
-ERR_ARG = 1
 
 
 # ---- 1. the ABI and the header ------------------------------------------------------------------------------------------------------------
@@ -50,16 +46,15 @@ def test_struct_size_is_the_librarys():
 
 
 def test_header_states_the_struct_and_the_rule():
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
-    body = re.search(r"typedef struct phx_accumulate \{(.*?)\} phx_accumulate;", hdr, re.S).group(1)
-    assert re.findall(r"\b(\w+)(?:\[2\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S)) == FIELDS[1:]
+    hdr, body = NL.header(), NL.struct_body("phx_accumulate", strip_comments=False)
+    assert re.findall(r"\b(\w+)(?:\[2\])?;", NL.struct_body("phx_accumulate")) == FIELDS[1:]
     assert re.search(r"uint32_t\s+width,\s*height;", body) and re.search(r"float\s+tau;", body) and re.search(r"float\s+floor;", body)
     assert re.search(r"uint64_t\s+pixels,\s*invalid,\s*converged,\s*samples;\s*\} phx_accumulate_summary;", hdr)
     assert re.search(r"int\s+phx_dev_film_accumulate\(phx_device\* dev, const phx_accumulate\* a, float\* acc, const float\* frame_film, "
                      r"phx_accumulate_summary\* summary", hdr)
     assert re.search(r"int\s+phx_dev_accumulate_times\(const phx_device\* dev, double\* ms", hdr)
     rule = hdr[hdr.index("film accumulation across frames (DESIGN 20)"):hdr.index("typedef struct phx_accumulate")]
-    flat = " ".join(rule.replace("*", " ").split())
+    flat = NL.flat(rule)
     for phrase in ["n_b = samples_offset_b ? (double)samples_b : (double)spp_b", "n = n_a + n_b", "n_b == 0: the pixel of acc is not touched",
                    "n_a == 0: primary rgb, m2 := the frame's floats bit for bit; samples := fp32(n_b)", "Q_a = (m2_a n_a) n_a", "Q_b = (m2_b n_b) n_b",
                    "d = V_b - V_a", "V = fp32(V_a + (d n_b) / n)", "Q = (Q_a + Q_b) + ((d d) (n_a n_b)) / n", "m2 = fp32((Q / n) / n)",
@@ -104,22 +99,13 @@ def test_render_refuses_progressive_without_moments():
 # ---- 2. the refusals ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def check():
-    """tests/native/libhost_accumulate.so: (abi.Accumulate, acc address, frame film address) -> (status, message)"""
+    """the host_accumulate library: (abi.Accumulate, acc address, frame film address) -> (status, message)"""
     from phosphorus_mk2_amd import abi
-    so = os.path.join(NATIVE, "libhost_accumulate.so")
-    hdr = [os.path.join(CSRC, "accumulate_check.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + hdr):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
-    lib = C.CDLL(so)
-    lib.ha_check.argtypes = [C.POINTER(abi.Accumulate), C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32]; lib.ha_check.restype = C.c_int
+    lib = NL.load("host_accumulate")
+    ha_check = NL.checker(lib, "ha_check", [C.POINTER(abi.Accumulate), C.c_void_p, C.c_void_p])
     lib.ha_sizeof.restype = C.c_uint32; lib.ha_sizeof_summary.restype = C.c_uint32
     assert lib.ha_sizeof() == C.sizeof(abi.Accumulate) and lib.ha_sizeof_summary() == C.sizeof(abi.AccumulateSummary)
-
-    def run(q, acc=0x10000, frame=1 << 44):  # (far apart: the largest film is 2^32 pixels of 96 bytes)
-        err = C.create_string_buffer(256)
-        rc = lib.ha_check(C.byref(q), acc, frame, err, 256)
-        return rc, err.value.decode()
-    return run
+    return lambda q, acc=0x10000, frame=1 << 44: ha_check(C.byref(q), acc, frame)  # (far apart: the largest film is 2^32 pixels of 96 bytes)
 
 
 def good(**kw):
@@ -149,12 +135,12 @@ REFUSED = [("width", dict(width=0)), ("width", dict(width=65537)), ("height", di
            ("floor", dict(floor=-1.0)), ("floor", dict(floor=float("nan"))), ("floor", dict(floor=float("inf")))]
 
 
-@pytest.mark.parametrize("kw", ACCEPTED, ids=[",".join(f"{k}={v}" for k, v in kw.items()) or "defaults" for kw in ACCEPTED])
+@pytest.mark.parametrize("kw", ACCEPTED, ids=NL.case_ids(ACCEPTED))
 def test_check_accepts(check, kw):
     assert check(good(**kw)) == (0, "")
 
 
-@pytest.mark.parametrize("field,kw", REFUSED, ids=[",".join(f"{k}={v}" for k, v in kw.items()) for _, kw in REFUSED])
+@pytest.mark.parametrize("field,kw", REFUSED, ids=NL.case_ids(kw for _, kw in REFUSED))
 def test_check_refuses_and_names_the_field(check, field, kw):
     rc, msg = check(good(**kw))
     assert rc == ERR_ARG and re.search(rf"\b{field}\b", msg), (rc, msg)
@@ -191,12 +177,8 @@ def test_check_refuses_reserved_words_and_bad_films(check):
 
 def test_the_check_under_the_sanitizers(tmp_path):
     """host_accumulate.cpp's own main() under AddressSanitizer and UBSan: its cases get the answers above, and the program ends without a report"""
-    exe = str(tmp_path / "host_accumulate_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_ACCUMULATE_MAIN"] +
-                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
-    got = {l.split()[0]: (int(l.split()[1]), l) for l in r.stdout.splitlines()}
+    stdout = NL.run_sanitized(tmp_path, "host_accumulate", "HOST_ACCUMULATE_MAIN")
+    got = {l.split()[0]: (int(l.split()[1]), l) for l in stdout.splitlines()}
     want = {"good": None, "same": "frame_film", "overlap": "frame_film", "null-acc": "acc", "null-frame": "frame_film", "width": "width", "height": "height",
             "xstride-a": "xstride_a", "xstride-b": "xstride_b", "m2-wrap": "m2_offset_a", "normals-overlap": "normals_offset_b",
             "no-samples-a": "samples_offset_a", "samples-past": "samples_offset_b", "spp": "spp_b", "on-device": "on_device", "tau-nan": "tau",

@@ -4,20 +4,16 @@ output on an iid film, and what it does to the oracle's films.  The device is he
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import denoise64 as dn
-from conftest import ROOT, bits_equal
+import native_lib as NL
+from conftest import bits_equal
+from native_lib import ERR_ARG
 
 F, D = np.float32, np.float64
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
-HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off"]
-SOURCES = [os.path.join(NATIVE, "host_denoise.cpp"), os.path.join(CSRC, "denoise_check.cpp")]
-ERR_ARG = 1
 
 
 # ---- 1. the ABI and the header ------------------------------------------------------------------------------------------------------------
@@ -47,14 +43,13 @@ def test_struct_size_is_the_librarys():
 
 
 def test_header_states_the_struct_and_the_rule():
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
-    body = re.search(r"typedef struct phx_denoise \{(.*?)\} phx_denoise;", hdr, re.S).group(1)
-    assert re.findall(r"\b(\w+)(?:\[5\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S)) == ["height", "xstride", "normals_offset", "m2_offset", "samples_offset", "spp", "iterations",
+    hdr, body = NL.header(), NL.struct_body("phx_denoise", strip_comments=False)
+    assert re.findall(r"\b(\w+)(?:\[5\])?;", NL.struct_body("phx_denoise")) == ["height", "xstride", "normals_offset", "m2_offset", "samples_offset", "spp", "iterations",
                                                        "sigma_l", "normal_power_log2", "on_device", "reserved"]
     assert re.search(r"uint32_t\s+width,\s*height;", body)
     assert re.search(r"int\s+phx_dev_denoise\(phx_device\* dev, const phx_denoise\* d, const float\* film_in, float\* film_out\);", hdr)
     rule = hdr[hdr.index("film denoiser (DESIGN 18)"):hdr.index("typedef struct phx_denoise")]
-    flat = " ".join(rule.replace("*", " ").split())
+    flat = NL.flat(rule)
     for phrase in ["V_c = fp32(m2_c (n / (n - 1)))", "(0.2126 C_r + 0.7152 C_g) + 0.0722 C_b", "(0.2126 sqrt(V_r) + 0.7152 sqrt(V_g)) + 0.0722 sqrt(V_b)",
                    "k3 = (1/4, 1/2, 1/4)", "k5 = (1/16, 1/4, 3/8, 1/4, 1/16)", "sig = sigma_l sqrt(S_p)", "d = d > 0 ? d : 0",
                    "u = fabs(l_q - l_p) / sig", "w_l = u < 1 ? t t : 0", "w = (h w_n) w_l", "A_c += w (C_q,c - C_p,c)", "B_c += (w w) V_q,c",
@@ -90,22 +85,13 @@ def test_render_refuses_denoise_without_moments():
 # ---- 2. the refusals ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def check():
-    """tests/native/libhost_denoise.so: (abi.Denoise, film_in address, film_out address) -> (status, message)"""
+    """the host_denoise library: (abi.Denoise, film_in address, film_out address) -> (status, message)"""
     from phosphorus_mk2_amd import abi
-    so = os.path.join(NATIVE, "libhost_denoise.so")
-    hdr = [os.path.join(CSRC, "denoise_check.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + hdr):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
-    lib = C.CDLL(so)
-    lib.hd_check.argtypes = [C.POINTER(abi.Denoise), C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32]; lib.hd_check.restype = C.c_int
+    lib = NL.load("host_denoise")
+    hd_check = NL.checker(lib, "hd_check", [C.POINTER(abi.Denoise), C.c_void_p, C.c_void_p])
     lib.hd_sizeof.restype = C.c_uint32
     assert lib.hd_sizeof() == C.sizeof(abi.Denoise)
-
-    def run(q, film_in=0x10000, film_out=0x10000):
-        err = C.create_string_buffer(256)
-        rc = lib.hd_check(C.byref(q), film_in, film_out, err, 256)
-        return rc, err.value.decode()
-    return run
+    return lambda q, film_in=0x10000, film_out=0x10000: hd_check(C.byref(q), film_in, film_out)
 
 
 def good(**kw):
@@ -132,12 +118,12 @@ REFUSED = [("width", dict(width=0)), ("width", dict(width=65537)), ("height", di
            ("normal_power_log2", dict(normal_power_log2=11)), ("on_device", dict(on_device=2))]
 
 
-@pytest.mark.parametrize("kw", ACCEPTED, ids=[",".join(f"{k}={v}" for k, v in kw.items()) or "defaults" for kw in ACCEPTED])
+@pytest.mark.parametrize("kw", ACCEPTED, ids=NL.case_ids(ACCEPTED))
 def test_check_accepts(check, kw):
     assert check(good(**kw)) == (0, "")
 
 
-@pytest.mark.parametrize("field,kw", REFUSED, ids=[",".join(f"{k}={v}" for k, v in kw.items()) for _, kw in REFUSED])
+@pytest.mark.parametrize("field,kw", REFUSED, ids=NL.case_ids(kw for _, kw in REFUSED))
 def test_check_refuses_and_names_the_field(check, field, kw):
     rc, msg = check(good(**kw))
     assert rc == ERR_ARG and re.search(rf"\b{field}\b", msg), (rc, msg)
@@ -161,12 +147,8 @@ def test_check_refuses_reserved_words_and_bad_films(check):
 
 def test_the_check_under_the_sanitizers(tmp_path):
     """host_denoise.cpp's own main() under AddressSanitizer and UBSan: its cases get the answers above, and the program ends without a report"""
-    exe = str(tmp_path / "host_denoise_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_DENOISE_MAIN"] +
-                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
-    got = {l.split()[0]: (int(l.split()[1]), l) for l in r.stdout.splitlines()}
+    stdout = NL.run_sanitized(tmp_path, "host_denoise", "HOST_DENOISE_MAIN")
+    got = {l.split()[0]: (int(l.split()[1]), l) for l in stdout.splitlines()}
     want = {"good": None, "in-place": None, "overlap": "film_out", "null-in": "film_in", "null-out": "film_out", "width": "width", "height": "height",
             "xstride": "xstride", "m2-wrap": "m2_offset", "normals-overlap": "normals_offset", "samples-past": "samples_offset", "spp": "spp",
             "iterations": "iterations", "sigma-nan": "sigma_l", "power": "normal_power_log2", "on-device": "on_device", "reserved": "reserved"}

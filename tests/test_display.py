@@ -5,21 +5,15 @@ import ctypes as C
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import display_model as dm
-from conftest import ROOT
+import native_lib as NL
+from native_lib import ERR_ARG
 
 F, D = np.float32, np.float64
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
-HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off"]
-SOURCES = [os.path.join(NATIVE, "host_display.cpp"), os.path.join(CSRC, "display_check.cpp")]
-HEADERS = [os.path.join(CSRC, h) for h in ("display_check.h", "display_rule.h", "film_checks.h", "phx_math.h")] + [os.path.join(ROOT, "include", "phx_xpu.h")]
-ERR_ARG = 1
 FIELDS = ["width", "height", "xstride", "image_pitch", "on_device", "flags", "tone", "scale", "white", "key", "low_q16", "high_q16", "min_scale",
           "max_scale", "reserved"]
 SUMMARY = ["pixels", "invalid", "unlit", "counted", "scale", "from_histogram"]
@@ -53,9 +47,8 @@ def test_struct_sizes_are_the_librarys():
 
 
 def test_header_states_the_structs_and_the_rule():
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
-    body = re.search(r"typedef struct phx_display \{(.*?)\} phx_display;", hdr, re.S).group(1)
-    assert re.findall(r"\b(\w+)(?:\[2\])?;", re.sub(r"/\*.*?\*/", "", body, flags=re.S)) == FIELDS[1:]
+    hdr, body = NL.header(), NL.struct_body("phx_display", strip_comments=False)
+    assert re.findall(r"\b(\w+)(?:\[2\])?;", NL.struct_body("phx_display")) == FIELDS[1:]
     assert re.search(r"uint32_t\s+width,\s*height;", body) and all(re.search(rf"float\s+{f};", body) for f in ("scale", "white", "key", "min_scale", "max_scale"))
     assert re.search(r"uint64_t\s+pixels,\s*invalid,\s*unlit,\s*counted;\s*float\s+scale;[^}]*uint32_t\s+from_histogram;[^}]*\} phx_display_summary;", hdr)
     assert re.search(r"int\s+phx_dev_film_display\(phx_device\* dev, const phx_display\* p, const float\* film, uint8_t\* image,\s*"
@@ -63,7 +56,7 @@ def test_header_states_the_structs_and_the_rule():
     assert re.search(r"int\s+phx_dev_display_times\(const phx_device\* dev, double\* ms", hdr)
     assert re.search(r"PHX_DISPLAY_DITHER = 1, PHX_DISPLAY_AUTO_EXPOSURE = 2", hdr) and re.search(r"PHX_TONE_CLAMP = 0, PHX_TONE_REINHARD = 1, PHX_TONE_ACES = 2", hdr)
     rule = hdr[hdr.index("the display pass (DESIGN 21)"):hdr.index("typedef struct phx_display")]
-    flat = " ".join(rule.replace("*", " ").split())
+    flat = NL.flat(rule)
     for phrase in ["(x, y) = (i mod width, i div width)", "`invalid` when r, g or b is not finite", "Y = fp32((0.2126 r + 0.7152 g) + 0.0722 b)",
                    "in binary64", "Y <= 0 counts as `unlit`", "bin = clamp((bits(Y) >> 20) - 888, 0, 255)", "counted = the sum of the bins = pixels - invalid - unlit",
                    "linear inside its octave", "up to 0.09 stop", "N == 0: scale := the struct's scale, from_histogram = 0",
@@ -111,14 +104,11 @@ def test_save_ppm_round_trip(tmp_path):
 # ---- 2. display_rule.h on the host against the model ----------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host():
-    """tests/native/libhost_display.so"""
+    """the host_display library; .check is hd_check -> (status, message)"""
     from phosphorus_mk2_amd import abi
-    so = os.path.join(NATIVE, "libhost_display.so")
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + HEADERS):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
-    lib = C.CDLL(so)
+    lib = NL.load("host_display")
     vp = C.c_void_p
-    lib.hd_check.argtypes = [C.POINTER(abi.Display), vp, vp, C.c_char_p, C.c_uint32]; lib.hd_check.restype = C.c_int
+    lib.check = NL.checker(lib, "hd_check", [C.POINTER(abi.Display), vp, vp])
     lib.hd_sizeof.restype = C.c_uint32; lib.hd_sizeof_summary.restype = C.c_uint32
     lib.hd_bins.argtypes = [C.c_uint64, vp, vp]; lib.hd_bins.restype = None
     lib.hd_exposure.argtypes = [vp, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]; lib.hd_exposure.restype = None
@@ -404,9 +394,7 @@ FILM, IMAGE = 0x10000, 1 << 44  # far apart: the largest film is 2^32 pixels of 
 
 
 def check(host, q, film=FILM, image=IMAGE):
-    err = C.create_string_buffer(256)
-    rc = host.hd_check(C.byref(q), film, image, err, 256)
-    return rc, err.value.decode()
+    return host.check(C.byref(q), film, image)
 
 
 @pytest.mark.parametrize("kw", ACCEPTED, ids=[str(i) for i in range(len(ACCEPTED))])
@@ -444,12 +432,8 @@ def test_pointers(host):
 def test_the_rule_and_the_check_under_the_sanitizers(host, tmp_path):
     """host_display.cpp's own main() under AddressSanitizer and UBSan: the check's cases get their answers, the whole call on a film of special
     pixels with a padded pitch gives the model's image and summary, and the program ends without a report"""
-    exe = str(tmp_path / "host_display_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_DISPLAY_MAIN"] +
-                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
-    got = {l.split()[0]: l.split()[1:] for l in r.stdout.splitlines()}
+    stdout = NL.run_sanitized(tmp_path, "host_display", "HOST_DISPLAY_MAIN")
+    got = {l.split()[0]: l.split()[1:] for l in stdout.splitlines()}
     want = {"good": None, "null-film": "film", "null-image": "image", "misaligned": "image", "overlap": "image", "width": "width", "height": "height",
             "xstride": "xstride", "pitch": "image_pitch", "on-device": "on_device", "flags": "flags", "tone": "tone", "scale": "scale", "white": "white",
             "key": "key", "low": "low_q16", "high": "high_q16", "min-scale": "min_scale", "max-scale": "max_scale", "reserved": "reserved"}

@@ -13,12 +13,13 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from native_lib import ERR_ARG
 from phosphorus_mk2_amd import abi, scenes
 from test_analytic_direct_light import H_LAMP, LAMP, RHO, SPP, W
 from test_gpu_textures import np_lookup
 from test_light_sampling import (TWO_LAMPS, G_rect, LightTable, _camera, _floor, floor_points, light_sample, moments, rect_nodes, rects_mesh, tri_areas,
                                  z_scores)
-from test_scene_flatten import ERR_ARG, SC_TEX_LOBES, flat  # noqa: F401  (flat: the fixture that builds tests/native/libhost_flatten.so)
+from test_scene_flatten import SC_TEX_LOBES, flat  # noqa: F401  (flat: the fixture that loads the host_flatten library)
 
 F = np.float32
 SEED = 5  # the striped lamp's and the atlas room's renders

@@ -4,17 +4,15 @@ PHX_LIGHT_INCLUDE_ENVIRONMENT), the parts that need no GPU: the ABI and the Pyth
 the properties the rule promises, and flatten_scene against the restatement through tests/native/host_flatten_env.cpp."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import native_lib as NL
 from phosphorus_mk2_amd import abi, scenes
 from test_light_power import DECADES, PHI, SC_LIGHTS_BY_POWER, PowerTable, lamps_scene, select
-from test_scene_flatten import ARRAYS, CSRC, HOST_FLAGS, NATIVE, SC_LIGHTS_BY_AREA, SC_TEX_ENV, WORDS, _rocm_include
+from test_scene_flatten import ARRAYS, SC_LIGHTS_BY_AREA, SC_TEX_ENV, WORDS
 
 F = np.float32
 D = np.float64
@@ -27,7 +25,7 @@ ONE_MINUS_EPS = F(1) - F(2.0 ** -23)  # 1 - FLT_EPSILON
 # ---- (a) ABI and Python ---------------------------------------------------------------------------------------------------------------------
 def test_abi_environment_sampling():
     from phosphorus_mk2_amd import xpu
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
+    hdr = NL.header()
     m = re.search(r"\bPHX_LIGHT_INCLUDE_ENVIRONMENT\s*=\s*(0x[0-9a-fA-F]+|\d+)", hdr)
     assert m and int(m.group(1), 0) == abi.LIGHT_INCLUDE_ENVIRONMENT == 0x200
     assert re.search(r"#define\s+PHX_LIGHT_ENVIRONMENT\(x\)\s+\(\(x\)\s*&\s*0x200u\)", hdr)
@@ -299,14 +297,8 @@ def test_the_polynomial_is_the_sine():
 # ---- (d) flatten_scene ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def flat_env():
-    """tests/native/libhost_flatten_env.so: test_light_power's flatten() plus the environment's tables ("env_cdf", "env_p", "env_w")"""
-    so = os.path.join(NATIVE, "libhost_flatten_env.so")
-    src = [os.path.join(NATIVE, "host_flatten_env.cpp"), os.path.join(CSRC, "scene_flatten.cpp")]
-    dep = src + [os.path.join(NATIVE, "host_flatten.cpp"), os.path.join(NATIVE, "host_flatten_power.cpp"), os.path.join(ROOT, "include", "phx_xpu.h")] + \
-        [os.path.join(CSRC, h) for h in ("scene_flatten.h", "kernels.h", "bsdf.h", "bvh8.h", "phx_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in dep):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-I", _rocm_include()] + HOST_FLAGS + ["-o", so] + src, check=True)
-    lib = C.CDLL(so)
+    """the host_flatten_env library: test_light_power's flatten() plus the environment's tables ("env_cdf", "env_p", "env_w")"""
+    lib = NL.load("host_flatten_env")
     lib.hf_flatten.restype = C.c_void_p; lib.hf_flatten.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Options)]
     lib.hf_free.argtypes = [C.c_void_p]
     lib.hf_status.argtypes = [C.c_void_p]

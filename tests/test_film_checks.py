@@ -5,19 +5,14 @@ ranges include/phx_xpu.h states for phx_denoise, phx_accumulate and phx_outlier_
 other field."""
 import ctypes as C
 import itertools
-import os
 import re
-import subprocess
 
-import pytest
-
+import native_lib as NL
 import test_accumulate as TA
 import test_denoise as TD
 import test_outlier_clamp as TO
-from conftest import ROOT
+from native_lib import ERR_ARG
 
-NATIVE, CSRC, HOST_FLAGS = TD.NATIVE, TD.CSRC, TD.HOST_FLAGS
-ERR_ARG = 1
 WRAP = [0xfffffffe, 0xffffffff]
 XSTRIDES = list(range(3, 13))
 OFFSETS = list(range(0, 13)) + WRAP
@@ -51,15 +46,6 @@ def first_invalid(xstride, normals, m2, samples, lo, hi, samples_required, m2_re
     return None
 
 
-def wrapper(name, sources):
-    """tests/native/lib<name>.so, built as the module that owns it builds it"""
-    so = os.path.join(NATIVE, f"lib{name}.so")
-    deps = sources + [os.path.join(CSRC, "film_checks.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + sources, check=True)
-    return C.CDLL(so)
-
-
 def answer(rc, text, call, struct, suffix=""):
     """(status, refusal text) -> the field the refusal names without `suffix`, or None; the text is the one every check gives"""
     if rc == 0:
@@ -72,7 +58,7 @@ def answer(rc, text, call, struct, suffix=""):
 
 def test_every_small_layout_and_the_wrapping_offsets():
     from phosphorus_mk2_amd import abi
-    hd, ha = wrapper("host_denoise", TD.SOURCES), wrapper("host_accumulate", TA.SOURCES)
+    hd, ha = NL.load("host_denoise"), NL.load("host_accumulate")
     hd.hd_check.argtypes = [C.POINTER(abi.Denoise), C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32]
     ha.ha_check.argtypes = [C.POINTER(abi.Accumulate), C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32]
     err = C.create_string_buffer(256)
@@ -95,7 +81,7 @@ def test_every_small_layout_and_the_wrapping_offsets():
     for k in refused:  # the grid reaches every answer of every check
         assert set(refused[k]) == {None, "xstride", "m2_offset", "normals_offset", "samples_offset"}, (k, refused[k])
     # the clamp's film: no normals, m2 optional
-    ho = wrapper("host_outlier_clamp", TO.SOURCES)
+    ho = NL.load("host_outlier_clamp")
     ho.ho_check.argtypes = [C.POINTER(abi.OutlierClamp)] + [C.c_void_p] * 3 + [C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
     c, copy = TO.good(), C.c_int(0)
     assert ho.ho_check(C.byref(c), *TO.FAR, err, 256, C.byref(copy)) == 0
@@ -113,14 +99,8 @@ def test_every_small_layout_and_the_wrapping_offsets():
 def test_the_corner_cases_under_the_sanitizers(tmp_path):
     """host_film_checks.cpp's main() under AddressSanitizer and UBSan: its corner cases get the restatement's answers, and the program ends
     without a report"""
-    exe = str(tmp_path / "host_film_checks_asan")
-    sources = [os.path.join(NATIVE, "host_film_checks.cpp")]
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan"] + HOST_FLAGS + ["-o", exe] + sources,
-                   check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
     index = {None: -1, "xstride": 0, "normals_offset": 1, "m2_offset": 2, "samples_offset": 3}
-    lines = r.stdout.splitlines()
+    lines = NL.run_sanitized(tmp_path, "host_film_checks").splitlines()
     assert len(lines) == 8 * 13 ** 3
     for line in lines:
         xs, n, m2, s, *got = (int(w) for w in line.split())

@@ -4,22 +4,18 @@ tests/native/host_frame_plan.cpp wraps the planner for ctypes; the same source i
 UBSan.  Nothing here reads the C++."""
 import ctypes as C
 import itertools
-import os
-import subprocess
 
 import pytest
 
 import adaptive64
 import frame_cases
-from conftest import ROOT
+import native_lib as NL
+from native_lib import ERR_ARG
 from phosphorus_mk2_amd import abi
-from test_scene_flatten import CSRC, HOST_FLAGS, NATIVE
 
-ERR_ARG = 1
 M = 1 << 20
 NONE = 0xffffffff  # no back-off limit
 AMPLE = 1 << 40
-SOURCES = [os.path.join(NATIVE, "host_frame_plan.cpp"), os.path.join(CSRC, "frame_plan.cpp")]
 
 
 # ---- the rules, restated ----------------------------------------------------------------------------------------------------------------
@@ -127,12 +123,8 @@ class Planner:
 
 @pytest.fixture(scope="module")
 def plan():
-    """tests/native/libhost_frame_plan.so behind a Planner"""
-    so = os.path.join(NATIVE, "libhost_frame_plan.so")
-    hdr = [os.path.join(CSRC, "frame_plan.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + hdr):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
-    return Planner(C.CDLL(so))
+    """the host_frame_plan library behind a Planner"""
+    return Planner(NL.load("host_frame_plan"))
 
 
 # ---- 1. the film's pixel layout ----------------------------------------------------------------------------------------------------------
@@ -321,12 +313,7 @@ def check_line(line):
 def test_the_planner_under_the_sanitizers(tmp_path):
     """host_frame_plan.cpp's own main(): the cases of this file in exactly sized heap arrays, every decision printed; each line is checked
     against the models above, and the program ends without a report."""
-    exe = str(tmp_path / "host_frame_plan_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_FRAME_PLAN_MAIN"] +
-                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
-    lines = r.stdout.splitlines()
+    lines = NL.run_sanitized(tmp_path, "host_frame_plan", "HOST_FRAME_PLAN_MAIN").splitlines()
     assert [sum(l.startswith(w) for l in lines) for w in ("layout", "cap", "passes", "cut")] == [12, 7, 15, 9]
     for line in lines:
         assert check_line(line), line

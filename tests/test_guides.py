@@ -4,21 +4,17 @@ refusal of the argument checks (csrc/guides_check.cpp through tests/native/host_
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import denoise64 as dn
 import guides64 as gd
-from conftest import ROOT, bits_equal
+import native_lib as NL
+from conftest import bits_equal
+from native_lib import ERR_ARG
 
 F, D = np.float32, np.float64
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
-HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off"]
-SOURCES = [os.path.join(NATIVE, "host_guides.cpp"), os.path.join(CSRC, "guides_check.cpp")]
-ERR_ARG = 1
 
 
 # ---- 1. the ABI and the header ------------------------------------------------------------------------------------------------------------
@@ -47,17 +43,14 @@ def test_struct_sizes_are_the_librarys():
 
 
 def test_header_states_the_structs_and_the_rules():
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
-    strip = lambda body: re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    body = strip(re.search(r"typedef struct phx_guides \{(.*?)\} phx_guides;", hdr, re.S).group(1))
-    assert re.findall(r"\b(\w+)(?:\[4\])?;", body) == ["sampler_seed", "samples", "on_device", "reserved"]
-    body = strip(re.search(r"typedef struct phx_denoise_guides \{(.*?)\} phx_denoise_guides;", hdr, re.S).group(1))
-    assert re.findall(r"\b(\w+)(?:\[4\])?;", body) == ["guides", "xstride", "flags", "albedo_floor", "sigma_x", "plane_scale", "reserved"]
+    hdr = NL.header()
+    assert re.findall(r"\b(\w+)(?:\[4\])?;", NL.struct_body("phx_guides")) == ["sampler_seed", "samples", "on_device", "reserved"]
+    assert re.findall(r"\b(\w+)(?:\[4\])?;", NL.struct_body("phx_denoise_guides")) == ["guides", "xstride", "flags", "albedo_floor", "sigma_x", "plane_scale", "reserved"]
     assert re.search(r"enum \{ PHX_GUIDE_DEMODULATE = 1, PHX_GUIDE_PLANE = 2 \};", hdr)
     assert re.search(r"int\s+phx_dev_render_guides\(phx_device\* dev, const phx_guides\* g, float\* film", hdr)
     assert re.search(r"int\s+phx_dev_denoise_guided\(phx_device\* dev, const phx_denoise\* d, const phx_denoise_guides\* g, const float\* film_in, float\* film_out\);", hdr)
     rule = hdr[hdr.index("first-hit guide channels (DESIGN 19)"):hdr.index("typedef struct phx_denoise_guides")]
-    flat = " ".join(rule.replace("*", " ").split())
+    flat = NL.flat(rule)
     for phrase in ["X_c = o_c + t d_c", "albedo_sum_c (1.0f / (float)G)", "(float)hits (1.0f / (float)G)", "X_sum_c / (float)hits, or 0 when hits == 0",
                    "t_sum / (float)hits, or 0 when hits == 0", "contribute (1, 1, 1)", "fp32 without contraction", "in lobe order",
                    "D_c = max((double)albedo_c, (double)albedo_floor)", "C_c = fp32(primary_c / D_c)", "V_c = fp32((m2_c (n / (n - 1))) / (D_c D_c))",
@@ -78,28 +71,15 @@ def test_plane_scale_is_the_cameras_pixel():
 # ---- 2. the refusals ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def check():
-    """tests/native/libhost_guides.so -> (check of phx_guides, check of phx_denoise_guides), each -> (status, message)"""
+    """the host_guides library -> (check of phx_guides, check of phx_denoise_guides), each -> (status, message)"""
     from phosphorus_mk2_amd import abi
-    so = os.path.join(NATIVE, "libhost_guides.so")
-    hdr = [os.path.join(CSRC, "guides_check.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + hdr):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
-    lib = C.CDLL(so)
-    lib.hg_check_guides.argtypes = [C.POINTER(abi.Guides), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_char_p, C.c_uint32]; lib.hg_check_guides.restype = C.c_int
-    lib.hg_check_denoise_guides.argtypes = [C.POINTER(abi.Denoise), C.POINTER(abi.DenoiseGuides), C.c_char_p, C.c_uint32]; lib.hg_check_denoise_guides.restype = C.c_int
+    lib = NL.load("host_guides")
+    check_guides = NL.checker(lib, "hg_check_guides", [C.POINTER(abi.Guides), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p])
+    check_denoise_guides = NL.checker(lib, "hg_check_denoise_guides", [C.POINTER(abi.Denoise), C.POINTER(abi.DenoiseGuides)])
     lib.hg_sizeof_guides.restype = lib.hg_sizeof_denoise_guides.restype = C.c_uint32
     assert lib.hg_sizeof_guides() == C.sizeof(abi.Guides) and lib.hg_sizeof_denoise_guides() == C.sizeof(abi.DenoiseGuides)
-
-    def guides(g, width=64, height=48, spp=16, film=0x10000):
-        err = C.create_string_buffer(256)
-        rc = lib.hg_check_guides(C.byref(g), width, height, spp, film, err, 256)
-        return rc, err.value.decode()
-
-    def denoise_guides(d, g):
-        err = C.create_string_buffer(256)
-        rc = lib.hg_check_denoise_guides(C.byref(d), C.byref(g), err, 256)
-        return rc, err.value.decode()
-    return guides, denoise_guides
+    guides = lambda g, width=64, height=48, spp=16, film=0x10000: check_guides(C.byref(g), width, height, spp, film)
+    return guides, lambda d, g: check_denoise_guides(C.byref(d), C.byref(g))
 
 
 def good_guides(**kw):
@@ -137,7 +117,7 @@ D_REFUSED = [("flags", dict(flags=4)), ("flags", dict(flags=0x80000001)), ("xstr
              ("sigma_x", dict(sigma_x=0.0)), ("sigma_x", dict(sigma_x=-1.0)), ("sigma_x", dict(sigma_x=NAN)), ("sigma_x", dict(sigma_x=INF)),
              ("plane_scale", dict(plane_scale=0.0)), ("plane_scale", dict(plane_scale=-1.0)), ("plane_scale", dict(plane_scale=NAN)),
              ("plane_scale", dict(flags=2, plane_scale=INF)), ("guides", dict(guides=0))]
-ids = lambda cases: [",".join(f"{k}={v}" for k, v in kw.items()) or "defaults" for kw in cases]
+ids = NL.case_ids
 
 
 @pytest.mark.parametrize("kw", G_ACCEPTED, ids=ids(G_ACCEPTED))
@@ -193,12 +173,8 @@ def test_denoise_guides_check_refuses_reserved_words_and_plane_without_normals(c
 
 def test_the_checks_under_the_sanitizers(tmp_path):
     """host_guides.cpp's own main() under AddressSanitizer and UBSan: its cases get the answers above, and the program ends without a report"""
-    exe = str(tmp_path / "host_guides_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_GUIDES_MAIN"] +
-                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
-    got = {l.split()[0]: (int(l.split()[1]), l) for l in r.stdout.splitlines()}
+    stdout = NL.run_sanitized(tmp_path, "host_guides", "HOST_GUIDES_MAIN")
+    got = {l.split()[0]: (int(l.split()[1]), l) for l in stdout.splitlines()}
     want = {"good": None, "all-samples": None, "no-samples": "samples", "samples-past-spp": "samples", "samples-wrap": "samples", "on-device": "on_device",
             "reserved": "reserved", "null-film": "film", "d-good": None, "d-flags": "flags", "d-plane-without-normals": "normals_offset",
             "d-demodulate-without-normals": None, "d-xstride": "xstride", "d-floor-zero": "albedo_floor", "d-floor-nan": "albedo_floor", "d-floor-unused": None,

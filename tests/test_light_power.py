@@ -4,21 +4,19 @@ sums by np.cumsum, fp32 elsewhere; tests/test_gpu_light_power.py holds the devic
 flatten_scene against the restatement through tests/native/host_flatten_power.cpp, and the variance model of the seven-lamp film."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import native_lib as NL
 from phosphorus_mk2_amd import abi, scenes
 from test_analytic_direct_light import H_LAMP, LE, RHO, SPP
 from test_emission_textures import light_corner_uvs, sample_st
 from test_gpu_textures import np_lookup
 from test_light_sampling import (LE2, STRIPS, G_rect, LightTable, _camera, _floor, edge_draws, floor_points, moments, pick_by_area, rect_nodes, rects_mesh,
                                  striped_scene, two_lamp_scene)
-from test_scene_flatten import ARRAYS, CSRC, HOST_FLAGS, NATIVE, SC_LIGHTS_BY_AREA, WORDS, _rocm_include
+from test_scene_flatten import ARRAYS, SC_LIGHTS_BY_AREA, WORDS
 
 F = np.float32
 D = np.float64
@@ -30,7 +28,7 @@ AREA_POWER = abi.LIGHTS_BY_AREA | 0x100
 # ---- (a) ABI and Python ---------------------------------------------------------------------------------------------------------------------
 def test_abi_light_selection():
     from phosphorus_mk2_amd import xpu
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
+    hdr = NL.header()
     m = re.search(r"\bPHX_LIGHT_SELECT_BY_POWER\s*=\s*(0x[0-9a-fA-F]+|\d+)", hdr)
     assert m and int(m.group(1), 0) == abi.LIGHT_SELECT_BY_POWER == 0x100
     assert float(re.search(r"#define\s+PHX_LIGHT_POWER_FLOOR\s+([0-9.]+)", hdr).group(1)) == PHI
@@ -272,14 +270,8 @@ def test_lamp_showroom_is_one_lamp_and_sixty_four_leds():
 # ---- (d) flatten_scene ----------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def flat_power():
-    """tests/native/libhost_flatten_power.so: test_scene_flatten's flatten() plus the selection table ("light_pcdf")"""
-    so = os.path.join(NATIVE, "libhost_flatten_power.so")
-    src = [os.path.join(NATIVE, "host_flatten_power.cpp"), os.path.join(CSRC, "scene_flatten.cpp")]
-    dep = src + [os.path.join(NATIVE, "host_flatten.cpp"), os.path.join(ROOT, "include", "phx_xpu.h")] + [os.path.join(CSRC, h) for h in
-                                                                                                          ("scene_flatten.h", "kernels.h", "bsdf.h", "bvh8.h", "phx_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in dep):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-I", _rocm_include()] + HOST_FLAGS + ["-o", so] + src, check=True)
-    lib = C.CDLL(so)
+    """the host_flatten_power library: test_scene_flatten's flatten() plus the selection table ("light_pcdf")"""
+    lib = NL.load("host_flatten_power")
     lib.hf_flatten.restype = C.c_void_p; lib.hf_flatten.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Options)]
     lib.hf_free.argtypes = [C.c_void_p]
     lib.hf_status.argtypes = [C.c_void_p]

@@ -10,14 +10,13 @@ Every case states what the REFERENCE arithmetic yields for it (the -0, the tie, 
 on its edge fails as such.  The reference arithmetic is restated here in float32 with a correctly rounded fma; mt_intersect runs through
 tests/native/host_mt_accept.cpp, compiled on first use."""
 import ctypes as C
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import native_lib as NL
+
 F = np.float32
 EPS = F(0.00000001)
 FLT_MAX = np.finfo(np.float32).max
@@ -29,12 +28,7 @@ down = lambda x: np.nextafter(F(x), F(-np.inf))
 
 @pytest.fixture(scope="module")
 def shim():
-    d = os.path.join(ROOT, "tests", "native")
-    so, src = os.path.join(d, "libhost_mt_accept.so"), os.path.join(d, "host_mt_accept.cpp")
-    hdr = [os.path.join(ROOT, "phosphorus_mk2_amd", "csrc", h) for h in ("bvh8.h", "phx_math.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in [src] + hdr):
-        subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-march=haswell", "-mfma", "-ffp-contract=off", "-o", so, src], check=True)
-    lib = C.CDLL(so)
+    lib = NL.load("host_mt_accept")
     f32p, u32p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
     lib.hmt_accept.argtypes = [C.c_uint32, f32p, u32p, f32p, f32p, f32p, u32p, u8p, f32p, f32p, f32p]
     lib.hmt_accept.restype = None

@@ -8,21 +8,16 @@ import itertools
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import native_lib as NL
 import outlier_clamp64 as oc
 import outlier_clamp_cases as OC
-from conftest import ROOT
+from native_lib import ERR_ARG
 
 F, D = np.float32, np.float64
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
-HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off"]
-SOURCES = [os.path.join(NATIVE, "host_outlier_clamp.cpp"), os.path.join(CSRC, "outlier_clamp_check.cpp")]
-ERR_ARG = 1
 FIELDS = ["width", "height", "xstride_a", "m2_offset_a", "samples_offset_a", "xstride_b", "on_device", "flags", "radius", "trim", "min_taps", "gamma", "floor",
           "clamped_history", "reserved"]
 SUMMARY = ["pixels", "skipped", "unbounded", "inside", "clamped", "capped"]
@@ -53,9 +48,8 @@ def test_struct_size_is_the_librarys():
 
 
 def test_header_states_the_struct_and_the_rule():
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
-    body = re.search(r"typedef struct phx_outlier_clamp \{(.*?)\} phx_outlier_clamp;", hdr, re.S).group(1)
-    names = re.findall(r"\b(\w+)(?:\[2\])?\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    hdr = NL.header()
+    names = re.findall(r"\b(\w+)(?:\[2\])?\s*[,;]", NL.struct_body("phx_outlier_clamp"))
     assert names == FIELDS
     assert re.search(r"uint64_t\s+pixels,\s*skipped,\s*unbounded,\s*inside,\s*clamped,\s*capped;\s*\} phx_outlier_clamp_summary;", hdr)
     assert re.search(r"enum \{ PHX_OUTLIER_EXCLUDE_CENTRE = 1, PHX_OUTLIER_UPPER_ONLY = 2 \};", hdr)
@@ -63,7 +57,7 @@ def test_header_states_the_struct_and_the_rule():
                      r"\s+phx_outlier_clamp_summary\* summary", hdr)
     assert re.search(r"int\s+phx_dev_outlier_clamp_times\(const phx_device\* dev, double\* ms", hdr)
     rule = hdr[hdr.index("the outlier clamp (DESIGN 23)"):hdr.index("typedef struct phx_outlier_clamp {")]
-    flat = " ".join(rule.replace("*", " ").split())
+    flat = NL.flat(rule)
     for phrase in ["binary64, without contraction", "dy = -r .. r outer, dx = -r .. r inner", "l_q = (0.2126 R + 0.7152 G) + 0.0722 B",
                    "among equals the earlier one in tap order", "k < min_taps", "sums starting at 0.0", "mu = (sum of B_q,c) / k",
                    "s = (sum of (B_q,c - mu) (B_q,c - mu)) / k", "w = gamma sqrt(s) + floor", "hi = mu + w; lo = mu - w", "A'_c = fp32(hi)",
@@ -108,12 +102,8 @@ def test_film_layout_is_the_layout_film_has():
 @pytest.fixture(scope="module")
 def host():
     from phosphorus_mk2_amd import abi
-    so = os.path.join(NATIVE, "libhost_outlier_clamp.so")
-    hdr = [os.path.join(CSRC, "outlier_clamp_check.h"), os.path.join(CSRC, "film_checks.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + hdr):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
-    lib = C.CDLL(so)
-    lib.ho_check.argtypes = [C.POINTER(abi.OutlierClamp)] + [C.c_void_p] * 3 + [C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]; lib.ho_check.restype = C.c_int
+    lib = NL.load("host_outlier_clamp")
+    lib.check = NL.checker(lib, "ho_check", [C.POINTER(abi.OutlierClamp)] + [C.c_void_p] * 3, extra=[C.POINTER(C.c_int)])
     lib.ho_sizeof.restype = C.c_uint32; lib.ho_sizeof_summary.restype = C.c_uint32
     assert lib.ho_sizeof() == C.sizeof(abi.OutlierClamp) and lib.ho_sizeof_summary() == C.sizeof(abi.OutlierClampSummary)
     return lib
@@ -125,9 +115,9 @@ FAR = (1 << 40, 2 << 40, 3 << 40)  # film, ref, film_out far apart: the largest 
 @pytest.fixture(scope="module")
 def check(host):
     def run(q, ptrs=FAR, copy=False):
-        err, cp = C.create_string_buffer(256), C.c_int(-1)
-        rc = host.ho_check(C.byref(q), *ptrs, err, 256, C.byref(cp))
-        return (rc, err.value.decode(), cp.value) if copy else (rc, err.value.decode())
+        cp = C.c_int(-1)
+        rc, msg = host.check(C.byref(q), *ptrs, C.byref(cp))
+        return (rc, msg, cp.value) if copy else (rc, msg)
     return run
 
 
@@ -158,16 +148,12 @@ REFUSED = [("width", dict(width=0)), ("width", dict(width=65537)), ("height", di
            ("floor", dict(floor=INF)), ("clamped_history", dict(samples_offset_a=0, clamped_history=1))]
 
 
-def ident(kw):
-    return ",".join(f"{k}={v}" for k, v in kw.items()) or "defaults"
-
-
-@pytest.mark.parametrize("kw", ACCEPTED, ids=[ident(kw) for kw in ACCEPTED])
+@pytest.mark.parametrize("kw", ACCEPTED, ids=NL.case_ids(ACCEPTED))
 def test_check_accepts(check, kw):
     assert check(good(**kw)) == (0, "")
 
 
-@pytest.mark.parametrize("field,kw", REFUSED, ids=[ident(kw) for _, kw in REFUSED])
+@pytest.mark.parametrize("field,kw", REFUSED, ids=NL.case_ids(kw for _, kw in REFUSED))
 def test_check_refuses_and_names_the_field(check, field, kw):
     rc, msg = check(good(**kw))
     assert rc == ERR_ARG and msg == f"outlier_clamp: {field} is outside its range (phx_outlier_clamp)", (rc, msg)
@@ -224,12 +210,8 @@ def test_every_way_two_films_can_share_a_byte(check):
 
 def test_the_check_under_the_sanitizers(tmp_path):
     """host_outlier_clamp.cpp's own main() under AddressSanitizer and UBSan: its cases get the answers above, and the program ends without a report"""
-    exe = str(tmp_path / "host_outlier_clamp_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_OUTLIER_CLAMP_MAIN"] +
-                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
-    got = {l.split()[0]: (int(l.split()[1]), int(l.split()[2]), l) for l in r.stdout.splitlines()}
+    stdout = NL.run_sanitized(tmp_path, "host_outlier_clamp", "HOST_OUTLIER_CLAMP_MAIN")
+    got = {l.split()[0]: (int(l.split()[1]), int(l.split()[2]), l) for l in stdout.splitlines()}
     want = {"good": (None, 0), "in-place": (None, 0), "self": (None, 0), "self-in-place": (None, 1), "out-is-ref": (None, 1),
             "ref-overlaps-film": ("ref", 0), "out-overlaps-film": ("film_out", 0), "out-overlaps-ref": ("film_out", 0), "null-film": ("film", 0),
             "null-ref": ("ref", 0), "null-out": ("film_out", 0), "self-other-stride": ("ref", 0), "width": ("width", 0), "height": ("height", 0),

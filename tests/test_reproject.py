@@ -7,21 +7,16 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import native_lib as NL
 import reproject64 as rp
 import reproject_cases as RC
-from conftest import ROOT
+from native_lib import ERR_ARG
 
 F, D = np.float32, np.float64
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
-HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off"]
-SOURCES = [os.path.join(NATIVE, "host_reproject.cpp"), os.path.join(CSRC, "reproject_check.cpp")]
-ERR_ARG = 1
 FIELDS = ["width", "height", "xstride_a", "normals_offset_a", "m2_offset_a", "samples_offset_a", "xstride_g", "on_device", "from", "to",
           "sigma_plane", "sigma_dist", "max_history", "reserved"]
 
@@ -50,9 +45,8 @@ def test_struct_size_is_the_librarys():
 
 
 def test_header_states_the_struct_and_the_rule():
-    hdr = open(os.path.join(ROOT, "include", "phx_xpu.h")).read()
-    body = re.search(r"typedef struct phx_reproject \{(.*?)\} phx_reproject;", hdr, re.S).group(1)
-    names = re.findall(r"\b(\w+)(?:\[3\])?\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    hdr = NL.header()
+    names = re.findall(r"\b(\w+)(?:\[3\])?\s*[,;]", NL.struct_body("phx_reproject"))
     assert names == FIELDS
     assert re.search(r"uint64_t\s+pixels,\s*reused,\s*no_geometry,\s*disoccluded,\s*samples;\s*\} phx_reproject_summary;", hdr)
     assert re.search(r"int\s+phx_dev_set_camera\(phx_device\* dev, const phx_camera\* camera\)", hdr)
@@ -60,7 +54,7 @@ def test_header_states_the_struct_and_the_rule():
                      r"const float\* guides_to,\s+float\* acc_to, phx_reproject_summary\* summary", hdr)
     assert re.search(r"int\s+phx_dev_reproject_times\(const phx_device\* dev, double\* ms", hdr)
     rule = hdr[hdr.index("reprojection (DESIGN 22)"):hdr.index("typedef struct phx_reproject {")]
-    flat = " ".join(rule.replace("*", " ").split())
+    flat = NL.flat(rule)
     for phrase in ["A = e k - f h", "det = (a A + b B) + c C", "zoom = 1.12 tan((double)fov 0.5)", "c_j = (D_x I_0j + D_y I_1j) + D_z I_2j",
                    "fx = ((c_x / t) / (ratio zoom) + 0.5) W", "fy = (0.5 - (c_y / t) / zoom) H", "sx = x + (fx_from - fx_to)", "x0 = floor(sx)",
                    "tol = plane_scale_from distance_q", "fabs(r) <= sigma_plane tol", "dd <= lim lim", "u_i = w_i / Wsum",
@@ -93,12 +87,8 @@ def test_python_settings_are_the_accumulators_layout():
 @pytest.fixture(scope="module")
 def host():
     from phosphorus_mk2_amd import abi
-    so = os.path.join(NATIVE, "libhost_reproject.so")
-    hdr = [os.path.join(CSRC, "reproject_check.h"), os.path.join(CSRC, "film_checks.h"), os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SOURCES + hdr):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so] + SOURCES, check=True)
-    lib = C.CDLL(so)
-    lib.hr_check.argtypes = [C.POINTER(abi.Reproject)] + [C.c_void_p] * 4 + [C.c_char_p, C.c_uint32]; lib.hr_check.restype = C.c_int
+    lib = NL.load("host_reproject")
+    lib.check = NL.checker(lib, "hr_check", [C.POINTER(abi.Reproject)] + [C.c_void_p] * 4)
     lib.hr_camera.argtypes = [C.POINTER(abi.Camera), C.POINTER(C.c_double)]; lib.hr_camera.restype = C.c_int
     lib.hr_sizeof.restype = C.c_uint32; lib.hr_sizeof_summary.restype = C.c_uint32
     assert lib.hr_sizeof() == C.sizeof(abi.Reproject) and lib.hr_sizeof_summary() == C.sizeof(abi.ReprojectSummary)
@@ -110,11 +100,7 @@ FAR = (0x10000, 1 << 40, 2 << 40, 3 << 40)  # far apart: the largest film is 2^3
 
 @pytest.fixture(scope="module")
 def check(host):
-    def run(q, ptrs=FAR):
-        err = C.create_string_buffer(256)
-        rc = host.hr_check(C.byref(q), *ptrs, err, 256)
-        return rc, err.value.decode()
-    return run
+    return lambda q, ptrs=FAR: host.check(C.byref(q), *ptrs)
 
 
 def good(cam=None, **kw):
@@ -153,12 +139,12 @@ REFUSED_CAMERAS = [("film_width", 63), ("film_height", 49), ("fov", NAN), ("fov"
                    ("to_world", {4: 1.0, 5: 0.0, 6: 0.0})]
 
 
-@pytest.mark.parametrize("kw", ACCEPTED, ids=[",".join(f"{k}={v}" for k, v in kw.items()) or "defaults" for kw in ACCEPTED])
+@pytest.mark.parametrize("kw", ACCEPTED, ids=NL.case_ids(ACCEPTED))
 def test_check_accepts(check, kw):
     assert check(good(**kw)) == (0, "")
 
 
-@pytest.mark.parametrize("field,kw", REFUSED, ids=[",".join(f"{k}={v}" for k, v in kw.items()) for _, kw in REFUSED])
+@pytest.mark.parametrize("field,kw", REFUSED, ids=NL.case_ids(kw for _, kw in REFUSED))
 def test_check_refuses_and_names_the_field(check, field, kw):
     rc, msg = check(good(**kw))
     assert rc == ERR_ARG and msg == f"reproject: {field} is outside its range (phx_reproject)", (rc, msg)
@@ -220,12 +206,8 @@ def test_check_refuses_reserved_words_and_bad_films(check):
 
 def test_the_check_under_the_sanitizers(tmp_path):
     """host_reproject.cpp's own main() under AddressSanitizer and UBSan: its cases get the answers above, and the program ends without a report"""
-    exe = str(tmp_path / "host_reproject_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_REPROJECT_MAIN"] +
-                   HOST_FLAGS + ["-o", exe] + SOURCES, check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and r.stderr == "", (r.stdout[-2000:], r.stderr[-2000:])
-    got = {l.split()[0]: (int(l.split()[1]), l) for l in r.stdout.splitlines()}
+    stdout = NL.run_sanitized(tmp_path, "host_reproject", "HOST_REPROJECT_MAIN")
+    got = {l.split()[0]: (int(l.split()[1]), l) for l in stdout.splitlines()}
     want = {"good": None, "same": "acc_to", "overlap-guides-from": "acc_to", "overlap-guides-to": "acc_to", "null-acc-from": "acc_from",
             "null-guides-from": "guides_from", "null-guides-to": "guides_to", "null-acc-to": "acc_to", "width": "width", "height": "height",
             "xstride-a": "xstride_a", "m2-wrap": "m2_offset_a", "no-normals": "normals_offset_a", "no-samples": "samples_offset_a", "xstride-g": "xstride_g",

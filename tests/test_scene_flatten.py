@@ -4,21 +4,17 @@ of tests/test_light_sampling.py, and the scene classification that selects the s
 function for ctypes; the same source is a stand-alone program for a run under AddressSanitizer / UBSan."""
 import copy
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, tri_abc
+import native_lib as NL
+from conftest import tri_abc
+from native_lib import ERR_ARG
 from phosphorus_mk2_amd import abi, scenes
 from test_light_sampling import LightTable, striped_scene, two_lamp_scene
 
 F = np.float32
-ERR_ARG = 1
-NATIVE = os.path.join(ROOT, "tests", "native")
-CSRC = os.path.join(ROOT, "phosphorus_mk2_amd", "csrc")
-HOST_FLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-D__HIP_PLATFORM_AMD__", "-ffp-contract=off"]
 SC_TEX_LOBES, SC_TEX_ENV, SC_TEX_MASK, SC_LIGHTS_BY_AREA = 1, 2, 4, 8  # kernels.h: DevScene::any_tex
 LIGHT = np.dtype([("first_tri", "<u4"), ("num_tris", "<u4"), ("area", "<f4"), ("material", "<u4"), ("lpdf", "<f4"), ("e", "<f4", 3)])
 LIGHT_TRI = np.dtype([("abc", "<f4", 9), ("n", "<f4", 3), ("prim", "<u4"), ("smooth", "<u4"), ("mesh_mat", "<u4"), ("face", "<u4")])
@@ -28,19 +24,10 @@ ARRAYS = {"abc": (0, F), "prim_material": (1, np.uint32), "prim_normals": (2, F)
 WORDS = {"any_smooth": 0, "any_tex": 1, "diffuse_only": 2, "any_per_hit": 3, "num_lights": 4, "env_tex": 5, "num_materials": 6}
 
 
-def _rocm_include():
-    return os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
-
-
 @pytest.fixture(scope="module")
 def flat():
-    """tests/native/libhost_flatten.so, and flatten(scene, light_sampling, tweak) -> the status, the message and every array as numpy"""
-    so = os.path.join(NATIVE, "libhost_flatten.so")
-    src = [os.path.join(NATIVE, "host_flatten.cpp"), os.path.join(CSRC, "scene_flatten.cpp")]
-    hdr = [os.path.join(CSRC, h) for h in ("scene_flatten.h", "kernels.h", "bsdf.h", "bvh8.h", "phx_math.h")] + [os.path.join(ROOT, "include", "phx_xpu.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src + hdr):
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-I", _rocm_include()] + HOST_FLAGS + ["-o", so] + src, check=True)
-    lib = C.CDLL(so)
+    """the host_flatten library, and flatten(scene, light_sampling, tweak) -> the status, the message and every array as numpy"""
+    lib = NL.load("host_flatten")
     lib.hf_flatten.restype = C.c_void_p; lib.hf_flatten.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.Options)]
     lib.hf_free.argtypes = [C.c_void_p]
     lib.hf_status.argtypes = [C.c_void_p]
@@ -383,9 +370,5 @@ def test_scene_classification(flat):
 def test_out_of_range_indices_are_refused_before_they_are_used(tmp_path):
     """host_flatten.cpp's own main(): a good scene and one per index family with the bad index at the last face, in arrays of exactly
     their size.  A check that came after the read would stop the program with a sanitizer report."""
-    exe = str(tmp_path / "host_flatten_asan")
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-static-libasan", "-static-libubsan", "-DHOST_FLATTEN_MAIN", "-I", _rocm_include()] + HOST_FLAGS +
-                   ["-o", exe, os.path.join(NATIVE, "host_flatten.cpp"), os.path.join(CSRC, "scene_flatten.cpp")], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
-    assert r.stdout.split() == ["good", "0", "as-expected"] + [w for name in ("face", "vertex", "normal", "uv", "material") for w in (name, "1", "as-expected")]
+    stdout = NL.run_sanitized(tmp_path, "host_flatten", "HOST_FLATTEN_MAIN")
+    assert stdout.split() == ["good", "0", "as-expected"] + [w for name in ("face", "vertex", "normal", "uv", "material") for w in (name, "1", "as-expected")]
