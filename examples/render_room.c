@@ -3,7 +3,7 @@
  * Python, no C++ and no torch in the process.  Renders a small room (floor, back wall, emissive ceiling panel, two
  * tilted triangles) and writes the raw fp32 film (H x W x 4) to argv[1].
  *   make -C examples
- *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K] [display [auto]] [despeckle] [orbit K [clamp]]
+ *   ./render_room film.f32 [host-bvh|device-bvh|auto-bvh] [N] [area-lights|power-lights|sample-environment] [error-estimate] [adaptive TAU] [denoise|denoise-guided] [progressive K [tiles TAU]] [display [auto]] [despeckle] [orbit K [clamp]]
  * area-lights (anywhere behind the film's name): next-event estimation picks a light's triangle by area (PHX_LIGHTS_BY_AREA) instead of by
  * index as the reference does; the room's panel is two equal triangles, so the film is the same.
  * power-lights: that, and the light itself by power instead of uniformly (PHX_LIGHTS_BY_AREA | PHX_LIGHT_SELECT_BY_POWER); the room has one
@@ -23,6 +23,10 @@
  * progressive K: K frames of 8 samples at seeds 7, 8, ... are pooled into one accumulator film (phx_dev_film_accumulate: primary rgba, m2 rgb, samples),
  * each frame carrying the error estimate; after every frame the host prints the call's summary (the samples pooled so far and the pixels whose
  * standard error is at most 0.05 * (|value| + 0.01)).  The accumulator is what the later steps (denoise) see and what is written.
+ * progressive K tiles TAU: the same, but from the second frame on a frame renders only the 32 x 32 tiles that phx_dev_film_tile_map of the
+ * accumulator leaves open at the threshold TAU (floor 0.01), through a queue of phx_tiles_make_list; the frame films carry "samples", so the
+ * pooling leaves the pixels of a tile that was not rendered alone.  Per frame the host prints `tiles: frame k open O of T rendered P pixels`,
+ * and it stops early once no tile is open.
  * display [auto]: after every other step the film at hand goes through the display pass (phx_dev_film_display: exposure 1, or with `auto` taken from
  * the film's own luminance histogram so that its logarithmic mean between the 50th and 95th percentile lands on 0.18; the ACES curve, the sRGB
  * transfer function, ordered dither) and the 8-bit image is written to argv[1] + ".ppm"; the host prints the scale and the call's counters.
@@ -194,7 +198,8 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0, orbit_cameras = 0, orbit_clamp = 0, despeckle = 0;
+  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0, orbit_cameras = 0, orbit_clamp = 0, despeckle = 0, tile_stop = 0;
+  float tile_tau = 0.0f;
   phx_adaptive ad;
   memset(&ad, 0, sizeof(ad));
   for (int i = 2; i < argc; ++i)
@@ -206,8 +211,10 @@ int main(int argc, char** argv) {
     } else if (strcmp(argv[i], "progressive") == 0 && i + 1 < argc) {
       progressive = atoi(argv[i + 1]);
       if (progressive < 1 || progressive > 1024) progressive = 1;
-      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
-      argc -= 2; --i;
+      const int take = i + 3 < argc && strcmp(argv[i + 2], "tiles") == 0 ? 4 : 2;  /* the keyword, its number and, optionally, `tiles TAU` */
+      if (take == 4) { tile_stop = 1; tile_tau = (float)atof(argv[i + 3]); }
+      for (int k = i; k + take < argc; ++k) argv[k] = argv[k + take];
+      argc -= take; --i;
     } else if (strcmp(argv[i], "orbit") == 0 && i + 1 < argc) {
       orbit_cameras = atoi(argv[i + 1]);
       if (orbit_cameras < 1 || orbit_cameras > 1024) orbit_cameras = 1;
@@ -269,7 +276,15 @@ int main(int argc, char** argv) {
     if (!devs[i]) return fail("phx_dev_make");
     if (phx_dev_preprocess(devs[i], &scene) != PHX_OK) return fail("phx_dev_preprocess"); /* every device holds its own copy + BVH */
     if (adaptive && phx_dev_set_adaptive(devs[i], &ad) != PHX_OK) return fail("phx_dev_set_adaptive"); /* the setting is the device's, not the frame's */
+    if (tile_stop && !adaptive) { /* frames over a tile subset: their films carry "samples", 0 in a pixel no tile covered.  One round that ends at spp: no decision is ever taken */
+      phx_adaptive mark;
+      memset(&mark, 0, sizeof(mark));
+      mark.threshold = 0.0f; mark.floor = 0.0f; mark.min_samples = opt.samples_per_pixel > 2 ? opt.samples_per_pixel : 2; mark.step = 1;
+      if (phx_dev_set_adaptive(devs[i], &mark) != PHX_OK) return fail("phx_dev_set_adaptive");
+    }
   }
+  if (tile_stop && despeckle) { fprintf(stderr, "despeckle cannot be combined with progressive K tiles TAU: the clamp would read unrendered tiles as taps\n"); return 1; }
+  const int samples_channel = adaptive || tile_stop; /* the frame film carries the channel "samples" at float 7 */
 
   if (orbit_cameras) { /* a path of cameras on the first device, in place of the one frame below */
     const int rc = argc > 1 ? orbit(devs[0], &scene, &opt, orbit_cameras, orbit_clamp, argv[1]) : 1;
@@ -277,8 +292,8 @@ int main(int argc, char** argv) {
     return rc;
   }
   if (adaptive || denoise || progressive || despeckle) error_estimate = 1; /* the stopping rule, the denoiser and the pooling read the estimate: such a frame must carry it */
-  int has_samples = adaptive; /* the film at hand carries the channel "samples" at float 7 */
-  size_t xstride = 4 + (error_estimate ? 3 : 0) + (adaptive ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */
+  int has_samples = samples_channel; /* the film at hand carries the channel "samples" at float 7 */
+  size_t xstride = 4 + (error_estimate ? 3 : 0) + (samples_channel ? 1 : 0); /* primary rgba [, m2 rgb [, samples]] */
   float* film = (float*)calloc((size_t)W * H * xstride, sizeof(float));
   phx_tiles* tiles = phx_tiles_make(W, H, 32, 0, 1); /* ONE job::tiles_t for all devices */
   phx_frame frame;
@@ -330,24 +345,52 @@ int main(int argc, char** argv) {
     phx_accumulate pa;
     memset(&pa, 0, sizeof(pa));
     pa.width = W; pa.height = H; pa.xstride_a = (uint32_t)xa; pa.m2_offset_a = 4; pa.samples_offset_a = 7;
-    pa.xstride_b = (uint32_t)xstride; pa.m2_offset_b = 4; pa.samples_offset_b = adaptive ? 7 : 0; pa.spp_b = opt.samples_per_pixel;
+    pa.xstride_b = (uint32_t)xstride; pa.m2_offset_b = 4; pa.samples_offset_b = samples_channel ? 7 : 0; pa.spp_b = opt.samples_per_pixel;
     pa.tau = 0.05f; pa.floor = 0.01f;
+    /* tiles TAU: from the second frame on a frame renders only the tiles the tile map of the accumulator leaves open */
+    phx_tile_map tm;
+    memset(&tm, 0, sizeof(tm));
+    tm.width = W; tm.height = H; tm.xstride = (uint32_t)xa; tm.m2_offset = 4; tm.samples_offset = 7; tm.tile_width = tm.tile_height = 32;
+    tm.tau = tile_tau; tm.floor = pa.floor;
+    const uint32_t num_records = ((W + 31u) / 32u) * ((H + 31u) / 32u);
+    phx_tile_record* records = (phx_tile_record*)calloc(num_records, sizeof(phx_tile_record));
+    phx_tile* open_list = (phx_tile*)calloc(num_records, sizeof(phx_tile));
+    if (!records || !open_list) return 1;
+    if (tile_stop) printf("tiles: frame 1 open %u of %u rendered %llu pixels\n", num_records, num_records, (unsigned long long)W * H);
     for (int k = 0; k < progressive; ++k) {
       if (k > 0) { /* the next frame: the same film and queue, a NEW seed (the same seed would be the same samples again) */
         memset(film, 0, (size_t)W * H * xstride * sizeof(float));
         phx_tiles_reset(tiles);
+        phx_tiles* open_queue = NULL;
+        if (tile_stop) {
+          phx_tile_map_summary ts;
+          if (phx_dev_film_tile_map(devs[0], &tm, acc, records, &ts) != PHX_OK) return fail("phx_dev_film_tile_map");
+          uint32_t open = 0; unsigned long long rendered = 0;
+          for (uint32_t r = 0; r < num_records; ++r)
+            if (records[r].converged < records[r].tile.w * records[r].tile.h - records[r].invalid || records[r].starved > 0) {
+              open_list[open++] = records[r].tile; rendered += (unsigned long long)records[r].tile.w * records[r].tile.h;
+            }
+          if ((uint64_t)open != ts.open) { fprintf(stderr, "the tile map's summary counts %llu open tiles, its records %u\n", (unsigned long long)ts.open, open); return 1; }
+          printf("tiles: frame %d open %u of %u rendered %llu pixels\n", k + 1, open, num_records, rendered);
+          if (open == 0) break; /* every tile has converged */
+          open_queue = phx_tiles_make_list(open_list, open);
+          if (!open_queue) return fail("phx_tiles_make_list");
+          frame.tiles_user = open_queue;
+        }
         frame.sampler_seed = 7 + (uint64_t)k;
         for (int i = 0; i < num_devices; ++i)
           if (phx_dev_start(devs[i], &frame) != PHX_OK) return fail("phx_dev_start");
         for (int i = 0; i < num_devices; ++i)
           if (phx_dev_join(devs[i]) != PHX_OK) return fail("phx_dev_join");
         if (despeckle && despeckle_film(devs[0], film, xstride, adaptive, k + 1)) return 1;
+        if (open_queue) { phx_tiles_free(open_queue); frame.tiles_user = tiles; }
       }
       phx_accumulate_summary ps;
       if (phx_dev_film_accumulate(devs[0], &pa, acc, film, &ps) != PHX_OK) return fail("phx_dev_film_accumulate");
       printf("progressive: frame %d seed %llu samples %llu converged %llu of %llu invalid %llu\n", k + 1, (unsigned long long)frame.sampler_seed,
              (unsigned long long)ps.samples, (unsigned long long)ps.converged, (unsigned long long)ps.pixels, (unsigned long long)ps.invalid);
     }
+    free(records); free(open_list);
     free(film);
     film = acc; xstride = xa; has_samples = 1;
   }

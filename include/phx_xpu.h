@@ -559,6 +559,52 @@ typedef struct phx_accumulate_summary {
   uint64_t pixels, invalid, converged, samples;
 } phx_accumulate_summary;
 
+/* ---- the tile map: an accumulator film -> one convergence record per tile, so that a frame can leave converged tiles out ----- */
+/* A pass of its own beside the frame (phx_dev_film_tile_map): it reads an accumulator film (phx_accumulate's acc: "primary", "m2" and
+ * "samples" are read, 7 floats a pixel; normals and every other float of a pixel are not), launches none of the frame's kernels and changes
+ * no film.  It writes one phx_tile_record per tile of a grid over the film:
+ *     tx = ceil(width / tile_width)      ty = ceil(height / tile_height)
+ *     record j * tx + i covers x in [i * tile_width, min((i + 1) * tile_width, width)) and y in [j * tile_height, min((j + 1) * tile_height, height))
+ *   rows run top to bottom and tiles left to right: for tile_width == tile_height this is the list phx_tiles_make(width, height, tile_size,
+ *   0, 1) produces, in its order; the ragged edge tiles are the narrower ones.  record.tile is usable as a frame's tile as it is.
+ * Per pixel, in binary64, without contraction, in the order written, fp32 inputs widened first; V_c its primary, m_c its m2, n = (double)samples:
+ *     valid      all six floats finite, every m_c >= 0, n finite and n >= 2               (phx_accumulate's summary: not "invalid")
+ *     starved    n finite and 0 <= n < 2, whatever the other floats hold.  A starved pixel is also invalid; it is counted separately
+ *                because more samples cure it and never cure a NaN
+ *   for a valid pixel, q = n / (n - 1), and per colour
+ *     L = m_c * q;   den = fabs(V_c) + floor;   b = tau * den;   ok_c = L <= b * b
+ *     converged = ok_r && ok_g && ok_b                                                    (phx_accumulate's summary criterion word for word)
+ *     r_c = den > 0 ? sqrt(L) / den : (L == 0 ? 0 : +inf)
+ *     r   = fp32(max(r_r, r_g, r_b))        the relative standard error, rounded to fp32 once; it may round to +inf
+ * Per tile:
+ *     invalid, starved, converged    the counts of those pixels
+ *     samples    the sum over the valid pixels of (uint64_t)min(n, 2^53)
+ *     worst      the largest r of the tile's valid pixels, +0.0f when there are none
+ *   every quantity is an integer count or a maximum of non-negative non-NaN floats, so the result does not depend on the reduction's order.
+ * A tile is OPEN when converged < w * h - invalid or starved > 0: a valid pixel still misses the criterion, or a pixel waits for samples.
+ * summary (optional): the sums of the records' counts over all tiles (pixels = width * height), tiles = tx * ty, and open, the number of open
+ * tiles.  Its first four fields equal phx_accumulate_summary of the same film, tau and floor. */
+typedef struct phx_tile_map {
+  uint32_t width, height;      /* 1 .. 65536 each */
+  uint32_t xstride;            /* floats per pixel of acc; 7 .. 24 */
+  uint32_t m2_offset;          /* required: >= 3, m2_offset + 3 <= xstride */
+  uint32_t samples_offset;     /* required: >= 3, < xstride */
+  uint32_t tile_width, tile_height; /* 4 .. 1024 each */
+  uint32_t on_device;          /* 0: film and records are host memory, 1: both are device memory (HBM), 2: the film is device memory and the records host memory */
+  float    tau;                /* the criterion's threshold; finite, >= 0 */
+  float    floor;              /* the criterion's floor in film units; finite, >= 0 */
+  uint32_t reserved[4];        /* must be 0 */
+} phx_tile_map;
+typedef struct phx_tile_record { /* 40 bytes */
+  phx_tile tile;               /* x, y, w, h */
+  uint32_t invalid, starved, converged;
+  float    worst;
+  uint64_t samples;
+} phx_tile_record;
+typedef struct phx_tile_map_summary {
+  uint64_t pixels, invalid, converged, samples, tiles, open;
+} phx_tile_map_summary;
+
 /* ---- the display pass: a film's linear radiance -> an 8-bit sRGB image, with the exposure taken from the film itself -------- */
 /* A pass of its own beside the frame (phx_dev_film_display): it reads a finished film of ANY layout (only the first three floats of a pixel,
  * "primary" rgb), launches none of the frame's kernels and changes no film.  The image is width x height pixels of 4 bytes, R, G, B, 255,
@@ -882,6 +928,10 @@ int         phx_dev_set_camera(phx_device* dev, const phx_camera* camera);
  * number >= 3 coprime to world (diagonals over the film: balanced whatever the row length). */
 typedef struct phx_tiles phx_tiles;
 phx_tiles*  phx_tiles_make(uint32_t width, uint32_t height, uint32_t tile_size, uint32_t rank, uint32_t world);
+/* make_list(): a queue of the caller's own tiles in the caller's order (the open tiles of a tile map).  The list is copied;
+ * count == 0 (tiles may then be NULL) gives a queue that is drained at once.  No geometry is checked here: the frame's own "tile outside
+ * the film" check stays the only one.  NULL (PHX_ERR_ARG) for a null list with count > 0. */
+phx_tiles*  phx_tiles_make_list(const phx_tile* tiles, uint32_t count);
 int         phx_tiles_next(void* tiles /* phx_tiles* */, phx_tile* out); /* a phx_next_tile_fn */
 uint32_t    phx_tiles_count(const phx_tiles* tiles);
 void        phx_tiles_reset(phx_tiles* tiles);
@@ -999,6 +1049,18 @@ int phx_dev_film_accumulate(phx_device* dev, const phx_accumulate* a, float* acc
 /* Times of the last phx_dev_film_accumulate of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the
  * host's clock (the allocations and, for host films, the uploads and the download included). */
 int phx_dev_accumulate_times(const phx_device* dev, double* ms /* 2 */);
+
+/* The tile map (phx_tile_map above states the rule): acc, width x height pixels of xstride floats, row-major, is read, and records receives
+ * ceil(width / tile_width) * ceil(height / tile_height) records; summary is host memory whatever on_device says and may be NULL.
+ * Synchronous, one kernel launch, a workgroup per tile.  It needs a device but no scene.  PHX_ERR_STATE while a frame is started and not
+ * joined; PHX_ERR_ARG, with the field's name in the message, for a value outside the ranges stated at the struct, channels that overlap
+ * "primary" or each other, a non-zero reserved word, a null pointer ("acc", "records") or records sharing a byte with acc: records and
+ * summary are then untouched.  Its working memory (the counters and, for host memory, the copies of film and records) is allocated in the
+ * call and freed before it returns (PHX_ERR_OOM if it cannot be had): phx_stats.device_bytes and every later frame are what they were. */
+int phx_dev_film_tile_map(phx_device* dev, const phx_tile_map* m, const float* acc, phx_tile_record* records, phx_tile_map_summary* summary /* may be NULL */);
+/* Times of the last phx_dev_film_tile_map of this device in milliseconds: ms[0] the kernel (HIP events), ms[1] the whole call on the
+ * host's clock (the allocations and, for host memory, the upload and the download included). */
+int phx_dev_tile_map_times(const phx_device* dev, double* ms /* 2 */);
 
 /* The display pass (phx_display above states the rule): film, width x height pixels of xstride floats, row-major, becomes image, height
  * rows of width RGBA8 pixels image_pitch bytes apart; image must be 4-byte aligned, and film and image must not share a byte.  summary and

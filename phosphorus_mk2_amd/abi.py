@@ -230,6 +230,27 @@ class OutlierClampSummary(C.Structure):
                 ("capped", C.c_uint64)]
 
 
+class TileMap(C.Structure):
+    """phx_tile_map: the accumulator's layout, the tile grid and the criterion of the tile map (phx_dev_film_tile_map)"""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32), ("xstride", C.c_uint32), ("m2_offset", C.c_uint32), ("samples_offset", C.c_uint32),
+        ("tile_width", C.c_uint32), ("tile_height", C.c_uint32), ("on_device", C.c_uint32), ("tau", C.c_float), ("floor", C.c_float),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class TileRecord(C.Structure):
+    """phx_tile_record: what a phx_dev_film_tile_map call knows of one tile (40 bytes)"""
+    _fields_ = [("tile", Tile), ("invalid", C.c_uint32), ("starved", C.c_uint32), ("converged", C.c_uint32), ("worst", C.c_float),
+                ("samples", C.c_uint64)]
+
+
+class TileMapSummary(C.Structure):
+    """phx_tile_map_summary: the counters of a phx_dev_film_tile_map call"""
+    _fields_ = [("pixels", C.c_uint64), ("invalid", C.c_uint64), ("converged", C.c_uint64), ("samples", C.c_uint64), ("tiles", C.c_uint64),
+                ("open", C.c_uint64)]
+
+
 DISPLAY_DITHER, DISPLAY_AUTO_EXPOSURE = 1, 2  # Display.flags (PHX_DISPLAY_*)
 TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2  # Display.tone (PHX_TONE_*)
 
@@ -280,6 +301,7 @@ EXPORTS = [
     "phx_dev_film_accumulate", "phx_dev_accumulate_times", "phx_dev_film_display", "phx_dev_display_times",
     "phx_dev_set_camera", "phx_dev_film_reproject", "phx_dev_reproject_times",
     "phx_dev_film_outlier_clamp", "phx_dev_outlier_clamp_times",
+    "phx_dev_film_tile_map", "phx_dev_tile_map_times", "phx_tiles_make_list",
 ]
 
 
@@ -295,6 +317,7 @@ def declare(lib):
     lib.phx_last_error.argtypes = []; lib.phx_last_error.restype = C.c_char_p
     lib.phx_dev_get_stats.argtypes = [vp, C.POINTER(Stats)]; lib.phx_dev_get_stats.restype = C.c_int
     lib.phx_tiles_make.argtypes = [C.c_uint32] * 5; lib.phx_tiles_make.restype = vp
+    lib.phx_tiles_make_list.argtypes = [C.POINTER(Tile), C.c_uint32]; lib.phx_tiles_make_list.restype = vp
     lib.phx_tiles_next.argtypes = [vp, C.POINTER(Tile)]; lib.phx_tiles_next.restype = C.c_int
     lib.phx_tiles_count.argtypes = [vp]; lib.phx_tiles_count.restype = C.c_uint32
     lib.phx_tiles_reset.argtypes = [vp]; lib.phx_tiles_reset.restype = None
@@ -328,5 +351,7 @@ def declare(lib):
     lib.phx_dev_reproject_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_reproject_times.restype = C.c_int
     lib.phx_dev_film_outlier_clamp.argtypes = [vp, C.POINTER(OutlierClamp), vp, vp, vp, C.POINTER(OutlierClampSummary)]; lib.phx_dev_film_outlier_clamp.restype = C.c_int
     lib.phx_dev_outlier_clamp_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_outlier_clamp_times.restype = C.c_int
+    lib.phx_dev_film_tile_map.argtypes = [vp, C.POINTER(TileMap), vp, vp, C.POINTER(TileMapSummary)]; lib.phx_dev_film_tile_map.restype = C.c_int
+    lib.phx_dev_tile_map_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_tile_map_times.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
     return lib

@@ -358,6 +358,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 19: return sizeof(phx_display); case 20: return sizeof(phx_display_summary);
     case 21: return sizeof(phx_reproject); case 22: return sizeof(phx_reproject_summary);
     case 23: return sizeof(phx_outlier_clamp); case 24: return sizeof(phx_outlier_clamp_summary);
+    case 25: return sizeof(phx_tile_map); case 26: return sizeof(phx_tile_record); case 27: return sizeof(phx_tile_map_summary);
     default: return 0;
   }
 }
@@ -394,6 +395,13 @@ phx_tiles* phx_tiles_make(uint32_t width, uint32_t height, uint32_t ts, uint32_t
       if ((x + s * y) % world == rank) q->tiles.push_back(phx_tile{x * ts, y * ts, tw, th});
     }
   } catch (...) { delete q; fail(PHX_ERR_OOM, "host memory allocation failed"); return nullptr; }
+  return q;
+}
+phx_tiles* phx_tiles_make_list(const phx_tile* tiles, uint32_t count) {
+  if (count && !tiles) { fail(PHX_ERR_ARG, "phx_tiles_make_list: null list"); return nullptr; }
+  phx_tiles* q = new (std::nothrow) phx_tiles();
+  if (!q) { fail(PHX_ERR_OOM, "host memory allocation failed"); return nullptr; }
+  try { if (count) q->tiles.assign(tiles, tiles + count); } catch (...) { delete q; fail(PHX_ERR_OOM, "host memory allocation failed"); return nullptr; }
   return q;
 }
 int phx_tiles_next(void* tiles, phx_tile* out) {

@@ -166,7 +166,7 @@ struct phx_device {
   phx_adaptive adaptive{}; bool adaptive_on = false;
   // the milliseconds of each film call's last run (film_calls.cpp: FilmCall writes them, a phx_dev_*_times getter copies its array out whole,
   // times_of): kernel and call; the display's histogram + exposure, encode and call; the denoiser's pack, iterations 1 .. 8, unpack and call
-  double guides_ms[2] = {}, accumulate_ms[2] = {}, reproject_ms[2] = {}, outlier_clamp_ms[2] = {};
+  double guides_ms[2] = {}, accumulate_ms[2] = {}, reproject_ms[2] = {}, outlier_clamp_ms[2] = {}, tile_map_ms[2] = {};
   double display_ms[3] = {};
   double denoise_ms[11] = {};
 

@@ -1,6 +1,7 @@
 // film_calls.cpp — the entry points that work on a film and launch no frame: phx_dev_film_moments, phx_dev_denoise / _guided (denoise.hip),
 // phx_dev_render_guides (guides.hip), phx_dev_film_accumulate (accumulate.hip), phx_dev_film_reproject (reproject.hip),
-// phx_dev_film_outlier_clamp (outlier_clamp.hip), phx_dev_film_display (display.hip), phx_dev_adaptive_select and the six *_times getters.
+// phx_dev_film_outlier_clamp (outlier_clamp.hip), phx_dev_film_display (display.hip), phx_dev_film_tile_map (tile_map.hip),
+// phx_dev_adaptive_select and the seven *_times getters.
 //
 // None of them reads a scene but the guide pass, which reads the camera and the tree.  Their argument checks are host-only (the *_check.cpp
 // files over film_checks.h) and run before the device is selected.  What the large calls share is stated once below: the refusals (refused);
@@ -14,6 +15,7 @@
 #include "guides_check.h"
 #include "outlier_clamp_check.h"
 #include "reproject_check.h"
+#include "tile_map_check.h"
 
 using namespace phx;
 
@@ -256,6 +258,46 @@ int phx_dev_film_accumulate(phx_device* d, const phx_accumulate* a, float* acc, 
 }
 
 int phx_dev_accumulate_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::accumulate_ms, ms, "accumulate_times: null argument"); }
+
+// The tile map (phx_tile_map; tile_map.hip).
+// (no stage_hook: the call reads a film and no scene)
+int phx_dev_film_tile_map(phx_device* d, const phx_tile_map* m, const float* acc, phx_tile_record* records, phx_tile_map_summary* summary) {
+  return guarded([&]() -> int {
+    if (const int rc = refused(d, "tile_map", m != nullptr)) return rc;
+    std::string why;
+    if (const int rc = tile_map_check(*m, acc, records, why)) return fail(rc, why);
+    FilmCall call{d, d->tile_map_ms};
+    if (const int rc = call.begin(2)) return rc;
+    const size_t npix = (size_t)m->width * m->height;
+    const uint32_t tiles_x = tile_map_tiles(m->width, m->tile_width), num_tiles = tiles_x * tile_map_tiles(m->height, m->tile_height);
+    static_assert(sizeof(phx_tile_record) == 10 * sizeof(float), "a record is staged as ten 4-byte words");
+    SummarySlots counters;
+    const float* src = acc; phx_tile_record* dst = records;
+    if (m->on_device == 0u) {  // a host film: a device copy
+      float* copy = nullptr;
+      if (const int rc = call.stage(acc, npix * m->xstride, nullptr, copy)) return rc;
+      src = copy;
+    }
+    if (m->on_device != 1u) {  // host records: device records, copied back behind the wait
+      float* words = nullptr;
+      if (const int rc = call.stage(nullptr, (size_t)num_tiles * 10u, reinterpret_cast<float*>(records), words)) return rc;
+      dst = reinterpret_cast<phx_tile_record*>(words);
+    }
+    if (summary) if (const int rc = counters.zero(d->stream)) return rc;
+    TileMapArgs A{};
+    A.width = m->width; A.height = m->height; A.xstride = m->xstride; A.m2_offset = m->m2_offset; A.samples_offset = m->samples_offset;
+    A.tile_width = m->tile_width; A.tile_height = m->tile_height; A.tiles_x = tiles_x; A.tau = (double)m->tau; A.floor = (double)m->floor;
+    if (const int rc = call.run([&] { launch_tile_map(d->stream, A, num_tiles, src, dst, counters.p); })) return rc;
+    if (summary) {
+      uint64_t c[6];
+      if (const int rc = counters.read(c, 6)) return rc;
+      summary->pixels = c[0]; summary->invalid = c[1]; summary->converged = c[2]; summary->samples = c[3]; summary->tiles = c[4]; summary->open = c[5];
+    }
+    return call.kernel_and_call_times();
+  });
+}
+
+int phx_dev_tile_map_times(const phx_device* d, double* ms) { return times_of(d, &phx_device::tile_map_ms, ms, "tile_map_times: null argument"); }
 
 // Reprojection (phx_reproject; reproject.hip).
 // (no stage_hook: the call reads four films and two cameras of its own, and no scene)

@@ -1,5 +1,5 @@
-// film_pass.h — what the kernels of the film passes with a summary share on the device (accumulate.hip, reproject.hip, outlier_clamp.hip;
-// DESIGN 24): the summary's counter path in two halves around the kernel's own barrier, and the test of a valid accumulator pixel.
+// film_pass.h — what the kernels of the film passes with a summary share on the device (accumulate.hip, reproject.hip, outlier_clamp.hip,
+// tile_map.hip): the summary's counter path in two halves around the kernel's own barrier, and the test of a valid accumulator pixel.
 // (display.hip counts 258 values a workgroup in LDS atomics: a scheme of its own.)
 #pragma once
 #include "kernels.h"

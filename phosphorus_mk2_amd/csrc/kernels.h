@@ -10,6 +10,7 @@
 //   denoise.hip        k_denoise_pack, k_denoise_iteration, k_denoise_unpack: the film denoiser, a post-process no frame launches
 //   guides.hip         k_guides: the first-hit guide film (albedo, coverage, position, distance), a pass of its own no frame launches
 //   accumulate.hip     k_accumulate: pools a finished film into an accumulator film and counts its summary, a pass of its own no frame launches
+//   tile_map.hip       k_tile_map: an accumulator film's convergence, one record per tile of a grid, and its summary, a pass of its own no frame launches
 //   reproject.hip      k_reproject: carries an accumulator film from one camera to another by the guide films' first hits, a pass of its own no frame launches
 //   outlier_clamp.hip  k_outlier_clamp: clamps a film's pixels to bounds taken from a reference film's neighbourhoods (despeckle, history clamp), a pass of its own no frame launches
 //   display.hip        k_display_histogram, k_display_exposure, k_display_encode: a film's radiance to an RGBA8 sRGB image, a pass of its own no frame launches
@@ -241,7 +242,7 @@ void launch_guides(hipStream_t stream, const DevScene& sc, const PassBuffers& pb
 // its instantiations, for init_kernels_on_current_device (the per-lane traversal stack is dynamic LDS): -> how many were written to out[0 .. 3]
 uint32_t guides_kernels(const void** out);
 
-// Summary slots: the `counters` of launch_accumulate, launch_reproject and launch_outlier_clamp (film_pass.h has the device's side,
+// Summary slots: the `counters` of launch_accumulate, launch_tile_map, launch_reproject and launch_outlier_clamp (film_pass.h has the device's side,
 // film_calls.cpp's SummarySlots the host's).  nullptr, or PHX_SUMMARY_SLOTS zeroed slots of PHX_SUMMARY_SLOT_WORDS 64-bit words, a 128-byte
 // line each: a workgroup adds its counts, in the order of the call's summary struct, to the first words of slot (workgroup id % SLOTS), and
 // the caller sums the slots.  One line sustains some 90 atomics a microsecond, and a 2160p film has 32 400 workgroups.
@@ -261,6 +262,17 @@ struct AccumulateArgs {
 enum { PHX_ACCUMULATE_SPAN = 256 };
 // counters: summary slots (above); pixels, invalid, converged, samples (phx_accumulate_summary)
 void launch_accumulate(hipStream_t stream, const AccumulateArgs& A, float* acc, const float* frame_film, unsigned long long* counters);
+
+// The tile map (phx_tile_map in phx_xpu.h states the rule; tile_map.hip): one launch, a workgroup of PHX_TILE_MAP_BLOCK threads
+// per tile of the grid, tiles_x tiles a row.  Consecutive threads take consecutive pixels of a tile's row and read their 7 floats straight
+// from memory; the workgroup reduces its counts and writes its own record, so no two workgroups write the same word but in the summary.
+struct TileMapArgs {
+  uint32_t width, height, xstride, m2_offset, samples_offset, tile_width, tile_height, tiles_x;
+  double tau, floor;
+};
+enum { PHX_TILE_MAP_BLOCK = 256 };
+// counters: summary slots (above); pixels, invalid, converged, samples, tiles, open (phx_tile_map_summary)
+void launch_tile_map(hipStream_t stream, const TileMapArgs& A, uint32_t num_tiles, const float* acc, phx_tile_record* records, unsigned long long* counters);
 
 // The display pass (phx_display in phx_xpu.h states the rule; display.hip, over display_rule.h): up to three launches on one stream
 // with no host round trip between them.

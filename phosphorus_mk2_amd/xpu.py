@@ -113,6 +113,17 @@ class Tiles:
             raise DeviceError(lib.phx_last_error().decode())
         return Tiles(h, lib, width, height)
 
+    @staticmethod
+    def from_list(tiles, width, height):
+        """A native queue of the caller's own tiles (x, y, w, h) in the caller's order (phx_tiles_make_list): the open tiles of a tile map,
+        say.  The list is copied; an empty one gives a queue that is drained at once.  width, height: the film's, as make() keeps them."""
+        lib = load_library()
+        arr = np.ascontiguousarray(np.asarray(list(tiles), np.int64).reshape(-1, 4).astype(np.uint32))  # x, y, w, h: a phx_tile each
+        h = lib.phx_tiles_make_list(arr.ctypes.data_as(C.POINTER(abi.Tile)), len(arr))
+        if not h:
+            raise DeviceError(lib.phx_last_error().decode())
+        return Tiles(h, lib, width, height)
+
     def next(self):
         t = abi.Tile()
         if self._lib.phx_tiles_next(self._h, C.byref(t)):
@@ -479,6 +490,29 @@ class HipDevice:
         """milliseconds of the last accumulate(): dict of kernel (HIP events) and call (host clock)"""
         return self._times("phx_dev_accumulate_times", 2, ("kernel", "call"))
 
+    def tile_map(self, acc, tile_size=32, threshold=0.0, floor=0.0, primary_components=4, normals=False, device_ptr=None, summary=True):
+        """The tile map (phx_dev_film_tile_map; include/phx_xpu.h states the rule): acc, a film in the accumulator's layout
+        (accumulator()), is read, and every tile of the tile_size x tile_size grid over it (an int, or (tile_width, tile_height)) gets a record
+        -> (records, summary).  records: a numpy structured array (TILE_RECORD: x, y, w, h, invalid, starved, converged, worst, samples), one
+        entry per tile, rows top to bottom, tiles left to right: for a square tile the list Tiles.make(W, H, tile_size) serves.  A tile is
+        open when converged < w * h - invalid or starved > 0; `converged` counts the valid pixels whose standard error is at most
+        threshold * (|value| + floor), as accumulate()'s summary does.  summary: a dict of pixels, invalid, converged, samples, tiles and
+        open (None with summary=False).  device_ptr: the address of a device-resident film; acc then is only its shape (H, W, xstride), and
+        40 bytes a tile come back instead of the film.  Needs no scene; it changes no film."""
+        q = tile_map_settings(_film_shape(acc, device_ptr is not None), tile_size, threshold, floor, primary_components, normals)
+        q.on_device = 0 if device_ptr is None else 2
+        keep = None if device_ptr is not None else np.ascontiguousarray(acc, np.float32)
+        tx, ty = -(-q.width // q.tile_width), -(-q.height // q.tile_height)
+        records = np.zeros(tx * ty, TILE_RECORD)
+        s = abi.TileMapSummary() if summary else None
+        _check(self._lib, self._lib.phx_dev_film_tile_map(self._h, C.byref(q), int(device_ptr) if device_ptr is not None else keep.ctypes.data,
+                                                          records.ctypes.data, C.byref(s) if summary else None), "phx_dev_film_tile_map")
+        return records, _summary_dict(s)
+
+    def tile_map_times(self):
+        """milliseconds of the last tile_map(): dict of kernel (HIP events) and call (host clock)"""
+        return self._times("phx_dev_tile_map_times", 2, ("kernel", "call"))
+
     def reproject(self, acc, guides_from, guides_to, camera_from, camera_to, sigma_plane=1.0, sigma_dist=4.0, max_history=64, primary_components=4,
                   summary=True, device_ptrs=None):
         """Reprojection (phx_dev_film_reproject; include/phx_xpu.h states the rule): acc, an accumulator film with normals
@@ -810,6 +844,47 @@ def accumulate_settings(shape_a, shape_b, spp, primary_components=4, normals=Fal
                           spp_b=int(spp), on_device=0, tau=float(threshold), floor=float(floor))
 
 
+# a phx_tile_record as numpy reads it (40 bytes, abi.TileRecord)
+TILE_RECORD = np.dtype([("x", np.uint32), ("y", np.uint32), ("w", np.uint32), ("h", np.uint32), ("invalid", np.uint32), ("starved", np.uint32),
+                        ("converged", np.uint32), ("worst", np.float32), ("samples", np.uint64)])
+
+
+def tile_map_settings(shape, tile_size=32, threshold=0.0, floor=0.0, primary_components=4, normals=False):
+    """abi.TileMap for an accumulator film of `shape` (H, W, xstride) with the channels derived as Film derives them (xpu.accumulator's
+    layout) and a grid of tile_size x tile_size tiles (an int, or (tile_width, tile_height)).  ValueError for a film of another layout."""
+    if len(shape) != 3:
+        raise ValueError("tile_map: the film must be (height, width, xstride)")
+    H, W, xs = (int(v) for v in shape)
+    _, m2_offset, samples_offset, want = film_layout(primary_components, normals, True, True)
+    if xs != want:
+        raise ValueError(f"tile_map: an accumulator has {want} floats per pixel in this layout (xpu.accumulator), this one {xs}")
+    tw, th = (int(tile_size),) * 2 if np.isscalar(tile_size) else (int(v) for v in tile_size)
+    return abi.TileMap(width=W, height=H, xstride=xs, m2_offset=m2_offset, samples_offset=samples_offset, tile_width=tw, tile_height=th,
+                       on_device=0, tau=float(threshold), floor=float(floor))
+
+
+def open_tiles(records, coverage=1.0):
+    """The tiles of a tile map's records a progressive frame still renders -> list of (x, y, w, h), in the records' order.  coverage == 1: the
+    open tiles as phx_tile_map defines them; coverage < 1 closes a tile once converged >= coverage * (w * h - invalid) and starved == 0."""
+    converged, starved = records["converged"].astype(np.int64), records["starved"]
+    valid = records["w"].astype(np.int64) * records["h"] - records["invalid"]
+    if coverage >= 1.0:
+        is_open = (converged < valid) | (starved > 0)
+    else:
+        is_open = ~((converged >= float(coverage) * valid) & (starved == 0))
+    return [tuple(t) for t in np.stack([records[f] for f in ("x", "y", "w", "h")], 1)[is_open].tolist()]
+
+
+def tile_map_grid(width, height, tile_size):
+    """The tile map's grid without a film: TILE_RECORD entries with only x, y, w, h set, in the records' order (phx_tile_map states it)"""
+    tw, th = (int(tile_size),) * 2 if np.isscalar(tile_size) else (int(v) for v in tile_size)
+    tx, ty = -(-width // tw), -(-height // th)
+    out = np.zeros(tx * ty, TILE_RECORD)
+    x, y = np.tile(np.arange(tx) * tw, ty), np.repeat(np.arange(ty) * th, tx)  # rows top to bottom, tiles left to right
+    out["x"], out["y"], out["w"], out["h"] = x, y, np.minimum(tw, width - x), np.minimum(th, height - y)
+    return out
+
+
 def pack_camera(camera):
     """abi.Camera of a CameraDesc, field by field as SceneDesc.pack fills the scene's"""
     c = abi.Camera()
@@ -898,7 +973,7 @@ def display(film, **settings):
 
 
 def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None, adaptive=None, pps=1, depth=9, normals=False, tile_size=32,
-                       display=None, despeckle=None, **options):
+                       display=None, despeckle=None, tiles=None, **options):
     """Progressive rendering on ONE device: the scene is preprocessed once, then frame k = 0, 1, ... is rendered at `spp` samples
     with sampler seed (seed + k) mod 2^64 and moments=True and pooled into an accumulator film (HipDevice.accumulate).  A generator: after
     every frame it yields (film, summary, frames_done); film is the accumulator (H, W, xstride) f32 in xpu.accumulator's layout, a view that
@@ -911,18 +986,40 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
     then yields (film, summary, frames_done, image), the image (or (image, summary) under summary=True) of the film it yields: with denoise,
     of the denoised copy (DESIGN 21).  despeckle: a dict of HipDevice.clamp_outliers' settings (radius=, gamma=, floor=, trim=, min_taps=;
     {} for the defaults): every frame film is then clamped in place against its own neighbourhoods, the centre excluded and upper only,
-    before it is pooled (biased: the fireflies' energy is gone).  options: further Options fields (samples_in_flight=,
-    light_sampling=, ...)."""
+    before it is pooled (biased: the fireflies' energy is gone).
+    tiles: dict(size=32, coverage=1.0, min_frames=1) stops converged TILES; it needs stop.  Frames 0 .. min_frames - 1 render
+    every tile; before each later frame HipDevice.tile_map reads the accumulator with stop's threshold and floor, and the frame renders only
+    the tiles that are open (coverage < 1 closes a tile once converged >= coverage * (w * h - invalid) and starved == 0: open_tiles).  The
+    loop then also ends once no tile is open.  A closed tile is never looked at again, and neighbouring tiles end with different "samples".
+    The frame films carry "samples", so that an unrendered pixel holds n_b == 0 and accumulate leaves it alone: without adaptive= the device
+    is set to set_adaptive(0, 0, max(spp, 2), 1), one round that ends at spp and takes no decision.  summary gains tiles, tiles_open (of
+    the frame just rendered) and rendered_pixels (the frame's).  tiles= with despeckle= raises ValueError: the clamp's window would read the
+    black pixels of unrendered neighbouring tiles as taps.
+    options: further Options fields (samples_in_flight=, light_sampling=, ...)."""
     if frames < 1:
         raise ValueError("render_progressive: frames must be at least 1")
     stop = dict(stop) if stop is not None else None
     coverage = float(stop.pop("coverage", 0.95)) if stop is not None else None
     if stop is not None and "threshold" not in stop:
         raise ValueError("render_progressive: stop needs a threshold")
+    if tiles is not None:
+        if stop is None:
+            raise ValueError("render_progressive: tiles= needs stop: the tile map reads its threshold and floor")
+        if despeckle is not None:
+            raise ValueError("render_progressive: despeckle= cannot be combined with tiles=: the clamp would read unrendered neighbouring tiles as taps")
+        tiles = dict(tiles)
+        map_size, tile_coverage, min_frames = int(tiles.pop("size", 32)), float(tiles.pop("coverage", 1.0)), int(tiles.pop("min_frames", 1))
+        if tiles:
+            raise ValueError(f"render_progressive: tiles= does not know {sorted(tiles)}")
+        if min_frames < 1:
+            raise ValueError("render_progressive: tiles' min_frames must be at least 1")
+    by_tiles = tiles is not None
     dev = HipDevice.make(Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, **options))
     try:
         if adaptive is not None:
             dev.set_adaptive(**adaptive)
+        elif by_tiles:  # only marks samples = spp: one round that ends at spp, no decision is ever taken
+            dev.set_adaptive(threshold=0.0, floor=0.0, min_samples=max(spp, 2), step=1)
         dev.preprocess(scene_desc)
         W, H = scene_desc.camera.width, scene_desc.camera.height
         acc = accumulator(W, H, 4, normals)
@@ -934,14 +1031,28 @@ def render_progressive(scene_desc, spp, frames, seed=1, stop=None, denoise=None,
                 gset = dict(gset)
                 guides = dev.render_guides(seed, min(int(gset.pop("samples", 4)), spp))
                 settings.update(gset)
+        with_samples = adaptive is not None or by_tiles
         for k in range(frames):
-            film = Film(W, H, 4, normals, True, adaptive is not None)
-            dev.start(scene_desc, FrameState((seed + k) % (1 << 64), Tiles.make(W, H, tile_size), film, native_sink=True))
+            film = Film(W, H, 4, normals, True, with_samples)
+            queue, frame_tiles = None, None
+            if by_tiles:
+                if k < min_frames:
+                    records = tile_map_grid(W, H, map_size)
+                    frame_tiles = [tuple(t) for t in np.stack([records[f] for f in ("x", "y", "w", "h")], 1).tolist()]
+                else:
+                    records, _ = dev.tile_map(acc, map_size, stop["threshold"], stop.get("floor", 0.0), 4, normals, summary=False)
+                    frame_tiles = open_tiles(records, tile_coverage)
+                    if not frame_tiles:
+                        return
+                queue = Tiles.from_list(frame_tiles, W, H)
+            dev.start(scene_desc, FrameState((seed + k) % (1 << 64), queue if by_tiles else Tiles.make(W, H, tile_size), film, native_sink=True))
             dev.join()
             if despeckle is not None:
                 dev.clamp_outliers(film.data, **{**despeckle, "exclude_centre": True, "upper_only": True, "primary_components": 4, "normals": normals,
                                                  "moments": True, "samples": adaptive is not None, "summary": False})
-            _, summary = dev.accumulate(acc, film.data, spp, 4, normals, adaptive is not None, **(stop or {}))
+            _, summary = dev.accumulate(acc, film.data, spp, 4, normals, with_samples, **(stop or {}))
+            if by_tiles:
+                summary.update(tiles=len(records), tiles_open=len(frame_tiles), rendered_pixels=sum(t[2] * t[3] for t in frame_tiles))
             out = acc if settings is None else dev.denoise(acc, spp, 4, normals, True, guides=guides, **settings)
             if display is None:
                 yield out, summary, k + 1
@@ -1039,7 +1150,7 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
     denoise: a dict of HipDevice.denoise's settings (iterations=, sigma_l=, normal_power_log2=; {} for the defaults) filters the film that is
     returned; it needs moments=True.  Its entry guides=dict(samples=4, demodulate=True, plane=False, albedo_floor=, sigma_x=) renders the
     first-hit guide film with the frame's seed (HipDevice.render_guides) and runs the guided filter; plane=True needs normals=True.
-    progressive: dict(frames=, stop=None) drains render_progressive (frames of spp samples at seeds seed, seed + 1, ... pooled into
+    progressive: dict(frames=, stop=None, tiles=None) drains render_progressive (frames of spp samples at seeds seed, seed + 1, ... pooled into
     one film, until `frames` are done or stop's coverage is met) and returns (the last film it yields, in xpu.accumulator's layout, the last
     summary or None); it needs moments=True and renders the whole film on one device."""
     if denoise is not None and not moments:
@@ -1051,7 +1162,7 @@ def render(scene_desc, spp=16, pps=1, depth=9, seed=1, normals=False, tile_size=
             raise ValueError("progressive renders whole films on one device: no callback_tiles, rank or world")
         last = None
         for last in render_progressive(scene_desc, spp, int(progressive["frames"]), seed, progressive.get("stop"), denoise, adaptive, pps, depth, normals,
-                                       tile_size, samples_in_flight=samples_in_flight, tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder,
+                                       tile_size, tiles=progressive.get("tiles"), samples_in_flight=samples_in_flight, tiles_per_batch=tiles_per_batch, bvh_builder=bvh_builder,
                                        light_sampling=light_sampling, light_selection=light_selection, environment_sampling=environment_sampling):
             pass
         return np.array(last[0]), last[1]
