@@ -141,6 +141,46 @@ static int orbit(phx_device* dev, const phx_scene* scene, const phx_options* opt
   return 0;
 }
 
+/* `animate K`: the two tilted triangles (vertices 12 .. 17) slide along x over K frames.  Every frame the host hands the moved vertices to
+ * phx_dev_update_geometry (a refit: the tree keeps its topology), prints what the update cost and renders one fresh film;
+ * nothing is accumulated across geometry.  The last film is written to `path`. */
+static int animate(phx_device* dev, phx_scene* scene, phx_mesh* mesh, int frames, const char* path) {
+  float moved[54];
+  const float* rest = mesh->vertices;
+  if (mesh->num_vertices != 18) { fprintf(stderr, "animate: the room's mesh has 18 vertices, not %u\n", mesh->num_vertices); return 1; }
+  float* film = (float*)calloc((size_t)W * H * 4, sizeof(float));
+  if (!film) return 1;
+  for (int k = 1; k <= frames; ++k) {
+    memcpy(moved, rest, sizeof(moved));
+    for (int v = 12; v < 18; ++v) moved[3 * v] = rest[3 * v] + 0.8f * (float)k / (float)frames;
+    mesh->vertices = moved;
+    phx_geometry_update u;
+    memset(&u, 0, sizeof(u));
+    u.mode = PHX_UPDATE_REFIT;
+    phx_geometry_summary gs;
+    if (phx_dev_update_geometry(dev, scene, &u, &gs) != PHX_OK) { mesh->vertices = rest; free(film); return fail("phx_dev_update_geometry"); }
+    double ms[4];
+    if (phx_dev_update_geometry_times(dev, ms) != PHX_OK) { mesh->vertices = rest; free(film); return fail("phx_dev_update_geometry_times"); }
+    printf("update: frame %d refit %.3f ms\n", k, ms[3]);
+    phx_tiles* tiles = phx_tiles_make(W, H, 32, 0, 1);
+    phx_frame frame;
+    memset(&frame, 0, sizeof(frame));
+    frame.tiles_user = tiles; frame.next_tile = phx_tiles_next;
+    frame.sampler_seed = 7; frame.primary_components = 4; frame.host_film = film;
+    const int bad = phx_dev_start(dev, &frame) != PHX_OK || phx_dev_join(dev) != PHX_OK;
+    phx_tiles_free(tiles);
+    if (bad) { mesh->vertices = rest; free(film); return fail("phx_dev_start / phx_dev_join"); }
+    printf("animate: frame %d triangles %u nodes %u levels %u bounds x %.3f .. %.3f\n", k, gs.triangles, gs.nodes, gs.levels, (double)gs.bounds[0], (double)gs.bounds[3]);
+  }
+  mesh->vertices = rest;
+  FILE* f = fopen(path, "wb");
+  const int ok = f != NULL && fwrite(film, sizeof(float), (size_t)W * H * 4, f) == (size_t)W * H * 4;
+  if (f) fclose(f);
+  free(film);
+  if (!ok) { fprintf(stderr, "cannot write %s\n", path); return 1; }
+  return 0;
+}
+
 /* despeckle: a joined frame film of `xstride` floats a pixel (primary rgba, m2 rgb [, samples]) against its own neighbourhoods, in place */
 static int despeckle_film(phx_device* dev, float* film, size_t xstride, int has_samples, int frame_number) {
   phx_outlier_clamp oc;
@@ -198,7 +238,7 @@ int main(int argc, char** argv) {
   phx_options opt;
   memset(&opt, 0, sizeof(opt));
   opt.samples_per_pixel = 8; opt.paths_per_sample = 1; opt.path_depth = 5; opt.device_ordinal = -1;
-  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0, orbit_cameras = 0, orbit_clamp = 0, despeckle = 0, tile_stop = 0;
+  int error_estimate = 0, adaptive = 0, denoise = 0, progressive = 0, display = 0, orbit_cameras = 0, orbit_clamp = 0, despeckle = 0, tile_stop = 0, animate_frames = 0;
   float tile_tau = 0.0f;
   phx_adaptive ad;
   memset(&ad, 0, sizeof(ad));
@@ -222,6 +262,10 @@ int main(int argc, char** argv) {
       orbit_clamp = take == 3;
       for (int k = i; k + take < argc; ++k) argv[k] = argv[k + take];
       argc -= take; --i;
+    } else if (strcmp(argv[i], "animate") == 0 && i + 1 < argc) {  /* the keyword and its number */
+      animate_frames = atoi(argv[i + 1]);
+      for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+      argc -= 2; --i;
     } else if (strcmp(argv[i], "display") == 0) {  /* the keyword and, optionally, `auto` */
       const int take = i + 1 < argc && strcmp(argv[i + 1], "auto") == 0 ? 2 : 1;
       display = take;
@@ -286,6 +330,11 @@ int main(int argc, char** argv) {
   if (tile_stop && despeckle) { fprintf(stderr, "despeckle cannot be combined with progressive K tiles TAU: the clamp would read unrendered tiles as taps\n"); return 1; }
   const int samples_channel = adaptive || tile_stop; /* the frame film carries the channel "samples" at float 7 */
 
+  if (animate_frames > 0) { /* moving geometry on the first device, in place of the one frame below */
+    const int rc = argc > 1 ? animate(devs[0], &scene, &mesh, animate_frames, argv[1]) : 1;
+    for (int i = 0; i < num_devices; ++i) phx_dev_destroy(devs[i]);
+    return rc;
+  }
   if (orbit_cameras) { /* a path of cameras on the first device, in place of the one frame below */
     const int rc = argc > 1 ? orbit(devs[0], &scene, &opt, orbit_cameras, orbit_clamp, argv[1]) : 1;
     for (int i = 0; i < num_devices; ++i) phx_dev_destroy(devs[i]);

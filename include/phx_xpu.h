@@ -1109,6 +1109,56 @@ int phx_dev_outlier_clamp_times(const phx_device* dev, double* ms /* 2 */);
  * (lo.xyz, cell.xyz; origin = fma(i, cell, lo)). */
 int phx_dev_copy_bvh(phx_device* dev, void* out, uint64_t capacity, uint64_t* bytes, float* grid6);
 
+/* ---- geometry updates -----------------------------------------------------------------------------------------------------
+ * phx_dev_update_geometry takes new vertex positions and normals for the preprocessed scene at a fraction of phx_dev_preprocess's cost.
+ * `moved` is the committed scene with other vertex positions and normals.  The call re-derives everything that geometry feeds: the
+ * triangle records of the pool (v0, e0 = b - a, e1 = c - a), the nodelets, the scene grid, the shade records (flat normals), the vertex
+ * normals by pool element, the light tables (every light's area and pick density, the light triangles' positions and normals, the area
+ * CDF, the power selection table with the environment's entry: a lamp that is stretched changes its pdf and its selection weight exactly
+ * as under a fresh preprocess) — and the corner UVs' order when a rebuild moved the elements.  It does not re-read, re-bake or re-upload
+ * materials, lobes, textures and texels, the environment image and its CDF, UV values, options, or the camera (phx_dev_set_camera).
+ *
+ * PHX_UPDATE_REFIT keeps the tree's topology — slots, masks, child bases, the triangles' places — and recomputes every box bottom-up:
+ * a triangle's box from its three vertices, grown by the tree's tolerance delta = 2^-18 (largest extent + largest coordinate of the new
+ * bounds); a nodelet's box as the fp32 min / max of its children's; every nodelet encoded again on the scene grid of the NEW bounds, so a
+ * scene that moved outside its old bounds needs no fallback.  The pool is then what the builder's emission would write for this topology
+ * over the new triangles.  Slot order and cuts are those of the OLD geometry: trace speed degrades with deformation, phx_stats.bvh_cost_model
+ * keeps the build's value, and when to rebuild is the caller's decision.  PHX_UPDATE_REBUILD runs the same path but builds a new tree
+ * (by options.bvh_builder) and recomputes the traversal plan: the fallback when a deformation has ruined the topology.
+ *
+ * A frame after an update equals, bit for bit, the frame of a device freshly preprocessed with the moved scene (the film depends on the
+ * triangles, not on the tree).  Films accumulated before an update are stale.  Topology changes need phx_dev_preprocess.
+ *
+ * Refused with PHX_ERR_ARG, the device untouched and still serving its old scene, when any of these differ from the committed scene: the
+ * triangle count; a primitive's material word (material | smooth << 31) in scene_t::triangles() order; the number of lights or a light's
+ * triangle count; whether any face is smooth; the texture classes (some lobe or emitter reads an image at the hit's UV, some mix factor
+ * is an image); also for a vertex that is not finite, for geometry phx_dev_preprocess refuses, for an unknown mode and for a non-zero
+ * reserved word.  The face index arrays themselves are not compared: the triangles given are the triangles rendered.
+ * PHX_ERR_STATE without a preprocessed scene and while a frame is started and not joined.  A failure after the first device write leaves
+ * the device without a scene, as a failed phx_dev_preprocess does.  Everything the call allocates besides the scene's own tables (the new
+ * triangles, elem_of_prim, per-element boxes and marks, the tables in primitive order) lives only during the call.  After a refit the
+ * device holds no more memory after the call than before: phx_stats.device_bytes is unchanged.  A rebuild sizes the pool and the tables by
+ * pool element for the NEW tree and releases what the old one held beyond that: afterwards the device holds exactly what a device freshly
+ * preprocessed with the moved scene holds (more or less than before by the difference of the trees' element counts).  The call returns
+ * after synchronising the device's stream. */
+enum { PHX_UPDATE_REFIT = 0, PHX_UPDATE_REBUILD = 1 };
+typedef struct phx_geometry_update {
+  uint32_t mode;        /* PHX_UPDATE_* */
+  uint32_t reserved[3]; /* must be 0 */
+} phx_geometry_update;
+typedef struct phx_geometry_summary {
+  uint32_t mode, triangles, nodes, levels, lights, light_triangles; /* levels: of nodelets (phx_stats.bvh_depth) */
+  float bounds[6];      /* the geometry's new bounds, lo.xyz hi.xyz */
+  float delta;          /* the triangle boxes' inflation on those bounds */
+} phx_geometry_summary;
+int phx_dev_update_geometry(phx_device* dev, const phx_scene* moved, const phx_geometry_update* u, phx_geometry_summary* summary /* may be NULL */);
+/* Times of the last phx_dev_update_geometry of this device in milliseconds, on the host's clock: ms[0] the host's flattening of the moved
+ * scene (validation, the walk over the meshes, the light tables, the bounds), ms[1] the uploads (the triangles under a refit, normals,
+ * light tables), ms[2] the device's work, each stretch ending in a synchronise (the refit or the rebuild with its scratch allocations, the
+ * shade records and the permutations, the release of the call's device buffers; under a rebuild the builder uploads the triangles itself,
+ * so that upload is counted here and not in ms[1]), ms[3] the whole call. */
+int phx_dev_update_geometry_times(const phx_device* dev, double* ms /* 4 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,20 @@ class TileMapSummary(C.Structure):
                 ("open", C.c_uint64)]
 
 
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1  # GeometryUpdate.mode (PHX_UPDATE_*)
+
+
+class GeometryUpdate(C.Structure):
+    """phx_geometry_update: how phx_dev_update_geometry brings the tree up to date"""
+    _fields_ = [("mode", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class GeometrySummary(C.Structure):
+    """phx_geometry_summary: what a phx_dev_update_geometry call left behind"""
+    _fields_ = [("mode", C.c_uint32), ("triangles", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("lights", C.c_uint32),
+                ("light_triangles", C.c_uint32), ("bounds", C.c_float * 6), ("delta", C.c_float)]
+
+
 DISPLAY_DITHER, DISPLAY_AUTO_EXPOSURE = 1, 2  # Display.flags (PHX_DISPLAY_*)
 TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2  # Display.tone (PHX_TONE_*)
 
@@ -302,6 +316,7 @@ EXPORTS = [
     "phx_dev_set_camera", "phx_dev_film_reproject", "phx_dev_reproject_times",
     "phx_dev_film_outlier_clamp", "phx_dev_outlier_clamp_times",
     "phx_dev_film_tile_map", "phx_dev_tile_map_times", "phx_tiles_make_list",
+    "phx_dev_update_geometry", "phx_dev_update_geometry_times",
 ]
 
 
@@ -354,4 +369,6 @@ def declare(lib):
     lib.phx_dev_film_tile_map.argtypes = [vp, C.POINTER(TileMap), vp, vp, C.POINTER(TileMapSummary)]; lib.phx_dev_film_tile_map.restype = C.c_int
     lib.phx_dev_tile_map_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_tile_map_times.restype = C.c_int
     lib.phx_dev_copy_bvh.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64), f32p]; lib.phx_dev_copy_bvh.restype = C.c_int
+    lib.phx_dev_update_geometry.argtypes = [vp, C.POINTER(Scene), C.POINTER(GeometryUpdate), C.POINTER(GeometrySummary)]; lib.phx_dev_update_geometry.restype = C.c_int
+    lib.phx_dev_update_geometry_times.argtypes = [vp, C.POINTER(C.c_double)]; lib.phx_dev_update_geometry_times.restype = C.c_int
     return lib

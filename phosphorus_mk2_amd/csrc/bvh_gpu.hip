@@ -14,6 +14,7 @@
 //                   order: the same node semantics as the host builder.
 // Traversal results do not depend on which builder made the tree (conservative box tests, bvh8.h).
 #include "bvh_gpu.h"
+#include "bvh_refit.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -62,7 +63,7 @@ __global__ void __launch_bounds__(GB) k_prim_bounds(const float* __restrict__ ab
       clo[a] = fminf(clo[a], c); chi[a] = fmaxf(chi[a], c);
       glo[a] = fminf(glo[a], b.lo[a]); ghi[a] = fmaxf(ghi[a], b.hi[a]);
     }
-    pbox[i] = b;
+    if (pbox) pbox[i] = b;  // (the refit asks for the bounds alone)
   }
   for (int a = 0; a < 3; ++a) {
     float lo = clo[a], hi = chi[a];
@@ -399,41 +400,19 @@ __global__ void __launch_bounds__(64) k_collapse(Tree2 T, SceneGrid grid, const 
 
   Node8 nd;
   nd.imask = 0;
-  // origin on the scene grid, not above the node's lower corner; everything below is relative to the DECODED origin
-  uint32_t gi[3]; float org[3];
-  for (int a = 0; a < 3; ++a) { gi[a] = grid_index_below(nb.lo[a], grid.lo[a], grid.cell[a]); org[a] = fmaf((float)gi[a], grid.cell[a], grid.lo[a]); }
-  double scale[3]; uint8_t eb[3];
-  for (int a = 0; a < 3; ++a) {
-    const double ext = (double)nb.hi[a] - (double)org[a];
-    int ex = -126;
-    if (ext > 0.0) {
-      ex = (int)ceil(log2(ext * 1.00001 / 255.0));
-      while (ldexp(255.0, ex) < ext * 1.00001) ++ex;
-    }
-    ex = max(-126, min(127, ex));
-    eb[a] = (uint8_t)(ex + 127);
-    scale[a] = ldexp(1.0, ex);
-  }
-  nd.ex = eb[0]; nd.ey = eb[1]; nd.ez = eb[2];
+  // origin on the scene grid, exponents and outward planes: bvh_refit.h states the encode once, for this emission and for the refit
   uint32_t n_inner = 0, n_tri = 0, valid = 0;
+  float cbox[48];
   for (int s = 0; s < 8; ++s) {
     const int i = child_in_slot[s];
-    uint8_t ql[3] = {255, 255, 255}, qh[3] = {0, 0, 0};
-    if (i >= 0) {
-      valid |= 1u << s;
-      const Box6 b = T.nbox[ch[i]];
-      for (int a = 0; a < 3; ++a) {
-        double lo = floor(((double)b.lo[a] - (double)org[a]) / scale[a] - 1e-3);
-        double hi = ceil(((double)b.hi[a] - (double)org[a]) / scale[a] + 1e-3);
-        lo = fmax(0.0, fmin(255.0, lo)); hi = fmax(0.0, fmin(255.0, hi));
-        ql[a] = (uint8_t)lo; qh[a] = (uint8_t)hi;
-      }
-      if (leaf_count(T, ch[i]) <= 1u) ++n_tri;
-      else { nd.imask |= (uint8_t)(1u << s); ++n_inner; }
-    }
-    nd.qlox[s] = ql[0]; nd.qloy[s] = ql[1]; nd.qloz[s] = ql[2]; nd.qhix[s] = qh[0]; nd.qhiy[s] = qh[1]; nd.qhiz[s] = qh[2];
+    if (i < 0) continue;
+    valid |= 1u << s;
+    const Box6 b = T.nbox[ch[i]];
+    for (int a = 0; a < 3; ++a) { cbox[6 * s + a] = b.lo[a]; cbox[6 * s + 3 + a] = b.hi[a]; }
+    if (leaf_count(T, ch[i]) <= 1u) ++n_tri;
+    else { nd.imask |= (uint8_t)(1u << s); ++n_inner; }
   }
-  node_origin_encode(nd, gi[0], gi[1], gi[2], valid);
+  encode_node8(nd, grid, nb.lo, nb.hi, cbox, valid);
   // Pool elements and places in the next level's queue are handed out per WAVE: a scan of the lanes' needs (all children | inner
   // children << 16; a wave needs at most 512 of each) and one atomic per counter, each counter on its own 128-byte line — one
   // address sustains ~90 atomics per microsecond, and four per node on one line were a quarter of the 10 M-triangle build.  The
@@ -479,6 +458,22 @@ __global__ void __launch_bounds__(64) k_collapse(Tree2 T, SceneGrid grid, const 
 #define HCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::snprintf(err, errlen, "%s: %s", #x, hipGetErrorString(e_)); cleanup(); return 1; } } while (0)
 
 }  // namespace
+
+int geometry_bounds_gpu(hipStream_t stream, const float* d_abc, uint32_t n, float* lo, float* hi, char* err, size_t errlen) {
+  uint32_t* cb = nullptr;
+  auto cleanup = [&]() { if (cb) (void)hipFree(cb); cb = nullptr; };
+  if (hipMalloc((void**)&cb, 64) != hipSuccess) { cb = nullptr; std::snprintf(err, errlen, "hipMalloc failed (geometry bounds)"); return BVH_GPU_RECOVERABLE; }
+  const uint32_t init_cb[12] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+  HCHK(hipMemcpyAsync(cb, init_cb, sizeof(init_cb), hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_prim_bounds, dim3(std::min<uint32_t>((n + GB - 1) / GB, 2048u)), dim3(GB), 0, stream, d_abc, n, (Box6*)nullptr, cb);
+  HCHK(hipGetLastError());
+  uint32_t h_cb[12];
+  HCHK(hipMemcpyAsync(h_cb, cb, sizeof(h_cb), hipMemcpyDeviceToHost, stream));
+  HCHK(hipStreamSynchronize(stream));
+  for (int a = 0; a < 3; ++a) { lo[a] = ord2f(h_cb[6 + a]); hi[a] = ord2f(h_cb[9 + a]); }
+  cleanup();
+  return 0;
+}
 
 int build_bvh8_gpu(hipStream_t stream, const float* d_abc, const uint32_t* d_prim_material, uint32_t n, GpuBvh* out, char* err, size_t errlen, uint32_t* d_elem_of_prim) {
   std::memset(out, 0, sizeof(*out)); out->depth = 1;

@@ -17,6 +17,7 @@
 #include "scene_flatten.h"
 
 #include <atomic>
+#include <cfloat>
 #include <cstdio>
 #include <cstring>
 
@@ -106,6 +107,18 @@ int build_tree(phx_device* d, const FlatScene& fs, DevBuf<uint32_t>& elem_of_pri
   return PHX_OK;
 }
 
+// The tables of floats that ride directly behind the light records, each padded to whole records of the light table: the selection table
+// (shade_common.h: light_pcdf), then the area CDF (light_cdf), one float per light triangle.
+void append_light_tables(const DevScene& sc, FlatScene& fs) {
+  auto append_behind_lights = [&](const std::vector<float>& table) {
+    const size_t nl = fs.lights.size();
+    fs.lights.resize(nl + (table.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
+    std::memcpy(static_cast<void*>(fs.lights.data() + nl), table.data(), table.size() * sizeof(float));
+  };
+  if (sc.any_tex & SC_LIGHTS_BY_POWER) append_behind_lights(fs.light_pcdf);
+  if (sc.any_tex & SC_LIGHTS_BY_AREA) append_behind_lights(fs.light_cdf);
+}
+
 // Replaces the device's scene by `fs`.  From its first line to its last the device has NO scene (preprocessed == false): a failure on the
 // way — the device builder's fatal error, a tree too deep, a hipMalloc that fails — leaves buffers of the old and the new scene mixed, and
 // start / the stage hooks answer PHX_ERR_STATE until a preprocess succeeds.
@@ -124,14 +137,7 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   if (sc.stack_levels > PHX_MAX_BVH_DEPTH)
     return fail(PHX_ERR_ARG, "tree too deep: " + std::to_string(sc.stack_levels) + " levels, the traversal stack in LDS holds " + std::to_string(PHX_MAX_BVH_DEPTH));
   if ((rc = d->d_materials.upload(fs.materials))) return rc;
-  // a table of floats rides directly behind the light records, padded to whole records of the table's size
-  auto append_behind_lights = [&](const std::vector<float>& table) {
-    const size_t nl = fs.lights.size();
-    fs.lights.resize(nl + (table.size() * sizeof(float) + sizeof(DevLight) - 1) / sizeof(DevLight), DevLight{});
-    std::memcpy(static_cast<void*>(fs.lights.data() + nl), table.data(), table.size() * sizeof(float));
-  };
-  if (sc.any_tex & SC_LIGHTS_BY_POWER) append_behind_lights(fs.light_pcdf);  // the selection table (shade_common.h: light_pcdf)
-  if (sc.any_tex & SC_LIGHTS_BY_AREA) append_behind_lights(fs.light_cdf);    // behind it, the CDF (shade_common.h: light_cdf): one float per light triangle
+  append_light_tables(sc, fs);
   if ((rc = d->d_lights.upload(fs.lights)) || (rc = d->d_light_tris.upload(fs.light_tris))) return rc;
   // what shading reads of a hit triangle, 16 bytes per POOL ELEMENT: geometric normal + material word
   if ((rc = d->d_elem_shade.alloc(sc.num_elems))) return rc;
@@ -161,10 +167,10 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   if (sc.any_tex & SC_LIGHTS_ENV) { if ((rc = d->d_env_cdf.upload(fs.env_cdf))) return rc; } else d->d_env_cdf.release();
   if (any_image) {  // the texture table and the texels, and the one record through which the shade kernels find them
     if ((rc = d->d_textures.upload(fs.textures)) || (rc = d->d_texels.upload(fs.texels))) return rc;
-    const std::vector<DevTexScene> ts{DevTexScene{any_tex ? d->d_elem_uv.p : nullptr, d->d_textures.p, d->d_texels.p, any_tex ? d->d_lobe_tex.p : nullptr,
-                                                  fs.env_tex ? fs.env_tex - 1u : 0u, fs.env_mapping, fs.any_emit_tex ? 1u : 0u, fs.env_p,
-                                                  fs.any_emit_tex ? d->d_mat_emit_tex.p : nullptr, (sc.any_tex & SC_LIGHTS_ENV) ? d->d_env_cdf.p : nullptr}};
-    if ((rc = d->d_tex_scene.upload(ts))) return rc;
+    d->tex_scene = DevTexScene{any_tex ? d->d_elem_uv.p : nullptr, d->d_textures.p, d->d_texels.p, any_tex ? d->d_lobe_tex.p : nullptr,
+                               fs.env_tex ? fs.env_tex - 1u : 0u, fs.env_mapping, fs.any_emit_tex ? 1u : 0u, fs.env_p,
+                               fs.any_emit_tex ? d->d_mat_emit_tex.p : nullptr, (sc.any_tex & SC_LIGHTS_ENV) ? d->d_env_cdf.p : nullptr};
+    if ((rc = d->d_tex_scene.upload(std::vector<DevTexScene>{d->tex_scene}))) return rc;
   } else {
     d->d_textures.release(); d->d_texels.release(); d->d_tex_scene.release();
   }
@@ -192,6 +198,7 @@ int commit_scene(phx_device* d, FlatScene& fs) {
   d->env_tex = fs.env_tex; d->env_mapping = fs.env_mapping;
   for (int c = 0; c < 3; ++c) d->env_e[c] = fs.env_e[c];
   d->num_triangles = ntri;
+  d->geometry = std::move(fs.fingerprint);
   // Who reads (u, v) of a hit: a smooth face's normal, the corner UVs' interpolation (lobe images, masks, emitter images: SC_TEX_LOBES) and a
   // per-hit material — the classes flatten_scene made for launch_shade.  PHX_HIT_UV=1 (tests only) carries the stream on a scene that does not.
   {
@@ -199,6 +206,108 @@ int commit_scene(phx_device* d, FlatScene& fs) {
     d->hit_uv = fs.any_smooth || any_tex || sc.any_per_hit != 0 || (force && std::atoi(force) != 0);
   }
   d->budget_bytes = 0;  // the next frame asks the device again how much memory is free
+  d->preprocessed = true;
+  return PHX_OK;
+}
+
+// Brings the device's scene to the moved geometry `fs` (flatten_geometry's: accepted against d->geometry).  Refit: the pool is refitted in
+// place (bvh_refit.hip).  Rebuild: build_tree makes a new one, the corner UVs are carried over by the old and the new elem_of_prim, the
+// traversal plan and the spill buffer are recomputed.  Then the commit's geometry half, by commit_scene's own launches: shade records,
+// normals by pool element, the light tables and the light triangles' remaps.  As in commit_scene the device has no scene from the first
+// device write to the last line.  ms: uploads, device work (host clock; every stretch ends in a synchronise).  Under a rebuild the triangles go
+// up inside build_tree, so their upload is counted with the device's work.
+int update_scene_geometry(phx_device* d, FlatScene& fs, uint32_t mode, phx_geometry_summary* sum, double* ms) {
+  int rc;
+  DevScene& sc = d->scene;
+  const uint32_t ntri = (uint32_t)fs.prim_material.size();
+  const bool any_tex = (sc.any_tex & SC_TEX_LOBES) != 0, any_image = (sc.any_tex & SC_TEX_ANY) != 0, rebuild = mode == PHX_UPDATE_REBUILD;
+  double upload_ms = 0.0, device_ms = 0.0;
+  auto timed = [](double& acc, auto&& body) { const auto t = Clock::now(); const int r = body(); acc += ms_between(t, Clock::now()); return r; };
+  char msg[256] = {0};
+  DevBuf<float> d_abc, d_prim_normals; DevBuf<uint32_t> d_elem_of_prim; DevBuf<float2> d_prim_uv;
+  if (!rebuild) {
+    if ((rc = timed(upload_ms, [&] { return d_abc.upload(fs.abc); })) || (rc = d_elem_of_prim.alloc(ntri))) return rc;
+    d->preprocessed = false;
+    GpuRefit r{};
+    const int brc = timed(device_ms, [&] { return refit_bvh8_gpu(d->stream, d->d_pool.p, sc.num_elems, d_abc.p, ntri, d_elem_of_prim.p, &r, msg, sizeof(msg)); });
+    if (brc) return fail(brc == (int)BVH_GPU_RECOVERABLE ? PHX_ERR_OOM : PHX_ERR_DEVICE, std::string("update_geometry: ") + msg);
+    sc.grid = r.grid;
+  } else {
+    if (any_tex) {  // the corner UVs in primitive order, read back through the old tree's elem_of_prim: no UV value is read from the scene again
+      DevBuf<uint32_t> d_old;
+      if ((rc = d_old.alloc(ntri)) || (rc = d_prim_uv.alloc(3 * (size_t)ntri))) return rc;
+      const int brc = timed(device_ms, [&] {
+        const int e = pool_elem_of_prim_gpu(d->stream, d->d_pool.p, sc.num_elems, ntri, d_old.p, msg, sizeof(msg));
+        if (e) return e;
+        launch_gather_rows(d->stream, reinterpret_cast<const float*>(d->d_elem_uv.p), d_old.p, reinterpret_cast<float*>(d_prim_uv.p), ntri, 6, sc.num_elems);
+        return hipStreamSynchronize(d->stream) == hipSuccess ? 0 : 1;
+      });
+      if (brc) return fail(brc == (int)BVH_GPU_RECOVERABLE ? PHX_ERR_OOM : PHX_ERR_DEVICE, std::string("update_geometry: ") + msg);
+    }
+    d->preprocessed = false;
+    // Everything sized by the tree is released where the new tree's size differs, not kept at the larger of the two (DevBuf grows only): after
+    // a rebuild the device holds what a fresh preprocess of the moved scene holds.  The old pool has been read for the last time above.
+    const uint32_t elems_before = sc.num_elems;
+    d->d_pool.release();
+    const auto t_bvh0 = Clock::now();
+    if ((rc = build_tree(d, fs, d_elem_of_prim))) return rc;
+    d->bvh_build_ms = ms_between(t_bvh0, Clock::now()); device_ms += d->bvh_build_ms;
+    if (sc.stack_levels > PHX_MAX_BVH_DEPTH)
+      return fail(PHX_ERR_ARG, "tree too deep: " + std::to_string(sc.stack_levels) + " levels, the traversal stack in LDS holds " + std::to_string(PHX_MAX_BVH_DEPTH));
+    if (sc.num_elems != elems_before) { d->d_elem_shade.release(); d->d_elem_normals.release(); d->d_elem_uv.release(); }  // sized by pool element
+    if ((rc = d->d_elem_shade.alloc(sc.num_elems))) return rc;
+    if (fs.any_smooth && (rc = d->d_elem_normals.alloc(9 * (size_t)sc.num_elems))) return rc;
+    if (any_tex && (rc = d->d_elem_uv.alloc(3 * (size_t)sc.num_elems))) return rc;
+  }
+  append_light_tables(sc, fs);
+  rc = timed(upload_ms, [&] {
+    int r = d->d_lights.upload(fs.lights);
+    if (!r) r = d->d_light_tris.upload(fs.light_tris);
+    if (!r && fs.any_smooth) r = d_prim_normals.upload(fs.prim_normals);
+    return r;
+  });
+  if (rc) return rc;
+  const bool any_emit_tex = d->geometry.any_emit_tex;
+  rc = timed(device_ms, [&]() -> int {
+    launch_build_shade_recs(d->stream, reinterpret_cast<const TriRec*>(d->d_pool.p), d_elem_of_prim.p, d->d_elem_shade.p, ntri);
+    if (fs.any_smooth) {
+      launch_permute_normals(d->stream, d_prim_normals.p, d_elem_of_prim.p, d->d_elem_normals.p, ntri);
+      launch_remap_light_tris(d->stream, d->d_light_tris.p, (uint32_t)fs.light_tris.size(), d_elem_of_prim.p);
+    }
+    if (any_tex) {
+      if (rebuild) launch_permute_uvs(d->stream, d_prim_uv.p, d_elem_of_prim.p, d->d_elem_uv.p, ntri);
+      if (any_emit_tex) launch_remap_flat_light_tris(d->stream, d->d_light_tris.p, (uint32_t)fs.light_tris.size(), d_elem_of_prim.p);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(d->stream));  // d_elem_of_prim and the tables in primitive order go out of scope below
+    return PHX_OK;
+  });
+  if (rc) return rc;
+  if (any_image && ((sc.any_tex & SC_LIGHTS_ENV) || (rebuild && any_tex))) {  // the environment's interval moved with the bounds; a rebuild may have moved elem_uv
+    d->tex_scene.env_p = fs.env_p; d->tex_scene.elem_uv = any_tex ? d->d_elem_uv.p : nullptr;
+    if ((rc = timed(upload_ms, [&] { return d->d_tex_scene.upload(std::vector<DevTexScene>{d->tex_scene}); }))) return rc;
+  }
+  sc.elem_normals = fs.any_smooth ? d->d_elem_normals.p : nullptr;
+  sc.elem_shade = d->d_elem_shade.p;
+  sc.lights = d->d_lights.p; sc.light_tris = d->d_light_tris.p;
+  if (rebuild) {
+    sc.stack_spill = nullptr; sc.spill_stride = 0;
+    d->plan = trace_plan(sc);
+    const size_t spill = d->plan.spill_threads ? (size_t)d->plan.spill_threads * (d->plan.levels - d->plan.lds_levels) : 0;
+    if (spill != d->d_spill.n) d->d_spill.release();
+    if (spill) {
+      if ((rc = d->d_spill.alloc(spill))) return rc;
+      sc.stack_spill = d->d_spill.p; sc.spill_stride = d->plan.spill_threads;
+    }
+    d->budget_bytes = 0;
+  }
+  if (sum) {
+    *sum = phx_geometry_summary{mode, ntri, (uint32_t)d->bvh_nodes, sc.stack_levels, sc.num_lights, (uint32_t)fs.light_tris.size(),
+                                {fs.bounds[0], fs.bounds[1], fs.bounds[2], fs.bounds[3], fs.bounds[4], fs.bounds[5]}, tri_box_inflation(fs.bounds, fs.bounds + 3)};
+  }
+  // the call's own device buffers go here, inside the device's timer, not when the function returns
+  (void)timed(device_ms, [&] { d_abc.release(); d_elem_of_prim.release(); d_prim_normals.release(); d_prim_uv.release(); return 0; });
+  ms[1] = upload_ms; ms[2] = device_ms;
   d->preprocessed = true;
   return PHX_OK;
 }
@@ -273,6 +382,34 @@ int phx_dev_preprocess(phx_device* d, const phx_scene* s) {
     d->preprocess_ms = ms_between(t0, Clock::now());
     return PHX_OK;
   });
+}
+
+int phx_dev_update_geometry(phx_device* d, const phx_scene* s, const phx_geometry_update* u, phx_geometry_summary* summary) {
+  return guarded([&]() -> int {
+    if (!s || !u) return fail(PHX_ERR_ARG, "update_geometry: null argument");
+    // (the struct's own refusals need no device: they come first, as the film calls' checks do)
+    if (u->mode > PHX_UPDATE_REBUILD) return fail(PHX_ERR_ARG, "update_geometry: mode is outside its range (phx_geometry_update)");
+    if (u->reserved[0] || u->reserved[1] || u->reserved[2]) return fail(PHX_ERR_ARG, "update_geometry: reserved is outside its range (phx_geometry_update): it must be 0");
+    if (!d) return fail(PHX_ERR_ARG, "update_geometry: null device");
+    if (!d->preprocessed) return fail(PHX_ERR_STATE, "update_geometry before preprocess");
+    if (d->running) return fail(PHX_ERR_STATE, "update_geometry while a frame is running");
+    const auto t0 = Clock::now();
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};
+    FlatScene fs; std::string why;
+    if (const int rc = flatten_geometry(*s, d->opt, d->geometry, fs, why)) return fail(rc, why);
+    ms[0] = ms_between(t0, Clock::now());
+    DeviceScope on(d->hip_device);
+    if (!on.ok) return fail(PHX_ERR_DEVICE, "hipSetDevice failed");
+    if (const int rc = update_scene_geometry(d, fs, u->mode, summary, ms)) return rc;
+    ms[3] = ms_between(t0, Clock::now());
+    for (int k = 0; k < 4; ++k) d->update_geometry_ms[k] = ms[k];
+    return PHX_OK;
+  });
+}
+int phx_dev_update_geometry_times(const phx_device* d, double* ms) {
+  if (!d || !ms) return fail(PHX_ERR_ARG, "update_geometry_times: null argument");
+  for (int k = 0; k < 4; ++k) ms[k] = d->update_geometry_ms[k];
+  return PHX_OK;
 }
 
 // The camera is nine host-side words of d->scene (scene_flatten.cpp: flatten_camera) and nothing on the device: every launch takes the
@@ -359,6 +496,7 @@ uint32_t phx_abi_sizeof(int which) {
     case 21: return sizeof(phx_reproject); case 22: return sizeof(phx_reproject_summary);
     case 23: return sizeof(phx_outlier_clamp); case 24: return sizeof(phx_outlier_clamp_summary);
     case 25: return sizeof(phx_tile_map); case 26: return sizeof(phx_tile_record); case 27: return sizeof(phx_tile_map_summary);
+    case 28: return sizeof(phx_geometry_update); case 29: return sizeof(phx_geometry_summary);
     default: return 0;
   }
 }

@@ -7,6 +7,7 @@
 #include "../../include/phx_xpu.h"
 #include "frame_plan.h"
 #include "kernels.h"
+#include "scene_flatten.h"
 
 #include <algorithm>
 #include <chrono>
@@ -148,6 +149,9 @@ struct phx_device {
   uint32_t num_materials = 0, num_textures = 0;
   std::vector<uint8_t> mat_masked;  // per material: some lobe's factor is an image mask (the untextured KAT hooks refuse those)
   uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission
+  phx::GeometryFingerprint geometry;  // of the committed scene (host memory): what phx_dev_update_geometry accepts a moved scene against
+  phx::DevTexScene tex_scene{};       // the record in d_tex_scene as it was uploaded (an update changes env_p and elem_uv in it)
+  double update_geometry_ms[4] = {};  // the last phx_dev_update_geometry: host flatten, uploads, device work, call
   uint64_t bvh_nodes = 0, bvh_bytes = 0, num_triangles = 0;
   double preprocess_ms = 0, bvh_build_ms = 0;
 

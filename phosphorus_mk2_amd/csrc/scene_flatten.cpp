@@ -68,9 +68,11 @@ bool bake_material(const phx_material& m, float sheen_L5, DevMaterial& out, uint
 // their sums and the running table are binary64 in the order written (the file is compiled without contraction); pcdf, p_l and lpdf are fp32.
 // PHX_LIGHT_INCLUDE_ENVIRONMENT (w_env != nullptr): the environment is one more entry behind the mesh lights, with that weight; its interval
 // of the table goes to out.env_p.
-void light_power_table(const phx_scene& s, FlatScene& out, const double* w_env = nullptr) {
+// A light's weight is its area times `power[l]` (light_power_factors: what the materials and images contribute, kept with the committed scene so
+// that a geometry update rebuilds the table without reading either).
+void light_power_table(const std::vector<double>& power, FlatScene& out, const double* w_env = nullptr) {
   const size_t nm = out.lights.size(), nl = nm + (w_env ? 1u : 0u);  // mesh lights, table entries
-  std::vector<double> w(nl), img(3 * (size_t)s.num_textures, -1.0);  // img: an image's channel means, computed at its first use
+  std::vector<double> w(nl);
   bool finite = true; size_t npos = 0; double wsum = 0.0;
   for (size_t l = 0; l < nl; ++l) {
     if (l == nm) {
@@ -80,21 +82,7 @@ void light_power_table(const phx_scene& s, FlatScene& out, const double* w_env =
       wsum += w[l];
       break;
     }
-    const DevLight& L = out.lights[l];
-    double m[3] = {1.0, 1.0, 1.0};
-    if (const uint32_t t = s.materials[L.material].emission_uv_texture) {
-      double* mt = &img[3 * (size_t)(t - 1u)];
-      if (mt[0] < 0.0 || mt[0] != mt[0]) {  // (a NaN mean is recomputed: it stays NaN)
-        const phx_texture& T = s.textures[t - 1u];
-        const size_t nt = (size_t)T.width * T.height;
-        double sum[3] = {0.0, 0.0, 0.0};
-        for (size_t k = 0; k < nt; ++k) for (int c = 0; c < 3; ++c) sum[c] += std::fabs((double)T.texels[3 * k + c]);
-        for (int c = 0; c < 3; ++c) mt[c] = sum[c] / (double)nt;
-      }
-      for (int c = 0; c < 3; ++c) m[c] = mt[c];
-    }
-    const double er = std::fabs((double)L.ex), eg = std::fabs((double)L.ey), eb = std::fabs((double)L.ez);
-    w[l] = (double)L.area * ((0.2126 * er * m[0] + 0.7152 * eg * m[1]) + 0.0722 * eb * m[2]);
+    w[l] = (double)out.lights[l].area * power[l];
     if (!std::isfinite(w[l])) finite = false;
     if (w[l] > 0.0) ++npos;
     wsum += w[l];
@@ -114,6 +102,29 @@ void light_power_table(const phx_scene& s, FlatScene& out, const double* w_env =
     out.lights[l].lpdf = (1.0f / out.lights[l].area) * p;
   }
   if (w_env) out.env_p = out.light_pcdf[nm] - out.light_pcdf[nm - 1];  // (a scene has at least one mesh light)
+}
+
+// per mesh light: (0.2126 |e_r| m_r + 0.7152 |e_g| m_g) + 0.0722 |e_b| m_b, m the channel means of the image on its emission (1 without one)
+std::vector<double> light_power_factors(const phx_scene& s, const std::vector<DevLight>& lights) {
+  std::vector<double> power(lights.size()), img(3 * (size_t)s.num_textures, -1.0);  // img: an image's channel means, computed at its first use
+  for (size_t l = 0; l < lights.size(); ++l) {
+    const DevLight& L = lights[l];
+    double m[3] = {1.0, 1.0, 1.0};
+    if (const uint32_t t = s.materials[L.material].emission_uv_texture) {
+      double* mt = &img[3 * (size_t)(t - 1u)];
+      if (mt[0] < 0.0 || mt[0] != mt[0]) {  // (a NaN mean is recomputed: it stays NaN)
+        const phx_texture& T = s.textures[t - 1u];
+        const size_t nt = (size_t)T.width * T.height;
+        double sum[3] = {0.0, 0.0, 0.0};
+        for (size_t k = 0; k < nt; ++k) for (int c = 0; c < 3; ++c) sum[c] += std::fabs((double)T.texels[3 * k + c]);
+        for (int c = 0; c < 3; ++c) mt[c] = sum[c] / (double)nt;
+      }
+      for (int c = 0; c < 3; ++c) m[c] = mt[c];
+    }
+    const double er = std::fabs((double)L.ex), eg = std::fabs((double)L.ey), eb = std::fabs((double)L.ez);
+    power[l] = (0.2126 * er * m[0] + 0.7152 * eg * m[1]) + 0.0722 * eb * m[2];
+  }
+  return power;
 }
 
 // PHX_LIGHT_INCLUDE_ENVIRONMENT, the rule of include/phx_xpu.h: the importance g of every texel of the environment image T, the direction
@@ -163,67 +174,25 @@ void environment_tables(const phx_scene& s, FlatScene& out) {
   };
   const double G = build(false);
   if (!(G > 0.0) || !std::isfinite(G)) build(true);
+  out.fingerprint.env_mean = G / ((double)W * (double)H);
+}
+// the environment's weight in the selection table: the image's share env_mean = G / (W H) (environment_tables) times the area of the sphere
+// around the geometry's bounds — the one part of the environment's entry that moves with the geometry
+double environment_weight(const std::vector<float>& abc, double env_mean) {
   float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (size_t k = 0; k < out.abc.size(); ++k) { lo[k % 3] = std::min(lo[k % 3], out.abc[k]); hi[k % 3] = std::max(hi[k % 3], out.abc[k]); }
+  for (size_t k = 0; k < abc.size(); ++k) { lo[k % 3] = std::min(lo[k % 3], abc[k]); hi[k % 3] = std::max(hi[k % 3], abc[k]); }
   const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1], dz = (double)hi[2] - (double)lo[2];
   const double R = 0.5 * std::sqrt((dx * dx + dy * dy) + dz * dz);
-  out.env_w = ((((4.0 * kPiD) * R) * R) * (G / ((double)W * (double)H))) * (kPiD / 2.0);
+  return ((((4.0 * kPiD) * R) * R) * env_mean) * (kPiD / 2.0);
 }
 
-}  // namespace
-
-int flatten_camera(const phx_camera& c, DevScene& sc, std::string& err) {
-  auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
-  // (camera_t's constructor leaves focal_distance uninitialised, entities/camera.hpp:31-36: it means something only behind a lens)
-  if (!(std::fabs(c.aperture_radius) <= FLT_MAX) || (c.aperture_radius != 0.0f && !(std::fabs(c.focal_distance) <= FLT_MAX)))
-    return refuse("camera: aperture radius / focal distance not finite");
-  if (c.film_width == 0 || c.film_height == 0 || c.film_width > 65535 || c.film_height > 65535)
-    return refuse("film size out of range");
-  std::memcpy(sc.cam_m, c.to_world, sizeof(sc.cam_m));
-  sc.zoom = 1.12f * std::tan(c.fov * 0.5f);  // camera.hpp:113
-  sc.stepx = 1.0f / (float)c.film_width; sc.stepy = 1.0f / (float)c.film_height;
-  sc.ratio = (float)c.film_width / (float)c.film_height;
-  sc.width = c.film_width; sc.height = c.film_height;
-  sc.aperture_radius = c.aperture_radius; sc.focal_distance = c.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
-  return PHX_OK;
-}
-
-int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err) {
+// Which image lookups the scene's materials ask for, with their refusals: any_tex (some lobe reads an image at the hit's UV — a colour
+// texture or a mask — or some emitter's emission does), any_mask, any_emit_tex.  flatten_scene classifies the scene by them; flatten_geometry
+// refuses a scene whose classes are not the committed one's.
+int texture_classes(const phx_scene& s, bool& any_tex, bool& any_mask, bool& any_emit_tex, std::string& err) {
   auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
   auto material = [](uint32_t i) { return "material " + std::to_string(i); };
-  if (!s.meshes || !s.materials || s.num_materials == 0) return refuse("scene without meshes/materials");
-  {  // the camera's refusals come here, its fields at the end, where `out` has been reset: one function states both
-    DevScene checked{};
-    if (const int rc = flatten_camera(s.camera, checked, err)) return rc;
-  }
-  if (s.environment_material >= (int32_t)s.num_materials) return refuse("environment material out of range");
-  // the packed word: the triangle pick in the low byte, the light's selection above it, the environment's bit above that.  Valid: 0, 1, 0x101 and 0x301
-  if (PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) > PHX_LIGHTS_BY_AREA) return refuse("unknown light_sampling");
-  if (PHX_LIGHT_SELECTION(opt.light_sampling) & ~(uint32_t)(PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT))
-    return refuse("unknown light_sampling: bits above PHX_LIGHT_INCLUDE_ENVIRONMENT");
-  const bool lights_by_area = PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) == PHX_LIGHTS_BY_AREA;
-  const bool lights_by_power = (opt.light_sampling & PHX_LIGHT_SELECT_BY_POWER) != 0;
-  const bool lights_env = PHX_LIGHT_ENVIRONMENT(opt.light_sampling) != 0;
-  if (lights_by_power && !lights_by_area) return refuse("light_sampling: PHX_LIGHT_SELECT_BY_POWER needs PHX_LIGHTS_BY_AREA");
-  if (lights_env && !lights_by_power) return refuse("light_sampling: PHX_LIGHT_INCLUDE_ENVIRONMENT needs PHX_LIGHT_SELECT_BY_POWER");
-
-  // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
-  // non-emitting materials may carry one (an emitter's image is on its emission: emission_uv_texture)
-  if (s.num_textures && !s.textures) return refuse("scene with textures but a null texture table");
-  uint64_t total_texels = 0;
-  for (uint32_t t = 0; t < s.num_textures; ++t) {
-    const phx_texture& T = s.textures[t];
-    const std::string texture = "texture " + std::to_string(t);
-    if (T.width == 0 || T.height == 0) return refuse(texture + " has zero size");
-    if (T.width > 65536u || T.height > 65536u || (uint64_t)T.width * T.height > (1ull << 26))
-      return refuse(texture + " too large (at most 65536 x 65536 and 2^26 texels)");
-    if (!T.texels) return refuse(texture + " without texels");
-    if (T.filter > PHX_TEX_CLOSEST || T.swrap > PHX_WRAP_BLACK || T.twrap > PHX_WRAP_BLACK) return refuse(texture + " with an unknown filter or wrap mode");
-    total_texels += (uint64_t)T.width * T.height;
-  }
-  if (total_texels > (1ull << 30)) return refuse("textures too large (at most 2^30 texels in all)");
-  bool any_tex = false, any_mask = false;  // any_tex: some lobe reads an image at the hit's UV (colour texture or mask), or some emitter's emission does
-  bool any_emit_tex = false;
+  any_tex = any_mask = any_emit_tex = false;
   for (uint32_t i = 0; i < s.num_materials; ++i) {
     const phx_material& m = s.materials[i];
     for (uint32_t k = 0; k < m.num_lobes && k < PHX_MAX_LOBES; ++k) {
@@ -257,22 +226,21 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
       any_tex = any_emit_tex = true;
     }
   }
-  // a constant sky is served by cosine-weighted BSDF sampling; the refusal also keeps the option out of every kernel without the image lookup
-  if (lights_env && (s.environment_material < 0 || !s.materials[s.environment_material].emission_texture))
-    return refuse("light_sampling: PHX_LIGHT_INCLUDE_ENVIRONMENT needs an environment material with an emission_texture");
+  return PHX_OK;
+}
 
-  out = FlatScene{};
+// The geometry half of flattening: the triangles in scene_t::triangles() order with their material words, the vertex normals of a scene
+// with smooth faces, the corner UVs (with_uv), and per emissive face set a light with its triangles, its area and — by_area — its area CDF.
+// is_emitter: per material.  `out` has been reset and out.any_smooth is set.
+int walk_geometry(const phx_scene& s, const std::vector<uint8_t>& is_emitter, bool with_uv, bool lights_by_area, FlatScene& out, std::string& err) {
+  auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
   for (uint32_t mi = 0; mi < s.num_meshes; ++mi) {
     const phx_mesh& m = s.meshes[mi];
-    for (uint32_t f = 0; f < m.num_faces; ++f) if (m.smooth && m.smooth[f]) out.any_smooth = true;
-  }
-  for (uint32_t mi = 0; mi < s.num_meshes; ++mi) {
-    const phx_mesh& m = s.meshes[mi];
-    if (!m.vertices || !m.faces || (m.num_sets && !m.sets) || (any_tex && m.num_uvs && !m.uvs)) return refuse("mesh with null arrays");
+    if (!m.vertices || !m.faces || (m.num_sets && !m.sets) || (with_uv && m.num_uvs && !m.uvs)) return refuse("mesh with null arrays");
     for (uint32_t si = 0; si < m.num_sets; ++si) {
       const phx_face_set& fs = m.sets[si];
-      if (fs.material >= s.num_materials) return refuse("face set material out of range");
-      const bool emitter = s.materials[fs.material].is_emitter != 0;
+      if (fs.material >= is_emitter.size()) return refuse("face set material out of range");
+      const bool emitter = is_emitter[fs.material] != 0;
       DevLight L{(uint32_t)out.light_tris.size(), 0, 0.0f, fs.material, 0.0f, 0.0f, 0.0f, 0.0f};
       for (uint32_t k = 0; k < fs.num_faces; ++k) {
         const uint32_t f = fs.faces[k];
@@ -294,7 +262,7 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
           }
           out.prim_normals.insert(out.prim_normals.end(), nn, nn + 9);
         }
-        if (any_tex) {  // mesh_t::shading_parameters (mesh.cpp:239-257): UV indices per vertex or per face corner, like the normals; no UVs: (0, 0)
+        if (with_uv) {  // mesh_t::shading_parameters (mesh.cpp:239-257): UV indices per vertex or per face corner, like the normals; no UVs: (0, 0)
           float2 uv[3] = {make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f), make_float2(0.0f, 0.0f)};
           if (m.num_uvs) {
             const bool per_vertex = (m.flags & PHX_MESH_UV_PER_VERTEX) != 0;
@@ -324,6 +292,93 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
   }
   if (out.prim_material.empty()) return refuse("scene has no triangles");
   if (out.lights.empty()) return refuse("scene has no emissive face set (reference underflows nlights-1, SURVEY A-19)");
+  return PHX_OK;
+}
+
+// Everything of the light table that hangs on geometry, from the lights walk_geometry left (areas, CDFs) and the committed scene's
+// fingerprint (emissions, power factors, the environment's share): per light the pick pdf and the emission of its material, as k_shade
+// evaluated them per sample until round 2; then the selection table under PHX_LIGHT_SELECT_BY_POWER, with the environment's entry.
+void light_tables(FlatScene& out, const GeometryFingerprint& fp, bool lights_by_power, bool lights_env) {
+  const float nlf = (float)out.lights.size();
+  for (size_t l = 0; l < out.lights.size(); ++l) {
+    DevLight& L = out.lights[l];
+    L.lpdf = (1.0f / L.area) / nlf;
+    L.ex = fp.lights[l].ex; L.ey = fp.lights[l].ey; L.ez = fp.lights[l].ez;
+  }
+  if (lights_env) { out.env_w = environment_weight(out.abc, fp.env_mean); light_power_table(fp.light_power, out, &out.env_w); }
+  else if (lights_by_power) light_power_table(fp.light_power, out);
+}
+
+void scan_smooth(const phx_scene& s, FlatScene& out) {
+  for (uint32_t mi = 0; mi < s.num_meshes; ++mi) {
+    const phx_mesh& m = s.meshes[mi];
+    for (uint32_t f = 0; f < m.num_faces; ++f) if (m.smooth && m.smooth[f]) out.any_smooth = true;
+  }
+}
+
+}  // namespace
+
+int flatten_camera(const phx_camera& c, DevScene& sc, std::string& err) {
+  auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
+  // (camera_t's constructor leaves focal_distance uninitialised, entities/camera.hpp:31-36: it means something only behind a lens)
+  if (!(std::fabs(c.aperture_radius) <= FLT_MAX) || (c.aperture_radius != 0.0f && !(std::fabs(c.focal_distance) <= FLT_MAX)))
+    return refuse("camera: aperture radius / focal distance not finite");
+  if (c.film_width == 0 || c.film_height == 0 || c.film_width > 65535 || c.film_height > 65535)
+    return refuse("film size out of range");
+  std::memcpy(sc.cam_m, c.to_world, sizeof(sc.cam_m));
+  sc.zoom = 1.12f * std::tan(c.fov * 0.5f);  // camera.hpp:113
+  sc.stepx = 1.0f / (float)c.film_width; sc.stepy = 1.0f / (float)c.film_height;
+  sc.ratio = (float)c.film_width / (float)c.film_height;
+  sc.width = c.film_width; sc.height = c.film_height;
+  sc.aperture_radius = c.aperture_radius; sc.focal_distance = c.focal_distance;  // thin lens iff aperture_radius != 0 (camera_t::is_pinhole)
+  return PHX_OK;
+}
+
+int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err) {
+  auto refuse = [&err](std::string why) { err = std::move(why); return (int)PHX_ERR_ARG; };
+  if (!s.meshes || !s.materials || s.num_materials == 0) return refuse("scene without meshes/materials");
+  {  // the camera's refusals come here, its fields at the end, where `out` has been reset: one function states both
+    DevScene checked{};
+    if (const int rc = flatten_camera(s.camera, checked, err)) return rc;
+  }
+  if (s.environment_material >= (int32_t)s.num_materials) return refuse("environment material out of range");
+  // the packed word: the triangle pick in the low byte, the light's selection above it, the environment's bit above that.  Valid: 0, 1, 0x101 and 0x301
+  if (PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) > PHX_LIGHTS_BY_AREA) return refuse("unknown light_sampling");
+  if (PHX_LIGHT_SELECTION(opt.light_sampling) & ~(uint32_t)(PHX_LIGHT_SELECT_BY_POWER | PHX_LIGHT_INCLUDE_ENVIRONMENT))
+    return refuse("unknown light_sampling: bits above PHX_LIGHT_INCLUDE_ENVIRONMENT");
+  const bool lights_by_area = PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) == PHX_LIGHTS_BY_AREA;
+  const bool lights_by_power = (opt.light_sampling & PHX_LIGHT_SELECT_BY_POWER) != 0;
+  const bool lights_env = PHX_LIGHT_ENVIRONMENT(opt.light_sampling) != 0;
+  if (lights_by_power && !lights_by_area) return refuse("light_sampling: PHX_LIGHT_SELECT_BY_POWER needs PHX_LIGHTS_BY_AREA");
+  if (lights_env && !lights_by_power) return refuse("light_sampling: PHX_LIGHT_INCLUDE_ENVIRONMENT needs PHX_LIGHT_SELECT_BY_POWER");
+
+  // image textures: the table must be well formed whether or not a lobe uses it; a lobe's texture must exist, and only surface closures of
+  // non-emitting materials may carry one (an emitter's image is on its emission: emission_uv_texture)
+  if (s.num_textures && !s.textures) return refuse("scene with textures but a null texture table");
+  uint64_t total_texels = 0;
+  for (uint32_t t = 0; t < s.num_textures; ++t) {
+    const phx_texture& T = s.textures[t];
+    const std::string texture = "texture " + std::to_string(t);
+    if (T.width == 0 || T.height == 0) return refuse(texture + " has zero size");
+    if (T.width > 65536u || T.height > 65536u || (uint64_t)T.width * T.height > (1ull << 26))
+      return refuse(texture + " too large (at most 65536 x 65536 and 2^26 texels)");
+    if (!T.texels) return refuse(texture + " without texels");
+    if (T.filter > PHX_TEX_CLOSEST || T.swrap > PHX_WRAP_BLACK || T.twrap > PHX_WRAP_BLACK) return refuse(texture + " with an unknown filter or wrap mode");
+    total_texels += (uint64_t)T.width * T.height;
+  }
+  if (total_texels > (1ull << 30)) return refuse("textures too large (at most 2^30 texels in all)");
+  bool any_tex = false, any_mask = false, any_emit_tex = false;
+  if (const int rc = texture_classes(s, any_tex, any_mask, any_emit_tex, err)) return rc;
+  // a constant sky is served by cosine-weighted BSDF sampling; the refusal also keeps the option out of every kernel without the image lookup
+  if (lights_env && (s.environment_material < 0 || !s.materials[s.environment_material].emission_texture))
+    return refuse("light_sampling: PHX_LIGHT_INCLUDE_ENVIRONMENT needs an environment material with an emission_texture");
+
+  out = FlatScene{};
+  GeometryFingerprint& fp = out.fingerprint;
+  fp.is_emitter.resize(s.num_materials);
+  for (uint32_t i = 0; i < s.num_materials; ++i) fp.is_emitter[i] = s.materials[i].is_emitter != 0;
+  scan_smooth(s, out);
+  if (const int rc = walk_geometry(s, fp.is_emitter, any_tex, lights_by_area, out, err)) return rc;
 
   // sheen_L5: the first sheen lobe of the material table (bsdf.h)
   float L5 = 0.0f; bool have = false;
@@ -342,15 +397,14 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
   for (uint32_t i = 0; i < s.num_materials; ++i)
     for (uint32_t k = 0; k < mats[i].num_lobes; ++k) if (mats[i].lobes[k].fac_mode >= PHX_FAC_TEX_B) out.mat_masked[i] = 1;
 
-  {  // per light: the pick pdf and the emission of its material, as k_shade evaluated them per sample until round 2
-    const float nlf = (float)out.lights.size();
-    for (auto& L : out.lights) {
-      L.lpdf = (1.0f / L.area) / nlf;
-      L.ex = mats[L.material].ex; L.ey = mats[L.material].ey; L.ez = mats[L.material].ez;
-    }
-  }
-  if (lights_env) { environment_tables(s, out); light_power_table(s, out, &out.env_w); }
-  else if (lights_by_power) light_power_table(s, out);
+  // the lights' tables (light_tables), from the fingerprint a geometry update will read them from again
+  fp.lights = out.lights;
+  for (auto& L : fp.lights) { L.ex = mats[L.material].ex; L.ey = mats[L.material].ey; L.ez = mats[L.material].ez; }
+  if (lights_by_power) fp.light_power = light_power_factors(s, fp.lights);
+  if (lights_env) environment_tables(s, out);
+  light_tables(out, fp, lights_by_power, lights_env);
+  fp.prim_material = out.prim_material;
+  fp.any_smooth = out.any_smooth; fp.any_tex = any_tex; fp.any_mask = any_mask; fp.any_emit_tex = any_emit_tex;
 
   // the environment's image, and every texture's texels as float4 (one 16-byte load per texel) behind a small table
   DevScene& sc = out.scene;
@@ -394,6 +448,38 @@ int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, st
   sc.num_lights = (uint32_t)out.lights.size();
   sc.max_depth = opt.path_depth;
   return flatten_camera(s.camera, sc, err);  // (accepted above)
+}
+
+int flatten_geometry(const phx_scene& s, const phx_options& opt, const GeometryFingerprint& fp, FlatScene& out, std::string& err) {
+  auto refuse = [&err](std::string why) { err = "update_geometry: " + std::move(why); return (int)PHX_ERR_ARG; };
+  if (!s.meshes || !s.materials || s.num_materials != fp.is_emitter.size()) return refuse("the scene's material table is not the committed scene's");
+  bool any_tex = false, any_mask = false, any_emit_tex = false;
+  if (const int rc = texture_classes(s, any_tex, any_mask, any_emit_tex, err)) return rc;
+  if (any_tex != fp.any_tex || any_mask != fp.any_mask || any_emit_tex != fp.any_emit_tex) return refuse("the texture classes (any_tex) differ from the committed scene's");
+  out = FlatScene{};
+  scan_smooth(s, out);
+  if (out.any_smooth != fp.any_smooth) return refuse("any_smooth differs from the committed scene's");
+  const bool lights_by_area = PHX_LIGHT_SAMPLING_MODE(opt.light_sampling) == PHX_LIGHTS_BY_AREA;
+  if (const int rc = walk_geometry(s, fp.is_emitter, false, lights_by_area, out, err)) return rc;
+  if (out.prim_material.size() != fp.prim_material.size())
+    return refuse("the triangle count differs from the committed scene's (" + std::to_string(out.prim_material.size()) + " for " + std::to_string(fp.prim_material.size()) + ")");
+  for (size_t p = 0; p < out.prim_material.size(); ++p)
+    if (out.prim_material[p] != fp.prim_material[p]) return refuse("the material word of primitive " + std::to_string(p) + " differs from the committed scene's");
+  if (out.lights.size() != fp.lights.size()) return refuse("the number of lights differs from the committed scene's");
+  for (size_t l = 0; l < out.lights.size(); ++l) {
+    if (out.lights[l].num_tris != fp.lights[l].num_tris) return refuse("the triangle count of light " + std::to_string(l) + " differs from the committed scene's");
+    if (out.lights[l].material != fp.lights[l].material) return refuse("the material of light " + std::to_string(l) + " differs from the committed scene's");
+  }
+  // one pass over the vertices: the finiteness check and the geometry's bounds (fp32 min / max, what k_prim_bounds gives: the summary's)
+  float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  const float* v = out.abc.data();
+  for (size_t k = 0, n = out.abc.size() / 3; k < n; ++k, v += 3) {
+    if (!(std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]))) return refuse("vertex " + std::to_string(k % 3) + " of primitive " + std::to_string(k / 3) + " is not finite");
+    for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
+  }
+  for (int a = 0; a < 3; ++a) { out.bounds[a] = lo[a]; out.bounds[3 + a] = hi[a]; }
+  light_tables(out, fp, (opt.light_sampling & PHX_LIGHT_SELECT_BY_POWER) != 0, PHX_LIGHT_ENVIRONMENT(opt.light_sampling) != 0);
+  return PHX_OK;
 }
 
 }  // namespace phx

@@ -15,6 +15,17 @@
 
 namespace phx {
 
+// What a geometry update (flatten_geometry, phx_dev_update_geometry) needs of the committed scene besides the moved scene itself, so that it
+// reads no material, lobe, texel or environment image again.  Host memory only; flatten_scene fills it, the device keeps it beside its tables.
+struct GeometryFingerprint {
+  std::vector<uint32_t> prim_material;  // per primitive: material | smooth << 31
+  std::vector<uint8_t> is_emitter;      // per material
+  std::vector<DevLight> lights;         // first_tri, num_tris, material and the material's emission as committed (area and lpdf are geometry's)
+  std::vector<double> light_power;      // PHX_LIGHT_SELECT_BY_POWER: per light, its weight in the selection table over its area
+  double env_mean = 0.0;                // PHX_LIGHT_INCLUDE_ENVIRONMENT: G / (W H) of the environment image
+  bool any_smooth = false, any_tex = false, any_mask = false, any_emit_tex = false;
+};
+
 struct FlatScene {
   // triangles in scene_t::triangles() order: mesh order x face-set order (scene.cpp:58-62, mesh.cpp:118-128)
   std::vector<float> abc;               // 9 floats per primitive
@@ -42,6 +53,8 @@ struct FlatScene {
   // every word of DevScene that needs no device: camera, film, environment, light count, any_tex, diffuse_only, any_per_hit, max_depth.
   // The pointers and the tree's words stay zero for the commit stage.
   DevScene scene{};
+  GeometryFingerprint fingerprint;      // flatten_scene only
+  float bounds[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};  // flatten_geometry only: the fp32 min / max of every vertex, lo.xyz hi.xyz
 };
 
 // The one statement of how a phx_camera becomes DevScene's camera fields (cam_m, zoom, stepx, stepy, ratio, width, height, aperture_radius,
@@ -50,5 +63,13 @@ int flatten_camera(const phx_camera& c, DevScene& sc, std::string& err);
 
 // PHX_OK, or PHX_ERR_ARG with the reason in `err`; `out` is meaningful only after PHX_OK
 int flatten_scene(const phx_scene& s, const phx_options& opt, FlatScene& out, std::string& err);
+
+// The geometry half alone, for a scene that is the committed one (`fp`: its fingerprint, `opt`: its options) with other vertex positions
+// and normals: fills abc, prim_material, prim_normals, any_smooth, lights, light_tris, light_cdf, light_pcdf, env_p, env_w and bounds — by the code
+// flatten_scene runs, so they are word for word flatten_scene's of the moved scene — and nothing else.  PHX_ERR_ARG, with the reason in
+// `err`, when the triangle count, a primitive's material word, the number of lights, a light's triangle count or material, any_smooth or the texture
+// classes differ from the fingerprint's, for a vertex that is not finite, and for geometry flatten_scene refuses.  The face index arrays
+// are not compared: the triangles given are the triangles rendered.
+int flatten_geometry(const phx_scene& s, const phx_options& opt, const GeometryFingerprint& fp, FlatScene& out, std::string& err);
 
 }  // namespace phx

@@ -684,3 +684,38 @@ def sun_floor(width=32, height=32, image=None, mapping=abi.ENV_LATLONG_Y_UP, loo
     img = sun_and_sky() if image is None else image
     return SceneDesc([floor, hidden], mats, CameraDesc(width, height, 0.6 if look == "down" else 1.9, to_world), environment_material=2, name="sun_floor",
                      textures=[TextureDesc(img, abi.TEX_CLOSEST, abi.WRAP_PERIODIC, abi.WRAP_CLAMP)])
+
+
+# ---- moved geometry (HipDevice.update_geometry) -----------------------------------------------------------------------------------
+def _moved(scene, meshes, name):
+    """a SceneDesc that shares everything of `scene` but its meshes"""
+    return replace(scene, meshes=meshes, name=name)
+
+
+def transformed(scene, transforms):
+    """`scene` with the meshes named in `transforms` moved: {mesh index: 3 x 4 matrix [m0 m1 m2 t]} -> a new SceneDesc; the input is left alone
+    and the meshes not named are shared with it.  Vertices are computed in float32 as (m0 x + m1 y) + m2 z + t, one rounding per
+    operation and no contraction, so every host computes the same bits; normals by the rotation part m0 m1 m2 in the same order (a
+    matrix that scales unevenly leaves them unnormalised and skewed: pass rotations, or recompute the normals)."""
+    meshes = list(scene.meshes)
+    for index, matrix in transforms.items():
+        m = np.asarray(matrix, np.float32).reshape(3, 4)
+        src = meshes[index]
+
+        def apply(p, translate):
+            out = ((p[:, 0:1] * m[None, :, 0]).astype(np.float32) + (p[:, 1:2] * m[None, :, 1]).astype(np.float32)).astype(np.float32)
+            out = (out + (p[:, 2:3] * m[None, :, 2]).astype(np.float32)).astype(np.float32)
+            return (out + m[None, :, 3]).astype(np.float32) if translate else out
+        meshes[index] = replace(src, vertices=apply(src.vertices, True), normals=apply(src.normals, False) if len(src.normals) else src.normals)
+    return _moved(scene, meshes, scene.name + "+moved")
+
+
+def wobbled(scene, amplitude, seed=0):
+    """`scene` with every vertex of every mesh displaced by an independent offset, uniform in [-amplitude, amplitude]^3 and drawn from
+    `seed` -> a new SceneDesc; the input is left alone.  Vertices shared by faces stay shared (a mesh does not tear); normals are kept."""
+    rng = np.random.default_rng(seed)
+    meshes = []
+    for src in scene.meshes:
+        d = rng.uniform(-amplitude, amplitude, src.vertices.shape).astype(np.float32)
+        meshes.append(replace(src, vertices=(src.vertices + d).astype(np.float32)))
+    return _moved(scene, meshes, scene.name + "+wobbled")

@@ -309,6 +309,28 @@ class HipDevice:
         _check(self._lib, self._lib.phx_dev_set_camera(self._h, C.byref(c)), "phx_dev_set_camera")
         self._camera = camera
 
+    def update_geometry(self, scene_desc, mode="refit"):
+        """New vertex positions and normals for the preprocessed scene (phx_dev_update_geometry): scene_desc is the
+        preprocessed scene with moved vertices (scenes.transformed, scenes.wobbled, or a SceneDesc of the caller's with the same faces,
+        face sets, materials and textures).  mode "refit" keeps the tree's topology and recomputes its boxes; "rebuild" builds a new
+        tree.  Either way the next frame is, bit for bit, what a device freshly preprocessed with scene_desc renders, and no material,
+        texture or environment table is read or uploaded again.  The camera stays the device's (the last set_camera's, else the
+        preprocessed scene's).  start() takes scene_desc from now on; films accumulated before the update are stale.  -> the summary as a
+        dict: mode, triangles, nodes, levels, lights, light_triangles, bounds (6 floats), delta."""
+        modes = {"refit": abi.UPDATE_REFIT, "rebuild": abi.UPDATE_REBUILD}
+        if mode not in modes:
+            raise ValueError(f"update_geometry: mode must be one of {sorted(modes)}, not {mode!r}")
+        s, keep = scene_desc.pack()
+        u, out = abi.GeometryUpdate(mode=modes[mode]), abi.GeometrySummary()
+        _check(self._lib, self._lib.phx_dev_update_geometry(self._h, C.byref(s), C.byref(u), C.byref(out)), "phx_dev_update_geometry")
+        self._scene = scene_desc
+        return {k: (list(getattr(out, k)) if k == "bounds" else getattr(out, k)) for k, _ in out._fields_}
+
+    def update_geometry_times(self):
+        """milliseconds of the last update_geometry(), host clock: dict of flatten (the host's pass over the moved scene), upload, device
+        (the refit or rebuild and the tables' kernels, to the last synchronise) and call"""
+        return self._times("phx_dev_update_geometry_times", 4, ("flatten", "upload", "device", "call"))
+
     def start(self, scene_desc, frame):
         assert scene_desc is self._scene, "start() must get the scene that was preprocessed"
         f = abi.Frame()
@@ -1121,6 +1143,34 @@ def render_camera_path(scene_desc, cameras, spp, frames_per_camera=1, seed=1, gu
                 else:
                     yield out, None, k, moved, dev.display(out, **display)
             previous, guides_before = camera, guides
+    finally:
+        dev.close()
+
+
+def render_animation(scene_descs, spp, mode="refit", rebuild_every=0, denoise=None, display=None, seed=1, pps=1, depth=9, tile_size=32, **options):
+    """Moving geometry on ONE device: the first scene of `scene_descs` is preprocessed, every later one — the same scene
+    with moved vertices — is taken by HipDevice.update_geometry(mode); with rebuild_every = k > 0 every k-th update is a "rebuild"
+    whatever `mode` says.  One FRESH film of `spp` samples is rendered per scene, with sampler seed `seed`: nothing is accumulated or
+    reprojected across geometry (a film of the old geometry says nothing about the new one).  A generator: per scene it yields (film,
+    summary, index) — film (H, W, 11) f32 with normals and moments, summary the update's dict (None for the first scene) — and with
+    display (..., image).  denoise, display: dicts of HipDevice.denoise's and HipDevice.display's settings; options: xpu.Options'."""
+    dev = HipDevice.make(Options(samples_per_pixel=spp, paths_per_sample=pps, path_depth=depth, **options))
+    try:
+        for index, scene_desc in enumerate(scene_descs):
+            summary = None
+            if index == 0:
+                dev.preprocess(scene_desc)
+            else:
+                summary = dev.update_geometry(scene_desc, "rebuild" if rebuild_every > 0 and index % rebuild_every == 0 else mode)
+            W, H = scene_desc.camera.width, scene_desc.camera.height
+            film = Film(W, H, 4, True, True, False)
+            dev.start(scene_desc, FrameState(seed, Tiles.make(W, H, tile_size), film, native_sink=True))
+            dev.join()
+            out = film.data if denoise is None else dev.denoise(film.data, spp, 4, True, False, **denoise)
+            if display is None:
+                yield out, summary, index
+            else:
+                yield out, summary, index, dev.display(out, **display)
     finally:
         dev.close()
 
