@@ -449,7 +449,7 @@ __global__ void __launch_bounds__(64) k_collapse(Tree2 T, SceneGrid grid, const 
       R.e1x = t[6] - t[0]; R.e1y = t[7] - t[1]; R.e1z = t[8] - t[2];
       R.prim = p; R.material = prim_material[p]; R.pad1 = 0; R.pad2[0] = R.pad2[1] = R.pad2[2] = R.pad2[3] = 0;
       pool[ei].tri = R;
-      if (elem_of_prim) elem_of_prim[p] = ei;  // the shade kernels find a smooth face's vertex normals by the HIT's pool index (device.cpp: elem_normals)
+      if (elem_of_prim) elem_of_prim[p] = ei;  // the shade kernels find a smooth face's vertex normals by the HIT's pool index (scene_commit.cpp: elem_normals)
     }
   }
   pool[n8].node = nd;

@@ -1,8 +1,9 @@
-// device_internal.h — what the host units of the C ABI share: device.cpp (the device object's life cycle, preprocess), frame_driver.cpp (the
-// frame), stage_hooks.cpp (the scene-reading stage hooks) and film_calls.cpp (the film calls no frame launches).
+// device_internal.h — what the host units of the C ABI share: device.cpp (the device object's life cycle, the entry points), scene_commit.cpp
+// (what preprocess and a geometry update write to the device), frame_driver.cpp (the frame), stage_hooks.cpp (the scene-reading stage hooks)
+// and film_calls.cpp (the film calls no frame launches).
 //
-// The last error, the HIP wrappers (HIPCHK, DeviceScope, DevBuf, PinnedBuf), guarded(), the clock, Staging, PathQueues and struct phx_device
-// itself.  Not installed and no part of the ABI: include/phx_xpu.h knows phx_device by name only.
+// The last error, the HIP wrappers (HIPCHK, DeviceScope, DevBuf, PinnedBuf), SceneTables, guarded(), the clock, Staging, PathQueues and struct
+// phx_device itself.  Not installed and no part of the ABI: include/phx_xpu.h knows phx_device by name only.
 #pragma once
 #include "../../include/phx_xpu.h"
 #include "frame_plan.h"
@@ -84,6 +85,29 @@ struct PinnedBuf {
   ~PinnedBuf() { release(); }
 };
 
+// The committed scene as the device holds it: its buffers, and the host facts that describe them.  scene_commit.cpp is their only writer
+// (commit_scene, update_scene_geometry); the stage hooks and phx_dev_copy_bvh read them.
+struct SceneTables {
+  DevBuf<PoolElem> d_pool; DevBuf<uint32_t> d_prim_material; DevBuf<float> d_elem_normals; DevBuf<float4> d_elem_shade; DevBuf<uint2> d_spill;
+  DevBuf<DevMaterial> d_materials; DevBuf<DevMatLite> d_mat_lite; DevBuf<DevLight> d_lights; DevBuf<DevLightTri> d_light_tris;
+  // image textures: held only while the preprocessed scene has a textured lobe
+  DevBuf<float2> d_elem_uv; DevBuf<DevTexture> d_textures; DevBuf<float4> d_texels; DevBuf<uint32_t> d_lobe_tex; DevBuf<DevTexScene> d_tex_scene;
+  DevBuf<uint32_t> d_mat_emit_tex;  // per material: the image on its emission + 1 (scenes with emitter images only)
+  DevBuf<float> d_env_cdf;          // PHX_LIGHT_INCLUDE_ENVIRONMENT: the environment's direction tables (FlatScene::env_cdf)
+  uint32_t num_materials = 0, num_textures = 0;
+  std::vector<uint8_t> mat_masked;  // per material: some lobe's factor is an image mask (the untextured KAT hooks refuse those)
+  uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission
+  GeometryFingerprint geometry;  // of the committed scene (host memory): what phx_dev_update_geometry accepts a moved scene against
+  // the tree's statistics (build_tree)
+  uint64_t bvh_nodes = 0, bvh_bytes = 0, num_triangles = 0;
+  double bvh_cost_model = 0; uint32_t bvh_built_on_device = 0;
+  uint64_t bytes() const {  // every buffer above: a new one is added here, beside its declaration
+    return d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
+           d_lights.bytes() + d_light_tris.bytes() + d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes() +
+           d_mat_emit_tex.bytes() + d_env_cdf.bytes();
+  }
+};
+
 // No C++ exception may cross the C ABI (the reference's own std::runtime_error cases become status codes): every entry
 // point that allocates or spawns runs its body through guarded().
 template <typename F>
@@ -138,21 +162,9 @@ struct phx_device {
   hipStream_t stream = nullptr;
   bool preprocessed = false;
 
-  // scene
-  phx::DevBuf<phx::PoolElem> d_pool; phx::DevBuf<uint32_t> d_prim_material; phx::DevBuf<float> d_elem_normals; phx::DevBuf<float4> d_elem_shade; phx::DevBuf<uint2> d_spill;
-  phx::DevBuf<phx::DevMaterial> d_materials; phx::DevBuf<phx::DevMatLite> d_mat_lite; phx::DevBuf<phx::DevLight> d_lights; phx::DevBuf<phx::DevLightTri> d_light_tris;
-  // image textures: held only while the preprocessed scene has a textured lobe
-  phx::DevBuf<float2> d_elem_uv; phx::DevBuf<phx::DevTexture> d_textures; phx::DevBuf<float4> d_texels; phx::DevBuf<uint32_t> d_lobe_tex; phx::DevBuf<phx::DevTexScene> d_tex_scene;
-  phx::DevBuf<uint32_t> d_mat_emit_tex;  // per material: the image on its emission + 1 (scenes with emitter images only)
-  phx::DevBuf<float> d_env_cdf;          // PHX_LIGHT_INCLUDE_ENVIRONMENT: the environment's direction tables (FlatScene::env_cdf)
+  phx::SceneTables tables;  // the committed scene's buffers and the host facts about them (scene_commit.cpp writes them)
   phx::DevScene scene{};
-  uint32_t num_materials = 0, num_textures = 0;
-  std::vector<uint8_t> mat_masked;  // per material: some lobe's factor is an image mask (the untextured KAT hooks refuse those)
-  uint32_t env_tex = 0, env_mapping = 0; float env_e[3] = {0.0f, 0.0f, 0.0f};  // the environment's image (texture + 1, 0 = none), mapping and emission
-  phx::GeometryFingerprint geometry;  // of the committed scene (host memory): what phx_dev_update_geometry accepts a moved scene against
-  phx::DevTexScene tex_scene{};       // the record in d_tex_scene as it was uploaded (an update changes env_p and elem_uv in it)
   double update_geometry_ms[4] = {};  // the last phx_dev_update_geometry: host flatten, uploads, device work, call
-  uint64_t bvh_nodes = 0, bvh_bytes = 0, num_triangles = 0;
   double preprocess_ms = 0, bvh_build_ms = 0;
 
   // pass buffers
@@ -188,9 +200,8 @@ struct phx_device {
   phx_stats stats{};
   phx::TracePlan plan{};
   uint64_t paths_in_flight = 0;
-  // the committed scene reads the barycentrics of a hit (commit_scene): the passes carry PassBuffers::hit_uv and the trace kernels run as UV = true
+  // the committed scene reads the barycentrics of a hit (scene_commit.cpp: commit_scene): the passes carry PassBuffers::hit_uv and the trace kernels run as UV = true
   bool hit_uv = false;
-  double bvh_cost_model = 0; uint32_t bvh_built_on_device = 0;
   enum class Launch { Trace, Primary, Shade, Pass /* begin-pass, film */ };
   struct Timed { size_t begin, end; Launch kind; };  // (event before, event behind, what ran between them)
   // The launches of a batch and the HIP events between them.  (Round 5 captured a batch's launches — memset, [begin-pass, camera rays,
@@ -227,9 +238,7 @@ struct phx_device {
   }
   // HBM held by this device object (phx_stats::device_bytes)
   uint64_t device_bytes() const {
-    return d_pool.bytes() + d_prim_material.bytes() + d_elem_normals.bytes() + d_elem_shade.bytes() + d_spill.bytes() + d_materials.bytes() + d_mat_lite.bytes() +
-           d_lights.bytes() + d_light_tris.bytes() + queues.bytes() + counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
-           d_elem_uv.bytes() + d_textures.bytes() + d_texels.bytes() + d_lobe_tex.bytes() + d_tex_scene.bytes() + d_mat_emit_tex.bytes() + d_env_cdf.bytes() +
+    return tables.bytes() + queues.bytes() + counters.bytes() + dstats.bytes() + pix_xy.bytes() + jitter.bytes() + acc.bytes() +
            w_acc.bytes() + w_xy.bytes() + sel_idx[0].bytes() + sel_idx[1].bytes() + sel_blocks.bytes();
   }
   // paths in flight this device may carry: up to 512 M (about 95 GB of queues + state: sized for 288 GB of HBM), but never more than 60 % of
@@ -256,6 +265,14 @@ struct phx_device {
 };
 
 namespace phx {
+
+// scene_commit.cpp: the two writers of the committed scene.  Each runs on its device (DeviceScope) with no frame running, and from its first
+// device write to its last line the device has NO scene (preprocessed == false).
+// Replaces the device's scene by `fs` (flatten_scene's).
+int commit_scene(phx_device* d, FlatScene& fs);
+// Brings the device's scene to the moved geometry `fs` (flatten_geometry's, accepted against d->tables.geometry); mode: PHX_UPDATE_REFIT /
+// PHX_UPDATE_REBUILD.  ms[1], ms[2]: the call's uploads and its device work.
+int update_scene_geometry(phx_device* d, FlatScene& fs, uint32_t mode, phx_geometry_summary* sum, double* ms);
 
 // Device copies of a stage hook's arrays.  in() uploads, out() allocates and remembers where the result goes, run() launches, waits and copies
 // back.  The first array enters the hook's device (after the hook's own argument checks, as ever), and the caller's device comes back when the

@@ -3,7 +3,7 @@
 // flatten_scene validates the scene (every caller-supplied index is checked here, and nowhere else), lays its triangles out in
 // scene_t::triangles() order, bakes the materials and the light table with the fp32 operations bit parity with the oracle depends on, and
 // classifies the scene for the shade kernels.  It makes no HIP call and touches no device: <hip/hip_runtime.h> is here for float2 / float4
-// alone, so the translation unit also compiles with a plain host compiler (tests/native/host_flatten.cpp).  device.cpp commits the result.
+// alone, so the translation unit also compiles with a plain host compiler (tests/native/host_flatten.cpp).  scene_commit.cpp commits the result.
 #pragma once
 #include <hip/hip_runtime.h>
 

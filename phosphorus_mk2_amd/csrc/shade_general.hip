@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_G) __attribute__((amdgpu_waves
     // 1.2 of 42.7 ms: profiles/r03_q_prefetch_ab.log.)
     uint32_t next_i = 0, next_tri = 0xffffffffu; bool next_live = false;
     // the hit's barycentrics are read where something consumes them: the corner UVs' interpolation (TEX) and a smooth face's normal
-    const bool want_uv = TEX || sc.elem_normals != nullptr;  // wave-uniform; either one makes the scene's hit_uv stream exist (device.cpp)
+    const bool want_uv = TEX || sc.elem_normals != nullptr;  // wave-uniform; either one makes the scene's hit_uv stream exist (scene_commit.cpp)
     float next_t = 0.f; float2 next_uv = make_float2(0.f, 0.f);
     float4 next_a = make_float4(0.f, 0.f, 0.f, 0.f), next_b = next_a, next_S = next_a;
     const uint32_t nslices = (min((uint32_t)WINDOW, count - base) + 63u) >> 6;

@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(PHX_SHADE_BLOCK_D) __attribute__((amdgpu_waves
       const v3 p = o + d * u2f(h.x);       // hits.p = p + wi*d
       const v3 wo = -d;                    // hits.wi = -wi
       v3 n(S.x, S.y, S.z);
-      if ((pm >> 31) != 0) {  // a smooth face: the scene has one, so the trace kernels wrote pb.hit_uv (device.cpp: the scene's hit_uv flag)
+      if ((pm >> 31) != 0) {  // a smooth face: the scene has one, so the trace kernels wrote pb.hit_uv (scene_commit.cpp: the scene's hit_uv flag)
         const float2 uv = pb.hit_uv[i];
         n = shading_normal(sc, tri, true, v3(0.0f), v3(0.0f), uv.x, uv.y);
       }

@@ -45,48 +45,48 @@ int phx_dev_trace(phx_device* d, uint32_t n, const float* o, const float* dir, c
 
 int phx_dev_bsdf_f(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* wo3, float* f3) {
   return stage_hook(d, "bsdf_f", [&](Staging& s) -> int {
-    if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
-    if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_f: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
+    if (material >= d->tables.num_materials) return fail(PHX_ERR_ARG, "material out of range");
+    if (d->tables.mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_f: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
     if (n == 0) return PHX_OK;
     const size_t n3s = 3 * (size_t)n;
     const float *a = s.in(n3, n3s), *b = s.in(wi3, n3s), *c = s.in(wo3, n3s); float* f = s.out(f3, n3s);
-    return s.run([&] { launch_bsdf_f(d->stream, d->d_materials.p + material, n, a, b, c, f); });
+    return s.run([&] { launch_bsdf_f(d->stream, d->tables.d_materials.p + material, n, a, b, c, f); });
   });
 }
 
 int phx_dev_bsdf_sample(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* u2,
                         float* wo3, float* f3, float* pdf, uint32_t* flags) {
   return stage_hook(d, "bsdf_sample", [&](Staging& s) -> int {
-    if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
-    if (d->mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_sample: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
+    if (material >= d->tables.num_materials) return fail(PHX_ERR_ARG, "material out of range");
+    if (d->tables.mat_masked[material]) return fail(PHX_ERR_ARG, "bsdf_sample: the material has image-masked lobes, whose weights need the hit's (s, t) (see phx_dev_lobe_weights)");
     if (n == 0) return PHX_OK;
     const size_t n3s = 3 * (size_t)n;
     const float *a = s.in(n3, n3s), *b = s.in(wi3, n3s), *c = s.in(u2, 2 * (size_t)n);
     float *wo = s.out(wo3, n3s), *f = s.out(f3, n3s), *p = s.out(pdf, n); uint32_t* fl = s.out(flags, n);
-    return s.run([&] { launch_bsdf_sample(d->stream, d->d_materials.p + material, n, a, b, c, wo, f, p, fl); });
+    return s.run([&] { launch_bsdf_sample(d->stream, d->tables.d_materials.p + material, n, a, b, c, wo, f, p, fl); });
   });
 }
 
 int phx_dev_texture_lookup(phx_device* d, uint32_t texture, uint32_t n, const float* st, float* rgb) {
   return stage_hook(d, "texture_lookup", [&](Staging& s) -> int {
-    if (texture >= d->num_textures) return fail(PHX_ERR_ARG, "texture out of range (textures are kept only for scenes with a textured lobe)");
+    if (texture >= d->tables.num_textures) return fail(PHX_ERR_ARG, "texture out of range (textures are kept only for scenes with a textured lobe)");
     if (n == 0) return PHX_OK;
     if (!st || !rgb) return fail(PHX_ERR_ARG, "texture_lookup: null argument");
     const float* a = s.in(st, 2 * (size_t)n); float* o = s.out(rgb, 3 * (size_t)n);
-    return s.run([&] { launch_texture_lookup(d->stream, d->d_textures.p, d->d_texels.p, texture, n, a, o); });
+    return s.run([&] { launch_texture_lookup(d->stream, d->tables.d_textures.p, d->tables.d_texels.p, texture, n, a, o); });
   });
 }
 
 int phx_dev_lobe_weights(phx_device* d, uint32_t material, uint32_t n, const float* n3, const float* wi3, const float* st, float* w, uint32_t* kept) {
   return stage_hook(d, "lobe_weights", [&](Staging& s) -> int {
-    if (material >= d->num_materials) return fail(PHX_ERR_ARG, "material out of range");
+    if (material >= d->tables.num_materials) return fail(PHX_ERR_ARG, "material out of range");
     if (n == 0) return PHX_OK;
     const bool tex = (d->scene.any_tex & SC_TEX_LOBES) != 0;  // the scene's lobes read images: st is needed
     if (!n3 || !wi3 || !w || !kept || (tex && !st)) return fail(PHX_ERR_ARG, "lobe_weights: null argument");
     const float *a = s.in(n3, 3 * (size_t)n), *b = s.in(wi3, 3 * (size_t)n), *c = tex ? s.in(st, 2 * (size_t)n) : nullptr;
     float* o = s.out(w, 3 * PHX_MAX_LOBES * (size_t)n); uint32_t* k = s.out(kept, n);
     return s.run([&] {
-      launch_lobe_weights(d->stream, d->d_materials.p + material, tex ? d->d_textures.p : nullptr, d->d_texels.p, tex ? d->d_lobe_tex.p + 8 * (size_t)material : nullptr,
+      launch_lobe_weights(d->stream, d->tables.d_materials.p + material, tex ? d->tables.d_textures.p : nullptr, d->tables.d_texels.p, tex ? d->tables.d_lobe_tex.p + 8 * (size_t)material : nullptr,
                           n, a, b, c, o, k);
     });
   });
@@ -94,11 +94,11 @@ int phx_dev_lobe_weights(phx_device* d, uint32_t material, uint32_t n, const flo
 
 int phx_dev_environment_lookup(phx_device* d, uint32_t n, const float* dirs, float* rgb) {
   return stage_hook(d, "environment_lookup", [&](Staging& s) -> int {
-    if (!d->env_tex) return fail(PHX_ERR_ARG, "environment_lookup: the scene's environment has no image");
+    if (!d->tables.env_tex) return fail(PHX_ERR_ARG, "environment_lookup: the scene's environment has no image");
     if (n == 0) return PHX_OK;
     if (!dirs || !rgb) return fail(PHX_ERR_ARG, "environment_lookup: null argument");
     const float* a = s.in(dirs, 3 * (size_t)n); float* o = s.out(rgb, 3 * (size_t)n);
-    return s.run([&] { launch_environment_lookup(d->stream, d->d_textures.p, d->d_texels.p, d->env_tex - 1u, d->env_mapping, d->env_e[0], d->env_e[1], d->env_e[2], n, a, o); });
+    return s.run([&] { launch_environment_lookup(d->stream, d->tables.d_textures.p, d->tables.d_texels.p, d->tables.env_tex - 1u, d->tables.env_mapping, d->tables.env_e[0], d->tables.env_e[1], d->tables.env_e[2], n, a, o); });
   });
 }
 
@@ -130,7 +130,7 @@ int phx_dev_environment_sample(phx_device* d, uint32_t n, const float* u3, uint3
     const float* a = s.in(u3, 3 * (size_t)n);
     uint32_t *ol = s.out(light, n), *ot = s.out(texel, 2 * (size_t)n);
     float *os = s.out(st, 2 * (size_t)n), *od = s.out(dir, 3 * (size_t)n), *op = s.out(pdf, n), *oe = s.out(e, 3 * (size_t)n);
-    return s.run([&] { launch_environment_sample(d->stream, d->scene, d->env_e[0], d->env_e[1], d->env_e[2], n, a, ol, ot, os, od, op, oe); });
+    return s.run([&] { launch_environment_sample(d->stream, d->scene, d->tables.env_e[0], d->tables.env_e[1], d->tables.env_e[2], n, a, ol, ot, os, od, op, oe); });
   });
 }
 

@@ -753,7 +753,7 @@ void launch_trace(hipStream_t stream, const DevScene& sc, const PassBuffers& pb,
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, g, b, lds, stream, sc, pb, q, sq, do_closest, do_shadow, E.refill, ntop, levels, E.min_chunks, E.target_chunks);
   };
-  // UV: the pass has a barycentrics stream exactly when the committed scene reads them (device.cpp), so its presence picks the instantiation
+  // UV: the pass has a barycentrics stream exactly when the committed scene reads them (scene_commit.cpp), so its presence picks the instantiation
   with_flag(pb.hit_uv != nullptr, [&](auto UV) {
     constexpr bool uv = decltype(UV)::value;
     if (P.lds_levels < P.levels || trace_pool_is_wide(sc)) { if (P.packed) go(&k_trace<1024, true, true, uv>); else go(&k_trace<1024, true, false, uv>); }  // deep tree: 1024-thread workgroups, the stack's deep levels in HBM

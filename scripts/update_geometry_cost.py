@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """What a geometry update costs against a fresh preprocess, and what a refitted tree costs the traversal.
 
-    python scripts/update_geometry_cost.py [--scenes soup100k,soup1m,bmw500k,textured500k] [--runs 5] [--parent DIR] [--variants parent,preprocess] [--out profiles/NAME.log]
+    python scripts/update_geometry_cost.py [--scenes soup100k,soup1m,bmw500k,textured500k] [--runs 5] [--parent DIR] [--variants parent,preprocess]
+                                           [--motions rigid] [--out profiles/NAME.log]
 
 Per scene, every variant in a fresh process of its own, the variants alternating run by run; medians with the spread (min .. max):
 
   preprocess(moved)        the yardstick: phx_stats.preprocess_ms of a device that is handed the moved scene
   parent                   the same on another checkout of the project (--parent DIR, its library built: the commit this one is compared
                            with), run by that checkout's own Python package: preprocess is not meant to change
+  parent-rebuild, parent-refit   the two updates on that checkout likewise (rigid move only), each run just before this tree's
   update(rebuild)          HipDevice.update_geometry(moved, "rebuild"): the call's four timers
   update(refit)            HipDevice.update_geometry(moved, "refit"): the call's four timers
   trace after refit / rebuild   phx_stats.trace_ms of one frame (the kernels' HIP events) for a rigid move of one object and for wobbles of
@@ -26,6 +28,7 @@ sys.path.insert(0, os.environ.get("PHX_COST_TREE") or ROOT)  # (a child measurin
 
 SCENES = {"soup100k": ("soup", 100_000), "soup1m": ("soup", 1_000_000), "bmw500k": ("bmw_showroom", 500_000), "textured500k": ("textured_showroom", 500_000)}
 MOTIONS = ["rigid", "wobble1", "wobble5", "wobble20"]
+VARIANTS = ["parent", "preprocess", "parent-rebuild", "rebuild", "parent-refit", "refit"]  # in the order they alternate in
 W, H, SPP = 640, 360, 4
 
 
@@ -59,14 +62,15 @@ def child(name, variant, motion):
     dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=SPP, paths_per_sample=1, path_depth=5))
     out = {"scene": name, "variant": variant, "motion": motion}
     try:
-        if variant in ("preprocess", "parent"):
+        mode = variant.split("-")[-1]  # (parent-rebuild, parent-refit: the parent checkout's update)
+        if mode in ("preprocess", "parent"):
             dev.preprocess(sc)  # warm: code objects, allocations
             dev.preprocess(new)
             out["ms"] = dev.stats()["preprocess_ms"]
         else:
             dev.preprocess(sc)
-            dev.update_geometry(sc, variant)  # warm
-            dev.update_geometry(new, variant)
+            dev.update_geometry(sc, mode)  # warm
+            dev.update_geometry(new, mode)
             out.update(dev.update_geometry_times()); out["ms"] = out["call"]
         frames = []
         for seed in (1, 2, 3):
@@ -85,8 +89,9 @@ def main():
     ap.add_argument("--scenes", default="soup100k,soup1m,bmw500k")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out")
-    ap.add_argument("--parent", help="another checkout of the project, built: its preprocess is timed beside this one's")
-    ap.add_argument("--variants", default="parent,preprocess,rebuild,refit", help="which of them to run")
+    ap.add_argument("--parent", help="another checkout of the project, built: its preprocess and its updates are timed beside this one's")
+    ap.add_argument("--variants", default=",".join(VARIANTS), help="which of them to run")
+    ap.add_argument("--motions", default=",".join(MOTIONS), help="which of them to run")
     ap.add_argument("--child", nargs=3)
     a = ap.parse_args()
     if a.child:
@@ -100,25 +105,27 @@ def main():
         results = {}
         for motion in MOTIONS:
             # the preprocess's time does not depend on the motion: it is measured under the rigid move; the wobbles compare the two updates' trees
-            variants = ([("parent")] if a.parent else []) + ["preprocess", "rebuild", "refit"] if motion == "rigid" else ["rebuild", "refit"]
-            variants = [v for v in variants if v in a.variants.split(",")]
+            variants = [v for v in VARIANTS if v in a.variants.split(",") and (a.parent or not v.startswith("parent")) and (motion == "rigid" or v in ("rebuild", "refit"))]
+            if motion not in a.motions.split(","):
+                continue
             for run in range(a.runs):
                 for variant in variants:  # alternating: one of each per round
-                    env = dict(os.environ, PHX_COST_TREE=os.path.abspath(a.parent)) if variant == "parent" else None
+                    env = dict(os.environ, PHX_COST_TREE=os.path.abspath(a.parent)) if variant.startswith("parent") else None
                     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, variant, motion], capture_output=True, text=True, timeout=600, env=env)
                     got = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
                     if r.returncode != 0 or not got:
                         say(f"{name} {variant} {motion}: child failed ({r.returncode}): {r.stderr[-300:]}")
                         return 1
                     results.setdefault((variant, motion), []).append(json.loads(got[0][7:]))
+                    print(f"  {name} {motion} run {run + 1} {variant}: {results[(variant, motion)][-1]['ms']:.3f} ms", file=sys.stderr, flush=True)  # progress
         say(f"== {name}: {W} x {H}, {SPP} spp, depth 5; ms, median (min .. max)")
         for motion in MOTIONS:
-            for variant in ("parent", "preprocess", "rebuild", "refit"):
+            for variant in VARIANTS:
                 if (variant, motion) not in results:
                     continue
                 rs = results[(variant, motion)]
-                text = f"{motion:9s} {variant:10s} n={len(rs)} call {fmt([r['ms'] for r in rs])}  trace/frame {fmt([r['trace_ms'] for r in rs])}"
-                if variant in ("rebuild", "refit"):
+                text = f"{motion:9s} {variant:14s} n={len(rs)} call {fmt([r['ms'] for r in rs])}  trace/frame {fmt([r['trace_ms'] for r in rs])}"
+                if variant.endswith(("rebuild", "refit")):
                     text += "  flatten {} upload {} device {}".format(*(fmt([r[k] for r in rs]) for k in ("flatten", "upload", "device")))
                 say(text)
     if a.out:

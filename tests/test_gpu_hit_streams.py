@@ -1,6 +1,6 @@
 """The hit record as two streams (kernels.h: PassBuffers::hit_tt / hit_uv).  Every closest-hit trace writes (t, triangle), 8 bytes; the
 barycentrics (u, v) are a second 8-byte stream that exists only while the committed scene reads them: a smooth face, a UV consumer (lobe
-images, masks, emitter images) or a per-hit material (device.cpp: commit_scene).  k_trace<.., UV> and k_trace_primary<.., UV> are picked by
+images, masks, emitter images) or a per-hit material (scene_commit.cpp: commit_scene).  k_trace<.., UV> and k_trace_primary<.., UV> are picked by
 the stream's presence.
 
 Each case here is rendered on a scene that takes one of the two paths and compared bit for bit, film and ray counts, with the CPU oracle

@@ -8,6 +8,10 @@
   example     examples/render_room.c `animate K` prints an update line per frame and writes the fresh film of the last position
   refusals    leave the next frame the old scene's; an update while a frame runs is PHX_ERR_STATE and the frame completes
   animation   xpu.render_animation yields the fresh-preprocess film of every scene
+  switch      a preprocess of another scene after a rebuild, and a refit after that, render what a fresh device renders: the steps preprocess
+              and an update share (scene_commit.cpp) leave nothing of the scene before
+  refused     a rebuild refused while committing (the fault-injection twin) leaves the device without a scene until a preprocess succeeds;
+              one whose device build fails recoverably under the auto builder falls back to the host builder and renders the fresh film
 
 A differing pixel is a finding to trace to its ray (scripts/pixel_*_probe.py), never a tolerance."""
 import numpy as np
@@ -227,6 +231,97 @@ def test_refusals_leave_the_old_scene_and_a_running_frame_is_left_alone(xpu):
             dev.update_geometry(scenes.wobbled(sc, 0.01))
         dev.join()
         assert bits_equal(film.data, film0)
+    finally:
+        dev.close()
+
+
+def test_a_scene_switch_after_updates_leaves_nothing_behind(xpu):
+    """textured room -> rebuilt -> Cornell (no image, no UV, another light count) -> refitted: every film, guide film and ray counter is the
+    fresh device's.  (device_bytes is not compared: buffers grow only across a preprocess.)"""
+    room, room_moved, _ = _film_case("textured")
+    box, box_moved, _ = _film_case("cornell")
+    a, b = make(xpu), make(xpu)
+    try:
+        a.preprocess(room)
+        a.update_geometry(room_moved, "rebuild")
+        for scene, arrive in ((box, lambda: a.preprocess(box)), (box_moved, lambda: a.update_geometry(box_moved, "refit"))):
+            arrive()
+            b.preprocess(scene)
+            film_a, rays_a = frame(xpu, a, scene)
+            film_b, rays_b = frame(xpu, b, scene)
+            differ = np.argwhere((film_a.view(np.uint32) != film_b.view(np.uint32)).any(-1))
+            assert len(differ) == 0, f"{len(differ)} pixels differ from the fresh device, the first at (y, x) {differ[:4].tolist()}"
+            assert rays_a == rays_b
+            assert bits_equal(a.render_guides(3, 4), b.render_guides(3, 4))
+    finally:
+        a.close(); b.close()
+
+
+def test_a_rebuild_refused_while_committing_leaves_the_device_without_a_scene(xpu):
+    """As test_gpu_parity.py's test_a_preprocess_that_fails_while_committing_..., for the update's rebuild: the device builder's fatal error,
+    forced in the fault-injection twin (libphx_hip_hooks.so), comes after the old pool is gone, so start and a further update answer
+    PHX_ERR_STATE (4) until a preprocess succeeds.  Under the auto builder a recoverable failure falls back to the host builder instead: the
+    film does not depend on the tree, so it is the product library's of a fresh preprocess.  Refused calls; nothing faults."""
+    import hashlib, json, os, subprocess, sys
+    from conftest import ROOT
+    from phosphorus_mk2_amd import scenes
+    hooks = os.path.join(ROOT, "phosphorus_mk2_amd", "libphx_hip_hooks.so")
+    assert os.path.exists(hooks), "build() makes the fault-injection twin"
+    code = ("import hashlib, json, os, sys; sys.path.insert(0, %r)\n"
+            "from phosphorus_mk2_amd import scenes, xpu\n"
+            "a = scenes.soup(500, width=32, height=32); moved = scenes.wobbled(a, 0.02, seed=1)\n"
+            "def device(builder):\n"
+            "    return xpu.HipDevice.make(xpu.Options(samples_per_pixel=4, paths_per_sample=1, path_depth=5, bvh_builder=builder))\n"
+            "def frame(dev, sc):\n"
+            "    film = xpu.Film(32, 32, 4)\n"
+            "    dev.start(sc, xpu.FrameState(1, xpu.Tiles.make(32, 32, 32), film)); dev.join()\n"
+            "    return film.data.copy()\n"
+            "def refused(call):\n"
+            "    try:\n"
+            "        call()\n"
+            "    except xpu.DeviceError as e:\n"
+            "        return str(e)\n"
+            "    return 'NOT REFUSED'\n"
+            "dev = device('device')\n"
+            "dev.preprocess(a)\n"
+            "first = frame(dev, a)\n"
+            "print('LIT', bool(first[..., :3].max() > 0.05))\n"
+            "os.environ['PHX_TEST_FAIL_DEVICE_BUILD'] = 'fatal'\n"
+            "print('REBUILD', refused(lambda: dev.update_geometry(moved, 'rebuild')))\n"
+            "print('START', refused(lambda: frame(dev, a)))\n"
+            "print('REFIT', refused(lambda: dev.update_geometry(moved, 'refit')))\n"
+            "del os.environ['PHX_TEST_FAIL_DEVICE_BUILD']\n"
+            "dev.preprocess(a)\n"
+            "print('AGAIN', first.tobytes() == frame(dev, a).tobytes())\n"
+            "dev.close()\n"
+            "dev = device('auto')\n"
+            "dev.preprocess(a)\n"
+            "print('DEVICE_BUILT', dev.stats()['bvh_built_on_device'])\n"
+            "os.environ['PHX_TEST_FAIL_DEVICE_BUILD'] = 'recoverable'\n"
+            "print('FELL_BACK', refused(lambda: dev.update_geometry(moved, 'rebuild')), dev.stats()['bvh_built_on_device'])\n"
+            "film = frame(dev, moved); st = dev.stats()\n"
+            "print('FILM', hashlib.sha1(film.tobytes()).hexdigest(), json.dumps([st[k] for k in %r]))\n"
+            "dev.close()\n") % (ROOT, COUNTERS)
+    env = {k: v for k, v in os.environ.items() if k != "PHX_TEST_FAIL_DEVICE_BUILD"}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, env=dict(env, PHX_LIB=hooks))
+    assert r.returncode == 0, (r.stdout, r.stderr[-800:])
+    out = {l.split(" ", 1)[0]: l.split(" ", 1)[1] for l in r.stdout.splitlines() if " " in l}
+    assert out["LIT"] == "True"
+    assert "(2)" in out["REBUILD"] and "device BVH build" in out["REBUILD"]  # PHX_ERR_DEVICE
+    assert "phx_dev_start failed (4)" in out["START"] and "start before preprocess" in out["START"]
+    assert "(4)" in out["REFIT"] and "before preprocess" in out["REFIT"]
+    assert out["AGAIN"] == "True"
+    assert out["DEVICE_BUILT"] == "1" and out["FELL_BACK"] == "NOT REFUSED 0" and "fell back to the host builder" in r.stderr
+    # the product library's fresh preprocess of the moved scene
+    moved = scenes.wobbled(scenes.soup(500, width=32, height=32), 0.02, seed=1)
+    dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=4, paths_per_sample=1, path_depth=5))
+    try:
+        dev.preprocess(moved)
+        film = xpu.Film(32, 32, 4)
+        dev.start(moved, xpu.FrameState(1, xpu.Tiles.make(32, 32, 32), film)); dev.join()
+        st = dev.stats()
+        assert st["bvh_built_on_device"] == 1
+        assert out["FILM"] == hashlib.sha1(film.data.tobytes()).hexdigest() + " " + json.dumps([st[k] for k in COUNTERS])
     finally:
         dev.close()
 
