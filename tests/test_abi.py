@@ -4,6 +4,7 @@ struct layouts match the ctypes mirror, and — with no device — every compute
 import ctypes as C
 import os
 import re
+import sys
 
 import pytest
 
@@ -125,7 +126,7 @@ def test_render_makes_one_device_on_a_multi_gpu_box(monkeypatch):
         made.append(options.device_ordinal)
         raise Stop()
 
-    monkeypatch.setattr(xpu, "load_library", lambda: FakeLib())
+    monkeypatch.setattr(sys.modules[xpu.load_library.__module__], "load_library", lambda: FakeLib())  # where discover() looks it up
     monkeypatch.setattr(xpu.HipDevice, "make", staticmethod(fake_make))
     with pytest.raises(Stop):
         xpu.render(scenes.cornell(32, 32), spp=1)

@@ -394,6 +394,36 @@ def test_render_camera_path_is_the_chain_of_its_calls(xpu, scene, cameras):
         d.close()
 
 
+def test_render_camera_path_denoises_by_each_cameras_guides_and_displays_that(xpu):
+    """guided denoise with plane=True and display={} on a 32 x 32 path of two cameras of different fov: over the chain above, each yielded film
+    is the denoise of the accumulator by that camera's guide film and that camera's plane scale, and each image the display of that film"""
+    w, h, spp = 32, 32, 4
+    sc = FC.SCENES["cornell"](w, h, 1.0)
+    path = [sc.camera, moved(sc.camera, (0.12, 0.05, -0.1), RC.rot_y(0.04), fov=0.9)]
+    got = [(film.copy(), image) for film, _, _, _, image in
+           xpu.render_camera_path(sc, path, spp, seed=5, guide_samples=4, reproject=PATH_SETTINGS, depth=4, denoise=dict(iterations=3, guides=dict(plane=True)), display={})]
+    assert len(got) == 2 and xpu.guide_plane_scale(path[0]) != xpu.guide_plane_scale(path[1])
+    d = xpu.HipDevice.make(xpu.Options(samples_per_pixel=spp, paths_per_sample=1, path_depth=4))
+    try:
+        d.preprocess(sc)
+        acc, before, guides_before = xpu.accumulator(w, h, 4, True), None, None
+        for k, cam in enumerate(path):
+            d.set_camera(cam)
+            guides = d.render_guides(5 + k, 4)
+            if before is not None:
+                acc, _ = rp.reproject(acc, guides_before, guides, model_camera(before), model_camera(cam), OFFS, **PATH_SETTINGS)
+            film = xpu.Film(w, h, 4, True, True, False)
+            d.start(sc, xpu.FrameState(5 + k, xpu.Tiles.make(w, h, 32), film, native_sink=True))
+            d.join()
+            acc = ac.accumulate(acc, film.data, OFFS, OFFS_FRAME, spp)
+            want = d.denoise(acc, spp, 4, True, True, iterations=3, guides=guides, plane=True, plane_scale=xpu.guide_plane_scale(cam))
+            assert bits_equal(got[k][0], want) and not bits_equal(want, acc), f"camera {k + 1}"
+            assert got[k][1].shape == (h, w, 4) and np.array_equal(got[k][1], d.display(want)), f"camera {k + 1}"
+            before, guides_before = cam, guides
+    finally:
+        d.close()
+
+
 def test_with_every_camera_equal_the_path_is_render_progressive(xpu, scene, cameras):
     """max_history large and every pixel with geometry: each reprojection is the copy, so the accumulators are render_progressive's bit for bit"""
     want = [film.copy() for film, _, _ in xpu.render_progressive(scene, SPP, 3, seed=9, depth=4, normals=True)]

@@ -345,6 +345,27 @@ def test_render_animation_yields_the_fresh_films(xpu):
             dev.close()
 
 
+def test_render_animation_denoises_the_fresh_films_and_displays_that(xpu):
+    """denoise={} and display={} on 32 x 32 films of 4 samples: each yielded film is the denoise of the scene's fresh frame, each image its display"""
+    from phosphorus_mk2_amd import scenes
+    sc = scenes.cornell(32, 32)
+    path = [sc, scenes.transformed(sc, {5: rigid(0.2, (0.1, -0.1, 0.0))}), scenes.transformed(sc, {5: rigid(0.4, (0.2, -0.2, 0.1)), 2: rigid(0.0, (0.0, 0.0, 0.3))})]
+    got = [(np.array(f), image) for f, _, _, image in xpu.render_animation(path, 4, mode="refit", denoise={}, display={}, seed=3, depth=5)]
+    assert len(got) == 3
+    for (film, image), scene in zip(got, path):
+        dev = xpu.HipDevice.make(xpu.Options(samples_per_pixel=4, paths_per_sample=1, path_depth=5))
+        try:
+            dev.preprocess(scene)
+            fresh = xpu.Film(32, 32, 4, True, True, False)
+            dev.start(scene, xpu.FrameState(3, xpu.Tiles.make(32, 32, 32), fresh, native_sink=True))
+            dev.join()
+            want = dev.denoise(fresh.data, 4, 4, True, False)
+            assert bits_equal(film, want) and not bits_equal(want, fresh.data)
+            assert image.shape == (32, 32, 4) and np.array_equal(image, dev.display(want))
+        finally:
+            dev.close()
+
+
 def test_plain_c_host_animates(xpu, tmp_path):
     """examples/render_room.c `animate 2`: one `update:` line per frame, and the film on file is the fresh film of the room with its two tilted
     triangles (vertices 12 .. 17) moved by 0.8 along x, the last of the two positions"""
